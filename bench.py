@@ -1,9 +1,16 @@
 #!/usr/bin/env python3
 """bench.py — billion pair-interactions/s of the all-pairs force path (BASELINE.json's metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times EXACTLY K steps, and prints the headline line (with `roofline` when the kernel's events were
+taken inside the timed region; null otherwise).  Everything else described below — cpu_baseline, strict_mode, configs, the N > 1
+extras and the separate kernel-events pass of a short step — runs only with --full.
+--dump-outputs DIR: after the timed steps, the state they left (what nbody_step() hands its caller: DIR/pos.npy and DIR/vel.npy,
+(N, 4) words in the run's precision) — at most 64 MB in all; past that, the same fixed, seeded sample of rows from both arrays.
+The inputs are seeded (--seed), so two builds can be compared output for output.
 
 A step = one pass of the hot path over all N bodies: force accumulation over all N^2 ordered pairs
 (self included, S/top_level.vhd:237-243), kick, drift — nbody_step() of include/nbody.h, state resident
@@ -26,7 +33,7 @@ scaling runs where a peer-copy number must not pass as the RCCL point).  Workers
 (nbody_comm_selftest: every received word checked) before the warm-up.  NBODY_VIRTUAL_HOSTS=1 in the environment rehearses an N-rank RCCL
 job on a box with fewer GPUs: every rank poses as its own host (NCCL_HOSTID) and RCCL connects them over loopback sockets.
 
-Extras (N > 1 only; the N = 1 path is untouched).  Rank 0 prints the headline line FIRST; then, in the same worker
+Extras (N > 1 and --full only; the N = 1 path is untouched).  Rank 0 prints the headline line FIRST; then, in the same worker
 processes, (a) three steps each of NBODY_COMM_RING with one launch per arriving slice, NBODY_COMM_DIRECT and
 NBODY_COMM_ALLGATHER -> "comm_forms": {form: {ms_per_step, comm_exposed_ms_per_step, value}} (ring
 against direct over xGMI) plus the all-gather with no overlap, whose exposed time is the transfer's own duration, and (b) at N = 8 BASELINE configs[4]: an fp64 N = 4,194,304 engine, 1 warm-up + 2 timed steps ->
@@ -36,7 +43,7 @@ The extras have their own deadline (--extras-deadline, 90 s after the first line
 line is returned with "extras": "timed out ..." and exit code 0 — an extra that hangs costs neither the headline nor the extras
 finished before it.
 
-Rank 0 prints ONE JSON line, always with:
+Rank 0 prints ONE JSON line, with --full always with:
   roofline      the force kernel priced at 20 flop per pair against the fp32 (157.3 TFLOP/s) or
                 fp64 (78.6: measured v_fma_f64 issue rate, profiles/r01_microbench_valu_issue.txt) VECTOR peak — no contraction for the matrix cores — with the kernel's
                 duration measured live by HIP events on the library's compute stream; beside it the instruction-issue
@@ -47,8 +54,8 @@ Rank 0 prints ONE JSON line, always with:
   cpu_baseline  the oracle (oracle/nbody_ref.c, kind "port": the reference is VHDL and has no CPU path) timed on
                 this box's host cores, rank 0, after the timed region, on a bounded row sample: about 15 s of host work at N = 1,
                 3 s on an N > 1 line (the other ranks wait at a barrier) — every line carries a measured value and its core count.
-One GPU: the benchmark runs in a supervised worker process (the parent never touches a GPU; --in-process for profilers).  The worker
-prints the headline line — complete, cpu_baseline included — BEFORE any study pass, then one more line after each of
+One GPU: the benchmark runs in a supervised worker process (the parent never touches a GPU; --in-process for profilers).  With --full
+the worker prints the headline line — complete, cpu_baseline included — BEFORE any study pass, then one more line after each of
   strict_mode   (fp32) the rate of NBODY_ARITH_STRICT — the arithmetic in which the GPU equals the CPU oracle bit for bit —
                 from up to 3 steps after the timed region: what the parity claim costs on this box; never `value`.
   configs       (the default line only) the other BASELINE configurations one GPU reaches, each {value, ms_per_step, frac}: config2 (N = 65536,
@@ -222,6 +229,24 @@ def matching_pmc(run_cfg):
     return None
 
 
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array of {name: (N, 4) array} as path/<name>.npy, in its own (float) dtype, `limit` bytes at most in all.
+    Past the limit, the same rows of every array: a sample fixed by its own seed, in ascending order, so that two runs of the same
+    arguments write the same bodies.  Returns the number of rows written."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a[0].nbytes for a in arrays.values())
+    rows = min(n, (limit - 1024 * len(arrays)) // row_bytes)         # (1 KB per file for the .npy header)
+    idx = None if rows == n else np.sort(np.random.default_rng(0).choice(n, rows, replace=False))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a if idx is None else a[idx])
+    return rows
+
+
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Supervision of the worker processes.  Nothing in this section imports torch or touches a GPU.
@@ -353,7 +378,14 @@ def main(argv=None):
                          "the fp64 arithmetic, measured after the headline line is out, at most --configs-budget seconds")
     ap.add_argument("--configs-budget", type=float, default=40.0)
     ap.add_argument("--config5-bodies", type=int, default=4194304, help="bodies of the extras pass's fp64 run (BASELINE configs[4]: 4,194,304)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: cpu_baseline, strict_mode, configs, the N > 1 extras and the separate "
+                         "kernel-events pass of a short step (the options above choose among them); off: the headline line alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the state the timed steps left as DIR/pos.npy and DIR/vel.npy (64 MB at most: a fixed row sample beyond)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     code = supervisor_main(args, argv)
     if code is not None:
         raise SystemExit(code)
@@ -397,8 +429,8 @@ def main(argv=None):
     import numpy as np
     MAXOP = dist.ReduceOp.MAX if world > 1 else None
     # extras (N > 1 only): the three transfer forms, and BASELINE configs[4] in fp64 at N = 8 (or when asked for)
-    want_forms = world > 1 and args.extras != "off"
-    want_c5 = world > 1 and (args.extras == "all" or (args.extras == "auto" and world == 8))
+    want_forms = args.full and world > 1 and args.extras != "off"
+    want_c5 = args.full and world > 1 and (args.extras == "all" or (args.extras == "auto" and world == 8))
 
     def allmax(vals):
         """MAX over the ranks of a few numbers (every rank calls it, also a peer-transport rank that holds no engine)"""
@@ -408,9 +440,11 @@ def main(argv=None):
         dist.all_reduce(t, op=MAXOP)
         return [float(x) for x in t]
 
-    def run_timed(e, steps, warmup, inline):
+    def run_timed(e, steps, warmup, inline, after_timed=None, kernel_pass=True):
         """W untimed steps, then EXACTLY K steps bracketed by barrier + torch.cuda.synchronize() on both sides; MAX over ranks.
-        e is None on the ranks of a peer-transport job that hold no GPU: they keep the collectives only."""
+        e is None on the ranks of a peer-transport job that hold no GPU: they keep the collectives only.
+        after_timed() runs on every rank on the state the K steps left, before the separate kernel-events pass (not inline), which
+        steps on; kernel_pass False: no such pass (the kernel's duration is then known only when inline)."""
         if e is not None:
             e.step(dt, warmup)
             e.sync()
@@ -427,9 +461,11 @@ def main(argv=None):
             torch.cuda.synchronize()
         barrier()
         elapsed = time.perf_counter() - t0
+        if after_timed is not None:
+            after_timed()
         kernel_steps, kernel_ms, launches, wait_ms, waits = steps, 0.0, 0, 0.0, 0
         if e is not None:
-            if not inline:
+            if not inline and kernel_pass:
                 # the timed region ran the path nbody_step() users get (one GPU: HIP-graph replay); the kernel's duration comes
                 # from a second pass with events around every launch
                 kernel_steps = min(steps, 50)
@@ -524,7 +560,14 @@ def main(argv=None):
 
     share = float(n) * float(n) / world
     inline = args.events == "inline" or (args.events == "auto" and share >= 1e10)
-    r = run_timed(eng, args.steps, args.warmup, inline)
+
+    def write_outputs():
+        """--dump-outputs: the state of the last timed step (every rank that holds an engine downloads: a collective in a multi-process job)"""
+        if args.dump_outputs and eng is not None:
+            p_all, v_all = eng.download()
+            if rank == 0:
+                dump_outputs(args.dump_outputs, {"pos": p_all, "vel": v_all})
+    r = run_timed(eng, args.steps, args.warmup, inline, after_timed=write_outputs, kernel_pass=args.full)
     elapsed, wait_ms, waits, kernel_steps = r["elapsed"], r["wait_ms"], r["waits"], r["kernel_steps"]
 
     out = None
@@ -543,11 +586,12 @@ def main(argv=None):
                    "kernel_source_sha": kernel_source_sha()}
         if args.arith != "fma3":
             run_cfg["arith"] = args.arith       # (absent = the timed arithmetic: the profiles of the headline keep matching)
-        roof = roofline_of(eng, cfg, r, n, args.fp64, inline)
-        if args.arith != "fma3":
+        # (a short step's kernel duration takes a pass of its own: --full only; without it the line has no roofline)
+        roof = roofline_of(eng, cfg, r, n, args.fp64, inline) if (inline or args.full) else None
+        if roof is not None and args.arith != "fma3":
             roof["note"] = ("study arithmetic %s, not the timed mode: the issue model beside it (30 cycles per wave-pair) is the timed arithmetic's; "
                             "strict adds 8 full-rate operations and a compare per pair (DESIGN.md 3.6)" % args.arith)
-        pj = matching_pmc(run_cfg)
+        pj = matching_pmc(run_cfg) if roof is not None else None
         if pj:
             roof["traffic"] = pj.get("hbm_bytes_per_launch")
             roof["pmc"] = {"source": "%s (rocprofv3 passes of this configuration, not this run)" % pj["_file"],
@@ -580,12 +624,13 @@ def main(argv=None):
             "roofline": roof,
         }
         if world > 1:
-            out["comm_exposed_ms_per_step"] = round(wait_ms / max(1, kernel_steps), 4)
-            out["comm_waits_per_step"] = round(waits / max(1, kernel_steps), 2)
+            timed_waits = roof is not None        # (the waits are timed by the same events as the kernels)
+            out["comm_exposed_ms_per_step"] = round(wait_ms / max(1, kernel_steps), 4) if timed_waits else None
+            out["comm_waits_per_step"] = round(waits / max(1, kernel_steps), 2) if timed_waits else None
             out["transport_used"] = "peer" if peer else ("rccl" if transport == "rccl" else "host")
     extras = want_forms or want_c5
     if rank == 0:
-        target_s = cpu_leg_seconds(world, args.cpu_baseline, args.no_cpu_baseline)
+        target_s = cpu_leg_seconds(world, args.cpu_baseline, args.no_cpu_baseline or not args.full)
         if target_s is not None:
             # after the timed region, on rank 0 (the other ranks wait at the barrier below, idle)
             try:
@@ -602,7 +647,7 @@ def main(argv=None):
             out[key] = value
             print(json.dumps(out), flush=True)
 
-    if world == 1:
+    if world == 1 and args.full:
         # one GPU: the study passes, each published as it finishes
         if not args.fp64 and args.strict_pass == "auto" and args.arith == "fma3":
             publish("strict_mode", strict_pass(eng, nb, n, dt, args.steps))

@@ -390,3 +390,20 @@ def test_every_line_gets_a_measured_cpu_baseline():
     assert bench.cpu_leg_seconds(8, "always") == 15.0 and bench.cpu_leg_seconds(8, "never") is None and bench.cpu_leg_seconds(1, "auto", True) is None
     cb = bench.cpu_baseline(8192, 42, False, target_s=0.3)
     assert cb["value"] > 0 and cb["cores"] >= 1 and cb["kind"] == "port" and "8192 sources" in cb["sample"]
+
+
+def test_dumped_outputs_are_whole_or_one_fixed_sample_within_the_budget(tmp_path):
+    """--dump-outputs: arrays that fit are written whole in their own dtype; past the budget, the same seeded rows of every array, in
+    ascending order and the same on every run (two builds are compared file for file)"""
+    import numpy as np
+    pos = np.arange(4000 * 4, dtype=np.float64).reshape(4000, 4)
+    arrays = {"pos": pos, "vel": -pos}
+    assert bench.dump_outputs(str(tmp_path / "whole"), arrays) == 4000
+    whole = np.load(tmp_path / "whole" / "pos.npy")
+    assert whole.dtype == np.float64 and np.array_equal(whole, pos)
+    limit = 100000
+    rows = bench.dump_outputs(str(tmp_path / "a"), arrays, limit=limit)
+    assert bench.dump_outputs(str(tmp_path / "b"), arrays, limit=limit) == rows and 0 < rows < 4000
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in ("pos.npy", "vel.npy")) <= limit
+    pa, va, pb = (np.load(tmp_path / d / f) for d, f in (("a", "pos.npy"), ("a", "vel.npy"), ("b", "pos.npy")))
+    assert pa.shape == (rows, 4) and np.array_equal(pa, pb) and np.array_equal(va, -pa) and np.all(np.diff(pa[:, 0]) > 0)

@@ -11,7 +11,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.gpu
 def test_one_gpu_line_carries_roofline_cpu_baseline_and_strict_mode():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bodies", "65536", "--steps", "8", "--warmup", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bodies", "65536", "--steps", "8", "--warmup", "2", "--full"],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -25,7 +25,7 @@ def test_one_gpu_line_carries_roofline_cpu_baseline_and_strict_mode():
     assert strict["arith"] == "NBODY_ARITH_STRICT" and strict["kernel"]["variant"] == "smem"
     assert 0.4 * j["value"] < strict["value"] < 0.9 * j["value"], (strict, j["value"])
     # ... and switched off on request, and absent from an fp64 line
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bodies", "16384", "--steps", "4", "--strict-pass", "never", "--cpu-baseline", "never"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bodies", "16384", "--steps", "4", "--full", "--strict-pass", "never", "--cpu-baseline", "never"],
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "strict_mode" not in json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 
@@ -34,7 +34,7 @@ def test_one_gpu_line_carries_roofline_cpu_baseline_and_strict_mode():
 def test_default_line_carries_the_other_baseline_configs():
     """the driver's own N = 1 invocation (default bodies; few steps here) yields ONE line whose `configs` hold BASELINE
     configs 1 and 2 and the fp64 arithmetic, measured after the headline line was out; `value` is untouched by them."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -53,3 +53,29 @@ def test_default_line_carries_the_other_baseline_configs():
     assert c["config2"]["kernel"]["variant"] == "isa" and c["config2_lds_tile256"]["kernel"]["variant"] == "lds" and c["config2_lds_tile256"]["kernel"]["tile"] == 256
     assert c["fp64"]["value"] > 500 and c["fp64"]["peak_tflops"] == 78.6 and 0.5 < c["fp64"]["frac_of_issue_bound"] <= 1.05, c["fp64"]
     assert c["config1"]["checksums_equal"] is True and c["config1"]["cpu_value"] > 0 and c["config1"]["value"] > 0, c["config1"]
+
+
+@pytest.mark.gpu
+def test_plain_line_times_the_steps_asked_for_and_dumps_their_state(nb, tmp_path):
+    """Without --full the line is the headline alone; --steps sets the timed steps, ms_per_step is one of them, and --dump-outputs
+    holds the state the timed path left: bit for bit what W + K steps of the same engine give."""
+    import numpy as np
+    n, steps, warmup = 16384, 6, 2
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--bodies", str(n), "--steps", str(steps), "--warmup", str(warmup),
+                        "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    j = json.loads(lines[0])
+    assert j["steps"] == steps and j["warmup"] == warmup and j["dtype"] == "f32" and j["higher_is_better"] is True
+    assert abs(j["value"] - float(n) * n / (j["ms_per_step"] * 1e-3) / 1e9) <= 0.01 * j["value"]
+    assert not {"cpu_baseline", "strict_mode", "configs"} & set(j) and j["roofline"] is None      # (a short step: no separate kernel pass)
+    gp, gv = np.load(tmp_path / "out" / "pos.npy"), np.load(tmp_path / "out" / "vel.npy")
+    assert gp.dtype == np.float32 and gv.dtype == np.float32 and gp.shape == gv.shape == (n, 4)
+    pos, vel = nb.make_bodies(n, seed=42)
+    with nb.NBody(n) as e:
+        e.upload(pos, vel)
+        e.step(0.01, warmup)
+        e.step(0.01, steps)
+        wp, wv = e.download()
+    assert np.array_equal(gp.view(np.uint32), wp.view(np.uint32)) and np.array_equal(gv.view(np.uint32), wv.view(np.uint32))

@@ -100,7 +100,7 @@ def test_bench_launches_and_supervises_its_own_workers(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["NBODY_OVERSUBSCRIBE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bodies", "262144", "--steps", "3", "--warmup", "1",
-                        ], env=env, capture_output=True, text=True, timeout=900)
+                        "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -135,7 +135,7 @@ def test_bench_peer_copy_transport(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["NBODY_OVERSUBSCRIBE"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bodies", "262144", "--steps", "3", "--warmup", "1",
-                        "--transport", "peer", "--no-cpu-baseline", "--extras", "all", "--config5-bodies", "65536"],
+                        "--transport", "peer", "--full", "--no-cpu-baseline", "--extras", "all", "--config5-bodies", "65536"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -215,7 +215,7 @@ def test_bench_under_torch_distributed_run(tmp_path, virtual_hosts):
         env["NBODY_VIRTUAL_HOSTS"] = "1"
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                         "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--bodies", "131072"], env=env, capture_output=True, text=True, timeout=900)
+                        "--bodies", "131072", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -292,7 +292,7 @@ def test_bench_rccl_attempt_with_virtual_hosts(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["NBODY_VIRTUAL_HOSTS"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--bodies", "262144", "--steps", "3", "--warmup", "1",
-                        "--no-cpu-baseline", "--extras", "all", "--config5-bodies", "65536", "--autotune"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--extras", "all", "--config5-bodies", "65536", "--autotune"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["value"] > 0 and out["config"]["finite"]

@@ -8,7 +8,7 @@ tag=$1; shift
 out=gpurun_out/prof_$tag
 mkdir -p $out
 export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --in-process --configs-pass never --strict-pass never --no-cpu-baseline "$@" > $out/bench_trace.json 2> $out/trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python3 bench.py --in-process --full --configs-pass never --strict-pass never --no-cpu-baseline "$@" > $out/bench_trace.json 2> $out/trace.err
 i=0
 for set in \
   "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA GRBM_GUI_ACTIVE GRBM_COUNT" \
@@ -18,7 +18,7 @@ for set in \
   "FETCH_SIZE" \
   "WRITE_SIZE TCC_HIT_sum TCC_MISS_sum"; do
   i=$((i+1))
-  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $out/pmc_$i -- python3 bench.py --in-process --configs-pass never --strict-pass never --no-cpu-baseline --steps 2 "$@" > $out/bench_pmc_$i.json 2> $out/pmc_$i.err
+  rocprofv3 --kernel-trace --pmc $set --output-format csv -d $out/pmc_$i -- python3 bench.py --in-process --full --configs-pass never --strict-pass never --no-cpu-baseline --steps 2 "$@" > $out/bench_pmc_$i.json 2> $out/pmc_$i.err
   echo "pass $i rc=$? : $set"
 done
 find $out -name "*.csv" | wc -l

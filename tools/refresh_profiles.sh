@@ -7,8 +7,8 @@
 #                     tools/parse_prof.py per configuration -> profiles/<round>_rocprofv3_<tag>_summary.txt, _kernel_stats.csv and
 #                     profiles/pmc_<tag>.json (what bench.py attaches as roofline.traffic / roofline.pmc when configuration and
 #                     product-kernel-source hash match), plus the traced run's own bench line
-#   then, so that the committed bench lines carry the new profile: gpurun -- 'bash tools/refresh_profiles.sh lines'  and
-#                     bash tools/refresh_profiles.sh keep r05
+#   then, so that the committed bench lines carry the new profile: on the GPU box  bash tools/refresh_profiles.sh lines <dir>
+#                     and here, with <dir> copied back:  bash tools/refresh_profiles.sh keep r05 <dir>
 set -u
 TAGS="fp32_n1048576 fp32_n65536 fp32_n16384 fp64_n262144 fp64_n4194304"
 args_of() { case $1 in fp32_n1048576) echo "";; fp32_n65536) echo "--bodies 65536";; fp32_n16384) echo "--bodies 16384";;
@@ -25,13 +25,14 @@ case ${1:-} in
     cp gpurun_out/prof_fp32_n1048576/bench_trace.json profiles/${r}_bench_n1_under_rocprof_trace.json
     grep -H -E "^cycles_per_wave_pair|^clock_ghz|^hbm_bytes_per_launch|force kernel avg" profiles/${r}_rocprofv3_*_summary.txt ;;
   lines)
-    mkdir -p gpurun_out/lines
-    python3 bench.py > gpurun_out/lines/bench_n1.json 2> gpurun_out/lines/bench_n1.err &&
-    python3 bench.py --steps 20 --warmup 5 > gpurun_out/lines/bench_n1_driver_form.json 2>/dev/null &&
-    python3 bench.py --fp64 --bodies 262144 > gpurun_out/lines/bench_fp64_n262144.json 2>/dev/null &&
-    python3 bench.py --bodies 65536 --steps 200 > gpurun_out/lines/bench_n65536.json 2>/dev/null; echo "lines done" ;;
+    d=${2:?output directory}
+    mkdir -p "$d"
+    python3 bench.py --full > "$d"/bench_n1.json 2> "$d"/bench_n1.err &&
+    python3 bench.py --full --steps 20 --warmup 5 > "$d"/bench_n1_driver_form.json 2>/dev/null &&
+    python3 bench.py --full --fp64 --bodies 262144 > "$d"/bench_fp64_n262144.json 2>/dev/null &&
+    python3 bench.py --full --bodies 65536 --steps 200 > "$d"/bench_n65536.json 2>/dev/null; echo "lines done" ;;
   keep)
-    r=${2:?round tag}
-    for f in bench_n1 bench_n1_driver_form bench_fp64_n262144 bench_n65536; do cp gpurun_out/lines/$f.json profiles/${r}_$f.json; done ;;
+    r=${2:?round tag}; d=${3:?directory the lines were written to}
+    for f in bench_n1 bench_n1_driver_form bench_fp64_n262144 bench_n65536; do cp "$d"/$f.json profiles/${r}_$f.json; done ;;
   *) sed -n 2,13p "$0"; exit 2 ;;
 esac

@@ -11,32 +11,38 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-s
 
 all: lib host oracle microbench
 
-# The library = ONE device translation unit (kernels.hip: the nbk kernels + the launch functions that pick an instantiation; ~45 s of hipcc)
-# and three host-only C++ files (context, comm, mailbox: seconds each) behind csrc/nbody_internal.hpp.  A host-side edit relinks in seconds.
+# The library = ONE device code object (device.hip: the force path's kernels.hip — the nbk kernels + the launch functions that pick an
+# instantiation, ~45 s of hipcc — and the energy pass's energy.hip) and four host-only C++ files (context, comm, mailbox, energy: seconds
+# each) behind csrc/nbody_internal.hpp.  A host-side edit relinks in seconds.
 HOSTFLAGS := -O2 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function
 OBJ      := build/obj
 KERNEL_SRC := $(CSRC)/kernels.hip $(CSRC)/nbody_kernels.hpp $(CSRC)/nbody_args.hpp $(CSRC)/force_loop_gfx950.inc
 HOST_HDR := $(CSRC)/nbody_internal.hpp $(CSRC)/nbody_args.hpp include/nbody.h
-HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o
+HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o $(OBJ)/energy.o
+# the energy diagnostics' device code (energy.hip, seconds of hipcc on its own) reads nbody_args.hpp and changes nothing of the force path's
+# hashed source; device.hip compiles it with kernels.hip into the library's one code object.  Its host side is energy.cpp, one of HOST_OBJ.
+ENERGY_SRC := $(CSRC)/energy.hip $(CSRC)/energy_args.hpp
+DEVICE_SRC := $(CSRC)/device.hip $(KERNEL_SRC) $(ENERGY_SRC)
 
 lib: $(PKG)/libnbody_hip.so
-$(OBJ)/kernels.o: $(KERNEL_SRC) $(HOST_HDR)
+$(OBJ)/device.o: $(DEVICE_SRC) $(HOST_HDR)
 	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/kernels.hip -o $@
+	$(HIPCC) $(HIPFLAGS) -c $(CSRC)/device.hip -o $@
 $(OBJ)/%.o: $(CSRC)/%.cpp $(HOST_HDR)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
-$(PKG)/libnbody_hip.so: $(OBJ)/kernels.o $(HOST_OBJ)
+$(OBJ)/energy.o: $(CSRC)/energy_args.hpp
+$(PKG)/libnbody_hip.so: $(OBJ)/device.o $(HOST_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -pthread -o $@ $^ -ldl
 
 # The diagnostic library: the same sources with kernels.hip built -DNBODY_DIAG_LOOPS — the experiment encodings of the hand-scheduled loop
 # and its TIMING-ONLY forms (wrong results) that profiles/r02_loop_diagnostics.md was measured with.  Not part of `all`, never loaded by
 # the package unless NBODY_LIB points at it (tools/profile_diag.sh does).  The host objects are the product's own.
 diag: $(PKG)/libnbody_hip_diag.so
-$(OBJ)/kernels_diag.o: $(KERNEL_SRC) $(HOST_HDR)
+$(OBJ)/device_diag.o: $(DEVICE_SRC) $(HOST_HDR)
 	@mkdir -p $(OBJ)
-	$(HIPCC) $(HIPFLAGS) -DNBODY_DIAG_LOOPS -c $(CSRC)/kernels.hip -o $@
-$(PKG)/libnbody_hip_diag.so: $(OBJ)/kernels_diag.o $(HOST_OBJ)
+	$(HIPCC) $(HIPFLAGS) -DNBODY_DIAG_LOOPS -c $(CSRC)/device.hip -o $@
+$(PKG)/libnbody_hip_diag.so: $(OBJ)/device_diag.o $(HOST_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -pthread -o $@ $^ -ldl
 
 # C host program (north_star: "host code stays in C"): links only the C-ABI

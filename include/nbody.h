@@ -311,6 +311,35 @@ int nbody_comm_time(double *wait_ms_total, long long *waits, int reset);
  * which = 0 current positions (full N), 1 velocities (own slice), 2 last forces (own slice). */
 int nbody_device_ptr(int which, void **ptr, size_t *bytes);
 
+/* ---- energy and potential: diagnostics of the state on the device (not in the reference) ----
+ * Unit masses, G = 1, eps = the force's softening (the binary32 with bits 0x3089705F, added to d2 exactly as the force adds it), so
+ * that the force the library computes is -grad phi of
+ *   phi_i = -sum_{j != i} (|r_j - r_i|^2 + eps)^(-1/2)    (the self pair is excluded exactly; coincident distinct bodies give 1/sqrt(eps))
+ *   U = 1/2 sum_i phi_i,   T = 1/2 sum_i |v_i|^2,   P = sum_i v_i,   L = sum_i r_i x v_i.
+ * Pair arithmetic follows NBODY_OPT_ARITH: d2 in the FMA3 form or the reference's five roundings; 1/sqrt by v_rsq_f32, or under a
+ * strict mode the IEEE value (float)(1.0 / sqrt((double)d2)).  fp64 contexts: the fma-contracted d2; the v_rsq_f64 seed refined to
+ * full precision by one third-order step, or under a strict mode IEEE sqrt and divide.
+ * ORDER (fixed by N alone; the variant, JSUB, JSLICES, WSPLIT, SUM_ORDER and the number of ranks play no part, so phi_i has the same
+ * bits however the context is sharded):
+ *   level 1: the sources in blocks of 1024 consecutive bodies, each block summed from zero in ascending j in the context precision,
+ *            j = i skipped;
+ *   level 2: the block sums converted to fp64 and added in ascending block order from zero, giving S_i;  phi_i = 0 - S_i, returned
+ *            rounded to the context precision.
+ *   Totals are accumulated in fp64 from the fp64 values (U from 0 - S_i, T from fma(vx, vx, fma(vy, vy, vz * vz))): the rows of a rank's
+ *   slice in groups of 256 from its first body, each group summed in ascending rows, the groups' sums in ascending order, T and U halved;
+ *   then the ranks' eight values added in rank order on every rank, so every rank returns the same bits, equal to those of a one-process
+ *   nbody_init(n, P, ., .) context (the totals of different rank counts agree to rounding).  No atomics: two calls return identical bits.
+ * nbody_energy(): out[NBODY_ENERGY_WORDS] of the whole system.  nbody_potential_rows(_d)(): phi of n_rows bodies from first_row, rows
+ * as in nbody_forces_rows.  Both bring the other slices' positions first (collective in nbody_init_rank contexts: every rank calls
+ * them) and leave the step state as it was: positions, velocities, the captured step graph and the force-kernel timer
+ * (nbody_kernel_time does not count energy launches).  NBODY_ERR_NOT_INIT without a context, NBODY_ERR_ARG for a null pointer or a bad
+ * range, NBODY_ERR_STATE for the other precision's entry point or while the mailbox is served. */
+enum { NBODY_ENERGY_KINETIC = 0, NBODY_ENERGY_POTENTIAL, NBODY_ENERGY_PX, NBODY_ENERGY_PY, NBODY_ENERGY_PZ,
+       NBODY_ENERGY_LX, NBODY_ENERGY_LY, NBODY_ENERGY_LZ, NBODY_ENERGY_WORDS };
+int nbody_energy(double *out);
+int nbody_potential_rows(int first_row, int n_rows, float *phi);
+int nbody_potential_rows_d(int first_row, int n_rows, double *phi);
+
 #ifdef __cplusplus
 }
 #endif

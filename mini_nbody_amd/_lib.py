@@ -22,6 +22,8 @@ COMM_RING, COMM_ALLGATHER, COMM_AUTO, COMM_DIRECT = 0, 1, 2, 3
  INFO_LAUNCHES_PER_STEP, INFO_HAS_COMM, INFO_WSPLIT, INFO_ISA_PHASE, INFO_LONG_BUFFERS, INFO_XCD_MAP, INFO_FUSE_COMBINE,
  INFO_COMM_FORM, INFO_COMM_PRIORITY, INFO_DIAG_BUILD, INFO_MAILBOX_SERVED, INFO_MAILBOX_SERVING) = range(1, 30)
 
+(ENERGY_KINETIC, ENERGY_POTENTIAL, ENERGY_PX, ENERGY_PY, ENERGY_PZ, ENERGY_LX, ENERGY_LY, ENERGY_LZ, ENERGY_WORDS) = range(9)
+
 ERR_NOT_INIT, ERR_ARG, ERR_NO_DEVICE, ERR_RCCL_LOAD, ERR_STATE, ERR_UNSUPPORTED = 1001, 1002, 1003, 1004, 1005, 1006
 
 # every symbol include/nbody.h declares (tests/test_abi.py checks the library exports exactly these)
@@ -33,7 +35,7 @@ SYMBOLS = [
     "nbody_set_host_gather", "nbody_download_slice", "nbody_comm_selftest", "nbody_forces_rows_d",
     "nbody_comm_selftest_virtual", "nbody_comm_plan", "nbody_comm_probe", "nbody_comm_time",
     "nbody_rsqrt_selftest", "nbody_rsqrt_strict", "nbody_strict_proof", "nbody_mailbox_open", "nbody_mailbox_rams",
-    "nbody_mailbox_serve",
+    "nbody_mailbox_serve", "nbody_energy", "nbody_potential_rows", "nbody_potential_rows_d",
 ]
 
 
@@ -87,6 +89,7 @@ def load():
         "nbody_strict_proof": [C.POINTER(C.c_ulonglong), C.POINTER(C.c_uint)],
         "nbody_mailbox_open": [i, i], "nbody_mailbox_rams": [C.POINTER(vp), C.POINTER(vp), C.POINTER(i)],
         "nbody_mailbox_serve": [i, i],
+        "nbody_energy": [dp], "nbody_potential_rows": [i, i, fp], "nbody_potential_rows_d": [i, i, dp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -250,6 +250,26 @@ int gather_sharded_multiprocess(Local& L, const void* own_rows) {
   return NBODY_OK;
 }
 
+// Multi-process: every rank's one word of dev_words (word `rank`, word_bytes bytes, written on the compute stream) to every rank,
+// host_words[q] = rank q's word, through the transport the context uses for positions: one in-place ncclAllGather, or the host
+// callback.  Never a reduction: what the ranks then add, they add in the same order.
+int allgather_rank_words(Local& L, void* dev_words, void* host_words, int word_bytes) {
+  const int P = g.nranks;
+  const size_t wb = (size_t)word_bytes;
+  HIPC(hipSetDevice(L.device));
+  HIPC(hipStreamSynchronize(L.compute));
+  if (g.host_gather) {
+    HIPC(hipMemcpy((char*)host_words + L.rank * wb, (char*)dev_words + L.rank * wb, wb, hipMemcpyDeviceToHost));
+    if (g.host_gather(g.host_gather_user, host_words, P, word_bytes, L.rank, P)) return NBODY_ERR_STATE;
+    return NBODY_OK;
+  }
+  if (!L.comm_h) return NBODY_ERR_STATE;
+  NCCLC(g_rccl.AllGather((char*)dev_words + L.rank * wb, dev_words, wb, ncclChar, L.comm_h, L.compute));
+  HIPC(hipStreamSynchronize(L.compute));
+  HIPC(hipMemcpy(host_words, dev_words, (size_t)P * wb, hipMemcpyDeviceToHost));
+  return NBODY_OK;
+}
+
 }  // namespace nbi
 
 using namespace nbi;

@@ -486,6 +486,9 @@ void free_local(Local& L) {
   if (L.force) (void)hipFree(L.force);
   if (L.tickets) (void)hipFree(L.tickets);
   if (L.full_scratch) (void)hipFree(L.full_scratch);
+  if (L.en_part) (void)hipFree(L.en_part);
+  if (L.en_tot) (void)hipFree(L.en_tot);
+  if (L.en_phi) (void)hipFree(L.en_phi);
   if (L.ev_own_ready) (void)hipEventDestroy(L.ev_own_ready);
   if (L.ev_comm_go) (void)hipEventDestroy(L.ev_comm_go);
   for (int s = 0; s < kMaxRanks; ++s) if (L.ev_gather[s]) (void)hipEventDestroy(L.ev_gather[s]);

@@ -1,0 +1,115 @@
+// energy.cpp — nbody_energy and nbody_potential_rows(_d): the energy pass (energy.hip) over the state on the device.  Host C++ only.
+// Flow: reconfigure(), complete_positions() (the other slices, as nbody_forces_rows brings them), one pass per local on its compute
+// stream, then the ranks' eight fp64 values added in rank order.  Processes exchange those values through the transport they use for
+// positions (allgather_rank_words), never a reduction, so every rank adds the same numbers in the same order.
+// The pass reads pos[cur] and vel and writes only the Local's en_* buffers: positions, velocities, arrival counters, partial forces,
+// the captured step graph and the force-kernel timer stay as they were.
+#include "nbody_internal.hpp"
+#include "energy_args.hpp"
+
+using namespace nbe;
+
+namespace nbi {
+
+namespace {
+
+int ensure_energy_buffers(Local& L) {
+  HIPC(hipSetDevice(L.device));
+  const size_t groups = ((size_t)L.n_local + kEnergyRows - 1) / kEnergyRows;
+  if (!L.en_part) HIPC(hipMalloc((void**)&L.en_part, (groups + 1) * kEnergyWords * sizeof(double)));
+  if (!L.en_tot) HIPC(hipMalloc((void**)&L.en_tot, (size_t)g.nranks * kEnergyWords * sizeof(double)));
+  if (!L.en_phi) HIPC(hipMalloc(&L.en_phi, ((size_t)L.n_local + 1) * sizeof(double)));
+  return NBODY_OK;
+}
+
+// rows [row0, row0 + row_count) of local L: phi into en_phi (totals = false) or the per-workgroup partials into en_part and their
+// sum into word `rank` of en_tot (totals = true)
+int launch_energy(Local& L, int row0, int row_count, bool totals) {
+  NBC(ensure_energy_buffers(L));
+  EnergyArgs a;
+  memset(&a, 0, sizeof(a));
+  a.src = L.pos[L.cur];
+  a.vel = totals ? L.vel : nullptr;
+  a.phi = totals ? nullptr : L.en_phi;
+  a.part = totals ? L.en_part : nullptr;
+  a.n_src = g.n;
+  a.first = L.first;
+  a.row0 = row0;
+  a.row_count = row_count;
+  HIPC((hipError_t)nbl::launch_energy_kernel(g.fp64, g.opt.arith, L.compute, a));
+  if (totals) {
+    const int groups = (row_count + kEnergyRows - 1) / kEnergyRows;
+    HIPC((hipError_t)nbl::launch_energy_reduce_kernel(L.compute, L.en_part, groups, L.en_tot + (size_t)L.rank * kEnergyWords));
+  }
+  return NBODY_OK;
+}
+
+int energy_impl(double* out) {
+  if (!g.init) return NBODY_ERR_NOT_INIT;
+  if (!out) return NBODY_ERR_ARG;
+  NBC(reconfigure());
+  NBC(complete_positions());
+  for (int l = 0; l < g.nlocal; ++l) NBC(launch_energy(g.loc[l], 0, g.loc[l].n_local, true));
+  std::vector<double> all((size_t)g.nranks * kEnergyWords, 0.0);
+  if (g.multiprocess && g.nranks > 1) {
+    Local& L = g.loc[0];
+    NBC(allgather_rank_words(L, L.en_tot, all.data(), kEnergyWords * (int)sizeof(double)));
+  } else {
+    for (int l = 0; l < g.nlocal; ++l) {
+      Local& L = g.loc[l];
+      HIPC(hipSetDevice(L.device));
+      const size_t off = (size_t)L.rank * kEnergyWords;
+      HIPC(hipStreamSynchronize(L.compute));   // then a blocking copy into the caller's pageable memory, as the other entry points do
+      HIPC(hipMemcpy(all.data() + off, L.en_tot + off, kEnergyWords * sizeof(double), hipMemcpyDeviceToHost));
+    }
+  }
+  for (int q = 0; q < kEnergyWords; ++q) {
+    double s = 0.0;
+    for (int r = 0; r < g.nranks; ++r) s += all[(size_t)r * kEnergyWords + q];   // rank order
+    out[q] = s;
+  }
+  return NBODY_OK;
+}
+
+// rows as in nbody_forces_rows: nbody_init contexts the GLOBAL index (the range may span devices), nbody_init_rank contexts the row
+// of this rank's own slice
+int potential_rows_impl(int first_row, int n_rows, void* phi) {
+  if (!g.init) return NBODY_ERR_NOT_INIT;
+  if (!phi) return NBODY_ERR_ARG;
+  const int base = g.multiprocess ? g.loc[0].first : 0;
+  const int limit = g.multiprocess ? g.loc[0].n_local : g.n;
+  if (first_row < 0 || n_rows <= 0 || first_row > limit - n_rows) return NBODY_ERR_ARG;
+  const int g0 = base + first_row;
+  NBC(reconfigure());
+  NBC(complete_positions());
+  const size_t es = g.fp64 ? sizeof(double) : sizeof(float);
+  for (int l = 0; l < g.nlocal; ++l) {
+    Local& L = g.loc[l];
+    const int b = std::max(g0, L.first), e = std::min(g0 + n_rows, L.first + L.n_local);
+    if (e <= b) continue;
+    NBC(launch_energy(L, b - L.first, e - b, false));
+    HIPC(hipStreamSynchronize(L.compute));
+    HIPC(hipMemcpy((char*)phi + (size_t)(b - g0) * es, L.en_phi, (size_t)(e - b) * es, hipMemcpyDeviceToHost));
+  }
+  return NBODY_OK;
+}
+
+}  // namespace
+
+}  // namespace nbi
+
+using namespace nbi;
+
+extern "C" {
+
+int nbody_energy(double* out) { NB_REFUSE_WHILE_SERVED(); return energy_impl(out); }
+int nbody_potential_rows(int first_row, int n_rows, float* phi) { NB_REFUSE_WHILE_SERVED();
+  if (g.init && g.fp64) return NBODY_ERR_STATE;
+  return potential_rows_impl(first_row, n_rows, phi);
+}
+int nbody_potential_rows_d(int first_row, int n_rows, double* phi) { NB_REFUSE_WHILE_SERVED();
+  if (g.init && !g.fp64) return NBODY_ERR_STATE;
+  return potential_rows_impl(first_row, n_rows, phi);
+}
+
+}  // extern "C"

@@ -3,7 +3,10 @@
 //   context.cpp   the context: options, launch configuration, buffers, the step and its HIP graph, state transfer, the strict gate
 //   comm.cpp      RCCL (resolved with dlopen), the transfer plans, the all-gather of a step, probes and self-tests
 //   mailbox.cpp   the reference's mailbox: RAM images, one request, the service thread
-// Only kernels.hip is device code (a minute of hipcc); the other three are host C++ (seconds).  gfx950 only, no CPU fallback anywhere.
+//   energy.hip    the energy pass's kernels (energy_args.hpp: its argument block and launch functions)
+//   energy.cpp    nbody_energy, nbody_potential_rows(_d): the energy pass on every local and the sum over the ranks
+// Only kernels.hip and energy.hip are device code (a minute of hipcc, as one code object through device.hip); the others are host
+// C++ (seconds).  gfx950 only, no CPU fallback anywhere.
 //
 // Data layout in HBM (per rank; N bodies in total, the rank owns n_local of them starting at first_body):
 //   pos[2]   2 x N words      full position set, double-buffered: a step reads pos[cur] and writes the
@@ -71,6 +74,9 @@ struct Local {
   const void* src_direct = nullptr;    // a mailbox request of a handful of bodies: sources and rows read from RAM A itself (no ingest launch) ...
   unsigned long long* t0_stamp = nullptr;   // ... and the launch's first wave stamps the tick count's start here (ForceArgs::t0_stamp)
   void* full_scratch = nullptr;        // N words: all-gather of a sharded array for the host (multi-process)
+  double* en_part = nullptr;           // energy pass (energy.cpp): per-workgroup fp64 partials of {T, U, P, L} ...
+  double* en_tot = nullptr;            // ... the ranks' totals, 8 doubles at word `rank` (all P after an all-gather) ...
+  void* en_phi = nullptr;              // ... and phi of the rows asked for (context precision)
   int cur = 0;
   bool all_present = true;             // pos[cur] holds every slice
   hipEvent_t ev_own_ready = nullptr;   // the rank's slice of pos[cur] is written
@@ -156,6 +162,8 @@ void comm_destroy(Local& L);
 int resolved_comm_form();
 int enqueue_gather(int buf);                                    // bring the other ranks' slices of pos[buf] to every local
 int gather_sharded_multiprocess(Local& L, const void* own_rows);   // a rank-sharded array into L.full_scratch
+// word `rank` of dev_words (word_bytes each, written on the compute stream) of every rank into host_words[0 .. P) on every rank
+int allgather_rank_words(Local& L, void* dev_words, void* host_words, int word_bytes);
 
 // ---- mailbox.cpp ----
 void mailbox_shutdown();          // stops the service thread, frees the RAM images

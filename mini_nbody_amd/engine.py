@@ -129,6 +129,25 @@ class NBody:
             L.check(self.lib.nbody_forces_rows(int(first_row), int(n_rows), out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
+    def energy(self):
+        """Energy and momenta of the state on the device (nbody_energy; unit masses, G = 1, the force's softening): dict(kinetic,
+        potential, total, momentum=(3,), angular_momentum=(3,)), fp64.  Collective in a multi-rank job; every rank gets the same bits."""
+        out = np.zeros(L.ENERGY_WORDS, np.float64)
+        L.check(self.lib.nbody_energy(out.ctypes.data_as(C.POINTER(C.c_double))))
+        t, u = float(out[L.ENERGY_KINETIC]), float(out[L.ENERGY_POTENTIAL])
+        return dict(kinetic=t, potential=u, total=t + u, momentum=out[L.ENERGY_PX:L.ENERGY_PZ + 1].copy(),
+                    angular_momentum=out[L.ENERGY_LX:L.ENERGY_LZ + 1].copy())
+
+    def potential_rows(self, first_row, n_rows):
+        """phi_i = -sum_{j != i} (|r_j - r_i|^2 + eps)^(-1/2) of n_rows bodies from first_row (rows as in forces_rows), in the
+        context precision, from the state on the device (nbody_potential_rows)."""
+        out = np.empty(int(n_rows), self.dtype)
+        if self.fp64:
+            L.check(self.lib.nbody_potential_rows_d(int(first_row), int(n_rows), out.ctypes.data_as(C.POINTER(C.c_double))))
+        else:
+            L.check(self.lib.nbody_potential_rows(int(first_row), int(n_rows), out.ctypes.data_as(C.POINTER(C.c_float))))
+        return out
+
     def comm_selftest(self):
         """Push a patterned array through the RCCL calls of the multi-GPU path (all-gather + one ring step); returns
         the bytes this rank received.  Needs the communicator of NBody(..., rank=, nranks=, uid=)."""

@@ -8,8 +8,12 @@
  *
  * usage: nbody [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K]
  *              [--sum seq|blocked] [--block K] [--one-launch | --two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16]
+ *              [--energy]
+ * --energy: E = T + U, T and U of the state on the device (nbody_energy) before the first iteration and after the last, and the
+ * relative drift, outside the timed region.
  */
 #define _POSIX_C_SOURCE 199309L
+#include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -26,8 +30,24 @@ static double now_s(void) {
 
 #define CHECK(call) do { int rc_ = (call); if (rc_) { fprintf(stderr, "%s failed: %s\n", #call, nbody_error_string(rc_)); return 1; } } while (0)
 
+/* one line of --energy: E, T and U of the state on the device after `step` iterations; *e0 is set on the first call */
+static int print_energy(int step, double *e0, int first) {
+  double w[NBODY_ENERGY_WORDS];
+  int rc = nbody_energy(w);
+  if (rc) { fprintf(stderr, "nbody_energy failed: %s\n", nbody_error_string(rc)); return 1; }
+  const double t = w[NBODY_ENERGY_KINETIC], u = w[NBODY_ENERGY_POTENTIAL], e = t + u;
+  if (first) {
+    *e0 = e;
+    printf("energy at step %d: E %.17g T %.17g U %.17g\n", step, e, t, u);
+  } else {
+    printf("energy at step %d: E %.17g T %.17g U %.17g relative drift %.3e\n", step, e, t, u, (e - *e0) / (*e0 != 0.0 ? fabs(*e0) : 1.0));
+  }
+  return 0;
+}
+
 int main(int argc, char **argv) {
-  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0;
+  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0;
+  double e0 = 0.0;
   unsigned long long seed = NBODY_IC_DEFAULT_SEED;
   for (int a = 1; a < argc; ++a) {
     if (!strcmp(argv[a], "--gpus") && a + 1 < argc) gpus = atoi(argv[++a]);
@@ -38,6 +58,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--host-loop")) host_loop = 1;
     else if (!strcmp(argv[a], "--strict")) strict = 1;
     else if (!strcmp(argv[a], "--rtl")) rtl = 1;
+    else if (!strcmp(argv[a], "--energy")) energy = 1;
     else if (!strcmp(argv[a], "--two-launch")) two_launch = 1;
     else if (!strcmp(argv[a], "--one-launch")) two_launch = 0;
     else if (!strcmp(argv[a], "--overlap") && a + 1 < argc) overlap = atoi(argv[++a]);
@@ -47,7 +68,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--block") && a + 1 < argc) block = atoi(argv[++a]);
     else if (argv[a][0] != '-' && npos == 0) { n = atoi(argv[a]); npos++; }
     else if (argv[a][0] != '-' && npos == 1) { iters = atoi(argv[a]); npos++; }
-    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16]\n", argv[0]); return 2; }
+    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy]\n", argv[0]); return 2; }
   }
   if (n <= 0 || iters < 2) { fprintf(stderr, "need N > 0 and iters >= 2 (iteration 1 is warm-up)\n"); return 2; }
   const float dt = 0.01f;
@@ -78,6 +99,7 @@ int main(int argc, char **argv) {
     if (!buf) return 3;
     BodySystem p = { buf, buf + words };
     nbody_ic_fill_f32(p.pos, p.vel, (size_t)n, 0, (size_t)n, seed);
+    if (energy) { CHECK(nbody_upload(&p)); if (print_energy(0, &e0, 1)) return 1; }
     if (host_loop) {
       for (int it = 1; it <= iters; ++it) {
         double t0 = now_s();
@@ -96,6 +118,7 @@ int main(int argc, char **argv) {
       total = now_s() - t0;
       CHECK(nbody_download(&p));
     }
+    if (energy) { if (host_loop) CHECK(nbody_upload(&p)); if (print_energy(iters, &e0, 0)) return 1; }
     double cx = 0, cy = 0, cz = 0;
     for (int i = 0; i < n; ++i) { cx += p.pos[4 * i]; cy += p.pos[4 * i + 1]; cz += p.pos[4 * i + 2]; }
     printf("checksum (sum of positions): %.9g %.9g %.9g\n", cx, cy, cz);
@@ -105,6 +128,7 @@ int main(int argc, char **argv) {
     if (!buf) return 3;
     BodySystemD p = { buf, buf + words };
     nbody_ic_fill_f64(p.pos, p.vel, (size_t)n, 0, (size_t)n, seed);
+    if (energy) { CHECK(nbody_upload_d(&p)); if (print_energy(0, &e0, 1)) return 1; }
     if (host_loop) {
       for (int it = 1; it <= iters; ++it) {
         double t0 = now_s();
@@ -123,6 +147,7 @@ int main(int argc, char **argv) {
       total = now_s() - t0;
       CHECK(nbody_download_d(&p));
     }
+    if (energy) { if (host_loop) CHECK(nbody_upload_d(&p)); if (print_energy(iters, &e0, 0)) return 1; }
     double cx = 0, cy = 0, cz = 0;
     for (int i = 0; i < n; ++i) { cx += p.pos[4 * i]; cy += p.pos[4 * i + 1]; cz += p.pos[4 * i + 2]; }
     printf("checksum (sum of positions): %.17g %.17g %.17g\n", cx, cy, cz);

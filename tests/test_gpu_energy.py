@@ -1,0 +1,330 @@
+"""Energy, momentum and per-body potential of the state on the device (nbody_energy, nbody_potential_rows(_d); include/nbody.h
+"energy and potential"): phi_i bit for bit against tests/potential_ref.c in the strict modes, within the north_star tolerance in the
+timed arithmetic, the same bits however the context is configured or sharded, totals against an fp64 evaluation of the downloaded
+state, no effect on the step, the physics of a circular orbit, the mailbox guard and the C host program's --energy lines."""
+import ctypes as C
+import os
+import re
+import socket
+import subprocess
+import sys
+import textwrap
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EPS = float(np.array([0x3089705F], np.uint32).view(np.float32)[0])
+
+
+class Ref:
+    """tests/potential_ref.c: phi in the documented order, IEEE 1/sqrt"""
+
+    def __init__(self, lib):
+        self.lib = lib
+
+    def phi32(self, pos, r0=0, nr=None, ref=False):
+        pos = np.ascontiguousarray(pos, np.float32)
+        nr = len(pos) - r0 if nr is None else nr
+        out = np.empty(nr, np.float32)
+        self.lib.potential_f32(pos.ctypes.data_as(C.c_void_p), len(pos), r0, nr, int(ref), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def phi64(self, pos, r0=0, nr=None):
+        pos = np.ascontiguousarray(pos, np.float64)
+        nr = len(pos) - r0 if nr is None else nr
+        out = np.empty(nr, np.float64)
+        self.lib.potential_f64(pos.ctypes.data_as(C.c_void_p), len(pos), r0, nr, out.ctypes.data_as(C.c_void_p))
+        return out
+
+
+@pytest.fixture(scope="module")
+def ref(tmp_path_factory):
+    so = str(tmp_path_factory.mktemp("potential_ref") / "potential_ref.so")
+    src = os.path.join(ROOT, "tests", "potential_ref.c")
+    for extra in (["-march=native", "-fopenmp"], ["-fopenmp"], []):   # every operation is IEEE-exact: vector width and threads change no bit
+        r = subprocess.run(["gcc", "-std=c11", "-O3", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math"] + extra + ["-o", so, src, "-lm"],
+                           capture_output=True, timeout=180)
+        if r.returncode == 0:
+            return Ref(C.CDLL(so))
+    pytest.fail("cannot compile tests/potential_ref.c: " + r.stderr.decode()[-2000:])
+
+
+def fp64_totals(ref, pos, vel):
+    """T, U, P, L of a downloaded state in fp64, and the scales |P| and |L| are relative to (sums of magnitudes)"""
+    p, v = pos[:, :3].astype(np.float64), vel[:, :3].astype(np.float64)
+    lv = np.cross(p, v)
+    u = 0.5 * ref.phi64(pos.astype(np.float64)).sum()
+    return dict(kinetic=0.5 * (v ** 2).sum(), potential=u, momentum=v.sum(0), angular_momentum=lv.sum(0),
+                p_scale=np.linalg.norm(v, axis=1).sum(), l_scale=np.linalg.norm(lv, axis=1).sum())
+
+
+def bits(e):
+    return np.array([e["kinetic"], e["potential"], *e["momentum"], *e["angular_momentum"]]).view(np.uint64)
+
+
+@pytest.mark.parametrize("arith", ["strict", "reference_strict"])
+def test_strict_fp32_rows_bit_for_bit(nb, ref, arith):
+    mode = {"strict": nb.ARITH_STRICT, "reference_strict": nb.ARITH_REFERENCE_STRICT}[arith]
+    for n in (1, 2, 63, 64, 65, 1000, 1025, 4099, 20000):
+        pos, vel = nb.make_bodies(n)
+        with nb.NBody(n) as eng:
+            eng.set_option(nb.OPT_ARITH, mode)
+            eng.upload(pos, vel)
+            got = eng.potential_rows(0, n)
+            want = ref.phi32(pos, ref=(mode == nb.ARITH_REFERENCE_STRICT))
+            assert np.array_equal(got.view(np.uint32), want.view(np.uint32)), (n, int((got != want).sum()))
+            if n == 1:
+                e = eng.energy()
+                assert got.view(np.uint32)[0] == 0 and e["potential"] == 0.0 and np.float64(e["potential"]).view(np.uint64) == 0
+
+
+def test_fp64_rows(nb, ref):
+    for n in (2, 1025, 4099):
+        pos, vel = nb.make_bodies(n, dtype=np.float64)
+        want = ref.phi64(pos)
+        with nb.NBody(n, fp64=True) as eng:
+            eng.upload(pos, vel)
+            fast = eng.potential_rows(0, n)
+            assert np.max(np.abs(fast - want) / np.abs(want)) < 1e-12, n
+            eng.set_option(nb.OPT_ARITH, nb.ARITH_STRICT)
+            strict = eng.potential_rows(0, n)
+            assert np.array_equal(strict.view(np.uint64), want.view(np.uint64)), (n, int((strict != want).sum()))
+
+
+def test_fast_fp32_rows_within_north_star_tolerance(nb, ref):
+    n = 65536
+    pos, vel = nb.make_bodies(n)
+    with nb.NBody(n) as eng:
+        eng.upload(pos, vel)
+        got = eng.potential_rows(0, n)
+    want = ref.phi64(pos.astype(np.float64))
+    assert np.max(np.abs(got - want) / np.abs(want)) < 1e-5
+    n = 1 << 20
+    pos, vel = nb.make_bodies(n)
+    with nb.NBody(n) as eng:
+        eng.upload(pos, vel)
+        p64 = pos.astype(np.float64)
+        for r0, cnt in ((0, 256), (n - 256, 256), (512 * 1024 - 100, 200)):    # first, last, across the block edge at 2^19
+            got = eng.potential_rows(r0, cnt)
+            want = ref.phi64(p64, r0, cnt)
+            assert np.max(np.abs(got - want) / np.abs(want)) < 1e-5, r0
+
+
+@pytest.mark.parametrize("fp64", [False, True])
+def test_totals_against_fp64(nb, ref, fp64):
+    n = 3000
+    dtype = np.float64 if fp64 else np.float32
+    pos, vel = nb.make_bodies(n, dtype=dtype)
+    with nb.NBody(n, fp64=fp64) as eng:
+        eng.upload(pos, vel)
+        done = 0
+        for steps in (0, 10, 100):
+            eng.step(0.01, steps - done)
+            done = steps
+            e = eng.energy()
+            assert np.array_equal(bits(e), bits(eng.energy())), "two calls differ"
+            p, v = eng.download()
+            w = fp64_totals(ref, p, v)
+            assert abs(e["kinetic"] - w["kinetic"]) <= 1e-12 * w["kinetic"], steps
+            assert abs(e["potential"] - w["potential"]) <= (1e-12 if fp64 else 1e-6) * abs(w["potential"]), steps
+            assert e["total"] == e["kinetic"] + e["potential"]
+            assert np.all(np.abs(e["momentum"] - w["momentum"]) <= 1e-12 * w["p_scale"]), steps
+            assert np.all(np.abs(e["angular_momentum"] - w["angular_momentum"]) <= 1e-12 * w["l_scale"]), steps
+
+
+def test_phi_bits_do_not_depend_on_the_force_configuration(nb):
+    n = 5000
+    pos, vel = nb.make_bodies(n)
+    with nb.NBody(n) as eng:
+        eng.upload(pos, vel)
+        base, ebase = eng.potential_rows(0, n), bits(eng.energy())
+        for key, val, default in ((nb.OPT_VARIANT, nb.VARIANT_SMEM, nb.VARIANT_AUTO), (nb.OPT_VARIANT, nb.VARIANT_LDS, nb.VARIANT_AUTO),
+                                  (nb.OPT_VARIANT, nb.VARIANT_READLANE, nb.VARIANT_AUTO), (nb.OPT_JSUB, 3, 0), (nb.OPT_JSLICES, 3, 0),
+                                  (nb.OPT_WSPLIT, 1, -1), (nb.OPT_WSPLIT, 16, -1), (nb.OPT_SUM_ORDER, nb.SUM_SEQ, nb.SUM_BLOCKED),
+                                  (nb.OPT_SUM_ORDER, nb.SUM_FPGA16, nb.SUM_BLOCKED)):
+            eng.set_option(key, val)
+            got = eng.potential_rows(0, n)
+            assert np.array_equal(got.view(np.uint32), base.view(np.uint32)), (key, val)
+            assert np.array_equal(bits(eng.energy()), ebase), (key, val)
+            eng.set_option(key, default)
+
+
+def test_phi_bits_do_not_depend_on_the_device_count(nb, monkeypatch):
+    monkeypatch.setenv("NBODY_OVERSUBSCRIBE", "1")
+    n = 3001
+    pos, vel = nb.make_bodies(n)
+    res = {}
+    for ngpus in (1, 3, 8):
+        with nb.NBody(n, ngpus=ngpus) as eng:
+            eng.upload(pos, vel)
+            # after a drift on the device each local holds only its own slice's new positions: the pass brings the rest first.  (A
+            # drift, not a step: r += v dt is per body, a step's force sums follow the slicing.)
+            eng.integrate(pos.copy(), vel.copy(), 0.01)
+            res[ngpus] = (eng.potential_rows(0, n), eng.potential_rows(900, 300), eng.energy())
+    phi1, win1, e1 = res[1]
+    assert np.array_equal(win1.view(np.uint32), phi1[900:1200].view(np.uint32))
+    for ngpus in (3, 8):
+        phi, win, e = res[ngpus]
+        assert np.array_equal(phi.view(np.uint32), phi1.view(np.uint32)), ngpus
+        assert np.array_equal(win.view(np.uint32), phi1[900:1200].view(np.uint32)), ngpus
+        for k in ("kinetic", "potential"):
+            assert abs(e[k] - e1[k]) <= 1e-12 * abs(e1[k]), (ngpus, k)
+        for k in ("momentum", "angular_momentum"):
+            assert np.all(np.abs(e[k] - e1[k]) <= 1e-12 * np.abs(e1[k]).sum()), (ngpus, k)
+
+
+WORKER = textwrap.dedent("""
+    import os, sys
+    import numpy as np
+    sys.path.insert(0, {root!r})
+    import torch
+    import mini_nbody_amd as nb
+    import mini_nbody_amd.distributed as D
+    rank, world, local = D.init_process_group("gloo")
+    n = {n}
+    eng = D.make_engine(n, transport="host")
+    eng.set_option(nb.OPT_JSUB, 2)
+    pos, vel = nb.make_bodies(n, seed=33)
+    eng.upload(pos, vel)
+    eng.step(0.01, 3)
+    e = eng.energy()
+    phi = eng.potential_rows(0, eng.config["n_local"])
+    p, v = eng.download()
+    w = np.array([e["kinetic"], e["potential"], *e["momentum"], *e["angular_momentum"]])
+    np.save({out!r} + "_%d_energy.npy" % rank, w)
+    np.save({out!r} + "_%d_phi.npy" % rank, phi)
+    if rank == 0:
+        np.save({out!r} + "_pos.npy", p)
+        open({out!r} + "_wsplit.txt", "w").write(str(eng.config["wsplit"]))
+    eng.close()
+    import torch.distributed as dist
+    dist.barrier(); dist.destroy_process_group()
+""")
+
+
+def test_two_processes_host_transport_equal_one_process(nb, tmp_path, monkeypatch):
+    n, world = 6007, 2
+    out = str(tmp_path / "en")
+    script = tmp_path / "worker.py"
+    script.write_text(WORKER.format(root=ROOT, n=n, out=out))
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    procs = []
+    for r in range(world):
+        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
+                   MASTER_PORT=str(port), NBODY_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
+        procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
+    for p in procs:
+        o, _ = p.communicate(timeout=300)
+        assert p.returncode == 0, o.decode()[-3000:]
+    monkeypatch.setenv("NBODY_OVERSUBSCRIBE", "1")
+    pos, vel = nb.make_bodies(n, seed=33)
+    with nb.NBody(n, ngpus=world) as one:
+        one.set_option(nb.OPT_JSUB, 2)
+        one.set_option(nb.OPT_WSPLIT, int(open(out + "_wsplit.txt").read()))
+        one.upload(pos, vel)
+        one.step(0.01, 3)
+        e = one.energy()
+        phi = one.potential_rows(0, n)
+        wp, _ = one.download()
+    assert np.array_equal(np.load(out + "_pos.npy").view(np.uint32), wp.view(np.uint32)), "the two runs' states differ"
+    want = np.array([e["kinetic"], e["potential"], *e["momentum"], *e["angular_momentum"]])
+    for r in range(world):
+        assert np.array_equal(np.load(out + "_%d_energy.npy" % r).view(np.uint64), want.view(np.uint64)), r
+    got_phi = np.concatenate([np.load(out + "_%d_phi.npy" % r) for r in range(world)])
+    assert np.array_equal(got_phi.view(np.uint32), phi.view(np.uint32))
+
+
+def run_steps(nb, n, pos, vel, plan, graph, probe, timing=False):
+    with nb.NBody(n) as eng:
+        eng.set_option(nb.OPT_GRAPH, graph)
+        if timing:
+            eng.set_option(nb.OPT_TIMING, 1)
+        eng.upload(pos, vel)
+        for k in plan:
+            eng.step(0.01, k)
+            if probe:
+                eng.energy()
+                eng.potential_rows(0, n)
+                eng.potential_rows(n // 3, 7)
+        p, v = eng.download()
+        launches = eng.kernel_time()[1] if timing else None
+    return p, v, launches
+
+
+def test_energy_calls_leave_the_step_untouched(nb):
+    n = 1500
+    pos, vel = nb.make_bodies(n)
+    for plan, graph, timing in (([1] * 12, 0, False), ([64, 64, 6, 64], 1, False), ([3, 5, 2], 0, True)):
+        a = run_steps(nb, n, pos, vel, plan, graph, False, timing)
+        b = run_steps(nb, n, pos, vel, plan, graph, True, timing)
+        assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)), (plan, graph)
+        assert np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)), (plan, graph)
+        assert a[2] == b[2], "energy launches were counted by nbody_kernel_time"
+
+
+def test_circular_two_body_orbit(nb):
+    """Separation 1, unit masses: the force is (1 + eps)^(-3/2), v^2 / (1/2) = F, E_0 = v^2 - (1 + eps)^(-1/2); symplectic Euler
+    keeps the energy error bounded (no secular drift) and the momentum at zero."""
+    f = (1.0 + EPS) ** -1.5
+    v = np.sqrt(0.5 * f)
+    period = 2 * np.pi * 0.5 / v
+    dt, steps = period / 1000, 2000
+    pos = np.array([[-0.5, 0, 0, 0], [0.5, 0, 0, 0]], np.float64)
+    vel = np.array([[0, -v, 0, 0], [0, v, 0, 0]], np.float64)
+    e0_analytic = v * v - (1.0 + EPS) ** -0.5
+    with nb.NBody(2, fp64=True) as eng:
+        eng.upload(pos, vel)
+        e = eng.energy()
+        assert abs(e["total"] - e0_analytic) <= 1e-12 * abs(e0_analytic)
+        de, pmax = [], 0.0
+        for _ in range(steps):
+            eng.step(dt, 1)
+            e = eng.energy()
+            de.append(abs(e["total"] - e0_analytic))
+            pmax = max(pmax, float(np.abs(e["momentum"]).max()))
+    first, second = max(de[:steps // 2]), max(de[steps // 2:])
+    assert 0 < first and second <= 1.5 * first, (first, second)
+    assert pmax <= 1e-12
+
+
+def test_entry_points_refused_while_the_mailbox_is_served(nb):
+    lib = nb._lib.load()
+    out = np.zeros(8, np.float64)
+    phi32, phi64 = np.zeros(4, np.float32), np.zeros(4, np.float64)
+    calls = (lambda: lib.nbody_energy(out.ctypes.data_as(C.POINTER(C.c_double))),
+             lambda: lib.nbody_potential_rows(0, 4, phi32.ctypes.data_as(C.POINTER(C.c_float))),
+             lambda: lib.nbody_potential_rows_d(0, 4, phi64.ctypes.data_as(C.POINTER(C.c_double))))
+    with nb.Mailbox(capacity=1024, faithful=False) as mb:
+        mb.serve(True, clock_khz=300000)
+        try:
+            assert [c() for c in calls] == [nb._lib.ERR_STATE] * 3
+        finally:
+            mb.serve(False)
+        assert [c() for c in calls] == [0, 0, nb._lib.ERR_STATE]       # served no more: an fp32 context again
+
+
+def test_c_host_program_energy_lines(nb):
+    exe = os.path.join(ROOT, "build", "nbody")
+    n, iters = 4096, 3
+    r = subprocess.run([exe, str(n), str(iters), "--energy"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = re.findall(r"energy at step (\d+): E (\S+) T (\S+) U (\S+)", r.stdout)
+    assert [int(l[0]) for l in lines] == [0, iters], r.stdout
+    assert re.search(r"energy at step %d: .* relative drift \S+" % iters, r.stdout)
+    plain = subprocess.run([exe, str(n), str(iters)], capture_output=True, text=True, timeout=300)
+    assert plain.returncode == 0 and "energy" not in plain.stdout
+    pos, vel = nb.make_bodies(n)
+    with nb.NBody(n) as eng:
+        eng.upload(pos, vel)
+        want = [eng.energy()]
+        eng.step(0.01, iters)
+        want.append(eng.energy())
+    for line, w in zip(lines, want):
+        e, t, u = (float(x) for x in line[1:])
+        for got, ref_ in ((e, w["total"]), (t, w["kinetic"]), (u, w["potential"])):
+            assert abs(got - ref_) <= 1e-6 * abs(ref_), (line, w)

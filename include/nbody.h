@@ -272,8 +272,10 @@ int nbody_forces_rows_d(int first_row, int n_rows, double *force_words);
  *   polls memory.  (NUM_PTS = 0, a refused request, a context over several ranks: the host writes word 0, ticks from its own clock.)
  *   Returns NBODY_ERR_STATE if BEGIN is not set (the FSM stays in `waiting`: nothing read, nothing written), NBODY_ERR_ARG if NUM_PTS
  *   exceeds the capacity (the RTL has no such case: its RAM always holds 32767 bodies).
- *   The context's N, options, uploaded state's size and step graph are as before on return (its position buffer is overwritten, as by
- *   nbody_forces).  A context over several devices or ranks keeps its fixed N (NUM_PTS must equal it).
+ *   The context's N, options, uploaded state's size and step graph are as before on return.  Its position buffer is overwritten, as by
+ *   nbody_forces, except by a request that reads RAM A in place and leaves the buffer as it was: the faithful mode with the device's
+ *   completion and NUM_PTS <= NBODY_MAILBOX_DIRECT_MAX (environment; 256 by default).  A context over several devices or ranks keeps its
+ *   fixed N (NUM_PTS must equal it).
  * nbody_mailbox_serve(on, clock_khz): the mailbox WITHOUT a call per request.  on = 1: a library thread takes the place of the PL block's
  *   FSM — it samples word 0 of the context's own RAM A (nbody_mailbox_rams) as the RTL does every clock (S/top_level.vhd:180-186) and runs
  *   each request it finds exactly as nbody_mailbox_run would; the device rewrites word 0 (ticks in bits 63:32, BEGIN cleared LAST, so

@@ -60,6 +60,11 @@ void comm_destroy(Local& L) {
 
 namespace {
 
+int ensure_full_scratch(Local& L) {   // L.full_scratch: N words (+ slack), allocated on the current device (L's) at first use
+  if (!L.full_scratch) HIPC(hipMalloc(&L.full_scratch, (size_t)(g.n + 64) * word_bytes()));
+  return NBODY_OK;
+}
+
 // Host-staged all-gather of one sharded device array (words [first, first+count) are this rank's): D2H own part,
 // callback (the host framework's all-gather fills the rest of g.host_stage), H2D everything else on the comm stream.
 int host_exchange(Local& L, void* dev_full, int first, int count, bool wait_own_ready) {
@@ -236,7 +241,7 @@ int enqueue_gather(int buf) {
 int gather_sharded_multiprocess(Local& L, const void* own_rows) {
   const size_t wb = word_bytes();
   HIPC(hipSetDevice(L.device));
-  if (!L.full_scratch) HIPC(hipMalloc(&L.full_scratch, (size_t)(g.n + 64) * wb));
+  NBC(ensure_full_scratch(L));
   HIPC(hipMemcpyAsync(word_ptr(L.full_scratch, L.first), own_rows, (size_t)L.n_local * wb, hipMemcpyDeviceToDevice, L.comm));
   if (g.host_gather) {
     HIPC(hipStreamSynchronize(L.comm));
@@ -300,7 +305,7 @@ int nbody_comm_selftest(long long* bytes_moved) { NB_REFUSE_WHILE_SERVED();
   const size_t wb = word_bytes();
   const int P = g.nranks;
   HIPC(hipSetDevice(L.device));
-  if (!L.full_scratch) HIPC(hipMalloc(&L.full_scratch, (size_t)(g.n + 64) * wb));
+  NBC(ensure_full_scratch(L));
   // (1) all-gather: word w of rank q's slice = q * 2^24 + (w mod 2^24), in every 4-byte lane of the word
   std::vector<uint32_t> host((size_t)g.n * (wb / 4));
   HIPC(hipMemset(L.full_scratch, 0xff, (size_t)g.n * wb));
@@ -437,15 +442,16 @@ int nbody_comm_probe(long long bytes, int when, double* comm_ms, double* force_m
   NBC(complete_positions());
   NBC(sync_all());
   HIPC(hipSetDevice(L.device));
-  if (!L.full_scratch) HIPC(hipMalloc(&L.full_scratch, (size_t)(g.n + 64) * wb));
+  NBC(ensure_full_scratch(L));
   struct Evs { hipEvent_t e[6] = {}; ~Evs() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } ev;
   for (hipEvent_t& x : ev.e) HIPC(hipEventCreate(&x));
   const Finish fin = {false, false, true};
   auto force_pass = [&](hipEvent_t begin, hipEvent_t end) -> int {
     if (begin) HIPC(hipEventRecord(begin, L.compute));
-    int rc = launch_force(L, 0, L.n_local, g.nslices - 1, g.nslices, fin, 0.f, 0.0);
-    if (!rc) rc = launch_combine(L, 0, L.n_local, fin, 0.f, 0.0);
-    if (rc) { g.tickets_dirty = true; return rc; }
+    TicketGuard guard;
+    NBC(launch_force(L, 0, L.n_local, g.cfg.nslices - 1, g.cfg.nslices, fin, 0.f, 0.0));
+    NBC(launch_combine(L, 0, L.n_local, fin, 0.f, 0.0));
+    guard.done();
     HIPC(hipEventRecord(end, L.compute));
     return NBODY_OK;
   };

@@ -34,44 +34,46 @@ inline size_t part_stride(int rows) { return ((size_t)rows + 63) / 64 * 64; }
 // one body per lane (16 waves per SIMD worth of work, 8 resident) beats 2/4/8 bodies per lane — hipcc software-pipelines
 // the 8 sources of a scalar-load group across the single chain, and more resident waves hide the transcendental — and
 // cutting the sources into pieces so that a launch has >= 16k workgroups adds ~8 % (load balance across the 256 CUs).
-void resolve_config() {
+LaunchConfig resolve_config(int n, int nranks, int fp64, const Options& opt, int cu_count) {
+  LaunchConfig c;
+  const long long wb = fp64 ? 32 : 16;   // bytes per body word
   // the largest slice (ceil(N / P)): every rank of a multi-process job resolves the same segmentation from it
-  const int n_local = std::max(1, (g.n + g.nranks - 1) / g.nranks);
-  g.nslices = g.nranks > 1 ? g.nranks : (g.opt.jslices > 0 ? g.opt.jslices : 1);
+  const int n_local = std::max(1, (n + nranks - 1) / nranks);
+  c.nslices = nranks > 1 ? nranks : (opt.jslices > 0 ? opt.jslices : 1);
   // AUTO: the hand-scheduled ISA loop (+6 % over hipcc's schedule of the same operations, profiles/r01_sweep_isa.txt)
-  g.variant = g.opt.variant == NBODY_VARIANT_AUTO ? NBODY_VARIANT_ISA : g.opt.variant;
-  if (g.fp64 && g.variant != NBODY_VARIANT_ISA) g.variant = NBODY_VARIANT_SMEM;   // fp64: ISA loop or the compiled SMEM kernel
+  c.variant = opt.variant == NBODY_VARIANT_AUTO ? NBODY_VARIANT_ISA : opt.variant;
+  if (fp64 && c.variant != NBODY_VARIANT_ISA) c.variant = NBODY_VARIANT_SMEM;   // fp64: ISA loop or the compiled SMEM kernel
   // fp64 strict arithmetic (IEEE sqrt and divide: bit-identical to the oracle) exists in the compiled kernel only
-  if (g.fp64 && (g.opt.arith & 2)) g.variant = NBODY_VARIANT_SMEM;
+  if (fp64 && (opt.arith & 2)) c.variant = NBODY_VARIANT_SMEM;
   // the hand-scheduled loops exist for the timed arithmetic only; the study modes use the C++ kernels
-  if (g.variant == NBODY_VARIANT_ISA && (g.opt.arith != NBODY_ARITH_FMA3 || g.opt.sum_order == NBODY_SUM_FPGA16)) g.variant = NBODY_VARIANT_SMEM;
-  int R = g.opt.iblock;
-  if (R == 0) R = (g.variant == NBODY_VARIANT_LDS || g.variant == NBODY_VARIANT_READLANE) ? 2 : 1;
-  if (g.variant == NBODY_VARIANT_ISA) R = 1;
-  if (g.fp64 && R > 4) R = 4;
-  if (g.opt.sum_order == NBODY_SUM_FPGA16 && !g.fp64) R = 1;
-  g.R = R;
+  if (c.variant == NBODY_VARIANT_ISA && (opt.arith != NBODY_ARITH_FMA3 || opt.sum_order == NBODY_SUM_FPGA16)) c.variant = NBODY_VARIANT_SMEM;
+  int R = opt.iblock;
+  if (R == 0) R = (c.variant == NBODY_VARIANT_LDS || c.variant == NBODY_VARIANT_READLANE) ? 2 : 1;
+  if (c.variant == NBODY_VARIANT_ISA) R = 1;
+  if (fp64 && R > 4) R = 4;
+  if (opt.sum_order == NBODY_SUM_FPGA16 && !fp64) R = 1;
+  c.R = R;
   // The wave split (ForceArgs::wsplit) exists in the scalar-delivery kernels with one body per lane; the LDS and READLANE
   // deliveries stage sources for the whole workgroup.  (The FPGA order has its own use of 16-wave workgroups, below.)
-  const bool fpga32 = !g.fp64 && g.opt.sum_order == NBODY_SUM_FPGA16;
-  const bool can_split = (g.variant == NBODY_VARIANT_ISA || g.variant == NBODY_VARIANT_SMEM) && R == 1;
+  const bool fpga32 = !fp64 && opt.sum_order == NBODY_SUM_FPGA16;
+  const bool can_split = (c.variant == NBODY_VARIANT_ISA || c.variant == NBODY_VARIANT_SMEM) && R == 1;
   // automatic: wherever it exists, except for NBODY_SUM_SEQ in fp32, whose meaning is ONE sequential sum per segment (what a CPU
   // nbody.c does); fp64 contexts, which always sum sequentially and have 29 bits to spare, take the split
-  const bool auto_split = g.fp64 || g.opt.sum_order != NBODY_SUM_SEQ;
+  const bool auto_split = fp64 || opt.sum_order != NBODY_SUM_SEQ;
   // ... with 16 waves per workgroup where a rank's bodies fill at most half the CUs with 64-row workgroups (n_local <= 8192):
   // there a step is latency and the 16-wave form needs the fewest global partial sums for the same number of waves (measured
   // per step, profiles/r03_small_n.md: N = 2048 7.5 us against 9.1 with 4 waves, N = 4096 9.7 / 10.2, N = 8192 22.0 / 22.1; from
   // N = 16384 up the two are level in fp32 and 4 waves win by 4 % in fp64, so 4 it is)
-  const int cus_ = g.cu_count > 0 ? g.cu_count : 256;
+  const int cus_ = cu_count > 0 ? cu_count : 256;
   // (one-rank contexts only: 8 virtual ranks of 8192 bodies each ran 2335 G pairs/s with 16 waves, 2553 with 4)
-  const int auto_ws = (!g.fp64 && g.nslices == 1 && (n_local + 63) / 64 <= cus_ / 2) ? 16 : 4;
-  g.wsplit = !can_split ? 1 : (g.opt.wsplit == 4 || g.opt.wsplit == 16) ? g.opt.wsplit : (g.opt.wsplit < 0 && auto_split) ? auto_ws : 1;
+  const int auto_ws = (!fp64 && c.nslices == 1 && (n_local + 63) / 64 <= cus_ / 2) ? 16 : 4;
+  c.wsplit = !can_split ? 1 : (opt.wsplit == 4 || opt.wsplit == 16) ? opt.wsplit : (opt.wsplit < 0 && auto_split) ? auto_ws : 1;
   // The FPGA order's "split" is of another kind: its sixteen partial sums per row go to the sixteen waves of a workgroup
   // (force_fpga16w_f32) — the same chains, rotation and tree, hence the same bits as one lane holding all sixteen (NBODY_OPT_WSPLIT 1,
   // force_fpga16_f32), with sixteen times the waves: automatic, since the mode's home is N <= 32767 (the mailbox), where one wave per
   // 64 rows leaves the chip empty
-  if (fpga32) g.wsplit = (can_split && g.opt.wsplit != 1) ? 16 : 1;
-  if (g.wsplit == 16 && g.variant == NBODY_VARIANT_ISA && !g.fp64 && g.opt.isa_phase > 1) g.wsplit = 4;   // diagnostic loop forms: 4 waves
+  if (fpga32) c.wsplit = (can_split && opt.wsplit != 1) ? 16 : 1;
+  if (c.wsplit == 16 && c.variant == NBODY_VARIANT_ISA && !fp64 && opt.isa_phase > 1) c.wsplit = 4;   // diagnostic loop forms: 4 waves
   // Small launches and large ones want different things (profiles/r02_small_n.md, one process, wall clock per step):
   //   large (even 64 segments give >= 16 workgroups per CU; N >= 16384 on one GPU): many short segments for load
   //     balance over the 256 CUs — 128 workgroups per CU in the launch, up to 64 segments of >= 128 sources (N = 65536:
@@ -81,42 +83,42 @@ void resolve_config() {
   //   small: the step is latency, not issue: ~2 workgroups per CU (N = 4096: 32 segments 16.0 us per step, 16: 18.4,
   //     64: 19.4; N = 8192: 16 segments 27.2, 64: 31.8) and the sums added by a second small kernel — in one launch the
   //     hand-off is exposed (N = 4096: 22.7 us, N = 8192: 36.4).
-  const int cus = g.cu_count > 0 ? g.cu_count : 256;
+  const int cus = cu_count > 0 ? cu_count : 256;
   const int blocks = blocks_for(n_local, R, 1);   // in workgroups of 256*R rows: `sub` below counts pieces of a slice as round 2 did
   // "small" = the latency regime: fp32: where the 16-wave workgroups are the automatic choice (n_local <= 8192); between there
   // and N = 16384 round 2's small-launch rule (2 workgroups per CU, combine kernel) measured 21-30 % behind the large-launch one
   // (profiles/r03_sweep_boundary_n*.txt: N = 12288 59.5 us per step against 41.6); fp64, which has no 16-wave regime: never
   // (small-launch rule against large: N = 512 13.7 / 12.8 us per step, 1024: 14.4 / 13.0, 2048: 15.5 / 13.6, 4096: 24.6 / 19.9,
   //  8192: 63.6 / 49.6, 12288: 130.8 / 97.6)
-  const bool small = g.fp64 ? false : (n_local + 63) / 64 <= cus / 2;
-  int sub = g.opt.jsub;
+  const bool small = fp64 ? false : (n_local + 63) / 64 <= cus / 2;
+  int sub = opt.jsub;
   if (sub == 0) {
     // workgroups per launch-slice: the step's launches together have 128 (2) per CU whatever the rank count, so that
     // P GPUs see the same segment length as one (N = 1M: 8 pieces per slice for P = 1, 2, 4, 8; two virtual ranks with
     // 2 pieces of 262144 sources ran 2.3 % behind one rank, with 8 pieces level)
-    const int target_blocks = std::max(1, (small ? 2 : 128) * cus / g.nslices);
+    const int target_blocks = std::max(1, (small ? 2 : 128) * cus / c.nslices);
     sub = (target_blocks + blocks - 1) / blocks;
-    int slice_len = g.n / g.nslices;
+    int slice_len = n / c.nslices;
     // keep >= 128 sources per piece of a slice (a wave walks its piece serially); fp64, whose loop takes 4 sources per
     // iteration, >= 64 (N = 4096 fp64: 16 segments x 4 pieces of 64 sources 19.9 us per step, 8 x 4 of 128: 23.1)
-    int max_sub = std::max(1, slice_len / (g.fp64 ? 64 : 128));
+    int max_sub = std::max(1, slice_len / (fp64 ? 64 : 128));
     sub = std::max(sub, (slice_len + 131071) / 131072);   // and <= 131072 sources (a workgroup's lifetime: the launch's tail)
     // ... unless the partial sums (nseg words per body) would then exceed 16 GiB per rank (288 GB are there to be used): at that
     // size (N >= 32M fp32, 16M fp64) a workgroup's lifetime is a negligible part of a step of minutes anyway; never below 8 segments
-    const long long words_cap = (16LL << 30) / (long long)word_bytes() / n_local;
-    const int mem_sub = (int)std::max(1LL, std::max(8LL, words_cap) / g.nslices);
+    const long long words_cap = (16LL << 30) / wb / n_local;
+    const int mem_sub = (int)std::max(1LL, std::max(8LL, words_cap) / c.nslices);
     sub = std::min(sub, std::max(mem_sub, (target_blocks + blocks - 1) / blocks));
     sub = std::max(1, std::min(std::min(sub, 64), max_sub));
     // (the FPGA order's sixteen waves are not a split of the segment: its segmentation stays what one lane per body resolves to, so
     //  that NBODY_OPT_WSPLIT changes no bit there with NBODY_OPT_JSUB automatic either)
     if (fpga32) {
-    } else if (g.wsplit == 16) {
+    } else if (c.wsplit == 16) {
       // 16-wave workgroups: about one workgroup per CU over the step's launches (N = 4096: 4 segments = 256 workgroups 9.7 us
       // per step, 2: 13.6, 8: 11.9; N = 2048: 4: 7.5, 2: 9.5; N = 8192: 2: 22.0, 4: 23.2, 1: 36.6), pieces of >= 32 sources
       const int blocks64 = (n_local + 63) / 64;
-      sub = std::max(1, (cus / g.nslices + blocks64 - 1) / std::max(1, blocks64));
+      sub = std::max(1, (cus / c.nslices + blocks64 - 1) / std::max(1, blocks64));
       sub = std::max(1, std::min(sub, slice_len / 512));
-    } else if (g.wsplit > 1) {
+    } else if (c.wsplit > 1) {
       // With the wave split a workgroup has a quarter of the rows and its waves a quarter of the segment each: the same
       // number of workgroups and the same walk per wave come from a QUARTER of the global segments (partial sums, tickets,
       // last-arriver rounds).  Two corrections, both measured (profiles/r03_traffic_wsplit.md, r03_sweep_segments_*.txt):
@@ -125,18 +127,19 @@ void resolve_config() {
       //    its 8 MiB from the Infinity Cache (43 GB); N = 4M fp64 on one GPU: 64 segments instead of 8 (4.9 TB per step);
       //  - a P-rank job halves instead of quartering: its launches are P times smaller and want the finer grain (8 virtual
       //    ranks at N = 1M: 1 / 2 / 4 segments per slice 4631 / 4643 / 4661 G pairs/s, one rank 4660)
-      const long long slice_bytes = (long long)slice_len * (long long)word_bytes();
+      const long long slice_bytes = (long long)slice_len * wb;
       const int l2_sub = (int)std::min<long long>(std::min(64, std::max(1, mem_sub)), (slice_bytes + (2LL << 20) - 1) / (2LL << 20));
-      const int div = g.nslices > 1 ? 2 : g.wsplit;
+      const int div = c.nslices > 1 ? 2 : c.wsplit;
       sub = std::max((sub + div - 1) / div, l2_sub);
       // ... and a body never has more than 64 partial sums (8 virtual ranks at N = 262144 with 16 segments per slice, 128 in
       // all, ran 3.2 % behind one rank)
-      if (g.nslices > 1) sub = std::max(1, std::min(sub, std::max(l2_sub, 64 / g.nslices)));
+      if (c.nslices > 1) sub = std::max(1, std::min(sub, std::max(l2_sub, 64 / c.nslices)));
     }
   }
-  g.sub = sub;
-  g.nseg = g.nslices * g.sub;
-  g.fuse = g.opt.fuse < 0 ? (small ? 0 : 1) : g.opt.fuse;
+  c.sub = sub;
+  c.nseg = c.nslices * c.sub;
+  c.fuse = opt.fuse < 0 ? (small ? 0 : 1) : opt.fuse;
+  return c;
 }
 
 namespace {
@@ -165,9 +168,9 @@ int alloc_local(Local& L) {
   for (int b = 0; b < 2; ++b) { HIPC(hipMalloc(&L.pos[b], (g.n + pad) * wb)); HIPC(hipMemset(L.pos[b], 0, (g.n + pad) * wb)); }
   HIPC(hipMalloc(&L.vel, (L.n_local + pad) * wb));
   HIPC(hipMalloc(&L.force, (L.n_local + pad) * wb));
-  const size_t nt = ticket_words(L.n_local);
-  HIPC(hipMalloc((void**)&L.tickets, nt * sizeof(unsigned)));
-  HIPC(hipMemset(L.tickets, 0, nt * sizeof(unsigned)));
+  L.ticket_words = ticket_words(L.n_local);
+  HIPC(hipMalloc((void**)&L.tickets, L.ticket_words * sizeof(unsigned)));
+  HIPC(hipMemset(L.tickets, 0, L.ticket_words * sizeof(unsigned)));
   HIPC(hipMemset(L.vel, 0, (L.n_local + pad) * wb));
   HIPC(hipMemset(L.force, 0, (L.n_local + pad) * wb));
   HIPC(hipEventCreateWithFlags(&L.ev_own_ready, hipEventDisableTiming));
@@ -185,8 +188,8 @@ void drop_step_graph() {
   g.graph_cur = -1;
 }
 
-int ensure_partial(Local& L) {
-  const size_t need = (size_t)g.nseg * part_stride(L.n_local);
+int ensure_partial(Local& L, int nseg) {
+  const size_t need = (size_t)nseg * part_stride(L.n_local);
   if (L.partial && need <= L.partial_words) return NBODY_OK;
   HIPC(hipSetDevice(L.device));
   drop_step_graph();   // captured launches hold the old buffer's address (a mailbox request of another size may be what grows it)
@@ -196,27 +199,29 @@ int ensure_partial(Local& L) {
   return NBODY_OK;
 }
 
-int reconfigure() {
-  const int o_variant = g.variant, o_R = g.R, o_sub = g.sub, o_nsl = g.nslices, o_fuse = g.fuse, o_ws = g.wsplit;
-  resolve_config();
-  // (a step that failed after some of its launches leaves arrival counters at a partial count: the next step would combine
-  //  early.  Every failing path sets tickets_dirty; the counters are re-zeroed here, before anything else is launched.)
-  const bool changed = o_variant != g.variant || o_R != g.R || o_sub != g.sub || o_nsl != g.nslices || o_fuse != g.fuse || o_ws != g.wsplit ||
-                       g.tickets_dirty;
-  g.tickets_dirty = false;
-  if (changed) drop_step_graph();
+TicketGuard::~TicketGuard() { if (!ok) g.tickets_dirty = true; }
+
+// every counter as allocated (a mailbox request may have switched n_local), stream-ordered with the kernels that use them
+int zero_tickets() {
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
-    NBC(ensure_partial(L));
-    if (changed) {
-      // the arrival counters are zero between steps by construction (the last arriver resets its own); a change of
-      // the row-block shape is the one moment to re-zero them all (stream-ordered with the kernels that use them).
-      HIPC(hipSetDevice(L.device));
-      HIPC(hipMemsetAsync(L.tickets, 0, ticket_words(L.n_local) * sizeof(unsigned), L.compute));
-    }
+    HIPC(hipSetDevice(L.device));
+    HIPC(hipMemsetAsync(L.tickets, 0, L.ticket_words * sizeof(unsigned), L.compute));
   }
-  g.view.n = g.n; g.view.n_local = g.loc[0].n_local; g.view.variant = g.variant; g.view.R = g.R; g.view.sub = g.sub; g.view.nseg = g.nseg;
-  g.view.fuse = g.fuse; g.view.wsplit = g.wsplit;
+  g.tickets_dirty = false;
+  return NBODY_OK;
+}
+
+int reconfigure() {
+  const LaunchConfig next = resolve_config(g.n, g.nranks, g.fp64, g.opt, g.cu_count);
+  const bool changed = next != g.cfg || g.tickets_dirty;
+  g.cfg = next;
+  if (changed) drop_step_graph();
+  for (int l = 0; l < g.nlocal; ++l) NBC(ensure_partial(g.loc[l], g.cfg.nseg));
+  // the arrival counters are zero between steps by construction (the last arriver resets its own); a change of
+  // the row-block shape is the one moment to re-zero them all
+  if (changed) NBC(zero_tickets());
+  g.view = {g.n, g.loc[0].n_local, g.cfg};
   return NBODY_OK;
 }
 
@@ -256,25 +261,25 @@ namespace {
 inline bool isa_phase_is_diag(int ph) { return ph >= 2; }
 
 // how a launch finishes its rows: directly (one segment), by the last-arriving workgroup, or by combine_kernel
-inline int finish_mode() { return g.nseg == 1 ? kFinishDirect : (g.fuse ? kFinishLast : kFinishStore); }
+inline int finish_mode() { return g.cfg.nseg == 1 ? kFinishDirect : (g.cfg.fuse ? kFinishLast : kFinishStore); }
 
-void fill_args(Local& L, ForceArgs& a, int row0, int row_count, const Finish& fin, float dt, double dt64) {
+void fill_args(Local& L, ForceArgs& a, int row0, int row_count, const Finish& fin, float dt, double dt64, const Redirect* rd) {
   memset(&a, 0, sizeof(a));
   a.src = L.pos[L.cur];
   a.rows = word_ptr(L.pos[L.cur], (size_t)L.first);
-  if (L.src_direct) { a.src = L.src_direct; a.rows = L.src_direct; }   // (one-rank mailbox request: first = 0)
+  if (rd && rd->src_direct) { a.src = rd->src_direct; a.rows = rd->src_direct; }   // (one-rank mailbox request: first = 0)
   a.partial = L.partial;
   a.vel = L.vel;
   a.pos_next_rows = word_ptr(L.pos[L.cur ^ 1], (size_t)L.first);
-  a.force_out = fin.store_force ? (L.force_dst ? L.force_dst : L.force) : nullptr;
+  a.force_out = fin.store_force ? (rd && rd->force_dst ? rd->force_dst : L.force) : nullptr;
   a.tickets = L.tickets;
   a.n_src = g.n; a.n_rows = L.n_local; a.row0 = row0; a.row_count = row_count;
-  a.nslices = g.nslices; a.sub = g.sub; a.nseg = g.nseg;
+  a.nslices = g.cfg.nslices; a.sub = g.cfg.sub; a.nseg = g.cfg.nseg;
   a.finish = finish_mode();
   a.do_kick = fin.kick; a.do_drift = fin.drift;
   a.sum_block = (!g.fp64 && g.opt.sum_order == NBODY_SUM_BLOCKED) ? g.opt.sum_block : 0;
   a.fpga16 = g.opt.sum_order == NBODY_SUM_FPGA16;
-  a.wsplit = g.wsplit;
+  a.wsplit = g.cfg.wsplit;
   a.part_stride = (int)part_stride(row_count);
   a.dt = dt; a.dt64 = dt64;
 }
@@ -282,7 +287,7 @@ void fill_args(Local& L, ForceArgs& a, int row0, int row_count, const Finish& fi
 }  // namespace
 
 bool takes_rows16(int row_count) {
-  if (g.fp64 || g.opt.sum_order != NBODY_SUM_FPGA16 || g.wsplit != 16 || g.nseg != 1 || g.opt.variant == NBODY_VARIANT_SMEM) return false;
+  if (g.fp64 || g.opt.sum_order != NBODY_SUM_FPGA16 || g.cfg.wsplit != 16 || g.cfg.nseg != 1 || g.opt.variant == NBODY_VARIANT_SMEM) return false;
   static const int force_rows16 = [] { const char* e = getenv("NBODY_FPGA_ROWS16"); return (e && *e) ? atoi(e) : -1; }();
   const int cus = g.cu_count > 0 ? g.cu_count : 256;
   return force_rows16 > 0 || (force_rows16 < 0 && (long long)row_count < 64LL * cus);
@@ -291,14 +296,14 @@ bool takes_rows16(int row_count) {
 // Launch the force kernel of local L for rows [row0, row0+row_count) against `nsl` source slices
 // starting at slice_start and descending (ring arrival order).  A step may take several launches (own slice, then
 // arrived slices); the rows are finished when the LAST of a row block's nseg segments has been summed.
-int launch_force(Local& L, int row0, int row_count, int slice_start, int nsl, const Finish& fin, float dt, double dt64) {
+int launch_force(Local& L, int row0, int row_count, int slice_start, int nsl, const Finish& fin, float dt, double dt64, const Redirect* rd) {
   if (row_count <= 0 || nsl <= 0) return NBODY_OK;
   HIPC(hipSetDevice(L.device));
   ForceArgs a;
-  fill_args(L, a, row0, row_count, fin, dt, dt64);
+  fill_args(L, a, row0, row_count, fin, dt, dt64, rd);
   a.slice_start = slice_start;
-  const int R = g.R;
-  dim3 grid(blocks_for(row_count, R, g.wsplit), nsl * g.sub, 1);
+  const int R = g.cfg.R;
+  dim3 grid(blocks_for(row_count, R, g.cfg.wsplit), nsl * g.cfg.sub, 1);
   // few waves per SIMD and short pieces: the scalar loads are no longer hidden by other waves
   const int cus = g.cu_count > 0 ? g.cu_count : 256;
   // XCD-aware placement of segments (block_segment): needs a multiple of 8 segment rows in the launch, or 1/2/4 of them and a
@@ -312,7 +317,7 @@ int launch_force(Local& L, int row0, int row_count, int slice_start, int nsl, co
   // (r03, wall clock per step: 16384 waves in the launch (N = 16384) 68.0 us with the long buffers against 69.5, 20480 waves
   //  101.7 / 102.9, 24576 waves 144.2 / 142.2, 32768 waves 249.6 / 246.6: the switch sits at 88 waves per CU)
   a.long_buffers = g.opt.long_buffers < 0 ? ((long long)grid.x * grid.y * (wg_threads(a.wsplit) / 64) < 88LL * cus ? 1 : 0) : g.opt.long_buffers;
-  nbl::KernelSel sel = {g.fp64, g.variant, R, g.opt.arith, g.tile, g.opt.isa_phase, g.opt.variant != NBODY_VARIANT_SMEM ? 1 : 0, 0, 0};
+  nbl::KernelSel sel = {g.fp64, g.cfg.variant, R, g.opt.arith, g.tile, g.opt.isa_phase, g.opt.variant != NBODY_VARIANT_SMEM ? 1 : 0, 0, 0};
   // The FPGA order with ONE segment (the mailbox's faithful mode) in a launch that would leave CUs idle with 64 rows per workgroup:
   // sixteen rows x sixteen chains per workgroup instead (force_fpga16r_f32) — the same bits from four times the workgroups.  Up to four
   // 16-row workgroups per CU (rows < 64 x CUs: there the 64-row form fills every CU too, with a quarter of the source fetches).
@@ -321,11 +326,11 @@ int launch_force(Local& L, int row0, int row_count, int slice_start, int nsl, co
     sel.fpga_rows16 = 1;
     grid = dim3((row_count + 15) / 16, 1, 1);
     a.xcd_map = 0;
-    a.t0_stamp = L.t0_stamp;
+    a.t0_stamp = rd ? rd->t0_stamp : nullptr;
   }
   // optional occupancy cap: k workgroups (= k waves per SIMD) per CU by giving each 160 KiB / k of dynamic LDS
   if (g.opt.waves_per_simd > 0 && g.opt.waves_per_simd < 8) {
-    const size_t static_lds = (g.variant == NBODY_VARIANT_LDS ? (size_t)g.tile * 32 : 0) + (a.wsplit > 1 ? (size_t)(a.wsplit - 1) * 64 * word_bytes() : 0) +
+    const size_t static_lds = (g.cfg.variant == NBODY_VARIANT_LDS ? (size_t)g.tile * 32 : 0) + (a.wsplit > 1 ? (size_t)(a.wsplit - 1) * 64 * word_bytes() : 0) +
                               ((a.fpga16 && a.wsplit == 16 && sel.fpga_lds) ? (size_t)32 * 1024 : 0);
     // (a workgroup of WS waves holds WS / 4 wave slots per SIMD: the cap is on workgroups per CU = waves_per_simd / (WS / 4))
     const size_t budget = (size_t)(160 * 1024) / (size_t)g.opt.waves_per_simd;
@@ -339,11 +344,11 @@ int launch_force(Local& L, int row0, int row_count, int slice_start, int nsl, co
 }
 
 // the two-launch form (NBODY_OPT_FUSE_COMBINE = 0): after the step's last force launch, add the partials
-int launch_combine(Local& L, int row0, int row_count, const Finish& fin, float dt, double dt64) {
+int launch_combine(Local& L, int row0, int row_count, const Finish& fin, float dt, double dt64, const Redirect* rd) {
   if (row_count <= 0 || finish_mode() != kFinishStore) return NBODY_OK;
   HIPC(hipSetDevice(L.device));
   ForceArgs c;
-  fill_args(L, c, row0, row_count, fin, dt, dt64);
+  fill_args(L, c, row0, row_count, fin, dt, dt64, rd);
   HIPC((hipError_t)nbl::launch_combine_kernel(g.fp64, L.compute, dim3((row_count + kBlock - 1) / kBlock), c));
   return NBODY_OK;
 }
@@ -359,14 +364,9 @@ int wait_for_slice(Local& L, hipEvent_t ev) {
   return timer_end(L.wait, L.compute, slot);
 }
 
-int enqueue_step_impl(float dt, double dt64);
 // One step on every local: forces on pos[cur], kick, drift into pos[cur^1], swap.
 int enqueue_step(float dt, double dt64) {
-  const int rc = enqueue_step_impl(dt, dt64);
-  if (rc) g.tickets_dirty = true;   // some launches of the step may have run: reconfigure() re-zeroes the arrival counters
-  return rc;
-}
-int enqueue_step_impl(float dt, double dt64) {
+  TicketGuard guard;
   const int P = g.nranks;
   const Finish fin = {true, true, false};
   const bool need_gather = !g.loc[0].all_present;
@@ -390,7 +390,7 @@ int enqueue_step_impl(float dt, double dt64) {
       if (l == 0) NBC(enqueue_gather(L.cur));
     }
     if (P == 1) {
-      NBC(launch_force(L, 0, L.n_local, g.nslices - 1, g.nslices, fin, dt, dt64));
+      NBC(launch_force(L, 0, L.n_local, g.cfg.nslices - 1, g.cfg.nslices, fin, dt, dt64));
     } else if (!need_gather) {
       NBC(launch_force(L, 0, L.n_local, L.rank, P, fin, dt, dt64));
     } else if (g.opt.overlap == 2) {
@@ -421,7 +421,7 @@ int enqueue_step_impl(float dt, double dt64) {
     L.all_present = (P == 1);
   }
   g.steps_done++;
-  return NBODY_OK;
+  return guard.done();
 }
 
 }  // namespace
@@ -472,6 +472,22 @@ int device_count(int* ndev) {
   return NBODY_OK;
 }
 
+int RowWindow::open(int first_row, int n_rows) {
+  const int base = g.multiprocess ? g.loc[0].first : 0;
+  const int limit = g.multiprocess ? g.loc[0].n_local : g.n;
+  if (first_row < 0 || n_rows <= 0 || first_row > limit - n_rows) return NBODY_ERR_ARG;
+  g0 = base + first_row;
+  count = n_rows;
+  return NBODY_OK;
+}
+
+bool RowWindow::rows_of(const Local& L, int* r0, int* n) const {
+  if (count < 0) { *r0 = 0; *n = L.n_local; return true; }
+  const int b = std::max(g0, L.first), e = std::min(g0 + count, L.first + L.n_local);
+  *r0 = b - L.first; *n = e - b;
+  return e > b;
+}
+
 namespace {
 
 void free_local(Local& L) {
@@ -509,60 +525,58 @@ int upload_impl(const void* pos, const void* vel) {
     HIPC(hipSetDevice(L.device));
     HIPC(hipMemcpyAsync(L.pos[L.cur], pos, (size_t)g.n * wb, hipMemcpyHostToDevice, L.compute));
     HIPC(hipMemcpyAsync(L.vel, (const char*)vel + (size_t)L.first * wb, (size_t)L.n_local * wb, hipMemcpyHostToDevice, L.compute));
-    // a fresh state starts from clean arrival counters whatever happened before (a failed step leaves them part-counted)
-    HIPC(hipMemsetAsync(L.tickets, 0, ticket_words(L.n_local) * sizeof(unsigned), L.compute));
     HIPC(hipEventRecord(L.ev_own_ready, L.compute));
     L.all_present = true;
   }
-  g.tickets_dirty = false;
+  NBC(zero_tickets());   // a fresh state starts from clean arrival counters whatever happened before
   return sync_all();
 }
 
-int download_impl(void* pos, void* vel) {
-  if (!g.init) return NBODY_ERR_NOT_INIT;
-  if (!pos || !vel) return NBODY_ERR_ARG;
+// Rank-sharded device arrays to the host, N words each by global body index: the positions (pos[cur]) into `pos` and the array
+// `rows` (&Local::vel or &Local::force) into `rows_host`, each if non-null.  One process: every local copies its own rows.  Several:
+// every process returns all N words — the positions completed in place, the other array gathered into full_scratch.  The compute
+// streams must be idle.
+int sharded_to_host(void* pos, void* rows_host, void* Local::*rows) {
   const size_t wb = word_bytes();
-  NBC(sync_all());
   if (g.multiprocess && g.nranks > 1) {
     Local& L = g.loc[0];
-    NBC(complete_positions());
-    NBC(gather_sharded_multiprocess(L, L.vel));
-    HIPC(hipMemcpy(pos, L.pos[L.cur], (size_t)g.n * wb, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy(vel, L.full_scratch, (size_t)g.n * wb, hipMemcpyDeviceToHost));
+    if (pos) NBC(complete_positions());
+    if (rows_host) NBC(gather_sharded_multiprocess(L, L.*rows));
+    if (pos) HIPC(hipMemcpy(pos, L.pos[L.cur], (size_t)g.n * wb, hipMemcpyDeviceToHost));
+    if (rows_host) HIPC(hipMemcpy(rows_host, L.full_scratch, (size_t)g.n * wb, hipMemcpyDeviceToHost));
     return NBODY_OK;
   }
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
     HIPC(hipSetDevice(L.device));
-    HIPC(hipMemcpy((char*)pos + (size_t)L.first * wb, word_ptr(L.pos[L.cur], L.first), (size_t)L.n_local * wb, hipMemcpyDeviceToHost));
-    HIPC(hipMemcpy((char*)vel + (size_t)L.first * wb, L.vel, (size_t)L.n_local * wb, hipMemcpyDeviceToHost));
+    if (pos) HIPC(hipMemcpy((char*)pos + (size_t)L.first * wb, word_ptr(L.pos[L.cur], L.first), (size_t)L.n_local * wb, hipMemcpyDeviceToHost));
+    if (rows_host) HIPC(hipMemcpy((char*)rows_host + (size_t)L.first * wb, L.*rows, (size_t)L.n_local * wb, hipMemcpyDeviceToHost));
   }
   return NBODY_OK;
 }
 
-// forces of the GLOBAL bodies [g0, g0 + count) (count < 0: all), each local for the part that lies in its slice, from
-// pos[cur] (made complete first)
-int forces_on_device_impl(int g0, int count) {
+int download_impl(void* pos, void* vel) {
+  if (!g.init) return NBODY_ERR_NOT_INIT;
+  if (!pos || !vel) return NBODY_ERR_ARG;
+  NBC(sync_all());
+  return sharded_to_host(pos, vel, &Local::vel);
+}
+
+// forces of the rows of window w, each local for the part that lies in its slice, from pos[cur] (made complete first)
+int forces_on_device(const RowWindow& w) {
+  TicketGuard guard;
   NBC(reconfigure());
   NBC(complete_positions());
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
-    int r0 = 0, cnt = L.n_local;
-    if (count >= 0) {
-      const int b = std::max(g0, L.first), e = std::min(g0 + count, L.first + L.n_local);
-      if (e <= b) continue;
-      r0 = b - L.first; cnt = e - b;
-    }
+    int r0, cnt;
+    if (!w.rows_of(L, &r0, &cnt)) continue;
     const Finish fin = {false, false, true};
-    NBC(launch_force(L, r0, cnt, g.nslices - 1, g.nslices, fin, 0.f, 0.0));
+    NBC(launch_force(L, r0, cnt, g.cfg.nslices - 1, g.cfg.nslices, fin, 0.f, 0.0));
     NBC(launch_combine(L, r0, cnt, fin, 0.f, 0.0));
   }
-  return sync_all();
-}
-int forces_on_device(int g0, int count) {
-  const int rc = forces_on_device_impl(g0, count);
-  if (rc) g.tickets_dirty = true;
-  return rc;
+  NBC(sync_all());
+  return guard.done();
 }
 
 int step_impl(float dt, double dt64, int nsteps) {
@@ -620,56 +634,47 @@ int body_force_impl(void* pos, void* vel, float dt, double dt64, int n) {
   if (n != g.n) return NBODY_ERR_ARG;
   NBC(upload_impl(pos, vel));
   NBC(reconfigure());
+  TicketGuard guard;
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
     const Finish fin = {true, false, true};
-    int rc = launch_force(L, 0, L.n_local, g.nslices - 1, g.nslices, fin, dt, dt64);
-    if (!rc) rc = launch_combine(L, 0, L.n_local, fin, dt, dt64);
-    if (rc) { g.tickets_dirty = true; return rc; }
+    NBC(launch_force(L, 0, L.n_local, g.cfg.nslices - 1, g.cfg.nslices, fin, dt, dt64));
+    NBC(launch_combine(L, 0, L.n_local, fin, dt, dt64));
   }
   NBC(sync_all());
-  // vel back (pos is read-only for bodyForce)
-  const size_t wb = word_bytes();
-  if (g.multiprocess && g.nranks > 1) {
-    Local& L = g.loc[0];
-    NBC(gather_sharded_multiprocess(L, L.vel));
-    HIPC(hipMemcpy(vel, L.full_scratch, (size_t)g.n * wb, hipMemcpyDeviceToHost));
-    return NBODY_OK;
-  }
-  for (int l = 0; l < g.nlocal; ++l) {
-    Local& L = g.loc[l];
-    HIPC(hipSetDevice(L.device));
-    HIPC(hipMemcpy((char*)vel + (size_t)L.first * wb, L.vel, (size_t)L.n_local * wb, hipMemcpyDeviceToHost));
-  }
-  return NBODY_OK;
+  guard.done();
+  return sharded_to_host(nullptr, vel, &Local::vel);   // vel back (pos is read-only for bodyForce)
 }
 
 int integrate_impl(void* pos, const void* vel, float dt, double dt64, int n) {
   if (!g.init) return NBODY_ERR_NOT_INIT;
   if (n != g.n) return NBODY_ERR_ARG;
   NBC(upload_impl(pos, vel));
-  const size_t wb = word_bytes();
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
     HIPC(hipSetDevice(L.device));
     HIPC((hipError_t)nbl::launch_drift_kernel(g.fp64, L.compute, word_ptr(L.pos[L.cur], L.first), L.vel, L.n_local, dt, dt64));
     HIPC(hipEventRecord(L.ev_own_ready, L.compute));
-    L.all_present = (g.nranks == 1);
+    L.all_present = (g.nranks == 1);   // the other locals' slices of pos are now stale: refreshed lazily
   }
   NBC(sync_all());
-  if (g.multiprocess && g.nranks > 1) {
-    NBC(complete_positions());
-    Local& L = g.loc[0];
-    HIPC(hipMemcpy(pos, L.pos[L.cur], (size_t)g.n * wb, hipMemcpyDeviceToHost));
-    return NBODY_OK;
-  }
+  return sharded_to_host(pos, nullptr, nullptr);
+}
+
+int forces_rows_impl(int first_row, int n_rows, void* force_words) {
+  if (!g.init) return NBODY_ERR_NOT_INIT;
+  if (!force_words) return NBODY_ERR_ARG;
+  RowWindow w;
+  NBC(w.open(first_row, n_rows));
+  NBC(forces_on_device(w));
+  const size_t wb = word_bytes();
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
+    int r0, cnt;
+    if (!w.rows_of(L, &r0, &cnt)) continue;
     HIPC(hipSetDevice(L.device));
-    HIPC(hipMemcpy((char*)pos + (size_t)L.first * wb, word_ptr(L.pos[L.cur], L.first), (size_t)L.n_local * wb, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy((char*)force_words + (size_t)(L.first + r0 - w.g0) * wb, word_ptr(L.force, r0), (size_t)cnt * wb, hipMemcpyDeviceToHost));
   }
-  // the other locals' copies of pos are now stale: refresh lazily
-  for (int l = 0; l < g.nlocal; ++l) g.loc[l].all_present = (g.nranks == 1);
   return NBODY_OK;
 }
 
@@ -686,45 +691,9 @@ int forces_impl(const void* pos_words, void* force_words, int n) {
     HIPC(hipMemcpyAsync(L.pos[L.cur], pos_words, (size_t)g.n * wb, hipMemcpyHostToDevice, L.compute));
     L.all_present = true;
   }
-  NBC(forces_on_device(0, -1));
-  if (g.multiprocess && g.nranks > 1) {   // every process returns all N force words: gather the other ranks' rows
-    Local& L = g.loc[0];
-    NBC(gather_sharded_multiprocess(L, L.force));
-    HIPC(hipMemcpy(force_words, L.full_scratch, (size_t)g.n * wb, hipMemcpyDeviceToHost));
-    return NBODY_OK;
-  }
-  for (int l = 0; l < g.nlocal; ++l) {
-    Local& L = g.loc[l];
-    HIPC(hipSetDevice(L.device));
-    HIPC(hipMemcpy((char*)force_words + (size_t)L.first * wb, L.force, (size_t)L.n_local * wb, hipMemcpyDeviceToHost));
-  }
-  return NBODY_OK;
+  NBC(forces_on_device(RowWindow()));
+  return sharded_to_host(nullptr, force_words, &Local::force);   // every process returns all N force words
 }
-
-namespace {
-
-// first_row: nbody_init contexts (one process, one or several devices): GLOBAL body index, the range may span devices;
-// nbody_init_rank contexts: row of this rank's own slice.
-int forces_rows_impl(int first_row, int n_rows, void* force_words) {
-  if (!g.init) return NBODY_ERR_NOT_INIT;
-  if (!force_words) return NBODY_ERR_ARG;
-  const int base = g.multiprocess ? g.loc[0].first : 0;
-  const int limit = g.multiprocess ? g.loc[0].n_local : g.n;
-  if (first_row < 0 || n_rows <= 0 || first_row + n_rows > limit) return NBODY_ERR_ARG;
-  const int g0 = base + first_row;
-  NBC(forces_on_device(g0, n_rows));
-  const size_t wb = word_bytes();
-  for (int l = 0; l < g.nlocal; ++l) {
-    Local& L = g.loc[l];
-    const int b = std::max(g0, L.first), e = std::min(g0 + n_rows, L.first + L.n_local);
-    if (e <= b) continue;
-    HIPC(hipSetDevice(L.device));
-    HIPC(hipMemcpy((char*)force_words + (size_t)(b - g0) * wb, word_ptr(L.force, b - L.first), (size_t)(e - b) * wb, hipMemcpyDeviceToHost));
-  }
-  return NBODY_OK;
-}
-
-}  // namespace
 
 }  // namespace nbi
 
@@ -951,10 +920,10 @@ int nbody_get_info(int key, long long* value) {
     case NBODY_INFO_FIRST_BODY: *value = L.first; break;
     case NBODY_INFO_RANK: *value = L.rank; break;
     case NBODY_INFO_NRANKS: *value = g.nranks; break;
-    case NBODY_INFO_VARIANT: *value = g.view.variant; break;
-    case NBODY_INFO_IBLOCK: *value = g.view.R; break;
-    case NBODY_INFO_JSUB: *value = g.view.sub; break;
-    case NBODY_INFO_NSEG: *value = g.view.nseg; break;
+    case NBODY_INFO_VARIANT: *value = g.view.cfg.variant; break;
+    case NBODY_INFO_IBLOCK: *value = g.view.cfg.R; break;
+    case NBODY_INFO_JSUB: *value = g.view.cfg.sub; break;
+    case NBODY_INFO_NSEG: *value = g.view.cfg.nseg; break;
     case NBODY_INFO_DEVICE: *value = L.device; break;
     case NBODY_INFO_CU_COUNT: *value = g.cu_count; break;
     case NBODY_INFO_CLOCK_KHZ: *value = g.clock_khz; break;
@@ -965,15 +934,15 @@ int nbody_get_info(int key, long long* value) {
     case NBODY_INFO_SUM_BLOCK: *value = (!g.fp64 && g.opt.sum_order == NBODY_SUM_BLOCKED) ? g.opt.sum_block : 0; break;
     case NBODY_INFO_LAUNCHES_PER_STEP: {
       const int force = g.nranks == 1 ? 1 : (g.opt.overlap == 2 ? g.nranks : (g.opt.overlap ? 2 : 1));
-      *value = force + ((g.view.nseg > 1 && !g.view.fuse) ? 1 : 0);   // (finish_mode() of the context's own configuration)
+      *value = force + ((g.view.cfg.nseg > 1 && !g.view.cfg.fuse) ? 1 : 0);   // (finish_mode() of the context's own configuration)
       break;
     }
     case NBODY_INFO_HAS_COMM: *value = L.comm_h ? 1 : 0; break;
-    case NBODY_INFO_WSPLIT: *value = g.view.wsplit; break;
+    case NBODY_INFO_WSPLIT: *value = g.view.cfg.wsplit; break;
     case NBODY_INFO_ISA_PHASE: *value = g.opt.isa_phase; break;
     case NBODY_INFO_LONG_BUFFERS: *value = g.opt.long_buffers; break;
     case NBODY_INFO_XCD_MAP: *value = g.opt.xcd_map; break;
-    case NBODY_INFO_FUSE_COMBINE: *value = g.view.fuse; break;
+    case NBODY_INFO_FUSE_COMBINE: *value = g.view.cfg.fuse; break;
     case NBODY_INFO_COMM_FORM: *value = g.nranks > 1 ? resolved_comm_form() : -1; break;
     case NBODY_INFO_COMM_PRIORITY: *value = g.comm_priority; break;
     case NBODY_INFO_MAILBOX_SERVED: *value = mailbox_served(); break;

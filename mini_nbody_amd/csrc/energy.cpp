@@ -71,25 +71,21 @@ int energy_impl(double* out) {
   return NBODY_OK;
 }
 
-// rows as in nbody_forces_rows: nbody_init contexts the GLOBAL index (the range may span devices), nbody_init_rank contexts the row
-// of this rank's own slice
 int potential_rows_impl(int first_row, int n_rows, void* phi) {
   if (!g.init) return NBODY_ERR_NOT_INIT;
   if (!phi) return NBODY_ERR_ARG;
-  const int base = g.multiprocess ? g.loc[0].first : 0;
-  const int limit = g.multiprocess ? g.loc[0].n_local : g.n;
-  if (first_row < 0 || n_rows <= 0 || first_row > limit - n_rows) return NBODY_ERR_ARG;
-  const int g0 = base + first_row;
+  RowWindow w;   // rows as in nbody_forces_rows
+  NBC(w.open(first_row, n_rows));
   NBC(reconfigure());
   NBC(complete_positions());
   const size_t es = g.fp64 ? sizeof(double) : sizeof(float);
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
-    const int b = std::max(g0, L.first), e = std::min(g0 + n_rows, L.first + L.n_local);
-    if (e <= b) continue;
-    NBC(launch_energy(L, b - L.first, e - b, false));
+    int r0, cnt;
+    if (!w.rows_of(L, &r0, &cnt)) continue;
+    NBC(launch_energy(L, r0, cnt, false));
     HIPC(hipStreamSynchronize(L.compute));
-    HIPC(hipMemcpy((char*)phi + (size_t)(b - g0) * es, L.en_phi, (size_t)(e - b) * es, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy((char*)phi + (size_t)(L.first + r0 - w.g0) * es, L.en_phi, (size_t)cnt * es, hipMemcpyDeviceToHost));
   }
   return NBODY_OK;
 }

@@ -69,24 +69,20 @@ int mailbox_rams() {   // RAM A and RAM B: capacity + 1 words each (+ slack), pi
 // CONTEXT's configuration (Global::view, published by reconfigure()), which a request never touches.
 struct ActiveN {
   bool armed = false;
-  int n = 0, n_local = 0, variant = 0, R = 0, sub = 0, nslices = 0, nseg = 0, fuse = 0, wsplit = 0;
+  Global::View saved;   // the context's own {n, n_local, cfg}
   int enter(int n_new) {
     Local& L = g.loc[0];
-    n = g.n; n_local = L.n_local; variant = g.variant; R = g.R; sub = g.sub; nslices = g.nslices; nseg = g.nseg; fuse = g.fuse; wsplit = g.wsplit;
+    saved = {g.n, L.n_local, g.cfg};
     armed = true;
     g.n = n_new; L.n_local = n_new;
-    resolve_config();
-    NBC(ensure_partial(L));
-    if (g.tickets_dirty) {   // a failed launch sequence left arrival counters part-counted (they are zero between requests otherwise)
-      HIPC(hipMemsetAsync(L.tickets, 0, ticket_words(g.cap) * sizeof(unsigned), L.compute));
-      g.tickets_dirty = false;
-    }
+    g.cfg = resolve_config(n_new, g.nranks, g.fp64, g.opt, g.cu_count);
+    NBC(ensure_partial(L, g.cfg.nseg));
+    if (g.tickets_dirty) NBC(zero_tickets());   // a failed launch sequence left arrival counters part-counted (TicketGuard)
     return NBODY_OK;
   }
   ~ActiveN() {
     if (!armed) return;
-    Local& L = g.loc[0];
-    g.n = n; L.n_local = n_local; g.variant = variant; g.R = R; g.sub = sub; g.nslices = nslices; g.nseg = nseg; g.fuse = fuse; g.wsplit = wsplit;
+    g.n = saved.n; g.loc[0].n_local = saved.n_local; g.cfg = saved.cfg;
   }
 };
 
@@ -127,21 +123,18 @@ int wait_seq(hipStream_t stream, unsigned seq) {
 // the launches of one request on the compute stream: RAM A's read port (which starts the tick count), the force pass storing into RAM B
 // (and its combine), and — device-written completion — the one-wave launch that rewrites word 0
 int mailbox_launches(Local& L, int num_pts, bool done_by_device, unsigned seq, int clock_khz) {
-  // bodies are words 1..N                                              S/top_level.vhd:55, 206-208
-  // A handful of bodies in the faithful mode: the 16-row kernel reads RAM A itself (its tile loads ARE the PCIe reads) and stamps the tick
-  // count's start; everything else goes through the ingest launch, which reads RAM A once for all workgroups.
-  const bool direct = done_by_device && num_pts <= mb_direct_max && takes_rows16(num_pts);
-  if (direct) { L.src_direct = (const char*)mb_a_dev + 16; L.t0_stamp = mb_t0_dev; }
-  else HIPC((hipError_t)nbl::launch_ingest_kernel(L.compute, L.pos[L.cur], (const char*)mb_a_dev + 16, num_pts, done_by_device ? mb_t0_dev : nullptr));
   // RAM B's write port: the force launch (or its combine) stores {Fx, Fy, Fz, 0} of body k at word k itself — row k - 1 of the launch
   // goes to force_dst[k - 1] and force_dst is word 1 —; word 0 and the words beyond N are never written       S/compute_store.vhd:213, 221-242
+  Redirect rd = {(char*)mb_b_dev + 16};
+  // bodies are words 1..N                                              S/top_level.vhd:55, 206-208
+  // A handful of bodies in the faithful mode: the 16-row kernel reads RAM A itself (its tile loads ARE the PCIe reads) and stamps the tick
+  // count's start; everything else goes through the ingest launch, which reads RAM A once for all workgroups (into pos[cur]).
+  if (done_by_device && num_pts <= mb_direct_max && takes_rows16(num_pts)) { rd.src_direct = (const char*)mb_a_dev + 16; rd.t0_stamp = mb_t0_dev; }
+  else HIPC((hipError_t)nbl::launch_ingest_kernel(L.compute, L.pos[L.cur], (const char*)mb_a_dev + 16, num_pts, done_by_device ? mb_t0_dev : nullptr));
   const Finish fin = {false, false, true};
-  L.force_dst = (char*)mb_b_dev + 16;
-  int rc = launch_force(L, 0, num_pts, g.nslices - 1, g.nslices, fin, 0.f, 0.0);
-  if (!rc) rc = launch_combine(L, 0, num_pts, fin, 0.f, 0.0);
-  L.force_dst = nullptr;
-  L.src_direct = nullptr; L.t0_stamp = nullptr;
-  if (rc || !done_by_device) return rc;
+  NBC(launch_force(L, 0, num_pts, g.cfg.nslices - 1, g.cfg.nslices, fin, 0.f, 0.0, &rd));
+  NBC(launch_combine(L, 0, num_pts, fin, 0.f, 0.0, &rd));
+  if (!done_by_device) return NBODY_OK;
   HIPC((hipError_t)nbl::launch_mailbox_done_kernel(L.compute, mb_a_dev, mb_seq_dev, mb_t0_dev, seq, (unsigned)clock_khz, (unsigned)mb_rt_khz));
   return NBODY_OK;
 }
@@ -160,14 +153,15 @@ int mailbox_request(const void* ram_a, void* ram_b, int num_pts, int clock_khz, 
   const bool by_device = mb_done_by_device != 0;
   const unsigned seq = by_device ? ++mb_seq_next : 0u;
   if (by_device && ram_a != mb_a) ((uint32_t*)mb_a)[0] = 1u;   // (the device clears THIS image's BEGIN; the caller's word 0 follows below)
+  TicketGuard guard;   // up to the request's completion
   const int rc = mailbox_launches(L, num_pts, by_device, seq, clock_khz);
   if (rc) {
-    g.tickets_dirty = true;
     if (by_device) { (void)hipStreamSynchronize(L.compute); --mb_seq_next; }   // nothing of this request may still be writing when word 0 is rewritten
     return rc;
   }
   if (by_device) { NBC(wait_seq(L.compute, seq)); *device_done = true; }
   else NBC(wait_stream(L.compute));
+  guard.done();
   if (ram_b != mb_b) memcpy((char*)ram_b + 16, (char*)mb_b + 16, (size_t)num_pts * 16);   // words 1..N; the caller's word 0 is not written either
   return NBODY_OK;
 }
@@ -274,7 +268,7 @@ int nbody_mailbox_open(int capacity, int faithful) {
   NBC(nbody_init(capacity, 1, 0, 0));
   int rc = mailbox_rams();
   // the partial sums of the largest segmentation any request can resolve to (64 segments), so that no request allocates
-  if (!rc) { const int nseg = g.nseg; g.nseg = 64; rc = ensure_partial(g.loc[0]); g.nseg = nseg; }
+  if (!rc) rc = ensure_partial(g.loc[0], 64);
   if (!rc && faithful) {
     // the PL block's own bits: its rounding points (S/dxy.vhd:113-122, S/dzsoft.vhd:201-202, S/dxyz_soft.vhd:149-150) with 1/sqrt rounded
     // once — after this device has proved that 1/sqrt —, its sixteen partial sums, rotation and adder tree (S/fxyz.vhd:129-184,

@@ -69,10 +69,8 @@ struct Local {
   void* partial = nullptr;
   size_t partial_words = 0;            // capacity of `partial`
   unsigned* tickets = nullptr;         // arrival counters: one per wave of every block of 256 rows
+  size_t ticket_words = 0;             // capacity of `tickets`
   void* force = nullptr;
-  void* force_dst = nullptr;           // where a launch stores {Fx,Fy,Fz,0} instead of `force` (a mailbox request: RAM B itself)
-  const void* src_direct = nullptr;    // a mailbox request of a handful of bodies: sources and rows read from RAM A itself (no ingest launch) ...
-  unsigned long long* t0_stamp = nullptr;   // ... and the launch's first wave stamps the tick count's start here (ForceArgs::t0_stamp)
   void* full_scratch = nullptr;        // N words: all-gather of a sharded array for the host (multi-process)
   double* en_part = nullptr;           // energy pass (energy.cpp): per-workgroup fp64 partials of {T, U, P, L} ...
   double* en_tot = nullptr;            // ... the ranks' totals, 8 doubles at word `rank` (all P after an all-gather) ...
@@ -97,6 +95,23 @@ struct Options {
 // what happens to the force of a row once all its segments are summed
 struct Finish { bool kick, drift, store_force; };
 
+// what one launch reads and writes instead of the context's buffers (a mailbox request); none by default
+struct Redirect {
+  void* force_dst = nullptr;                // {Fx,Fy,Fz,0} stored here instead of Local::force (RAM B itself)
+  const void* src_direct = nullptr;         // sources and rows read from here instead of pos[cur] (RAM A itself: no ingest launch) ...
+  unsigned long long* t0_stamp = nullptr;   // ... and the 16-row kernel's first wave stamps the tick count's start here (ForceArgs::t0_stamp)
+};
+
+// the resolved launch configuration: what resolve_config() makes of N, the rank count, precision, options and CU count
+struct LaunchConfig {
+  int variant = NBODY_VARIANT_SMEM, R = 4, sub = 1, nslices = 1, nseg = 1, fuse = 1;
+  int wsplit = 1;                 // 4: a workgroup owns 64 rows, its four waves walk a quarter of the segment each (ForceArgs::wsplit)
+  bool operator==(const LaunchConfig& o) const {
+    return variant == o.variant && R == o.R && sub == o.sub && nslices == o.nslices && nseg == o.nseg && fuse == o.fuse && wsplit == o.wsplit;
+  }
+  bool operator!=(const LaunchConfig& o) const { return !(*this == o); }
+};
+
 typedef int (*host_gather_fn)(void* user, void* host_words, int n_total, int word_bytes, int rank, int nranks);
 
 struct Global {
@@ -115,17 +130,15 @@ struct Global {
   bool multiprocess = false;
   Local loc[kMaxLocal];
   Options opt;
-  // resolved launch configuration
-  int variant = NBODY_VARIANT_SMEM, R = 4, sub = 1, nslices = 1, nseg = 1, fuse = 1;
-  int wsplit = 1;                 // 4: a workgroup owns 64 rows, its four waves walk a quarter of the segment each (ForceArgs::wsplit)
+  LaunchConfig cfg;
   bool comm_go_armed = false;     // the gather just enqueued recorded ev_comm_go (RCCL transport)
-  bool tickets_dirty = false;     // a step failed after some of its launches: the arrival counters may be non-zero
+  bool tickets_dirty = false;     // a launch sequence failed part-way (TicketGuard): the arrival counters may be non-zero
   int cu_count = 0, clock_khz = 0;
   int comm_priority = 0;          // HIP priority of the transfer streams (0 = default)
   long long steps_done = 0;
   // The CONTEXT's N and resolved configuration as nbody_get_info reports them: published by reconfigure(), never touched by a mailbox
-  // request (which switches the fields above for its own duration) — so the caller's thread may read them while the service thread works
-  struct View { int n = 0, n_local = 0, variant = 0, R = 0, sub = 0, nseg = 1, fuse = 1, wsplit = 1; } view;
+  // request (which switches n, n_local and cfg for its own duration) — so the caller's thread may read them while the service thread works
+  struct View { int n = 0, n_local = 0; LaunchConfig cfg; } view;
 };
 extern Global g;
 
@@ -136,17 +149,37 @@ inline int ring_slice(int rank, int s) { int q = (rank - s) % g.nranks; return q
 // strides of 4*R, padded to a multiple of 256 bytes
 inline size_t ticket_words(int n_local) { return ((size_t)(n_local + 63) / 64 + 32 + 63) / 64 * 64; }
 
+// A sequence of force launches that fails part-way leaves arrival counters at a partial count: the next launch would combine early.
+// Every such sequence (a step, forces_on_device, bodyForce, the comm probe's force pass, a mailbox request up to its completion) holds
+// a TicketGuard; any way out before done() marks the counters dirty, and the next upload, reconfigure() or mailbox request re-zeroes
+// them (zero_tickets) before it launches anything.
+struct TicketGuard {
+  bool ok = false;
+  int done() { ok = true; return NBODY_OK; }
+  ~TicketGuard();
+};
+
+// A window of rows as nbody_forces_rows and nbody_potential_rows take it — nbody_init contexts: GLOBAL body index, the range may span
+// devices; nbody_init_rank contexts: row of this rank's own slice — held as the global bodies [g0, g0 + count) (count < 0: all N)
+struct RowWindow {
+  int g0 = 0, count = -1;
+  int open(int first_row, int n_rows);                   // NBODY_ERR_ARG: not a non-empty range of the context's rows
+  bool rows_of(const Local& L, int* r0, int* n) const;   // rows [*r0, *r0 + *n) of L's slice are in the window; false: none are
+};
+
 // ---- context.cpp ----
-void resolve_config();
+LaunchConfig resolve_config(int n, int nranks, int fp64, const Options& opt, int cu_count);
 int reconfigure();
-int ensure_partial(Local& L);
+int ensure_partial(Local& L, int nseg);   // partial sums for nseg segments of L's rows
+int zero_tickets();                       // every local's arrival counters, and the dirty mark off (TicketGuard sets it)
 void drop_step_graph();
 int timer_begin(EventTimer& T, hipStream_t stream, int* slot);
 int timer_end(EventTimer& T, hipStream_t stream, int slot);
 int timer_drain(EventTimer& T, int keep);
 // the force kernel of local L for rows [row0, row0 + row_count) against `nsl` source slices starting at slice_start and descending
-int launch_force(Local& L, int row0, int row_count, int slice_start, int nsl, const Finish& fin, float dt, double dt64);
-int launch_combine(Local& L, int row0, int row_count, const Finish& fin, float dt, double dt64);
+int launch_force(Local& L, int row0, int row_count, int slice_start, int nsl, const Finish& fin, float dt, double dt64,
+                 const Redirect* rd = nullptr);
+int launch_combine(Local& L, int row0, int row_count, const Finish& fin, float dt, double dt64, const Redirect* rd = nullptr);
 // launch_force would take the 16-row FPGA kernel (force_fpga16r_f32) for a launch of row_count rows in the configuration as it stands
 bool takes_rows16(int row_count);
 int sync_all();

@@ -1,11 +1,12 @@
-// hip_stub.cpp — TEST INFRASTRUCTURE (tests/test_host_sanitizers.py): a host-only stand-in for the HIP runtime and for kernels.hip, so that
-// the library's three HOST translation units (context.cpp, comm.cpp, mailbox.cpp — everything that is not device code) can run on a
-// machine without a GPU under AddressSanitizer / UBSan / ThreadSanitizer (sanitizers run on the CPU build only; the GPU pool has none).
+// hip_stub.cpp — TEST INFRASTRUCTURE (tests/test_host_sanitizers.py): a host-only stand-in for the HIP runtime and for the launch functions of
+// kernels.hip and energy.hip, so that the library's four HOST translation units (context.cpp, comm.cpp, mailbox.cpp, energy.cpp — everything
+// that is not device code) can run on a machine without a GPU under AddressSanitizer / UBSan / ThreadSanitizer (sanitizers run on the CPU
+// build only; the GPU pool has none).
 // "Device" memory is malloc'd (so ASan sees every copy size and every index the host computed), streams execute synchronously, a stream
 // capture records closures that hipGraphLaunch replays, and the nbl:: launch functions run a SIMPLE stand-in force (F_i = sum over the
 // launch's segments of (r_j - r_i), float or double, segment by segment) through the REAL data flow of a launch: ForceArgs, segment
 // bounds, per-segment partial sums, one arrival counter per 64 rows, ascending combine, apply (store / kick / drift), the mailbox's
-// ingest and device-written completion.  It says nothing about the kernels' arithmetic (the GPU tests do); it checks the host's logic:
+// ingest and device-written completion.  The energy pass writes values a test can predict from what it reads (see energy()).  It says nothing about the kernels' arithmetic (the GPU tests do); it checks the host's logic:
 // buffer sizes, offsets, state switching per request, the service thread's hand-over, the guard, lifetimes.
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "../../mini_nbody_amd/csrc/nbody_internal.hpp"
+#include "../../mini_nbody_amd/csrc/energy_args.hpp"
 
 using nbk::ForceArgs;
 
@@ -94,12 +96,35 @@ void force(ForceArgs a, int ny) {
     }
   }
 }
+// the energy pass through the real EnergyArgs: phi of the row of global index i = x_i - i; the totals of a group of kEnergyRows rows =
+// rows x (q + 1) in word q, except word 2 (Px) = the sum of the rows' vel.x
+template <typename T>
+void energy(const nbe::EnergyArgs& a) {
+  typedef W4<T> V;
+  for (int k = 0; k < a.row_count; ++k) {
+    const int i = a.first + a.row0 + k;
+    if (a.phi) ((T*)a.phi)[k] = ((const V*)a.src)[i].x - (T)i;
+    if (a.part) {
+      double* p = a.part + (size_t)(k / nbe::kEnergyRows) * nbe::kEnergyWords;
+      if (k % nbe::kEnergyRows == 0) for (int q = 0; q < nbe::kEnergyWords; ++q) p[q] = 0.0;
+      for (int q = 0; q < nbe::kEnergyWords; ++q) p[q] += q == 2 ? (double)((const V*)a.vel)[a.row0 + k].x : (double)(q + 1);
+    }
+  }
+}
+
+// hip_stub_lose_next_completion(): the next mailbox request's completion never arrives — no word is written — and the arrival counter of
+// its force launch's first rows is left part-counted, as a device fault part-way through the launch would leave it
+std::atomic<int> g_lose_completion{0};
+std::atomic<unsigned*> g_last_tickets{nullptr};
 }  // namespace
+
+extern "C" void hip_stub_lose_next_completion(void) { g_lose_completion.store(1); }
 
 namespace nbl {
 bool diag_build() { return false; }
 int launch_force_kernel(const KernelSel& k, hipStream_t, dim3 grid, const ForceArgs& a) {
   const int fp64 = k.fp64, ny = k.fpga_rows16 ? 1 : (int)grid.y;
+  g_last_tickets.store(a.tickets);
   return enqueue([=] { if (a.t0_stamp) *a.t0_stamp = (unsigned long long)(now_ms() * 1e5); if (fp64) force<double>(a, ny); else force<float>(a, ny); });
 }
 int launch_combine_kernel(int fp64, hipStream_t, dim3, const ForceArgs& a) {
@@ -117,12 +142,25 @@ int launch_ingest_kernel(hipStream_t, void* dst_words, const void* ram_a_bodies,
   return enqueue([=] { memcpy(dst_words, ram_a_bodies, (size_t)n * 16); if (t0) *t0 = (unsigned long long)(now_ms() * 1e5); });
 }
 int launch_mailbox_done_kernel(hipStream_t, void* word0, unsigned* seq_word, const unsigned long long* t0, unsigned seq, unsigned clock_khz, unsigned rt_khz) {
+  if (g_lose_completion.exchange(0)) { g_last_tickets.load()[0] += 1; return 0; }
   return enqueue([=] {
     unsigned* w0 = (unsigned*)word0;
     const unsigned long long dt = (unsigned long long)(now_ms() * 1e5) - *t0;
     w0[1] = (unsigned)(1ull + dt * clock_khz / ((unsigned long long)rt_khz * 1000ull)); w0[2] = 0; w0[3] = 0;
     __atomic_store_n(&w0[0], 0u, __ATOMIC_RELEASE);
     __atomic_store_n(seq_word, seq, __ATOMIC_RELEASE);
+  });
+}
+int launch_energy_kernel(int fp64, int, hipStream_t, const nbe::EnergyArgs& a) {
+  return enqueue([=] { if (fp64) energy<double>(a); else energy<float>(a); });
+}
+int launch_energy_reduce_kernel(hipStream_t, const double* part, int groups, double* out) {
+  return enqueue([=] {
+    for (int q = 0; q < nbe::kEnergyWords; ++q) {
+      double s = 0.0;
+      for (int gr = 0; gr < groups; ++gr) s += part[(size_t)gr * nbe::kEnergyWords + q];
+      out[q] = q < 2 ? 0.5 * s : s;
+    }
   });
 }
 int launch_rsqrt_selftest_kernel(unsigned, unsigned long long, unsigned long long* out3) { out3[0] = 0; out3[1] = 0; return 0; }

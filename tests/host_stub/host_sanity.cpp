@@ -1,5 +1,6 @@
 // host_sanity.cpp — TEST INFRASTRUCTURE: drives the C-ABI of include/nbody.h on top of hip_stub.cpp (no GPU) so that the library's HOST
 // code runs under sanitizers.  usage: host_sanity [serve_requests [mailbox-only]]   exit code 0 = every check held.
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -10,6 +11,8 @@
 #include <vector>
 
 #include "../../include/nbody.h"
+
+extern "C" void hip_stub_lose_next_completion(void);   // hip_stub.cpp
 
 #define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "host_sanity: line %d: %s\n", __LINE__, #cond); exit(1); } } while (0)
 #define OK(call) do { int rc_ = (call); if (rc_) { fprintf(stderr, "host_sanity: line %d: %s = %d (%s)\n", __LINE__, #call, rc_, nbody_error_string(rc_)); exit(1); } } while (0)
@@ -22,6 +25,29 @@ static void bodies(std::vector<float>& p, int n, unsigned seed) {
 
 static long long info(int key) { long long v = -1; OK(nbody_get_info(key, &v)); return v; }
 
+// nbody_energy and nbody_potential_rows(_d) on the uploaded state, against what the stub's energy pass writes (hip_stub.cpp energy()):
+// phi of body i = x_i - i; totals {n / 2, n, sum of vel.x, 4n, 5n, 6n, 7n, 8n}.  Windows: all rows, one across the first two slices of a
+// three-device context (N = 1001: 0..333 | 334..667), the last row; and ranges that leave the context's rows.
+template <typename T>
+static void check_energy(int n, const std::vector<T>& pos, const std::vector<T>& vel, int (*potential_rows)(int, int, T*)) {
+  double e[NBODY_ENERGY_WORDS];
+  OK(nbody_energy(e));
+  double px = 0.0, ax = 0.0;
+  for (int i = 0; i < n; ++i) { px += (double)vel[(size_t)i * 4]; ax += fabs((double)vel[(size_t)i * 4]); }
+  for (int q = 0; q < NBODY_ENERGY_WORDS; ++q)
+    CHECK(q == 2 ? fabs(e[q] - px) <= 1e-9 * (1.0 + ax) : e[q] == (q < 2 ? 0.5 : 1.0) * (q + 1) * (double)n);
+  const int mid = n / 3 > 50 ? n / 3 - 50 : 0;
+  const int windows[3][2] = {{0, n}, {mid, n - mid < 100 ? n - mid : 100}, {n - 1, 1}};
+  for (const auto& w : windows) {
+    std::vector<T> phi((size_t)w[1] + 1, (T)-1);
+    OK(potential_rows(w[0], w[1], phi.data()));
+    for (int k = 0; k < w[1]; ++k) CHECK(phi[k] == pos[(size_t)(w[0] + k) * 4] - (T)(w[0] + k));
+    CHECK(phi[w[1]] == (T)-1);
+  }
+  T buf[4];
+  CHECK(potential_rows(n - 1, 2, buf) == NBODY_ERR_ARG && potential_rows(-1, 1, buf) == NBODY_ERR_ARG && potential_rows(0, 0, buf) == NBODY_ERR_ARG);
+}
+
 int main(int argc, char** argv) {
   const int serve_requests = argc > 1 ? atoi(argv[1]) : 10000;
   const bool mailbox_only = argc > 2;
@@ -33,6 +59,7 @@ int main(int argc, char** argv) {
     OK(nbody_init(n, 1, 0, 0));
     BodySystem b = {pos.data(), vel.data()};
     OK(nbody_upload(&b));
+    check_energy(n, pos, vel, nbody_potential_rows);
     OK(nbody_step(0.01f, 70));                     // one eager step, graphs of 32 + the rest
     OK(nbody_sync());
     p2.assign((size_t)n * 4, 0.f); v2.assign((size_t)n * 4, 0.f);
@@ -60,6 +87,7 @@ int main(int argc, char** argv) {
     OK(nbody_init(n, 1, 1, 0));
     BodySystemD b = {dp.data(), dv.data()};
     OK(nbody_upload_d(&b)); OK(nbody_step_d(0.01, 9)); OK(nbody_download_d(&b));
+    check_energy(n, dp, dv, nbody_potential_rows_d);
     CHECK(nbody_step(0.01f, 1) == NBODY_ERR_STATE);
     nbody_shutdown();
     if (getenv("STUB_DEVICES") && atoi(getenv("STUB_DEVICES")) >= 3) {
@@ -67,6 +95,7 @@ int main(int argc, char** argv) {
       OK(nbody_init(n, 3, 0, 0));
       BodySystem bb = {pos.data(), vel.data()};
       for (int ov : {0, 1, 2}) { OK(nbody_set_option(NBODY_OPT_OVERLAP, ov)); OK(nbody_upload(&bb)); OK(nbody_step(0.01f, 4)); OK(nbody_download(&bb)); }
+      check_energy(n, pos, vel, nbody_potential_rows);                // after steps: the other slices are brought over first
       f.assign((size_t)n * 4, 0.f);
       OK(nbody_forces(pos.data(), f.data(), n));
       nbody_shutdown();
@@ -78,7 +107,12 @@ int main(int argc, char** argv) {
   uint32_t* ram_a; float* ram_b; int c = 0;
   OK(nbody_mailbox_rams((void**)&ram_a, (void**)&ram_b, &c));
   CHECK(c == cap);
-  bodies(pos, cap, 9);
+  bodies(pos, cap, 9); bodies(vel, cap, 10);
+  {  // the energy entry points on the mailbox's context, before a request overwrites its position buffer
+    BodySystem b = {pos.data(), vel.data()};
+    OK(nbody_upload(&b));
+    check_energy(cap, pos, vel, nbody_potential_rows);
+  }
   std::vector<std::vector<uint32_t>> first(cap + 1);
   auto post = [&](int n) { memcpy(ram_a + 4, pos.data(), (size_t)n * 16); ram_a[1] = (uint32_t)n; ram_a[2] = ram_a[3] = 0; };
   auto check_b = [&](const float* rb, int n, int words) {
@@ -125,7 +159,8 @@ int main(int argc, char** argv) {
       if (nbody_get_info(NBODY_INFO_WSPLIT, &v) || v != ws0) bad++;
       if (nbody_get_info(NBODY_INFO_MAILBOX_SERVING, &v) || v != 1) bad++;
       int rc;
-      switch (k++ % 9) {
+      double e[NBODY_ENERGY_WORDS];
+      switch (k++ % 11) {
         case 0: rc = nbody_step(0.01f, 1); break;
         case 1: rc = nbody_set_option(NBODY_OPT_JSUB, 2); break;
         case 2: rc = nbody_upload(&bs); break;
@@ -134,6 +169,8 @@ int main(int argc, char** argv) {
         case 5: rc = nbody_sync(); break;
         case 6: rc = nbody_mailbox_open(64, 0); break;
         case 7: rc = nbody_init(64, 1, 0, 0); break;
+        case 8: rc = nbody_energy(e); break;
+        case 9: rc = nbody_potential_rows(0, 1, buf.data()); break;
         default: rc = nbody_mailbox_run(ram_a, ram_b, 0); break;
       }
       if (rc != NBODY_ERR_STATE) bad++;
@@ -162,6 +199,19 @@ int main(int argc, char** argv) {
   fill(ram_b, cap + 1); post(300); ram_a[0] = 1;
   OK(nbody_mailbox_run(ram_a, ram_b, 0));
   check_b(ram_b, 300, cap + 1);
+  // a request whose completion wait fails (the stub loses the completion and leaves an arrival counter part-counted): the next request
+  // must start from clean counters.  Several segments combined by the last arriver, so that the counters are in use.
+  OK(nbody_set_option(NBODY_OPT_FUSE_COMBINE, 1)); OK(nbody_set_option(NBODY_OPT_JSUB, 3));
+  std::vector<uint32_t> want;
+  for (int k = 0; k < 3; ++k) {
+    fill(ram_b, cap + 1); post(300); ram_a[0] = 1;
+    if (k == 1) { hip_stub_lose_next_completion(); CHECK(nbody_mailbox_run(ram_a, ram_b, 0) == NBODY_ERR_STATE); continue; }
+    OK(nbody_mailbox_run(ram_a, ram_b, 0));
+    std::vector<uint32_t> got((uint32_t*)ram_b + 4, (uint32_t*)ram_b + 4 + 300 * 4);
+    for (uint32_t v : got) CHECK(v != 0xDEADBEEFu);
+    if (k == 0) want = got;
+    else CHECK(got == want);
+  }
   OK(nbody_mailbox_serve(1, 0));                                                               // shutdown with the thread still serving
   nbody_shutdown();
   printf("host_sanity ok: %d served requests, %lld looks by the second thread\n", serve_requests, looked.load());

@@ -1,12 +1,14 @@
-"""The library's HOST code — context.cpp, comm.cpp, mailbox.cpp: everything in libnbody_hip.so that is not device code — under
+"""The library's HOST code — context.cpp, comm.cpp, mailbox.cpp, energy.cpp: everything in libnbody_hip.so that is not device code — under
 AddressSanitizer + UBSan and under ThreadSanitizer, on the CPU (sanitizers run on the CPU build only; the GPU pool has none).
 tests/host_stub/hip_stub.cpp stands in for the HIP runtime ("device" memory is malloc'd, streams run synchronously, a capture
 records closures) and for kernels.hip (a simple stand-in force pushed through the REAL data flow of a launch: ForceArgs, segment
-bounds, partial sums, arrival counters, ascending combine, apply, the mailbox's ingest and device-written completion);
+bounds, partial sums, arrival counters, ascending combine, apply, the mailbox's ingest and device-written completion) and energy.hip
+(predictable values written through the real EnergyArgs);
 tests/host_stub/host_sanity.cpp drives the C-ABI: contexts of several sizes, 70-step loops (graph capture and replay), every
-segmentation / combine form / wave split, row windows, fp64, one process over three stub devices with ragged slices, the mailbox in
-every form with the RTL's address map checked against a sentinel, and the SERVED mailbox with a second thread hammering
-nbody_get_info and the refused entry points ("a TSan build of a host-only stub of the serve loop").
+segmentation / combine form / wave split, row windows, the energy entry points, fp64, one process over three stub devices with ragged
+slices, the mailbox in every form with the RTL's address map checked against a sentinel, a request whose completion wait fails, and
+the SERVED mailbox with a second thread hammering nbody_get_info and the refused entry points ("a TSan build of a
+host-only stub of the serve loop").
 What this checks is the host's logic — buffer sizes and offsets (ASan sees every index the host computed), the per-request switch of
 N, the service thread's hand-over, the guard, lifetimes at shutdown; the kernels' arithmetic is the GPU tests' business."""
 import os
@@ -17,7 +19,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CXX = "/opt/rocm/lib/llvm/bin/clang++"
-SRC = [os.path.join(ROOT, "mini_nbody_amd", "csrc", f) for f in ("context.cpp", "comm.cpp", "mailbox.cpp")] + \
+SRC = [os.path.join(ROOT, "mini_nbody_amd", "csrc", f) for f in ("context.cpp", "comm.cpp", "mailbox.cpp", "energy.cpp")] + \
       [os.path.join(ROOT, "tests", "host_stub", f) for f in ("hip_stub.cpp", "host_sanity.cpp")]
 
 

@@ -61,15 +61,14 @@ void comm_destroy(Local& L) {
 namespace {
 
 int ensure_full_scratch(Local& L) {   // L.full_scratch: N words (+ slack), allocated on the current device (L's) at first use
-  if (!L.full_scratch) HIPC(hipMalloc(&L.full_scratch, (size_t)(g.n + 64) * word_bytes()));
-  return NBODY_OK;
+  return L.full_scratch.ensure((size_t)(g.n + 64) * word_bytes());
 }
 
 // Host-staged all-gather of one sharded device array (words [first, first+count) are this rank's): D2H own part,
 // callback (the host framework's all-gather fills the rest of g.host_stage), H2D everything else on the comm stream.
 int host_exchange(Local& L, void* dev_full, int first, int count, bool wait_own_ready) {
   const size_t wb = word_bytes();
-  if (!g.host_stage) HIPC(hipHostMalloc(&g.host_stage, (size_t)(g.n + 64) * 32, hipHostMallocDefault));
+  NBC(g.host_stage.ensure((size_t)(g.n + 64) * 32, hipHostMallocDefault));
   if (wait_own_ready) HIPC(hipEventSynchronize(L.ev_own_ready));
   HIPC(hipMemcpy(word_ptr(g.host_stage, first), word_ptr(dev_full, first), (size_t)count * wb, hipMemcpyDeviceToHost));
   int rc = g.host_gather(g.host_gather_user, g.host_stage, g.n, (int)wb, L.rank, g.nranks);
@@ -172,7 +171,7 @@ int ring_step(Local& L, const void* send_ptr, size_t send_bytes, void* recv_ptr,
 // one in-place ncclAllGather (equal slices), or the plan above group by group.  ev[s] (s = 1..P-1), if given, is
 // recorded as soon as ring slice s has landed (RING: after its group, so the force kernel over it can start while the
 // next one travels; the single-kernel forms: all after the collective).
-int rccl_gather(Local& L, void* dev_full, hipEvent_t* ev) {
+int rccl_gather(Local& L, void* dev_full, const Event* ev) {
   const int P = g.nranks;
   const size_t wb = word_bytes();
   const int form = resolved_comm_form();
@@ -356,21 +355,17 @@ int nbody_comm_selftest_virtual(int vp, int form, long long* bytes_moved) { NB_R
   NBC(sync_all());
   const size_t wb = word_bytes(), lanes = wb / 4;
   HIPC(hipSetDevice(L.device));
-  struct Bufs {   // freed on every way out
-    std::vector<void*> d;
-    ~Bufs() { for (void* p : d) if (p) (void)hipFree(p); }
-  } bufs;
-  bufs.d.assign(vp, nullptr);
+  std::vector<DevMem> bufs(vp);
   std::vector<std::vector<CommOp>> plan(vp);
   std::vector<uint32_t> host((size_t)g.n * lanes);
   auto pattern = [](int w, size_t k) { return 0x5A000000u ^ ((uint32_t)w * 4u + (uint32_t)k) * 2654435761u; };
   for (int r = 0; r < vp; ++r) {
     NBC(comm_plan(form, r, vp, g.n, plan[r]));
-    HIPC(hipMalloc(&bufs.d[r], (size_t)(g.n + 64) * wb));
-    HIPC(hipMemset(bufs.d[r], 0xff, (size_t)g.n * wb));
+    NBC(bufs[r].ensure((size_t)(g.n + 64) * wb));
+    HIPC(hipMemset(bufs[r], 0xff, (size_t)g.n * wb));
     const int f = slice_first(r, g.n, vp), c = slice_first(r + 1, g.n, vp) - f;
     for (int w = f; w < f + c; ++w) for (size_t k = 0; k < lanes; ++k) host[(size_t)w * lanes + k] = pattern(w, k);
-    HIPC(hipMemcpy(word_ptr(bufs.d[r], f), &host[(size_t)f * lanes], (size_t)c * wb, hipMemcpyHostToDevice));
+    HIPC(hipMemcpy(word_ptr(bufs[r], f), &host[(size_t)f * lanes], (size_t)c * wb, hipMemcpyHostToDevice));
   }
   long long moved = 0;
   const int groups = plan[0].empty() ? 0 : plan[0].back().group;
@@ -385,8 +380,8 @@ int nbody_comm_selftest_virtual(int vp, int form, long long* bytes_moved) { NB_R
         for (const CommOp& q : plan[o.recv_peer])
           if (q.group == grp && q.send_peer == r && q.send_first == o.recv_first && q.send_count == o.recv_count) { snd = &q; break; }
         if (!snd) { NB_MARK(); return NBODY_ERR_STATE; }   // the plans do not pair up
-        NCCLC(g_rccl.Send(word_ptr(bufs.d[o.recv_peer], (size_t)snd->send_first), (size_t)snd->send_count * wb, ncclChar, 0, L.comm_h, L.comm));
-        NCCLC(g_rccl.Recv(word_ptr(bufs.d[r], (size_t)o.recv_first), (size_t)o.recv_count * wb, ncclChar, 0, L.comm_h, L.comm));
+        NCCLC(g_rccl.Send(word_ptr(bufs[o.recv_peer], (size_t)snd->send_first), (size_t)snd->send_count * wb, ncclChar, 0, L.comm_h, L.comm));
+        NCCLC(g_rccl.Recv(word_ptr(bufs[r], (size_t)o.recv_first), (size_t)o.recv_count * wb, ncclChar, 0, L.comm_h, L.comm));
         moved += o.recv_count * (long long)wb;
       }
     }
@@ -394,7 +389,7 @@ int nbody_comm_selftest_virtual(int vp, int form, long long* bytes_moved) { NB_R
   }
   HIPC(hipStreamSynchronize(L.comm));
   for (int r = 0; r < vp; ++r) {
-    HIPC(hipMemcpy(host.data(), bufs.d[r], (size_t)g.n * wb, hipMemcpyDeviceToHost));
+    HIPC(hipMemcpy(host.data(), bufs[r], (size_t)g.n * wb, hipMemcpyDeviceToHost));
     for (int w = 0; w < g.n; ++w)
       for (size_t k = 0; k < lanes; ++k)
         if (host[(size_t)w * lanes + k] != pattern(w, k)) { NB_MARK(); return NBODY_ERR_STATE; }
@@ -443,8 +438,8 @@ int nbody_comm_probe(long long bytes, int when, double* comm_ms, double* force_m
   NBC(sync_all());
   HIPC(hipSetDevice(L.device));
   NBC(ensure_full_scratch(L));
-  struct Evs { hipEvent_t e[6] = {}; ~Evs() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); } } ev;
-  for (hipEvent_t& x : ev.e) HIPC(hipEventCreate(&x));
+  Event ev[6];
+  for (Event& x : ev) HIPC(hipEventCreate(x.put()));
   const Finish fin = {false, false, true};
   auto force_pass = [&](hipEvent_t begin, hipEvent_t end) -> int {
     if (begin) HIPC(hipEventRecord(begin, L.compute));
@@ -456,30 +451,30 @@ int nbody_comm_probe(long long bytes, int when, double* comm_ms, double* force_m
     return NBODY_OK;
   };
   auto comm_step = [&]() -> int {
-    HIPC(hipEventRecord(ev.e[0], L.comm));
-    NBC(ring_step(L, L.full_scratch, (size_t)bytes, (char*)L.full_scratch + bytes, (size_t)bytes));
-    HIPC(hipEventRecord(ev.e[1], L.comm));
+    HIPC(hipEventRecord(ev[0], L.comm));
+    NBC(ring_step(L, L.full_scratch, (size_t)bytes, L.full_scratch.as<char>() + bytes, (size_t)bytes));
+    HIPC(hipEventRecord(ev[1], L.comm));
     return NBODY_OK;
   };
-  hipEvent_t from = ev.e[0];
-  if (when == 1) { NBC(comm_step()); NBC(force_pass(ev.e[2], ev.e[3])); }
-  else if (when == 2) { NBC(force_pass(ev.e[2], ev.e[3])); NBC(comm_step()); }
+  hipEvent_t from = ev[0];
+  if (when == 1) { NBC(comm_step()); NBC(force_pass(ev[2], ev[3])); }
+  else if (when == 2) { NBC(force_pass(ev[2], ev[3])); NBC(comm_step()); }
   else if (when >= 3) {
-    NBC(force_pass(nullptr, ev.e[4]));                       // pass A; e[4] = "own slice ready"
-    HIPC(hipStreamWaitEvent(L.comm, ev.e[4], 0));
+    NBC(force_pass(nullptr, ev[4]));                       // pass A; ev[4] = "own slice ready"
+    HIPC(hipStreamWaitEvent(L.comm, ev[4], 0));
     if (when == 4) HIPC(hipEventRecord(L.ev_comm_go, L.comm));
     NBC(comm_step());
     if (when == 4) HIPC(hipStreamWaitEvent(L.compute, L.ev_comm_go, 0));
-    NBC(force_pass(ev.e[2], ev.e[3]));                       // pass B
-    from = ev.e[4];
+    NBC(force_pass(ev[2], ev[3]));                       // pass B
+    from = ev[4];
   } else NBC(comm_step());
   NBC(sync_all());
   float ms = 0.f;
-  HIPC(hipEventElapsedTime(&ms, from, ev.e[1]));
+  HIPC(hipEventElapsedTime(&ms, from, ev[1]));
   if (comm_ms) *comm_ms = ms;
   if (force_ms) {
     *force_ms = 0.0;
-    if (when) { HIPC(hipEventElapsedTime(&ms, ev.e[2], ev.e[3])); *force_ms = ms; }
+    if (when) { HIPC(hipEventElapsedTime(&ms, ev[2], ev[3])); *force_ms = ms; }
   }
   return NBODY_OK;
 }

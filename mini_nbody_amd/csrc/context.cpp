@@ -19,7 +19,7 @@ namespace nbi {
 
 std::atomic<const char*> g_last_file{""};
 std::atomic<int> g_last_line{0};
-Global g;
+Global& g = *new Global;   // never destroyed: nbody_internal.hpp, at its declaration
 
 namespace {
 
@@ -146,7 +146,7 @@ namespace {
 
 int alloc_local(Local& L) {
   HIPC(hipSetDevice(L.device));
-  HIPC(hipStreamCreateWithFlags(&L.compute, hipStreamNonBlocking));
+  HIPC(hipStreamCreateWithFlags(L.compute.put(), hipStreamNonBlocking));
   {
     // The transfers' kernels (RCCL) and copies are small and the force launch beside them fills every wave slot of every
     // CU: the second stream gets the highest priority the device offers, so that its work is dispatched ahead of the
@@ -155,29 +155,27 @@ int alloc_local(Local& L) {
     const char* pe = getenv("NBODY_COMM_PRIORITY");
     const bool want = !(pe && *pe && atoi(pe) == 0);
     if (want && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest != least) {
-      HIPC(hipStreamCreateWithPriority(&L.comm, hipStreamNonBlocking, greatest));
+      HIPC(hipStreamCreateWithPriority(L.comm.put(), hipStreamNonBlocking, greatest));
       g.comm_priority = greatest;
     } else {
       (void)hipGetLastError();
-      HIPC(hipStreamCreateWithFlags(&L.comm, hipStreamNonBlocking));
+      HIPC(hipStreamCreateWithFlags(L.comm.put(), hipStreamNonBlocking));
       g.comm_priority = 0;
     }
   }
   const size_t wb = word_bytes();
   const size_t pad = 64;   // words of slack after the arrays (never read by the kernels; keeps SMEM groups in-bounds by construction anyway)
-  for (int b = 0; b < 2; ++b) { HIPC(hipMalloc(&L.pos[b], (g.n + pad) * wb)); HIPC(hipMemset(L.pos[b], 0, (g.n + pad) * wb)); }
-  HIPC(hipMalloc(&L.vel, (L.n_local + pad) * wb));
-  HIPC(hipMalloc(&L.force, (L.n_local + pad) * wb));
-  L.ticket_words = ticket_words(L.n_local);
-  HIPC(hipMalloc((void**)&L.tickets, L.ticket_words * sizeof(unsigned)));
-  HIPC(hipMemset(L.tickets, 0, L.ticket_words * sizeof(unsigned)));
+  for (int b = 0; b < 2; ++b) NBC(L.pos[b].ensure((g.n + pad) * wb, true));
+  NBC(L.vel.ensure((L.n_local + pad) * wb));
+  NBC(L.force.ensure((L.n_local + pad) * wb));
+  NBC(L.tickets.ensure(ticket_words(L.n_local) * sizeof(unsigned), true));
   HIPC(hipMemset(L.vel, 0, (L.n_local + pad) * wb));
   HIPC(hipMemset(L.force, 0, (L.n_local + pad) * wb));
-  HIPC(hipEventCreateWithFlags(&L.ev_own_ready, hipEventDisableTiming));
-  HIPC(hipEventCreateWithFlags(&L.ev_comm_go, hipEventDisableTiming));
-  for (int s = 0; s < g.nranks && s < kMaxRanks; ++s) HIPC(hipEventCreateWithFlags(&L.ev_gather[s], hipEventDisableTiming));
+  HIPC(hipEventCreateWithFlags(L.ev_own_ready.put(), hipEventDisableTiming));
+  HIPC(hipEventCreateWithFlags(L.ev_comm_go.put(), hipEventDisableTiming));
+  for (int s = 0; s < g.nranks && s < kMaxRanks; ++s) HIPC(hipEventCreateWithFlags(L.ev_gather[s].put(), hipEventDisableTiming));
   for (EventTimer* T : {&L.kern, &L.wait})
-    for (int k = 0; k < kTimerRing; ++k) { HIPC(hipEventCreate(&T->t0[k])); HIPC(hipEventCreate(&T->t1[k])); }
+    for (int k = 0; k < kTimerRing; ++k) { HIPC(hipEventCreate(T->t0[k].put())); HIPC(hipEventCreate(T->t1[k].put())); }
   return NBODY_OK;
 }
 
@@ -189,14 +187,11 @@ void drop_step_graph() {
 }
 
 int ensure_partial(Local& L, int nseg) {
-  const size_t need = (size_t)nseg * part_stride(L.n_local);
-  if (L.partial && need <= L.partial_words) return NBODY_OK;
   HIPC(hipSetDevice(L.device));
-  drop_step_graph();   // captured launches hold the old buffer's address (a mailbox request of another size may be what grows it)
-  if (L.partial) { HIPC(hipFree(L.partial)); L.partial = nullptr; L.partial_words = 0; }
-  HIPC(hipMalloc(&L.partial, (need + 64) * word_bytes()));
-  L.partial_words = need;
-  return NBODY_OK;
+  bool moved = false;
+  const int rc = L.partial.ensure(((size_t)nseg * part_stride(L.n_local) + 64) * word_bytes(), false, &moved);
+  if (moved) drop_step_graph();   // captured launches hold the old buffer's address (a mailbox request of another size may be what grows it)
+  return rc;
 }
 
 TicketGuard::~TicketGuard() { if (!ok) g.tickets_dirty = true; }
@@ -206,7 +201,7 @@ int zero_tickets() {
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
     HIPC(hipSetDevice(L.device));
-    HIPC(hipMemsetAsync(L.tickets, 0, L.ticket_words * sizeof(unsigned), L.compute));
+    HIPC(hipMemsetAsync(L.tickets, 0, L.tickets.bytes, L.compute));
   }
   g.tickets_dirty = false;
   return NBODY_OK;
@@ -272,7 +267,7 @@ void fill_args(Local& L, ForceArgs& a, int row0, int row_count, const Finish& fi
   a.vel = L.vel;
   a.pos_next_rows = word_ptr(L.pos[L.cur ^ 1], (size_t)L.first);
   a.force_out = fin.store_force ? (rd && rd->force_dst ? rd->force_dst : L.force) : nullptr;
-  a.tickets = L.tickets;
+  a.tickets = L.tickets.as<unsigned>();
   a.n_src = g.n; a.n_rows = L.n_local; a.row0 = row0; a.row_count = row_count;
   a.nslices = g.cfg.nslices; a.sub = g.cfg.sub; a.nseg = g.cfg.nseg;
   a.finish = finish_mode();
@@ -491,28 +486,12 @@ bool RowWindow::rows_of(const Local& L, int* r0, int* n) const {
 namespace {
 
 void free_local(Local& L) {
-  if (L.compute == nullptr && L.pos[0] == nullptr) return;
+  if (!L.compute) return;   // never allocated: alloc_local creates the compute stream first
   (void)hipSetDevice(L.device);
-  if (L.compute) (void)hipStreamSynchronize(L.compute);
+  (void)hipStreamSynchronize(L.compute);
   if (L.comm) (void)hipStreamSynchronize(L.comm);
   comm_destroy(L);
-  for (int b = 0; b < 2; ++b) if (L.pos[b]) (void)hipFree(L.pos[b]);
-  if (L.vel) (void)hipFree(L.vel);
-  if (L.partial) (void)hipFree(L.partial);
-  if (L.force) (void)hipFree(L.force);
-  if (L.tickets) (void)hipFree(L.tickets);
-  if (L.full_scratch) (void)hipFree(L.full_scratch);
-  if (L.en_part) (void)hipFree(L.en_part);
-  if (L.en_tot) (void)hipFree(L.en_tot);
-  if (L.en_phi) (void)hipFree(L.en_phi);
-  if (L.ev_own_ready) (void)hipEventDestroy(L.ev_own_ready);
-  if (L.ev_comm_go) (void)hipEventDestroy(L.ev_comm_go);
-  for (int s = 0; s < kMaxRanks; ++s) if (L.ev_gather[s]) (void)hipEventDestroy(L.ev_gather[s]);
-  for (EventTimer* T : {&L.kern, &L.wait})
-    for (int k = 0; k < kTimerRing; ++k) { if (T->t0[k]) (void)hipEventDestroy(T->t0[k]); if (T->t1[k]) (void)hipEventDestroy(T->t1[k]); }
-  if (L.compute) (void)hipStreamDestroy(L.compute);
-  if (L.comm) (void)hipStreamDestroy(L.comm);
-  L = Local();
+  L = Local();   // every handle of L released
 }
 
 int upload_impl(const void* pos, const void* vel) {
@@ -536,7 +515,7 @@ int upload_impl(const void* pos, const void* vel) {
 // `rows` (&Local::vel or &Local::force) into `rows_host`, each if non-null.  One process: every local copies its own rows.  Several:
 // every process returns all N words — the positions completed in place, the other array gathered into full_scratch.  The compute
 // streams must be idle.
-int sharded_to_host(void* pos, void* rows_host, void* Local::*rows) {
+int sharded_to_host(void* pos, void* rows_host, DevMem Local::*rows) {
   const size_t wb = word_bytes();
   if (g.multiprocess && g.nranks > 1) {
     Local& L = g.loc[0];
@@ -579,6 +558,17 @@ int forces_on_device(const RowWindow& w) {
   return guard.done();
 }
 
+// What enqueue_step changes on the host, put back when a capture of steps ends: capturing executes nothing
+struct CaptureRestore {
+  Local& L;
+  const long long done; const int cur; const bool present;
+  ~CaptureRestore() {
+    g.steps_done = done;
+    L.cur = cur; L.all_present = present;   // an even number of steps returns to the same buffer; a failed capture may have toggled
+    g.tickets_dirty = false;                // ... and has launched nothing
+  }
+};
+
 int step_impl(float dt, double dt64, int nsteps) {
   if (!g.init) return NBODY_ERR_NOT_INIT;
   if (nsteps < 0) return NBODY_ERR_ARG;
@@ -604,22 +594,17 @@ int step_impl(float dt, double dt64, int nsteps) {
     if (len > nsteps - s) len = (nsteps - s) & ~1;
     if (len >= 2 && (!g.step_graph || g.graph_len != len || g.graph_cur != L.cur || g.graph_dt != dt || g.graph_dt64 != dt64)) {
       drop_step_graph();
-      hipGraph_t graph = nullptr;
-      const long long done = g.steps_done;
-      const int cur0 = L.cur;
-      const bool present0 = L.all_present;
+      Graph graph;
       HIPC(hipStreamBeginCapture(L.compute, hipStreamCaptureModeThreadLocal));
-      int rc = 0;
-      for (int k = 0; k < len && !rc; ++k) rc = enqueue_step(dt, dt64);
-      hipError_t e = hipStreamEndCapture(L.compute, &graph);
-      g.steps_done = done;                       // capturing executes nothing
-      L.cur = cur0; L.all_present = present0;    // an even number of steps returns to the same buffer; a failed capture may have toggled
-      g.tickets_dirty = false;                   // ... and has launched nothing
-      if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-      if (e != hipSuccess) { if (graph) (void)hipGraphDestroy(graph); NB_MARK(); return (int)e; }
-      e = hipGraphInstantiate(&g.step_graph, graph, nullptr, nullptr, 0);
-      (void)hipGraphDestroy(graph);
+      int rc = 0; hipError_t e;
+      {
+        CaptureRestore restore{L, g.steps_done, L.cur, L.all_present};
+        for (int k = 0; k < len && !rc; ++k) rc = enqueue_step(dt, dt64);
+        e = hipStreamEndCapture(L.compute, graph.put());
+      }
+      NBC(rc);
       HIPC(e);
+      HIPC(hipGraphInstantiate(&g.step_graph, graph, nullptr, nullptr, 0));
       g.graph_cur = L.cur; g.graph_dt = dt; g.graph_dt64 = dt64; g.graph_len = len;
     }
     if (len >= 2) for (; s + len <= nsteps; s += len) { HIPC(hipGraphLaunch(g.step_graph, L.compute)); g.steps_done += len; }
@@ -702,6 +687,45 @@ using namespace nbi;
 // ============================================================================
 extern "C" {
 
+// What nbody_init and nbody_init_rank share once they have checked their arguments and described their locals (g.nranks, g.nlocal,
+// g.multiprocess; rank, device and rows of every g.loc[l]): buffers, device properties, peer access or the communicator, the first
+// configuration.  Any failure leaves no context behind (OpenGuard).
+static int open_context(const void* uid128) {
+  OpenGuard guard;
+  for (int l = 0; l < g.nlocal; ++l) NBC(alloc_local(g.loc[l]));
+  Local& L = g.loc[0];
+  hipDeviceProp_t prop;
+  HIPC(hipGetDeviceProperties(&prop, L.device));
+  g.cu_count = prop.multiProcessorCount; g.clock_khz = prop.clockRate;
+  for (int a = 0; a < g.nlocal; ++a)
+    for (int b = 0; b < g.nlocal; ++b) {
+      if (g.loc[a].device == g.loc[b].device) continue;
+      (void)hipSetDevice(g.loc[a].device);
+      hipError_t e = hipDeviceEnablePeerAccess(g.loc[b].device, 0);
+      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) { (void)hipGetLastError(); }
+    }
+  if (uid128) NBC(comm_create(L, g.nranks, L.rank, uid128));   // (also for nranks = 1: comm_create says why)
+  g.init = true; g.opt = Options();
+  NBC(reconfigure());
+  if (g.nranks > 1 && L.comm_h) {
+    // One all-gather of the (zeroed) position buffer now: RCCL sets up its rings/channels lazily on the first
+    // collective, and that must not land in a caller's first timed step.
+    HIPC(hipSetDevice(L.device));
+    HIPC(hipEventRecord(L.ev_own_ready, L.compute));
+    NBC(enqueue_gather(L.cur));
+    NBC(sync_all());
+  }
+  return guard.commit();
+}
+
+static void describe_local(Local& L, int rank, int device, int n, int nranks) {
+  L = Local();
+  L.rank = rank;
+  L.device = device;
+  L.first = slice_first(rank, n, nranks);
+  L.n_local = slice_first(rank + 1, n, nranks) - L.first;
+}
+
 int nbody_init(int n, int ngpus, int fp64, int tile) { NB_REFUSE_WHILE_SERVED();
   if (g.init) nbody_shutdown();
   if (ngpus <= 0 || ngpus > kMaxLocal) return NBODY_ERR_ARG;
@@ -714,36 +738,8 @@ int nbody_init(int n, int ngpus, int fp64, int tile) { NB_REFUSE_WHILE_SERVED();
   if (ngpus > ndev && !(ov && atoi(ov))) return NBODY_ERR_NO_DEVICE;
   if (n < ngpus) return NBODY_ERR_ARG;
   g.nranks = ngpus; g.nlocal = ngpus; g.multiprocess = false;
-  hipDeviceProp_t prop;
-  for (int r = 0; r < ngpus; ++r) {
-    Local& L = g.loc[r];
-    L = Local();
-    L.rank = r;
-    L.device = ngpus == 1 ? pick_device(0, ndev) : r % ndev;
-    L.first = slice_first(r, n, ngpus);
-    L.n_local = slice_first(r + 1, n, ngpus) - L.first;
-    int e = alloc_local(L);
-    if (e) { nbody_shutdown(); return e; }
-  }
-  {
-    hipError_t pe = hipGetDeviceProperties(&prop, g.loc[0].device);
-    if (pe != hipSuccess) { NB_MARK(); nbody_shutdown(); return (int)pe; }
-  }
-  g.cu_count = prop.multiProcessorCount; g.clock_khz = prop.clockRate;
-  if (ngpus > 1) {
-    for (int a = 0; a < ngpus; ++a)
-      for (int b = 0; b < ngpus; ++b) {
-        if (g.loc[a].device == g.loc[b].device) continue;
-        (void)hipSetDevice(g.loc[a].device);
-        hipError_t e = hipDeviceEnablePeerAccess(g.loc[b].device, 0);
-        if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) { (void)hipGetLastError(); }
-      }
-  }
-  g.init = true;
-  g.opt = Options();
-  int e = reconfigure();
-  if (e) { nbody_shutdown(); return e; }
-  return NBODY_OK;
+  for (int r = 0; r < ngpus; ++r) describe_local(g.loc[r], r, ngpus == 1 ? pick_device(0, ndev) : r % ndev, n, ngpus);
+  return open_context(nullptr);
 }
 
 int nbody_init_rank(int n, int fp64, int tile, int rank, int nranks, const void* uid128) { NB_REFUSE_WHILE_SERVED();
@@ -754,40 +750,8 @@ int nbody_init_rank(int n, int fp64, int tile, int rank, int nranks, const void*
   int ndev = 0;
   NBC(device_count(&ndev));
   g.nranks = nranks; g.nlocal = 1; g.multiprocess = true;
-  Local& L = g.loc[0];
-  L = Local();
-  L.rank = rank;
-  L.device = pick_device(rank, ndev);
-  L.first = slice_first(rank, n, nranks);
-  L.n_local = slice_first(rank + 1, n, nranks) - L.first;
-  int e = alloc_local(L);
-  if (e) { nbody_shutdown(); return e; }
-  hipDeviceProp_t prop;
-  {
-    hipError_t pe = hipGetDeviceProperties(&prop, L.device);
-    if (pe != hipSuccess) { NB_MARK(); nbody_shutdown(); return (int)pe; }
-  }
-  g.cu_count = prop.multiProcessorCount; g.clock_khz = prop.clockRate;
-  if (uid128) {
-    // a communicator is created whenever an id is given — also for nranks = 1, where it carries no traffic in a step
-    // but lets nbody_comm_selftest() push bytes through the same RCCL calls the multi-GPU job makes
-    e = comm_create(L, nranks, rank, uid128);
-    if (e) { nbody_shutdown(); return e; }
-  }
-  g.init = true;
-  g.opt = Options();
-  e = reconfigure();
-  if (e) { nbody_shutdown(); return e; }
-  if (nranks > 1 && L.comm_h) {
-    // One all-gather of the (zeroed) position buffer now: RCCL sets up its rings/channels lazily on the first
-    // collective, and that must not land in a caller's first timed step.
-    hipError_t he = hipSetDevice(L.device);
-    if (he == hipSuccess) he = hipEventRecord(L.ev_own_ready, L.compute);
-    e = he != hipSuccess ? (int)he : enqueue_gather(L.cur);
-    if (!e) e = sync_all();
-    if (e) { nbody_shutdown(); return e; }
-  }
-  return NBODY_OK;
+  describe_local(g.loc[0], rank, pick_device(rank, ndev), n, nranks);
+  return open_context(uid128);
 }
 
 // The strict 1/sqrt (NBODY_ARITH_STRICT, fp32) checked against its own definition on the device that will run it: needs no context.
@@ -797,16 +761,15 @@ static int rsqrt_device() {
   if (device_count(&ndev)) return -1;
   return pick_device(0, ndev);
 }
-struct DevBuf { void* p = nullptr; ~DevBuf() { if (p) (void)hipFree(p); } };
 
 static int rsqrt_selftest_on(int dev, unsigned first_bits, unsigned long long count, unsigned long long* res3) {
   HIPC(hipSetDevice(dev));
-  DevBuf out;
-  HIPC(hipMalloc(&out.p, 3 * sizeof(unsigned long long)));
+  DevMem out;
+  NBC(out.ensure(3 * sizeof(unsigned long long)));
   const unsigned long long zero[3] = {0, 0, ~0ull};
-  HIPC(hipMemcpy(out.p, zero, sizeof(zero), hipMemcpyHostToDevice));
-  HIPC((hipError_t)nbl::launch_rsqrt_selftest_kernel(first_bits, count, (unsigned long long*)out.p));
-  HIPC(hipMemcpy(res3, out.p, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  HIPC(hipMemcpy(out, zero, sizeof(zero), hipMemcpyHostToDevice));
+  HIPC((hipError_t)nbl::launch_rsqrt_selftest_kernel(first_bits, count, out.as<unsigned long long>()));
+  HIPC(hipMemcpy(res3, out, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return NBODY_OK;
 }
 
@@ -859,12 +822,12 @@ int nbody_rsqrt_strict(const float* x, float* y, int n, int ieee_only) { NB_REFU
   const int dev = rsqrt_device();
   if (dev < 0) return NBODY_ERR_NO_DEVICE;
   HIPC(hipSetDevice(dev));
-  DevBuf dx, dy;
-  HIPC(hipMalloc(&dx.p, (size_t)n * sizeof(float)));
-  HIPC(hipMalloc(&dy.p, (size_t)n * sizeof(float)));
-  HIPC(hipMemcpy(dx.p, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-  HIPC((hipError_t)nbl::launch_rsqrt_array_kernel((const float*)dx.p, (float*)dy.p, n, ieee_only));
-  HIPC(hipMemcpy(y, dy.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  DevMem dx, dy;
+  NBC(dx.ensure((size_t)n * sizeof(float)));
+  NBC(dy.ensure((size_t)n * sizeof(float)));
+  HIPC(hipMemcpy(dx, x, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  HIPC((hipError_t)nbl::launch_rsqrt_array_kernel(dx.as<float>(), dy.as<float>(), n, ieee_only));
+  HIPC(hipMemcpy(y, dy, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
   return NBODY_OK;
 }
 
@@ -872,7 +835,7 @@ void nbody_shutdown(void) {
   mailbox_shutdown();   // the mailbox's service thread, if one runs, ends before anything it uses is freed; then its RAM images go
   drop_step_graph();
   for (int l = 0; l < kMaxLocal; ++l) free_local(g.loc[l]);
-  if (g.host_stage) { (void)hipHostFree(g.host_stage); g.host_stage = nullptr; }
+  g.host_stage.reset();
   g.host_gather = nullptr; g.host_gather_user = nullptr;
   g.init = false; g.nlocal = 0; g.nranks = 1;
 }

@@ -16,10 +16,9 @@ namespace {
 int ensure_energy_buffers(Local& L) {
   HIPC(hipSetDevice(L.device));
   const size_t groups = ((size_t)L.n_local + kEnergyRows - 1) / kEnergyRows;
-  if (!L.en_part) HIPC(hipMalloc((void**)&L.en_part, (groups + 1) * kEnergyWords * sizeof(double)));
-  if (!L.en_tot) HIPC(hipMalloc((void**)&L.en_tot, (size_t)g.nranks * kEnergyWords * sizeof(double)));
-  if (!L.en_phi) HIPC(hipMalloc(&L.en_phi, ((size_t)L.n_local + 1) * sizeof(double)));
-  return NBODY_OK;
+  NBC(L.en_part.ensure((groups + 1) * kEnergyWords * sizeof(double)));
+  NBC(L.en_tot.ensure((size_t)g.nranks * kEnergyWords * sizeof(double)));
+  return L.en_phi.ensure(((size_t)L.n_local + 1) * sizeof(double));
 }
 
 // rows [row0, row0 + row_count) of local L: phi into en_phi (totals = false) or the per-workgroup partials into en_part and their
@@ -29,9 +28,9 @@ int launch_energy(Local& L, int row0, int row_count, bool totals) {
   EnergyArgs a;
   memset(&a, 0, sizeof(a));
   a.src = L.pos[L.cur];
-  a.vel = totals ? L.vel : nullptr;
-  a.phi = totals ? nullptr : L.en_phi;
-  a.part = totals ? L.en_part : nullptr;
+  a.vel = totals ? L.vel.as<void>() : nullptr;
+  a.phi = totals ? nullptr : L.en_phi.as<void>();
+  a.part = totals ? L.en_part.as<double>() : nullptr;
   a.n_src = g.n;
   a.first = L.first;
   a.row0 = row0;
@@ -39,7 +38,7 @@ int launch_energy(Local& L, int row0, int row_count, bool totals) {
   HIPC((hipError_t)nbl::launch_energy_kernel(g.fp64, g.opt.arith, L.compute, a));
   if (totals) {
     const int groups = (row_count + kEnergyRows - 1) / kEnergyRows;
-    HIPC((hipError_t)nbl::launch_energy_reduce_kernel(L.compute, L.en_part, groups, L.en_tot + (size_t)L.rank * kEnergyWords));
+    HIPC((hipError_t)nbl::launch_energy_reduce_kernel(L.compute, L.en_part.as<double>(), groups, L.en_tot.as<double>() + (size_t)L.rank * kEnergyWords));
   }
   return NBODY_OK;
 }
@@ -60,7 +59,7 @@ int energy_impl(double* out) {
       HIPC(hipSetDevice(L.device));
       const size_t off = (size_t)L.rank * kEnergyWords;
       HIPC(hipStreamSynchronize(L.compute));   // then a blocking copy into the caller's pageable memory, as the other entry points do
-      HIPC(hipMemcpy(all.data() + off, L.en_tot + off, kEnergyWords * sizeof(double), hipMemcpyDeviceToHost));
+      HIPC(hipMemcpy(all.data() + off, L.en_tot.as<double>() + off, kEnergyWords * sizeof(double), hipMemcpyDeviceToHost));
     }
   }
   for (int q = 0; q < kEnergyWords; ++q) {

@@ -26,13 +26,12 @@ namespace {
 constexpr int kMailboxMaxPoints = 32767;   // ram_depth - 1, S/top_level.vhd:45
 
 // the mailbox's two RAMs as the PS sees them (S/top_level.vhd:100-117, 148-163): pinned host memory the device reads (RAM A)
-// and writes (RAM B, and word 0 of RAM A on completion) itself; allocated on the first request or by nbody_mailbox_open
-void* mb_a = nullptr; void* mb_b = nullptr;
-void* mb_a_dev = nullptr; void* mb_b_dev = nullptr;   // the same memory as the device addresses it
-// completion as the device signals it (mailbox_done_kernel): a sequence word in pinned memory that the PS never writes, and the
-// device-side start stamp of the tick counter
-unsigned* mb_seq = nullptr; unsigned* mb_seq_dev = nullptr;
-unsigned long long* mb_t0_dev = nullptr;
+// and writes (RAM B, and word 0 of RAM A on completion) itself; allocated on the first request or by nbody_mailbox_open.  The context
+// owns them (Global::mb: a, b); here, the same memory as the device addresses it
+void* mb_a_dev = nullptr; void* mb_b_dev = nullptr;
+// completion as the device signals it (mailbox_done_kernel): a sequence word in pinned memory that the PS never writes (Global::mb: seq),
+// and the device-side start stamp of the tick counter (t0)
+unsigned* mb_seq_dev = nullptr;
 unsigned mb_seq_next = 0;       // sequence number of the last request whose completion the device was asked to write
 int mb_rt_khz = 100000;         // rate of s_memrealtime (100 MHz on gfx950; hipDeviceAttributeWallClockRate)
 int mb_done_by_device = 1;      // NBODY_MAILBOX_DONE=host: the host thread writes word 0 after hipStreamQuery says so (round 5's form; A/B)
@@ -43,18 +42,18 @@ int mb_direct_max = 256;        // requests of at most this many bodies whose fo
                                 // its 64 workgroups would read 16 KiB over PCIe): hence 256
 
 int mailbox_rams() {   // RAM A and RAM B: capacity + 1 words each (+ slack), pinned, mapped, coherent
-  if (mb_a && mb_b && mb_seq && mb_t0_dev) return NBODY_OK;
+  if (mb_seq_dev) return NBODY_OK;   // (the last thing that can fail below)
   Local& L = g.loc[0];
   HIPC(hipSetDevice(L.device));
   const unsigned flags = hipHostMallocMapped | hipHostMallocCoherent;
   const size_t bytes = ((size_t)g.cap + 1 + 64) * 16;
-  if (!mb_a) { HIPC(hipHostMalloc(&mb_a, bytes, flags)); memset(mb_a, 0, bytes); }
-  if (!mb_b) { HIPC(hipHostMalloc(&mb_b, bytes, flags)); memset(mb_b, 0, bytes); }
-  if (!mb_seq) { HIPC(hipHostMalloc((void**)&mb_seq, 64, flags)); memset(mb_seq, 0, 64); mb_seq_next = 0; }
-  if (!mb_t0_dev) { HIPC(hipMalloc((void**)&mb_t0_dev, 64)); HIPC(hipMemset(mb_t0_dev, 0, 64)); }
-  HIPC(hipHostGetDevicePointer(&mb_a_dev, mb_a, 0));
-  HIPC(hipHostGetDevicePointer(&mb_b_dev, mb_b, 0));
-  HIPC(hipHostGetDevicePointer((void**)&mb_seq_dev, mb_seq, 0));
+  NBC(g.mb.a.ensure(bytes, flags, true));
+  NBC(g.mb.b.ensure(bytes, flags, true));
+  NBC(g.mb.seq.ensure(64, flags, true));
+  NBC(g.mb.t0.ensure(64, true));
+  HIPC(hipHostGetDevicePointer(&mb_a_dev, g.mb.a, 0));
+  HIPC(hipHostGetDevicePointer(&mb_b_dev, g.mb.b, 0));
+  HIPC(hipHostGetDevicePointer((void**)&mb_seq_dev, g.mb.seq, 0));
   int khz = 0;
   if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, L.device) == hipSuccess && khz > 0) mb_rt_khz = khz;
   else (void)hipGetLastError();
@@ -104,13 +103,14 @@ int wait_stream(hipStream_t stream) {
 // call; after 300 us (N = 32767 takes 500) a blocking hipStreamSynchronize takes over, so nothing can spin for ever.
 int wait_seq(hipStream_t stream, unsigned seq) {
   const auto t0 = std::chrono::steady_clock::now();
+  const unsigned* const word = g.mb.seq.as<unsigned>();
   unsigned spins = 0;
   for (;;) {
-    if (__atomic_load_n(mb_seq, __ATOMIC_ACQUIRE) == seq) break;
+    if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == seq) break;
     __builtin_ia32_pause();
     if ((++spins & 63u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(300)) {
       HIPC(hipStreamSynchronize(stream));
-      if (__atomic_load_n(mb_seq, __ATOMIC_ACQUIRE) != seq) { NB_MARK(); return NBODY_ERR_STATE; }   // the queue drained and the word is not there
+      if (__atomic_load_n(word, __ATOMIC_ACQUIRE) != seq) { NB_MARK(); return NBODY_ERR_STATE; }   // the queue drained and the word is not there
       mb_since_query = 0;
       return NBODY_OK;
     }
@@ -126,16 +126,17 @@ int mailbox_launches(Local& L, int num_pts, bool done_by_device, unsigned seq, i
   // RAM B's write port: the force launch (or its combine) stores {Fx, Fy, Fz, 0} of body k at word k itself — row k - 1 of the launch
   // goes to force_dst[k - 1] and force_dst is word 1 —; word 0 and the words beyond N are never written       S/compute_store.vhd:213, 221-242
   Redirect rd = {(char*)mb_b_dev + 16};
+  unsigned long long* const t0 = g.mb.t0.as<unsigned long long>();
   // bodies are words 1..N                                              S/top_level.vhd:55, 206-208
   // A handful of bodies in the faithful mode: the 16-row kernel reads RAM A itself (its tile loads ARE the PCIe reads) and stamps the tick
   // count's start; everything else goes through the ingest launch, which reads RAM A once for all workgroups (into pos[cur]).
-  if (done_by_device && num_pts <= mb_direct_max && takes_rows16(num_pts)) { rd.src_direct = (const char*)mb_a_dev + 16; rd.t0_stamp = mb_t0_dev; }
-  else HIPC((hipError_t)nbl::launch_ingest_kernel(L.compute, L.pos[L.cur], (const char*)mb_a_dev + 16, num_pts, done_by_device ? mb_t0_dev : nullptr));
+  if (done_by_device && num_pts <= mb_direct_max && takes_rows16(num_pts)) { rd.src_direct = (const char*)mb_a_dev + 16; rd.t0_stamp = t0; }
+  else HIPC((hipError_t)nbl::launch_ingest_kernel(L.compute, L.pos[L.cur], (const char*)mb_a_dev + 16, num_pts, done_by_device ? t0 : nullptr));
   const Finish fin = {false, false, true};
   NBC(launch_force(L, 0, num_pts, g.cfg.nslices - 1, g.cfg.nslices, fin, 0.f, 0.0, &rd));
   NBC(launch_combine(L, 0, num_pts, fin, 0.f, 0.0, &rd));
   if (!done_by_device) return NBODY_OK;
-  HIPC((hipError_t)nbl::launch_mailbox_done_kernel(L.compute, mb_a_dev, mb_seq_dev, mb_t0_dev, seq, (unsigned)clock_khz, (unsigned)mb_rt_khz));
+  HIPC((hipError_t)nbl::launch_mailbox_done_kernel(L.compute, mb_a_dev, mb_seq_dev, t0, seq, (unsigned)clock_khz, (unsigned)mb_rt_khz));
   return NBODY_OK;
 }
 
@@ -148,11 +149,11 @@ int mailbox_request(const void* ram_a, void* ram_b, int num_pts, int clock_khz, 
   ActiveN scope;
   NBC(scope.enter(num_pts));
   // RAM A: the library's own pinned image is read in place; any other host buffer is copied into it first
-  if (ram_a != mb_a) memcpy((char*)mb_a + 16, (const char*)ram_a + 16, (size_t)num_pts * 16);
+  if (ram_a != g.mb.a) memcpy(g.mb.a.as<char>() + 16, (const char*)ram_a + 16, (size_t)num_pts * 16);
   L.all_present = true;
   const bool by_device = mb_done_by_device != 0;
   const unsigned seq = by_device ? ++mb_seq_next : 0u;
-  if (by_device && ram_a != mb_a) ((uint32_t*)mb_a)[0] = 1u;   // (the device clears THIS image's BEGIN; the caller's word 0 follows below)
+  if (by_device && ram_a != g.mb.a) g.mb.a.as<uint32_t>()[0] = 1u;   // (the device clears THIS image's BEGIN; the caller's word 0 follows below)
   TicketGuard guard;   // up to the request's completion
   const int rc = mailbox_launches(L, num_pts, by_device, seq, clock_khz);
   if (rc) {
@@ -162,7 +163,7 @@ int mailbox_request(const void* ram_a, void* ram_b, int num_pts, int clock_khz, 
   if (by_device) { NBC(wait_seq(L.compute, seq)); *device_done = true; }
   else NBC(wait_stream(L.compute));
   guard.done();
-  if (ram_b != mb_b) memcpy((char*)ram_b + 16, (char*)mb_b + 16, (size_t)num_pts * 16);   // words 1..N; the caller's word 0 is not written either
+  if (ram_b != g.mb.b) memcpy((char*)ram_b + 16, g.mb.b.as<char>() + 16, (size_t)num_pts * 16);   // words 1..N; the caller's word 0 is not written either
   return NBODY_OK;
 }
 
@@ -189,8 +190,8 @@ int mailbox_run_impl(void* ram_a, void* ram_b, int clock_khz, bool served) {
   if (rc && !served) return rc;
   if (device_done) {
     // `complete` was the device's: word 0 of the library's image already reads {ticks, BEGIN = 0}.  A caller's own image gets that word.
-    if (ram_a != mb_a) {
-      const uint32_t* d0 = (const uint32_t*)mb_a;
+    if (ram_a != g.mb.a) {
+      const uint32_t* d0 = g.mb.a.as<uint32_t>();
       w0[1] = d0[1]; w0[2] = 0; w0[3] = 0;
       __atomic_store_n(&w0[0], 0u, __ATOMIC_RELEASE);
     }
@@ -217,7 +218,7 @@ std::atomic<long long> g_served{0};
 std::atomic<int> g_serve_khz{0};
 
 void serve_loop() {
-  uint32_t* w0 = (uint32_t*)mb_a;
+  uint32_t* w0 = g.mb.a.as<uint32_t>();
   unsigned idle = 0;
   while (g_serve_on.load(std::memory_order_acquire)) {
     if (!(__atomic_load_n(&w0[0], __ATOMIC_ACQUIRE) & 1u)) {
@@ -228,7 +229,7 @@ void serve_loop() {
       continue;
     }
     idle = 0;
-    (void)mailbox_run_impl(mb_a, mb_b, g_serve_khz.load(std::memory_order_relaxed), true);
+    (void)mailbox_run_impl(g.mb.a, g.mb.b, g_serve_khz.load(std::memory_order_relaxed), true);
     g_served.fetch_add(1, std::memory_order_release);
   }
 }
@@ -245,10 +246,8 @@ struct ServeGuard { ~ServeGuard() { serve_stop(); } } g_serve_guard;
 
 void mailbox_shutdown() {
   serve_stop();
-  if (mb_a) { (void)hipHostFree(mb_a); mb_a = nullptr; mb_a_dev = nullptr; }
-  if (mb_b) { (void)hipHostFree(mb_b); mb_b = nullptr; mb_b_dev = nullptr; }
-  if (mb_seq) { (void)hipHostFree(mb_seq); mb_seq = nullptr; mb_seq_dev = nullptr; }
-  if (mb_t0_dev) { (void)hipFree(mb_t0_dev); mb_t0_dev = nullptr; }
+  g.mb = {};
+  mb_a_dev = mb_b_dev = nullptr; mb_seq_dev = nullptr;
   mb_seq_next = 0; mb_since_query = 0;
 }
 bool mailbox_serving() { return g_serve_on.load(std::memory_order_acquire) != 0; }
@@ -266,27 +265,27 @@ int nbody_mailbox_open(int capacity, int faithful) {
   if (capacity == 0) capacity = kMailboxMaxPoints;
   if (capacity < 1 || capacity > kMailboxMaxPoints) return NBODY_ERR_ARG;
   NBC(nbody_init(capacity, 1, 0, 0));
-  int rc = mailbox_rams();
+  OpenGuard guard;
+  NBC(mailbox_rams());
   // the partial sums of the largest segmentation any request can resolve to (64 segments), so that no request allocates
-  if (!rc) rc = ensure_partial(g.loc[0], 64);
-  if (!rc && faithful) {
+  NBC(ensure_partial(g.loc[0], 64));
+  if (faithful) {
     // the PL block's own bits: its rounding points (S/dxy.vhd:113-122, S/dzsoft.vhd:201-202, S/dxyz_soft.vhd:149-150) with 1/sqrt rounded
     // once — after this device has proved that 1/sqrt —, its sixteen partial sums, rotation and adder tree (S/fxyz.vhd:129-184,
     // S/final_adder.vhd:88-104) over ONE stream of all N sources per body (S/top_level.vhd:233-254)
-    rc = nbody_set_option(NBODY_OPT_ARITH, NBODY_ARITH_REFERENCE_STRICT);
-    if (!rc) rc = nbody_set_option(NBODY_OPT_SUM_ORDER, NBODY_SUM_FPGA16);
-    if (!rc) rc = nbody_set_option(NBODY_OPT_JSUB, 1);
+    NBC(nbody_set_option(NBODY_OPT_ARITH, NBODY_ARITH_REFERENCE_STRICT));
+    NBC(nbody_set_option(NBODY_OPT_SUM_ORDER, NBODY_SUM_FPGA16));
+    NBC(nbody_set_option(NBODY_OPT_JSUB, 1));
   }
-  if (rc) { nbody_shutdown(); return rc; }
-  return NBODY_OK;
+  return guard.commit();
 }
 
 int nbody_mailbox_rams(void** ram_a, void** ram_b, int* capacity) {
   if (!g.init) return NBODY_ERR_NOT_INIT;
   if (g.fp64 || g.nranks != 1) return NBODY_ERR_UNSUPPORTED;
   if (!mailbox_serving()) NBC(mailbox_rams());   // (a served mailbox has them already; nothing is allocated beside the service thread)
-  if (ram_a) *ram_a = mb_a;
-  if (ram_b) *ram_b = mb_b;
+  if (ram_a) *ram_a = g.mb.a;
+  if (ram_b) *ram_b = g.mb.b;
   if (capacity) *capacity = g.cap < kMailboxMaxPoints ? g.cap : kMailboxMaxPoints;
   return NBODY_OK;
 }

@@ -7,6 +7,8 @@
 //   energy.cpp    nbody_energy, nbody_potential_rows(_d): the energy pass on every local and the sum over the ranks
 // Only kernels.hip and energy.hip are device code (a minute of hipcc, as one code object through device.hip); the others are host
 // C++ (seconds).  gfx950 only, no CPU fallback anywhere.
+// Ownership: every stream, event, device and pinned allocation the context uses lives in an owning handle (Stream, Event, DevMem, Pinned,
+// below) that is a member of Global or of one of its Locals; nbody_shutdown() releases them all, and nothing does at process exit (see `g`).
 //
 // Data layout in HBM (per rank; N bodies in total, the rank owns n_local of them starting at first_body):
 //   pos[2]   2 x N words      full position set, double-buffered: a step reads pos[cur] and writes the
@@ -52,9 +54,50 @@ constexpr int kMaxRanks = 64;
 constexpr int kTimerRing = 256;
 constexpr int kGraphSteps = 32;    // steps per replayed HIP graph once a call brings at least twice as many
 
+// ---- owning handles: one HIP resource each, move-only, released by reset(), by assignment over them or by their destructor ----
+template <typename T, hipError_t (*Destroy)(T)>
+struct Owned {
+  T h = nullptr;
+  Owned() = default;
+  Owned(Owned&& o) noexcept : h(o.h) { o.h = nullptr; }
+  Owned& operator=(Owned&& o) noexcept { std::swap(h, o.h); return *this; }   // (what this held goes with o)
+  ~Owned() { reset(); }
+  void reset() { if (h) { (void)Destroy(h); h = nullptr; } }
+  T* put() { reset(); return &h; }   // for the HIP call that creates the resource
+  operator T() const { return h; }
+  template <typename U> U* as() const { return (U*)h; }   // memory: the typed pointer ForceArgs, EnergyArgs and RCCL calls take
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+using Graph = Owned<hipGraph_t, hipGraphDestroy>;   // scoped: a capture's graph until it is instantiated
+
+// device memory (on the device that is current when it is allocated)
+struct DevMem : Owned<void*, hipFree> {
+  size_t bytes = 0;
+  // at least `need` bytes: kept if large enough, else freed and allocated anew (*moved: the address is no longer what it was)
+  int ensure(size_t need, bool zero = false, bool* moved = nullptr) {
+    if (h && need <= bytes) return NBODY_OK;
+    if (moved) *moved = true;
+    reset(); bytes = 0;
+    HIPC(hipMalloc(&h, need));
+    bytes = need;
+    if (zero) HIPC(hipMemset(h, 0, need));
+    return NBODY_OK;
+  }
+};
+// pinned host memory; its users size it once per context, for the context's capacity
+struct Pinned : Owned<void*, hipHostFree> {
+  int ensure(size_t bytes, unsigned flags, bool zero = false) {
+    if (h) return NBODY_OK;
+    HIPC(hipHostMalloc(&h, bytes, flags));
+    if (zero) memset(h, 0, bytes);
+    return NBODY_OK;
+  }
+};
+
 // a ring of HIP event pairs whose durations are summed lazily (no host sync while a step is being enqueued)
 struct EventTimer {
-  hipEvent_t t0[kTimerRing] = {}, t1[kTimerRing] = {};
+  Event t0[kTimerRing], t1[kTimerRing];
   int head = 0, count = 0;
   double ms = 0.0;
   long long n = 0;
@@ -63,23 +106,21 @@ struct EventTimer {
 struct Local {
   int device = 0, rank = 0;
   int first = 0, n_local = 0;          // owned bodies
-  hipStream_t compute = nullptr, comm = nullptr;
-  void* pos[2] = {nullptr, nullptr};
-  void* vel = nullptr;
-  void* partial = nullptr;
-  size_t partial_words = 0;            // capacity of `partial`
-  unsigned* tickets = nullptr;         // arrival counters: one per wave of every block of 256 rows
-  size_t ticket_words = 0;             // capacity of `tickets`
-  void* force = nullptr;
-  void* full_scratch = nullptr;        // N words: all-gather of a sharded array for the host (multi-process)
-  double* en_part = nullptr;           // energy pass (energy.cpp): per-workgroup fp64 partials of {T, U, P, L} ...
-  double* en_tot = nullptr;            // ... the ranks' totals, 8 doubles at word `rank` (all P after an all-gather) ...
-  void* en_phi = nullptr;              // ... and phi of the rows asked for (context precision)
+  Stream compute, comm;                // (declared first: destroyed after everything that ran on them)
+  DevMem pos[2];
+  DevMem vel;
+  DevMem partial;                      // grown by ensure_partial
+  DevMem tickets;                      // arrival counters (unsigned): one per 64 rows, see ticket_words()
+  DevMem force;
+  DevMem full_scratch;                 // N words: all-gather of a sharded array for the host (multi-process)
+  DevMem en_part;                      // energy pass (energy.cpp): per-workgroup fp64 partials of {T, U, P, L} ...
+  DevMem en_tot;                       // ... the ranks' totals, 8 doubles at word `rank` (all P after an all-gather) ...
+  DevMem en_phi;                       // ... and phi of the rows asked for (context precision)
   int cur = 0;
   bool all_present = true;             // pos[cur] holds every slice
-  hipEvent_t ev_own_ready = nullptr;   // the rank's slice of pos[cur] is written
-  hipEvent_t ev_comm_go = nullptr;     // the transfer stream has seen ev_own_ready: its RCCL kernel is next on its queue
-  hipEvent_t ev_gather[kMaxRanks] = {};
+  Event ev_own_ready;                  // the rank's slice of pos[cur] is written
+  Event ev_comm_go;                    // the transfer stream has seen ev_own_ready: its RCCL kernel is next on its queue
+  Event ev_gather[kMaxRanks];
   ncclComm_t comm_h = nullptr;
   EventTimer kern;   // force kernels (NBODY_OPT_TIMING)
   EventTimer wait;   // how long the compute stream sat waiting for arriving slices: exposed communication
@@ -117,7 +158,9 @@ typedef int (*host_gather_fn)(void* user, void* host_words, int n_total, int wor
 struct Global {
   host_gather_fn host_gather = nullptr;   // multi-process fallback transport: slices exchanged through host memory
   void* host_gather_user = nullptr;
-  void* host_stage = nullptr;             // pinned staging buffer, N words
+  Pinned host_stage;                      // staging buffer, N words
+  // the mailbox's two RAMs as the PS sees them (mailbox.cpp: mailbox_rams), its completion word, and the device-side start stamp
+  struct MailboxMem { Pinned a, b, seq; DevMem t0; } mb;
   // HIP graph of an even number of consecutive steps (the position buffers swap every step, so a pair returns to the same state):
   // replayed by nbody_step when one GPU runs many short steps (launch-bound regime)
   hipGraphExec_t step_graph = nullptr;
@@ -140,7 +183,17 @@ struct Global {
   // request (which switches n, n_local and cfg for its own duration) — so the caller's thread may read them while the service thread works
   struct View { int n = 0, n_local = 0; LaunchConfig cfg; } view;
 };
-extern Global g;
+// The context is never destroyed: it is allocated once and its handles are released by nbody_shutdown() alone.  A process that exits
+// without nbody_shutdown() therefore frees nothing and makes no HIP call after main() returns (static destructors may run after the HIP
+// runtime's own teardown).
+extern Global& g;
+
+// nbody_shutdown() on every way out of opening a context (nbody_init, nbody_init_rank, nbody_mailbox_open) that is not commit()
+struct OpenGuard {
+  bool committed = false;
+  int commit() { committed = true; return NBODY_OK; }
+  ~OpenGuard() { if (!committed) nbody_shutdown(); }
+};
 
 inline size_t word_bytes() { return g.fp64 ? 32 : 16; }
 inline char* word_ptr(void* base, size_t word) { return (char*)base + word * word_bytes(); }

@@ -8,6 +8,8 @@
 // bounds, per-segment partial sums, one arrival counter per 64 rows, ascending combine, apply (store / kick / drift), the mailbox's
 // ingest and device-written completion.  The energy pass writes values a test can predict from what it reads (see energy()).  It says nothing about the kernels' arithmetic (the GPU tests do); it checks the host's logic:
 // buffer sizes, offsets, state switching per request, the service thread's hand-over, the guard, lifetimes.
+// For the failure paths: hip_stub_live(kind) counts what is outstanding of each kind of resource, and hip_stub_fail_nth(k) makes the k-th
+// creating call from now fail once, with hipErrorOutOfMemory and nothing created.
 #include <hip/hip_runtime.h>
 
 #include <atomic>
@@ -116,9 +118,23 @@ void energy(const nbe::EnergyArgs& a) {
 // its force launch's first rows is left part-counted, as a device fault part-way through the launch would leave it
 std::atomic<int> g_lose_completion{0};
 std::atomic<unsigned*> g_last_tickets{nullptr};
+
+enum { kDevice, kPinned, kEvent, kStream, kGraph, kGraphExec, kKinds };
+std::atomic<long> g_live[kKinds];
+std::atomic<int> g_fail_in{0};   // creating calls until the one that fails (0: none armed)
+// every creating call: false = this is the one to fail; else one more of `kind` is outstanding
+bool create(int kind) {
+  if (g_fail_in.load() > 0 && g_fail_in.fetch_sub(1) == 1) return false;
+  g_live[kind]++;
+  return true;
+}
+void destroyed(int kind, const void* p) { if (p) g_live[kind]--; }
 }  // namespace
 
 extern "C" void hip_stub_lose_next_completion(void) { g_lose_completion.store(1); }
+extern "C" long hip_stub_live(int kind) { return kind >= 0 && kind < kKinds ? g_live[kind].load() : -1; }
+extern "C" void hip_stub_fail_nth(int k) { g_fail_in.store(k); }
+extern "C" int hip_stub_fail_pending(void) { return g_fail_in.load(); }   // > 0: the armed failure has not been reached
 
 namespace nbl {
 bool diag_build() { return false; }
@@ -177,32 +193,32 @@ hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) { memset(p, 0, sizeof
 hipError_t hipDeviceGetAttribute(int* v, hipDeviceAttribute_t a, int) { *v = a == hipDeviceAttributeWallClockRate ? 100000 : 0; return hipSuccess; }
 hipError_t hipDeviceGetStreamPriorityRange(int* least, int* greatest) { *least = 0; *greatest = -1; return hipSuccess; }
 hipError_t hipDeviceEnablePeerAccess(int, unsigned) { return hipSuccess; }
-hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
-hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-hipError_t hipHostMalloc(void** p, size_t n, unsigned) { *p = aligned_alloc(64, (n + 63) / 64 * 64); return *p ? hipSuccess : hipErrorOutOfMemory; }
-hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+hipError_t hipMalloc(void** p, size_t n) { if (!create(kDevice)) return hipErrorOutOfMemory; *p = malloc(n ? n : 1); return hipSuccess; }
+hipError_t hipFree(void* p) { destroyed(kDevice, p); free(p); return hipSuccess; }
+hipError_t hipHostMalloc(void** p, size_t n, unsigned) { if (!create(kPinned)) return hipErrorOutOfMemory; *p = aligned_alloc(64, (n + 63) / 64 * 64); return hipSuccess; }
+hipError_t hipHostFree(void* p) { destroyed(kPinned, p); free(p); return hipSuccess; }
 hipError_t hipHostGetDevicePointer(void** d, void* h, unsigned) { *d = h; return hipSuccess; }
 hipError_t hipMemset(void* p, int v, size_t n) { memset(p, v, n); return hipSuccess; }
 hipError_t hipMemsetAsync(void* p, int v, size_t n, hipStream_t) { enqueue([=] { memset(p, v, n); }); return hipSuccess; }
 hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { memcpy(d, s, n); return hipSuccess; }
 hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t) { enqueue([=] { memcpy(d, s, n); }); return hipSuccess; }
 hipError_t hipMemcpyPeerAsync(void* d, int, const void* s, int, size_t n, hipStream_t) { enqueue([=] { memcpy(d, s, n); }); return hipSuccess; }
-hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = (hipStream_t)malloc(8); return hipSuccess; }
-hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { *s = (hipStream_t)malloc(8); return hipSuccess; }
-hipError_t hipStreamDestroy(hipStream_t s) { free(s); return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { if (!create(kStream)) return hipErrorOutOfMemory; *s = (hipStream_t)malloc(8); return hipSuccess; }
+hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned f, int) { return hipStreamCreateWithFlags(s, f); }
+hipError_t hipStreamDestroy(hipStream_t s) { destroyed(kStream, s); free(s); return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamQuery(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-hipError_t hipEventCreate(hipEvent_t* e) { *e = (hipEvent_t) new FakeEvent{0.0}; return hipSuccess; }
+hipError_t hipEventCreate(hipEvent_t* e) { if (!create(kEvent)) return hipErrorOutOfMemory; *e = (hipEvent_t) new FakeEvent{0.0}; return hipSuccess; }
 hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
-hipError_t hipEventDestroy(hipEvent_t e) { delete (FakeEvent*)e; return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t e) { destroyed(kEvent, e); delete (FakeEvent*)e; return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t) { if (!t_capturing) ((FakeEvent*)e)->ms = now_ms(); return hipSuccess; }
 hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventElapsedTime(float* ms, hipEvent_t a, hipEvent_t b) { *ms = (float)(((FakeEvent*)b)->ms - ((FakeEvent*)a)->ms); return hipSuccess; }
-hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { t_capture = new FakeGraph; t_capturing = true; return hipSuccess; }
+hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { t_capture = new FakeGraph; g_live[kGraph]++; t_capturing = true; return hipSuccess; }
 hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t* g) { t_capturing = false; *g = (hipGraph_t)t_capture; t_capture = nullptr; return hipSuccess; }
-hipError_t hipGraphInstantiate(hipGraphExec_t* x, hipGraph_t g, hipGraphNode_t*, char*, size_t) { *x = (hipGraphExec_t) new FakeGraph(*(FakeGraph*)g); return hipSuccess; }
-hipError_t hipGraphDestroy(hipGraph_t g) { delete (FakeGraph*)g; return hipSuccess; }
-hipError_t hipGraphExecDestroy(hipGraphExec_t x) { delete (FakeGraph*)x; return hipSuccess; }
+hipError_t hipGraphInstantiate(hipGraphExec_t* x, hipGraph_t g, hipGraphNode_t*, char*, size_t) { if (!create(kGraphExec)) return hipErrorOutOfMemory; *x = (hipGraphExec_t) new FakeGraph(*(FakeGraph*)g); return hipSuccess; }
+hipError_t hipGraphDestroy(hipGraph_t g) { destroyed(kGraph, g); delete (FakeGraph*)g; return hipSuccess; }
+hipError_t hipGraphExecDestroy(hipGraphExec_t x) { destroyed(kGraphExec, x); delete (FakeGraph*)x; return hipSuccess; }
 hipError_t hipGraphLaunch(hipGraphExec_t x, hipStream_t) { for (auto& f : ((FakeGraph*)x)->ops) f(); return hipSuccess; }
 }

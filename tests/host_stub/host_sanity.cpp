@@ -7,12 +7,16 @@
 #include <string.h>
 
 #include <atomic>
+#include <functional>
 #include <thread>
 #include <vector>
 
 #include "../../include/nbody.h"
 
 extern "C" void hip_stub_lose_next_completion(void);   // hip_stub.cpp
+extern "C" long hip_stub_live(int kind);               // outstanding: 0 device allocations, 1 pinned, 2 events, 3 streams, 4 graphs, 5 graph execs
+extern "C" void hip_stub_fail_nth(int k);              // the k-th creating call from now fails once (0: disarm)
+extern "C" int hip_stub_fail_pending(void);            // > 0: the armed failure has not been reached
 
 #define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "host_sanity: line %d: %s\n", __LINE__, #cond); exit(1); } } while (0)
 #define OK(call) do { int rc_ = (call); if (rc_) { fprintf(stderr, "host_sanity: line %d: %s = %d (%s)\n", __LINE__, #call, rc_, nbody_error_string(rc_)); exit(1); } } while (0)
@@ -24,6 +28,14 @@ static void bodies(std::vector<float>& p, int n, unsigned seed) {
 }
 
 static long long info(int key) { long long v = -1; OK(nbody_get_info(key, &v)); return v; }
+
+// nbody_shutdown() leaves nothing of any kind behind
+static void shutdown_at(int line) {
+  nbody_shutdown();
+  for (int kind = 0; kind < 6; ++kind)
+    if (hip_stub_live(kind)) { fprintf(stderr, "host_sanity: line %d: %ld of kind %d live after nbody_shutdown\n", line, hip_stub_live(kind), kind); exit(1); }
+}
+#define SHUTDOWN() shutdown_at(__LINE__)
 
 // nbody_energy and nbody_potential_rows(_d) on the uploaded state, against what the stub's energy pass writes (hip_stub.cpp energy()):
 // phi of body i = x_i - i; totals {n / 2, n, sum of vel.x, 4n, 5n, 6n, 7n, 8n}.  Windows: all rows, one across the first two slices of a
@@ -48,9 +60,108 @@ static void check_energy(int n, const std::vector<T>& pos, const std::vector<T>&
   CHECK(potential_rows(n - 1, 2, buf) == NBODY_ERR_ARG && potential_rows(-1, 1, buf) == NBODY_ERR_ARG && potential_rows(0, 0, buf) == NBODY_ERR_ARG);
 }
 
+// One entry point under creation-failure injection.  `setup` brings a fresh context to the point before the call (no injection), `call`
+// is the call, `verify` checks its results.  k = 1, 2, 3, ...: the k-th creating call (hipMalloc, hipHostMalloc, hipEventCreate*,
+// hipStreamCreate*, hipGraphInstantiate) inside `call` fails, until the call no longer reaches the armed failure.  Every k is walked, the
+// timer rings' 2 x 2 x 256 events per local included (no stride).  A failed call must say so, nbody_shutdown() must then leave nothing,
+// and the same call without injection must then work.  Returns the number of creating calls the call makes.
+static int sweep(const char* name, const std::function<void()>& setup, const std::function<int()>& call, const std::function<void()>& verify) {
+  for (int k = 1;; ++k) {
+    setup();
+    hip_stub_fail_nth(k);
+    const int rc = call();
+    const bool reached = hip_stub_fail_pending() == 0;
+    hip_stub_fail_nth(0);
+    if (reached && rc == 0) { fprintf(stderr, "host_sanity: %s: creating call %d failed and the call returned 0\n", name, k); exit(1); }
+    if (!reached) {
+      if (rc) { fprintf(stderr, "host_sanity: %s: %d (%s) without an injected failure\n", name, rc, nbody_error_string(rc)); exit(1); }
+      verify();
+      SHUTDOWN();
+      return k - 1;
+    }
+    SHUTDOWN();
+    setup();
+    OK(call());
+    verify();
+    SHUTDOWN();
+  }
+}
+
+// the bodies of seeds (1, 2) uploaded and stepped `steps` times (or, step_now = false, the context as the caller stepped it):
+// positions and velocities back as {pos, vel}
+static std::vector<float> stepped(int n, int steps, bool step_now = true) {
+  std::vector<float> p, v, out((size_t)n * 8);
+  bodies(p, n, 1); bodies(v, n, 2);
+  BodySystem b = {p.data(), v.data()};
+  if (step_now) { OK(nbody_upload(&b)); OK(nbody_step(0.01f, steps)); }
+  OK(nbody_sync());
+  BodySystem o = {out.data(), out.data() + (size_t)n * 4};
+  OK(nbody_download(&o));
+  CHECK(info(NBODY_INFO_STEPS_DONE) == steps);
+  return out;
+}
+
+// the failure paths of everything that creates a resource: see sweep()
+static void failure_sweeps(bool three_devices) {
+  const int n = 200, n3 = 100;   // n3: ragged over three devices (34, 33, 33)
+  std::vector<float> pos, vel;
+  bodies(pos, n, 1); bodies(vel, n, 2);
+  BodySystem b = {pos.data(), vel.data()};
+  auto fresh = [&] { OK(nbody_init(n, 1, 0, 0)); OK(nbody_upload(&b)); };
+  // what the calls give on contexts that never saw a failure
+  OK(nbody_init(n, 1, 0, 0));
+  const std::vector<float> want4 = stepped(n, 4);
+  SHUTDOWN();
+  fresh();
+  const std::vector<float> want70 = stepped(n, 70);
+  OK(nbody_set_option(NBODY_OPT_JSUB, 64));
+  std::vector<float> wantf((size_t)n * 4), f((size_t)n * 4);
+  OK(nbody_forces(pos.data(), wantf.data(), n));
+  SHUTDOWN();
+
+  int made = sweep("nbody_init", [] {}, [&] { return nbody_init(n, 1, 0, 0); }, [&] { CHECK(info(NBODY_INFO_N) == n && stepped(n, 4) == want4); });
+  CHECK(made >= 2 + 5 + 3 + 4 * 256);   // streams, buffers, events and both timer rings were all walked
+  if (three_devices) {
+    OK(nbody_init(n3, 3, 0, 0));
+    const std::vector<float> want3 = stepped(n3, 4);
+    SHUTDOWN();
+    made = sweep("nbody_init x 3", [] {}, [&] { return nbody_init(n3, 3, 0, 0); }, [&] { CHECK(info(NBODY_INFO_NRANKS) == 3 && stepped(n3, 4) == want3); });
+    CHECK(made >= 3 * (2 + 5 + 5 + 4 * 256));
+  }
+  made = sweep("nbody_init_rank", [] {}, [&] { return nbody_init_rank(n3, 0, 0, 1, 3, nullptr); },
+               [&] { CHECK(info(NBODY_INFO_NRANKS) == 3 && info(NBODY_INFO_RANK) == 1 && info(NBODY_INFO_FIRST_BODY) == 34 && info(NBODY_INFO_N_LOCAL) == 33); });
+  CHECK(made >= 2 + 5 + 5 + 4 * 256);
+  {  // the mailbox in its faithful mode (the strict proof allocates too): one request's RAM B against a context that never saw a failure
+    std::vector<uint32_t> a((size_t)(64 + 1) * 4), want_b;
+    std::vector<float> rb((size_t)(64 + 1) * 4);
+    auto request = [&] {
+      a[0] = 1; a[1] = 9; a[2] = a[3] = 0; memcpy(a.data() + 4, pos.data(), 9 * 16);
+      OK(nbody_mailbox_run(a.data(), rb.data(), 300000));
+      return std::vector<uint32_t>((uint32_t*)rb.data() + 4, (uint32_t*)rb.data() + 4 + 9 * 4);
+    };
+    OK(nbody_mailbox_open(64, 1));
+    want_b = request();
+    SHUTDOWN();
+    made = sweep("nbody_mailbox_open", [] {}, [] { return nbody_mailbox_open(64, 1); }, [&] { CHECK(info(NBODY_INFO_N) == 64 && request() == want_b); });
+    CHECK(made >= 2 + 5 + 3 + 4 * 256 + 4);
+  }
+  double e[NBODY_ENERGY_WORDS];
+  std::vector<float> phi(n);
+  made = sweep("nbody_energy", fresh, [&] { return nbody_energy(e); }, [&] { check_energy(n, pos, vel, nbody_potential_rows); });
+  CHECK(made == 3);
+  made = sweep("nbody_potential_rows", fresh, [&] { return nbody_potential_rows(0, n, phi.data()); }, [&] { check_energy(n, pos, vel, nbody_potential_rows); });
+  CHECK(made == 3);
+  made = sweep("nbody_step", fresh, [] { return nbody_step(0.01f, 70); }, [&] { CHECK(stepped(n, 70, false) == want70); });   // capture and instantiate
+  CHECK(made == 1);
+  made = sweep("nbody_forces", fresh, [&] { int rc = nbody_set_option(NBODY_OPT_JSUB, 64); return rc ? rc : nbody_forces(pos.data(), f.data(), n); },
+               [&] { CHECK(f == wantf); });                                                   // 64 segments: the partial sums grow
+  CHECK(made == 1);
+}
+
 int main(int argc, char** argv) {
   const int serve_requests = argc > 1 ? atoi(argv[1]) : 10000;
   const bool mailbox_only = argc > 2;
+  const bool three_devices = getenv("STUB_DEVICES") && atoi(getenv("STUB_DEVICES")) >= 3;
   std::vector<float> pos, vel, p2, v2, f, f2;
   // ---- a context, the step loop with its graphs, forces, row windows, options that re-segment ----
   for (int n : {1, 63, 1000, 2085}) {
@@ -78,7 +189,7 @@ int main(int argc, char** argv) {
     OK(nbody_set_option(NBODY_OPT_SUM_ORDER, NBODY_SUM_FPGA16)); OK(nbody_set_option(NBODY_OPT_JSUB, 1)); OK(nbody_set_option(NBODY_OPT_WSPLIT, -1));
     OK(nbody_forces(pos.data(), f2.data(), n));
     CHECK(bodyForce(pos.data(), vel.data(), 0.01f, n) == 0 && integrate(pos.data(), vel.data(), 0.01f, n) == 0);
-    nbody_shutdown();
+    SHUTDOWN();
   }
   if (!mailbox_only) {  // fp64, and one process driving three (stub) devices: peer copies, ragged slices
     const int n = 1001;
@@ -89,8 +200,8 @@ int main(int argc, char** argv) {
     OK(nbody_upload_d(&b)); OK(nbody_step_d(0.01, 9)); OK(nbody_download_d(&b));
     check_energy(n, dp, dv, nbody_potential_rows_d);
     CHECK(nbody_step(0.01f, 1) == NBODY_ERR_STATE);
-    nbody_shutdown();
-    if (getenv("STUB_DEVICES") && atoi(getenv("STUB_DEVICES")) >= 3) {
+    SHUTDOWN();
+    if (three_devices) {
       bodies(pos, n, 5); bodies(vel, n, 6);
       OK(nbody_init(n, 3, 0, 0));
       BodySystem bb = {pos.data(), vel.data()};
@@ -98,9 +209,10 @@ int main(int argc, char** argv) {
       check_energy(n, pos, vel, nbody_potential_rows);                // after steps: the other slices are brought over first
       f.assign((size_t)n * 4, 0.f);
       OK(nbody_forces(pos.data(), f.data(), n));
-      nbody_shutdown();
+      SHUTDOWN();
     }
   }
+  if (!mailbox_only) failure_sweeps(three_devices);
   // ---- the mailbox: the address map, every form, the guard ----
   const int cap = 700;
   OK(nbody_mailbox_open(cap, 0));
@@ -213,7 +325,7 @@ int main(int argc, char** argv) {
     else CHECK(got == want);
   }
   OK(nbody_mailbox_serve(1, 0));                                                               // shutdown with the thread still serving
-  nbody_shutdown();
+  SHUTDOWN();
   printf("host_sanity ok: %d served requests, %lld looks by the second thread\n", serve_requests, looked.load());
   return 0;
 }

@@ -6,7 +6,9 @@ bounds, partial sums, arrival counters, ascending combine, apply, the mailbox's 
 (predictable values written through the real EnergyArgs);
 tests/host_stub/host_sanity.cpp drives the C-ABI: contexts of several sizes, 70-step loops (graph capture and replay), every
 segmentation / combine form / wave split, row windows, the energy entry points, fp64, one process over three stub devices with ragged
-slices, the mailbox in every form with the RTL's address map checked against a sentinel, a request whose completion wait fails, and
+slices, the mailbox in every form with the RTL's address map checked against a sentinel, a request whose completion wait fails, the
+failure paths (the stub fails the k-th creating call of every entry point that allocates, k = 1, 2, ...: the call reports it, nothing is
+live after nbody_shutdown, the same call then works; and nothing is live after any nbody_shutdown of the harness), and
 the SERVED mailbox with a second thread hammering nbody_get_info and the refused entry points ("a TSan build of a
 host-only stub of the serve loop").
 What this checks is the host's logic — buffer sizes and offsets (ASan sees every index the host computed), the per-request switch of

@@ -2,7 +2,8 @@
  *
  * Plain C99: pointers, ints, floats.  No HIP, torch or C++ types cross this
  * boundary.  The library behind it is hand-written HIP for gfx950
- * (mini_nbody_amd/csrc/: kernels.hip + context.cpp, comm.cpp, mailbox.cpp); there is no CPU fallback: every entry
+ * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, field.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, field.cpp); there is
+ * no CPU fallback: every entry
  * point fails with NBODY_ERR_NO_DEVICE when no GPU is usable.
  *
  * WHAT EACH ENTRY POINT REPLACES.  The reference (/root/reference, a VHDL FPGA
@@ -341,6 +342,39 @@ enum { NBODY_ENERGY_KINETIC = 0, NBODY_ENERGY_POTENTIAL, NBODY_ENERGY_PX, NBODY_
 int nbody_energy(double *out);
 int nbody_potential_rows(int first_row, int n_rows, float *phi);
 int nbody_potential_rows_d(int first_row, int n_rows, double *phi);
+
+/* ---- field at arbitrary points: acceleration and potential of the bodies on the device where the caller asks (not in the reference) ----
+ * For a point x and the N bodies on the device, unit masses, G = 1, eps the force's softening (bits 0x3089705F):
+ *   a(x)   =  sum_j (r_j - x) * (|r_j - x|^2 + eps)^(-3/2)
+ *   phi(x) = -sum_j (|r_j - x|^2 + eps)^(-1/2)
+ * over ALL j: a point is not a body, so nothing is excluded by default.  A point that coincides with a body gets +0 from that body in a
+ * and 1/sqrt(eps) in -phi.  skip[p] = a global body index leaves that body out of point p's sums (-1: nothing); with points[p] = r_i
+ * and skip[p] = i, phi is the phi_i of nbody_potential_rows bit for bit, in every arithmetic.  What it is for: potential or
+ * acceleration maps on a line, slice or grid, tracer particles, profiles, the force against the gradient of the potential.
+ * Pair arithmetic follows NBODY_OPT_ARITH exactly as the potential's: dx = xj - x (dy, dz likewise), d2 in the FMA3 form or the
+ * reference's five roundings, inv = v_rsq_f32(d2) or under a strict mode (float)(1.0 / sqrt((double)d2)), then the force's cube
+ * inv2 = inv * inv, inv3 = inv * inv2.  fp64 contexts: the fma-contracted d2; inv the v_rsq_f64 seed refined by the potential's one
+ * third-order step, or under a strict mode IEEE sqrt and divide; the same cube.
+ * ORDER (fixed by N alone; it is the potential's):
+ *   level 1: the sources in blocks of 1024 consecutive bodies; per block four accumulators from +0 in ascending j in the context
+ *            precision: ax = fma(dx, inv3, ax), ay and az likewise, s = s + inv; for j == skip[p] all four keep their values;
+ *   level 2: the blocks' four sums converted to fp64 and added in ascending block order from zero; accel = (T){A}, phi = (T)(0 - S).
+ * The bits of a point's result depend on the N source positions, the point, its skip, the arithmetic and the precision — not on m, on
+ * where the point stands in the array, on the launch shape (NBODY_FIELD_SPLIT below), on the force configuration (variant, JSUB,
+ * JSLICES, WSPLIT, SUM_ORDER) or on the device or rank count.  No atomics: two calls return identical bits.
+ * points: m words {x, y, z, ignored} in the context precision, host memory.  accel: m words {ax, ay, az, 0}, or NULL.  phi: m values, or
+ * NULL (at least one of the two).  skip: NULL, or m ints, each -1 or a global body index in [0, N).
+ * nbody_init over several devices: the points are divided over the devices in contiguous ranges.  nbody_init_rank: every rank evaluates
+ * the points IT was given on its own device; the call is collective only because the other slices' positions are brought first — every
+ * rank calls it, m may differ between ranks.  Like the energy entry points it leaves positions, velocities, the arrival counters, the
+ * captured step graph and the force-kernel timer as they were.
+ * Environment, read on every call: NBODY_FIELD_SPLIT = k >= 1 walks the sources in min(k, blocks) chunks of whole blocks side by side
+ * (unset or 0: chosen from m and the CU count, so that few points still fill the device); NBODY_FIELD_SCRATCH_MB (default 256) bounds the
+ * per-block sums a split launch stores, larger calls go in consecutive batches of points.  Same bits in every case.
+ * NBODY_ERR_NOT_INIT without a context; NBODY_ERR_ARG, checked before anything is launched, for points == NULL, m < 1, both outputs
+ * NULL or a skip value outside [-1, N); NBODY_ERR_STATE for the other precision's entry point or while the mailbox is served. */
+int nbody_field(const float *points, int m, const int *skip, float *accel, float *phi);
+int nbody_field_d(const double *points, int m, const int *skip, double *accel, double *phi);
 
 #ifdef __cplusplus
 }

@@ -35,7 +35,7 @@ SYMBOLS = [
     "nbody_set_host_gather", "nbody_download_slice", "nbody_comm_selftest", "nbody_forces_rows_d",
     "nbody_comm_selftest_virtual", "nbody_comm_plan", "nbody_comm_probe", "nbody_comm_time",
     "nbody_rsqrt_selftest", "nbody_rsqrt_strict", "nbody_strict_proof", "nbody_mailbox_open", "nbody_mailbox_rams",
-    "nbody_mailbox_serve", "nbody_energy", "nbody_potential_rows", "nbody_potential_rows_d",
+    "nbody_mailbox_serve", "nbody_energy", "nbody_potential_rows", "nbody_potential_rows_d", "nbody_field", "nbody_field_d",
 ]
 
 
@@ -90,6 +90,7 @@ def load():
         "nbody_mailbox_open": [i, i], "nbody_mailbox_rams": [C.POINTER(vp), C.POINTER(vp), C.POINTER(i)],
         "nbody_mailbox_serve": [i, i],
         "nbody_energy": [dp], "nbody_potential_rows": [i, i, fp], "nbody_potential_rows_d": [i, i, dp],
+        "nbody_field": [fp, i, C.POINTER(i), fp, fp], "nbody_field_d": [dp, i, C.POINTER(i), dp, dp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

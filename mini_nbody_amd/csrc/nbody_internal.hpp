@@ -1,11 +1,13 @@
-// nbody_internal.hpp — what the four parts of libnbody_hip.so share (none of it crosses the C-ABI of include/nbody.h):
+// nbody_internal.hpp — what the parts of libnbody_hip.so share (none of it crosses the C-ABI of include/nbody.h):
 //   kernels.hip   the nbk kernels (nbody_kernels.hpp) and the thin launch functions that pick an instantiation (namespace nbl)
 //   context.cpp   the context: options, launch configuration, buffers, the step and its HIP graph, state transfer, the strict gate
 //   comm.cpp      RCCL (resolved with dlopen), the transfer plans, the all-gather of a step, probes and self-tests
 //   mailbox.cpp   the reference's mailbox: RAM images, one request, the service thread
 //   energy.hip    the energy pass's kernels (energy_args.hpp: its argument block and launch functions)
 //   energy.cpp    nbody_energy, nbody_potential_rows(_d): the energy pass on every local and the sum over the ranks
-// Only kernels.hip and energy.hip are device code (a minute of hipcc, as one code object through device.hip); the others are host
+//   field.hip     the field pass's kernels (field_args.hpp: its argument block and launch functions)
+//   field.cpp     nbody_field(_d): acceleration and potential at the caller's points, the points divided over the locals
+// Only kernels.hip, energy.hip and field.hip are device code (a minute of hipcc, as one code object through device.hip); the others are host
 // C++ (seconds).  gfx950 only, no CPU fallback anywhere.
 // Ownership: every stream, event, device and pinned allocation the context uses lives in an owning handle (Stream, Event, DevMem, Pinned,
 // below) that is a member of Global or of one of its Locals; nbody_shutdown() releases them all, and nothing does at process exit (see `g`).
@@ -116,6 +118,9 @@ struct Local {
   DevMem en_part;                      // energy pass (energy.cpp): per-workgroup fp64 partials of {T, U, P, L} ...
   DevMem en_tot;                       // ... the ranks' totals, 8 doubles at word `rank` (all P after an all-gather) ...
   DevMem en_phi;                       // ... and phi of the rows asked for (context precision)
+  DevMem fd_points, fd_skip;           // field pass (field.cpp): this local's range of the caller's points and skip indices ...
+  DevMem fd_accel, fd_phi;             // ... their outputs (context precision) ...
+  DevMem fd_scratch;                   // ... and the per-block level-1 sums of a launch whose sources are split (field_args.hpp)
   int cur = 0;
   bool all_present = true;             // pos[cur] holds every slice
   Event ev_own_ready;                  // the rank's slice of pos[cur] is written

@@ -148,6 +148,33 @@ class NBody:
             L.check(self.lib.nbody_potential_rows(int(first_row), int(n_rows), out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
+    def field(self, points, skip=None, accel=True, potential=True):
+        """(accel, phi) of the bodies on the device at arbitrary points (nbody_field): a(x) = sum_j (r_j - x) (|r_j - x|^2 + eps)^(-3/2),
+        phi(x) = -sum_j (|r_j - x|^2 + eps)^(-1/2) over ALL j.  points: (m, 4) words or (m, 3) in the context dtype; skip: None or m
+        ints, each -1 or the global index of a body to leave out of that point's sums.  accel: (m, 4) {ax, ay, az, 0} or None when not
+        asked for; phi: (m,) or None.  Collective in a multi-rank job (every rank brings its own points)."""
+        p = np.asarray(points, self.dtype)
+        if p.ndim != 2 or p.shape[1] not in (3, 4):
+            raise ValueError("expected an (m, 4) or (m, 3) array of %s" % np.dtype(self.dtype).name)
+        if p.shape[1] == 3:
+            p = np.concatenate([p, np.zeros((len(p), 1), self.dtype)], axis=1)
+        p = np.ascontiguousarray(p)
+        m = len(p)
+        ct = C.c_double if self.fp64 else C.c_float
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, np.int32)
+            if sk.shape != (m,):
+                raise ValueError("skip must hold one index per point")
+        if not (accel or potential):
+            raise ValueError("ask for accel, potential or both")
+        a = np.empty((m, 4), self.dtype) if accel else None
+        phi = np.empty(m, self.dtype) if potential else None
+        fn = self.lib.nbody_field_d if self.fp64 else self.lib.nbody_field
+        L.check(fn(p.ctypes.data_as(C.POINTER(ct)), m, sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None,
+                   a.ctypes.data_as(C.POINTER(ct)) if accel else None, phi.ctypes.data_as(C.POINTER(ct)) if potential else None))
+        return a, phi
+
     def comm_selftest(self):
         """Push a patterned array through the RCCL calls of the multi-GPU path (all-gather + one ring step); returns
         the bytes this rank received.  Needs the communicator of NBody(..., rank=, nranks=, uid=)."""

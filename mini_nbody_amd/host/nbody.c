@@ -8,9 +8,11 @@
  *
  * usage: nbody [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K]
  *              [--sum seq|blocked] [--block K] [--one-launch | --two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16]
- *              [--energy]
+ *              [--energy] [--field M]
  * --energy: E = T + U, T and U of the state on the device (nbody_energy) before the first iteration and after the last, and the
  * relative drift, outside the timed region.
+ * --field M: after the last iteration, acceleration and potential of the state on the device (nbody_field) at M points — the position
+ * words of an M-body system of the same initial conditions with seed 4242 — as plain ascending fp64 sums, outside the timed region.
  */
 #define _POSIX_C_SOURCE 199309L
 #include <math.h>
@@ -45,8 +47,42 @@ static int print_energy(int step, double *e0, int first) {
   return 0;
 }
 
+/* the line of --field: phi and the three components of a summed over m points, ascending, in fp64 */
+#define FIELD_SEED 4242u
+static int print_field(int m, int fp64) {
+  const size_t words = (size_t)m * 4;
+  double phi_sum = 0.0, a_sum[3] = { 0.0, 0.0, 0.0 };
+  int rc;
+  if (!fp64) {
+    float *buf = (float *)malloc((3 * words + (size_t)m) * sizeof(float));
+    if (!buf) return 3;
+    float *pts = buf, *acc = buf + 2 * words, *phi = buf + 3 * words;   /* buf + words: the velocities the fill also writes */
+    nbody_ic_fill_f32(pts, buf + words, (size_t)m, 0, (size_t)m, FIELD_SEED);
+    rc = nbody_field(pts, m, NULL, acc, phi);
+    for (int p = 0; p < m && !rc; ++p) {
+      phi_sum += (double)phi[p];
+      for (int c = 0; c < 3; ++c) a_sum[c] += (double)acc[4 * p + c];
+    }
+    free(buf);
+  } else {
+    double *buf = (double *)malloc((3 * words + (size_t)m) * sizeof(double));
+    if (!buf) return 3;
+    double *pts = buf, *acc = buf + 2 * words, *phi = buf + 3 * words;
+    nbody_ic_fill_f64(pts, buf + words, (size_t)m, 0, (size_t)m, FIELD_SEED);
+    rc = nbody_field_d(pts, m, NULL, acc, phi);
+    for (int p = 0; p < m && !rc; ++p) {
+      phi_sum += phi[p];
+      for (int c = 0; c < 3; ++c) a_sum[c] += acc[4 * p + c];
+    }
+    free(buf);
+  }
+  if (rc) { fprintf(stderr, "nbody_field failed: %s\n", nbody_error_string(rc)); return 1; }
+  printf("field of %d points: phi_sum %.17g a_sum %.17g %.17g %.17g\n", m, phi_sum, a_sum[0], a_sum[1], a_sum[2]);
+  return 0;
+}
+
 int main(int argc, char **argv) {
-  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0;
+  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0;
   double e0 = 0.0;
   unsigned long long seed = NBODY_IC_DEFAULT_SEED;
   for (int a = 1; a < argc; ++a) {
@@ -59,6 +95,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--strict")) strict = 1;
     else if (!strcmp(argv[a], "--rtl")) rtl = 1;
     else if (!strcmp(argv[a], "--energy")) energy = 1;
+    else if (!strcmp(argv[a], "--field") && a + 1 < argc) field = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--two-launch")) two_launch = 1;
     else if (!strcmp(argv[a], "--one-launch")) two_launch = 0;
     else if (!strcmp(argv[a], "--overlap") && a + 1 < argc) overlap = atoi(argv[++a]);
@@ -68,8 +105,9 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--block") && a + 1 < argc) block = atoi(argv[++a]);
     else if (argv[a][0] != '-' && npos == 0) { n = atoi(argv[a]); npos++; }
     else if (argv[a][0] != '-' && npos == 1) { iters = atoi(argv[a]); npos++; }
-    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy]\n", argv[0]); return 2; }
+    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M]\n", argv[0]); return 2; }
   }
+  if (field < 0) { fprintf(stderr, "--field needs M >= 1\n"); return 2; }
   if (n <= 0 || iters < 2) { fprintf(stderr, "need N > 0 and iters >= 2 (iteration 1 is warm-up)\n"); return 2; }
   const float dt = 0.01f;
   const size_t words = (size_t)n * 4;
@@ -118,7 +156,9 @@ int main(int argc, char **argv) {
       total = now_s() - t0;
       CHECK(nbody_download(&p));
     }
-    if (energy) { if (host_loop) CHECK(nbody_upload(&p)); if (print_energy(iters, &e0, 0)) return 1; }
+    if ((energy || field) && host_loop) CHECK(nbody_upload(&p));
+    if (energy && print_energy(iters, &e0, 0)) return 1;
+    if (field && print_field(field, 0)) return 1;
     double cx = 0, cy = 0, cz = 0;
     for (int i = 0; i < n; ++i) { cx += p.pos[4 * i]; cy += p.pos[4 * i + 1]; cz += p.pos[4 * i + 2]; }
     printf("checksum (sum of positions): %.9g %.9g %.9g\n", cx, cy, cz);
@@ -147,7 +187,9 @@ int main(int argc, char **argv) {
       total = now_s() - t0;
       CHECK(nbody_download_d(&p));
     }
-    if (energy) { if (host_loop) CHECK(nbody_upload_d(&p)); if (print_energy(iters, &e0, 0)) return 1; }
+    if ((energy || field) && host_loop) CHECK(nbody_upload_d(&p));
+    if (energy && print_energy(iters, &e0, 0)) return 1;
+    if (field && print_field(field, 1)) return 1;
     double cx = 0, cy = 0, cz = 0;
     for (int i = 0; i < n; ++i) { cx += p.pos[4 * i]; cy += p.pos[4 * i + 1]; cz += p.pos[4 * i + 2]; }
     printf("checksum (sum of positions): %.17g %.17g %.17g\n", cx, cy, cz);

@@ -12,19 +12,21 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-s
 all: lib host oracle microbench
 
 # The library = ONE device code object (device.hip: the force path's kernels.hip — the nbk kernels + the launch functions that pick an
-# instantiation, ~45 s of hipcc — the energy pass's energy.hip and the field pass's field.hip) and five host-only C++ files (context, comm,
-# mailbox, energy, field: seconds each) behind csrc/nbody_internal.hpp.  A host-side edit relinks in seconds.
+# instantiation, ~45 s of hipcc — the energy pass's energy.hip, the field pass's field.hip and the neighbour pass's neighbors.hip) and six
+# host-only C++ files (context, comm, mailbox, energy, field, neighbors: seconds each) behind csrc/nbody_internal.hpp.  A host-side edit relinks in seconds.
 HOSTFLAGS := -O2 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function
 OBJ      := build/obj
 KERNEL_SRC := $(CSRC)/kernels.hip $(CSRC)/nbody_kernels.hpp $(CSRC)/nbody_args.hpp $(CSRC)/force_loop_gfx950.inc
 HOST_HDR := $(CSRC)/nbody_internal.hpp $(CSRC)/nbody_args.hpp include/nbody.h
-HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o $(OBJ)/energy.o $(OBJ)/field.o
+HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o $(OBJ)/energy.o $(OBJ)/field.o $(OBJ)/neighbors.o
 # the energy diagnostics' device code (energy.hip, seconds of hipcc on its own) reads nbody_args.hpp and changes nothing of the force path's
 # hashed source; device.hip compiles it with kernels.hip into the library's one code object.  Its host side is energy.cpp, one of HOST_OBJ.
 ENERGY_SRC := $(CSRC)/energy.hip $(CSRC)/energy_args.hpp
 # the field pass (acceleration and potential at arbitrary points) in the same way: field.hip beside energy.hip, field.cpp one of HOST_OBJ
 FIELD_SRC := $(CSRC)/field.hip $(CSRC)/field_args.hpp
-DEVICE_SRC := $(CSRC)/device.hip $(KERNEL_SRC) $(ENERGY_SRC) $(FIELD_SRC)
+# the neighbour pass (nearest body, radius count, closest pair) likewise: neighbors.hip beside field.hip, neighbors.cpp one of HOST_OBJ
+NEIGHBORS_SRC := $(CSRC)/neighbors.hip $(CSRC)/neighbors_args.hpp
+DEVICE_SRC := $(CSRC)/device.hip $(KERNEL_SRC) $(ENERGY_SRC) $(FIELD_SRC) $(NEIGHBORS_SRC)
 
 lib: $(PKG)/libnbody_hip.so
 $(OBJ)/device.o: $(DEVICE_SRC) $(HOST_HDR)
@@ -35,6 +37,7 @@ $(OBJ)/%.o: $(CSRC)/%.cpp $(HOST_HDR)
 	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
 $(OBJ)/energy.o: $(CSRC)/energy_args.hpp
 $(OBJ)/field.o: $(CSRC)/field_args.hpp
+$(OBJ)/neighbors.o: $(CSRC)/neighbors_args.hpp
 $(PKG)/libnbody_hip.so: $(OBJ)/device.o $(HOST_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -pthread -o $@ $^ -ldl
 

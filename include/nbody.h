@@ -2,7 +2,7 @@
  *
  * Plain C99: pointers, ints, floats.  No HIP, torch or C++ types cross this
  * boundary.  The library behind it is hand-written HIP for gfx950
- * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, field.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, field.cpp); there is
+ * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, field.hip, neighbors.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, field.cpp, neighbors.cpp); there is
  * no CPU fallback: every entry
  * point fails with NBODY_ERR_NO_DEVICE when no GPU is usable.
  *
@@ -375,6 +375,47 @@ int nbody_potential_rows_d(int first_row, int n_rows, double *phi);
  * NULL or a skip value outside [-1, N); NBODY_ERR_STATE for the other precision's entry point or while the mailbox is served. */
 int nbody_field(const float *points, int m, const int *skip, float *accel, float *phi);
 int nbody_field_d(const double *points, int m, const int *skip, double *accel, double *phi);
+
+/* ---- nearest neighbour, radius count, closest pair: how close the bodies on the device get (not in the reference) ----
+ * A query is a point x with an optional excluded body.  In the context precision T, for every body j on the device:
+ *   dx = xj - x;  dy = yj - y;  dz = zj - z;   d2_j = fma(dx, dx, fma(dy, dy, dz * dz))
+ * the plain squared distance: no softening is added (a diagnostic of the distance itself: min d2, a time step from d / |v|, a collision
+ * candidate must see 0 where two bodies coincide), and it does not follow NBODY_OPT_ARITH — every operation is IEEE-exact, one
+ * definition per precision.  Over the N bodies, the body `skip` left out:
+ *   idx    the j with the smallest d2_j, on equal values the lowest j: what an ascending scan from (d2 = +inf, idx = -1) that replaces
+ *          on strict < arrives at.  A NaN d2_j is never chosen (nor is a d2_j that overflowed to +inf: it is not below +inf).  Without
+ *          a candidate (N = 1 with that body skipped, every d2_j NaN): idx = -1, d2 = +inf.
+ *   d2     that body's d2_j, in T.  A coincident distinct body gives +0, a legitimate answer.
+ *   count  the number of non-skipped j with d2_j <= r2; r2 is given already squared, in T.  NaN is never counted.
+ * A minimum and an integer count are exact: the bits depend on the N positions, the query and its skip alone — not on the number of
+ * queries, on where the query stands, on the launch shape (NBODY_NEIGHBORS_SPLIT below), on the arithmetic, on the force configuration
+ * or on the device or rank count.  No atomics: two calls return identical values.
+ * nbody_neighbors_rows(_d): the queries are the bodies themselves, each excluding itself; rows exactly as in nbody_forces_rows
+ *   (nbody_init: first_row is a global index, the range may span devices; nbody_init_rank: a row of the rank's own slice).  The idx
+ *   returned are always GLOBAL body indices.  idx, d2 or count may be NULL (at least one is not); count == NULL: no counting, r2 ignored.
+ * nbody_nearest(_d): the queries are m caller points; points (m words {x, y, z, ignored}) and skip (NULL, or m ints, -1 or a global
+ *   body index) mean what they mean for nbody_field.  A point on a body without a skip finds that body at d2 = +0.  The points are
+ *   divided over the devices as the field pass divides them; nbody_init_rank: every rank asks for its own points, m may differ.
+ * nbody_closest_pair(_d): the pair i < j with the smallest d2 over the whole system, ties to the lowest i, then the lowest j; N = 1 (or
+ *   no comparable pair): i = j = -1, d2 = +inf.  Any of the three may be NULL (not all).  It runs the rows pass over every device's or
+ *   rank's own rows and keeps each one's best row by a fixed-order reduction; the winner is picked in rank order with strict <.  In an
+ *   nbody_init_rank job it is collective and every rank returns the same values.
+ * All three bring the other slices' positions first (collective in nbody_init_rank contexts) and, like the energy and field entry
+ * points, leave positions, velocities, the arrival counters, the captured step graph and the force-kernel timer as they were.
+ * Environment, read on every call: NBODY_NEIGHBORS_SPLIT = k >= 1 walks the sources in min(k, blocks of 1024) chunks side by side
+ * (unset or 0: chosen from the number of queries and the CU count, so that few queries still fill the device);
+ * NBODY_NEIGHBORS_SCRATCH_MB (default 256, fractions allowed) bounds the 12 (fp64: 16) bytes per query and chunk a split launch stores,
+ * larger calls go in consecutive batches of queries; NBODY_NEIGHBORS_LOOP = 1 | 2 picks the hot loop's form.  Same
+ * values in every case.
+ * NBODY_ERR_NOT_INIT without a context; NBODY_ERR_ARG, checked before anything is launched, for every output NULL, a bad row range,
+ * points == NULL, m < 1 or a skip value outside [-1, N); NBODY_ERR_STATE for the other precision's entry point or while the mailbox
+ * is served. */
+int nbody_neighbors_rows(int first_row, int n_rows, int *idx, float *d2, float r2, int *count);
+int nbody_neighbors_rows_d(int first_row, int n_rows, int *idx, double *d2, double r2, int *count);
+int nbody_nearest(const float *points, int m, const int *skip, int *idx, float *d2, float r2, int *count);
+int nbody_nearest_d(const double *points, int m, const int *skip, int *idx, double *d2, double r2, int *count);
+int nbody_closest_pair(int *i, int *j, float *d2);
+int nbody_closest_pair_d(int *i, int *j, double *d2);
 
 #ifdef __cplusplus
 }

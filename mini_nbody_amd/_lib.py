@@ -36,6 +36,7 @@ SYMBOLS = [
     "nbody_comm_selftest_virtual", "nbody_comm_plan", "nbody_comm_probe", "nbody_comm_time",
     "nbody_rsqrt_selftest", "nbody_rsqrt_strict", "nbody_strict_proof", "nbody_mailbox_open", "nbody_mailbox_rams",
     "nbody_mailbox_serve", "nbody_energy", "nbody_potential_rows", "nbody_potential_rows_d", "nbody_field", "nbody_field_d",
+    "nbody_neighbors_rows", "nbody_neighbors_rows_d", "nbody_nearest", "nbody_nearest_d", "nbody_closest_pair", "nbody_closest_pair_d",
 ]
 
 
@@ -91,6 +92,10 @@ def load():
         "nbody_mailbox_serve": [i, i],
         "nbody_energy": [dp], "nbody_potential_rows": [i, i, fp], "nbody_potential_rows_d": [i, i, dp],
         "nbody_field": [fp, i, C.POINTER(i), fp, fp], "nbody_field_d": [dp, i, C.POINTER(i), dp, dp],
+        "nbody_neighbors_rows": [i, i, C.POINTER(i), fp, f, C.POINTER(i)], "nbody_neighbors_rows_d": [i, i, C.POINTER(i), dp, d, C.POINTER(i)],
+        "nbody_nearest": [fp, i, C.POINTER(i), C.POINTER(i), fp, f, C.POINTER(i)],
+        "nbody_nearest_d": [dp, i, C.POINTER(i), C.POINTER(i), dp, d, C.POINTER(i)],
+        "nbody_closest_pair": [C.POINTER(i), C.POINTER(i), fp], "nbody_closest_pair_d": [C.POINTER(i), C.POINTER(i), dp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

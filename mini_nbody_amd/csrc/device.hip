@@ -1,8 +1,9 @@
 // device.hip — what hipcc compiles for the library's device code: the force path's translation unit (kernels.hip, unchanged), the
-// energy pass's (energy.hip) and the field pass's (field.hip) as ONE gfx950 code object.  One object, not several: tests/test_strict_rsqrt.py
+// energy pass's (energy.hip), the field pass's (field.hip) and the neighbour pass's (neighbors.hip) as ONE gfx950 code object.  One object, not several: tests/test_strict_rsqrt.py
 // reads the strict kernels' branches out of the library's single code object, and a second offload bundle would be a second one.  Each
 // file still compiles on its own and shares nothing with the others beyond nbody_args.hpp; the force kernels' machine code is the same
 // either way.
 #include "kernels.hip"
 #include "energy.hip"
 #include "field.hip"
+#include "neighbors.hip"

@@ -7,8 +7,10 @@
 //   energy.cpp    nbody_energy, nbody_potential_rows(_d): the energy pass on every local and the sum over the ranks
 //   field.hip     the field pass's kernels (field_args.hpp: its argument block and launch functions)
 //   field.cpp     nbody_field(_d): acceleration and potential at the caller's points, the points divided over the locals
-// Only kernels.hip, energy.hip and field.hip are device code (a minute of hipcc, as one code object through device.hip); the others are host
-// C++ (seconds).  gfx950 only, no CPU fallback anywhere.
+//   neighbors.hip the neighbour pass's kernels (neighbors_args.hpp: its argument block and launch functions)
+//   neighbors.cpp nbody_neighbors_rows(_d), nbody_nearest(_d), nbody_closest_pair(_d): nearest body, radius count, closest pair
+// Only kernels.hip, energy.hip, field.hip and neighbors.hip are device code (a minute of hipcc, as one code object through device.hip);
+// the others are host C++ (seconds).  gfx950 only, no CPU fallback anywhere.
 // Ownership: every stream, event, device and pinned allocation the context uses lives in an owning handle (Stream, Event, DevMem, Pinned,
 // below) that is a member of Global or of one of its Locals; nbody_shutdown() releases them all, and nothing does at process exit (see `g`).
 //
@@ -121,6 +123,10 @@ struct Local {
   DevMem fd_points, fd_skip;           // field pass (field.cpp): this local's range of the caller's points and skip indices ...
   DevMem fd_accel, fd_phi;             // ... their outputs (context precision) ...
   DevMem fd_scratch;                   // ... and the per-block level-1 sums of a launch whose sources are split (field_args.hpp)
+  DevMem nb_points, nb_skip;           // neighbour pass (neighbors.cpp): this local's range of the caller's points and skip indices ...
+  DevMem nb_idx, nb_d2, nb_count;      // ... the queries' outputs (d2 in the context precision) ...
+  DevMem nb_scratch;                   // ... the chunks' results of a launch whose sources are split (neighbors_args.hpp) ...
+  DevMem nb_best;                      // ... and the ranks' closest pairs, one BestPair at word `rank` (all P after an all-gather)
   int cur = 0;
   bool all_present = true;             // pos[cur] holds every slice
   Event ev_own_ready;                  // the rank's slice of pos[cur] is written

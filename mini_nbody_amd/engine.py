@@ -29,6 +29,7 @@ class NBody:
         else:
             buf = C.create_string_buffer(bytes(uid), 128) if uid is not None else None
             L.check(self.lib.nbody_init_rank(self.n, int(self.fp64), int(tile), int(rank), int(nranks), buf))
+        self._by_rank = rank is not None   # rows are those of this rank's slice (nbody_init_rank)
         self._open = True
 
     # ---- options / info ----
@@ -174,6 +175,56 @@ class NBody:
         L.check(fn(p.ctypes.data_as(C.POINTER(ct)), m, sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None,
                    a.ctypes.data_as(C.POINTER(ct)) if accel else None, phi.ctypes.data_as(C.POINTER(ct)) if potential else None))
         return a, phi
+
+    def _near_out(self, m, r2):
+        ct = C.c_double if self.fp64 else C.c_float
+        idx, d2 = np.empty(m, np.int32), np.empty(m, self.dtype)
+        cnt = np.empty(m, np.int32) if r2 is not None else None
+        ip = C.POINTER(C.c_int)
+        return idx, d2, cnt, (idx.ctypes.data_as(ip), d2.ctypes.data_as(C.POINTER(ct)), float(self.dtype(0 if r2 is None else r2)),
+                              cnt.ctypes.data_as(ip) if cnt is not None else None)
+
+    def neighbors(self, first_row=0, n_rows=None, r2=None):
+        """(idx, d2, count) of n_rows bodies from first_row (rows as in forces_rows; default: all of them) from the state on the
+        device (nbody_neighbors_rows): idx the GLOBAL index of the nearest other body (-1: none), d2 its plain squared distance in the
+        context precision (no softening; +inf: none), count the number of other bodies with d2 <= r2 (r2 already squared), or None
+        when r2 is None.  Ties go to the lowest index.  Collective in a multi-rank job."""
+        if n_rows is None:
+            n_rows = self.info(L.INFO_N_LOCAL if self._by_rank else L.INFO_N) - int(first_row)
+        idx, d2, cnt, out = self._near_out(int(n_rows), r2)
+        fn = self.lib.nbody_neighbors_rows_d if self.fp64 else self.lib.nbody_neighbors_rows
+        L.check(fn(int(first_row), int(n_rows), *out))
+        return idx, d2, cnt
+
+    def nearest(self, points, skip=None, r2=None):
+        """(idx, d2, count) as neighbors(), of the bodies on the device at arbitrary points (nbody_nearest).  points: (m, 4) words or
+        (m, 3) in the context dtype; skip: None or m ints, each -1 or the global index of a body to leave out for that point.  A
+        point on a body without a skip finds that body at d2 = 0."""
+        p = np.asarray(points, self.dtype)
+        if p.ndim != 2 or p.shape[1] not in (3, 4):
+            raise ValueError("expected an (m, 4) or (m, 3) array of %s" % np.dtype(self.dtype).name)
+        if p.shape[1] == 3:
+            p = np.concatenate([p, np.zeros((len(p), 1), self.dtype)], axis=1)
+        p = np.ascontiguousarray(p)
+        m = len(p)
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, np.int32)
+            if sk.shape != (m,):
+                raise ValueError("skip must hold one index per point")
+        idx, d2, cnt, out = self._near_out(m, r2)
+        ct = C.c_double if self.fp64 else C.c_float
+        fn = self.lib.nbody_nearest_d if self.fp64 else self.lib.nbody_nearest
+        L.check(fn(p.ctypes.data_as(C.POINTER(ct)), m, sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None, *out))
+        return idx, d2, cnt
+
+    def closest_pair(self):
+        """(i, j, d2) of the pair i < j with the smallest plain squared distance over the whole system (nbody_closest_pair), ties to
+        the lowest i, then the lowest j; (-1, -1, inf) when N = 1.  Collective in a multi-rank job; every rank gets the same values."""
+        i, j = C.c_int(), C.c_int()
+        d2 = C.c_double() if self.fp64 else C.c_float()
+        L.check((self.lib.nbody_closest_pair_d if self.fp64 else self.lib.nbody_closest_pair)(C.byref(i), C.byref(j), C.byref(d2)))
+        return i.value, j.value, self.dtype(d2.value)
 
     def comm_selftest(self):
         """Push a patterned array through the RCCL calls of the multi-GPU path (all-gather + one ring step); returns

@@ -1,0 +1,279 @@
+// neighbors_sanity.cpp — TEST INFRASTRUCTURE (tests/test_neighbors_host_sanitizers.py): drives nbody_neighbors_rows, nbody_nearest and
+// nbody_closest_pair (and their _d forms) of the library's host code (neighbors.cpp beside context.cpp, comm.cpp, mailbox.cpp,
+// energy.cpp) against tests/host_stub/hip_stub.cpp and neighbors_stub.cpp under AddressSanitizer + UBSan.  What it checks is the host's
+// logic: the rows of a window and the division of the points over the devices, the upload and copy-back offsets, the choice of the
+// source split, the scratch size and the batches, the argument checks, the closest pair over the devices, lifetimes at shutdown and
+// the failure paths.  neighbors_stub.cpp states the values expected here.
+#include <math.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <functional>
+#include <vector>
+
+#include "../../include/nbody.h"
+
+extern "C" long hip_stub_live(int kind);               // hip_stub.cpp: outstanding 0 device allocations, 1 pinned, 2 events, 3 streams, 4 graphs, 5 graph execs
+extern "C" void hip_stub_fail_nth(int k);              // the k-th creating call from now fails once (0: disarm)
+extern "C" int hip_stub_fail_pending(void);            // > 0: the armed failure has not been reached
+
+#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "neighbors_sanity: line %d: %s\n", __LINE__, #cond); exit(1); } } while (0)
+#define OK(call) do { int rc_ = (call); if (rc_) { fprintf(stderr, "neighbors_sanity: line %d: %s = %d (%s)\n", __LINE__, #call, rc_, nbody_error_string(rc_)); exit(1); } } while (0)
+
+static void shutdown_at(int line) {
+  nbody_shutdown();
+  for (int kind = 0; kind < 6; ++kind)
+    if (hip_stub_live(kind)) { fprintf(stderr, "neighbors_sanity: line %d: %ld of kind %d live after nbody_shutdown\n", line, hip_stub_live(kind), kind); exit(1); }
+}
+#define SHUTDOWN() shutdown_at(__LINE__)
+
+static void set_env(const char* split, const char* scratch_mb) {
+  if (split) setenv("NBODY_NEIGHBORS_SPLIT", split, 1); else unsetenv("NBODY_NEIGHBORS_SPLIT");
+  if (scratch_mb) setenv("NBODY_NEIGHBORS_SCRATCH_MB", scratch_mb, 1); else unsetenv("NBODY_NEIGHBORS_SCRATCH_MB");
+}
+
+template <typename T> int upload(std::vector<T>& pos, std::vector<T>& vel);
+template <> int upload<float>(std::vector<float>& pos, std::vector<float>& vel) { BodySystem b = {pos.data(), vel.data()}; return nbody_upload(&b); }
+template <> int upload<double>(std::vector<double>& pos, std::vector<double>& vel) { BodySystemD b = {pos.data(), vel.data()}; return nbody_upload_d(&b); }
+static int rows(int f, int n, int* i, float* d, float r2, int* c) { return nbody_neighbors_rows(f, n, i, d, r2, c); }
+static int rows(int f, int n, int* i, double* d, double r2, int* c) { return nbody_neighbors_rows_d(f, n, i, d, r2, c); }
+static int nearest(const float* p, int m, const int* sk, int* i, float* d, float r2, int* c) { return nbody_nearest(p, m, sk, i, d, r2, c); }
+static int nearest(const double* p, int m, const int* sk, int* i, double* d, double r2, int* c) { return nbody_nearest_d(p, m, sk, i, d, r2, c); }
+static int pair(int* i, int* j, float* d) { return nbody_closest_pair(i, j, d); }
+static int pair(int* i, int* j, double* d) { return nbody_closest_pair_d(i, j, d); }
+
+// small integers everywhere: every value of neighbors_stub.cpp is exact in either precision
+template <typename T>
+struct Case {
+  int n, m;
+  std::vector<T> pos, vel, pts, d2;
+  std::vector<int> skip, idx, cnt;
+  Case(int n_, int m_) : n(n_), m(m_), pos((size_t)n_ * 4), vel((size_t)n_ * 4, (T)0), pts((size_t)m_ * 4), d2((size_t)std::max(n_, m_)),
+                         skip((size_t)m_), idx((size_t)std::max(n_, m_)), cnt((size_t)std::max(n_, m_)) {
+    for (int j = 0; j < n; ++j) { pos[4 * (size_t)j] = (T)((j * 37) % 101); pos[4 * (size_t)j + 1] = (T)(j % 7); pos[4 * (size_t)j + 2] = (T)1; pos[4 * (size_t)j + 3] = (T)(j % 977); }
+    for (int p = 0; p < m; ++p) {
+      pts[4 * (size_t)p] = (T)(p % 17); pts[4 * (size_t)p + 1] = (T)(p % 5); pts[4 * (size_t)p + 2] = (T)3; pts[4 * (size_t)p + 3] = (T)p;
+      skip[(size_t)p] = p % 3 == 0 ? -1 : (int)(((long long)p * 7919) % n);
+    }
+  }
+  void open(int ngpus) { OK(nbody_init(n, ngpus, sizeof(T) == 8, 0)); OK(upload<T>(pos, vel)); }
+  // what neighbors_stub.cpp makes of a query {x, w} with the excluded body sk
+  void expect(T x, T w, int sk, T r2, int* e_idx, T* e_d2, int* e_cnt) const {
+    *e_idx = -1; *e_d2 = (T)INFINITY; *e_cnt = 0;
+    for (int b = 0; b * 1024 < n; ++b) {
+      const int b0 = b * 1024, len = std::min(1024, n - b0), j = b0 + ((int)w + b) % len;
+      const T d = pos[4 * (size_t)j] - x, v = d < 0 ? -d : d;
+      if (j != sk && v < *e_d2) { *e_d2 = v; *e_idx = j; }
+      if ((T)b <= r2) *e_cnt += len - (sk >= b0 && sk < b0 + len ? 1 : 0);
+    }
+  }
+  void verify(int cnt_q, const std::function<void(int, T*, T*, int*)>& query, T r2, bool w_idx, bool w_d2, bool w_cnt) {
+    for (int k = 0; k < cnt_q; ++k) {
+      T x, w, e_d2; int sk, e_idx, e_cnt;
+      query(k, &x, &w, &sk);
+      expect(x, w, sk, r2, &e_idx, &e_d2, &e_cnt);
+      CHECK(idx[(size_t)k] == (w_idx ? e_idx : -77));
+      CHECK(d2[(size_t)k] == (w_d2 ? e_d2 : (T)-77));
+      CHECK(cnt[(size_t)k] == (w_cnt ? e_cnt : -77));
+    }
+    for (size_t k = (size_t)cnt_q; k < idx.size(); ++k) CHECK(idx[k] == -77 && d2[k] == (T)-77 && cnt[k] == -77);   // nothing beyond
+  }
+  void mark() { std::fill(idx.begin(), idx.end(), -77); std::fill(d2.begin(), d2.end(), (T)-77); std::fill(cnt.begin(), cnt.end(), -77); }
+  void run_rows(int first, int count, bool w_idx, bool w_d2, bool w_cnt, T r2) {
+    mark();
+    OK(rows(first, count, w_idx ? idx.data() : nullptr, w_d2 ? d2.data() : nullptr, r2, w_cnt ? cnt.data() : nullptr));
+    verify(count, [&](int k, T* x, T* w, int* sk) { *x = pos[4 * (size_t)(first + k)]; *w = pos[4 * (size_t)(first + k) + 3]; *sk = first + k; }, r2, w_idx, w_d2, w_cnt);
+  }
+  void run_points(bool with_skip, bool w_idx, bool w_d2, bool w_cnt, T r2, int p0 = 0, int count = -1) {
+    if (count < 0) count = m - p0;
+    mark();
+    OK(nearest(pts.data() + 4 * (size_t)p0, count, with_skip ? skip.data() + p0 : nullptr, w_idx ? idx.data() : nullptr, w_d2 ? d2.data() : nullptr, r2,
+               w_cnt ? cnt.data() : nullptr));
+    verify(count, [&](int k, T* x, T* w, int* sk) { *x = pts[4 * (size_t)(p0 + k)]; *w = pts[4 * (size_t)(p0 + k) + 3]; *sk = with_skip ? skip[(size_t)(p0 + k)] : -1; },
+           r2, w_idx, w_d2, w_cnt);
+  }
+  void run_pair() {
+    int bi = -1, bj = -1; T bd = (T)INFINITY;
+    for (int r = 0; r < n; ++r) {
+      int e_idx, e_cnt; T e_d2;
+      expect(pos[4 * (size_t)r], pos[4 * (size_t)r + 3], r, (T)0, &e_idx, &e_d2, &e_cnt);
+      if (e_d2 < bd) { bd = e_d2; bi = r; bj = e_idx; }
+    }
+    int i = -5, j = -5; T d = (T)-5;
+    OK(pair(&i, &j, &d));
+    CHECK(i == bi && j == bj && d == bd);
+    int j2 = -5;
+    OK(pair(nullptr, &j2, (T*)nullptr));
+    CHECK(j2 == bj);
+  }
+  void run_all() {
+    run_points(false, true, true, true, (T)1);
+    run_points(true, true, true, true, (T)0);
+    run_points(true, false, true, false, (T)0);
+    run_points(false, true, false, false, (T)0);
+    run_points(true, false, false, true, (T)2);
+    if (m > 2) run_points(true, true, true, true, (T)1, 1, m - 2);
+    const int rc = std::min(m, n);   // the row counts are the point counts, as far as there are rows
+    run_rows(0, rc, true, true, true, (T)1);
+    run_rows(n - rc, rc, true, true, false, (T)0);
+    run_rows((n - rc) / 2, rc, false, true, true, (T)0);   // a window in the middle: across the devices when there are three
+    run_rows((n - rc) / 2, rc, true, false, false, (T)0);
+    run_rows(n - 1, 1, false, false, true, (T)5);
+  }
+};
+
+template <typename T>
+static void shapes(int n, int ngpus) {
+  for (int m : {1, 255, 256, 257, 5000}) {
+    Case<T> c(n, m);
+    c.open(ngpus);
+    for (const char* split : {(const char*)nullptr, "0", "1", "2", "3", "1000"}) {
+      set_env(split, nullptr);
+      c.run_all();
+    }
+    set_env(nullptr, nullptr);
+    c.run_pair();
+    SHUTDOWN();
+  }
+}
+
+// the k-th creating call inside `call` fails, k = 1, 2, ... until the call no longer reaches the armed failure: a failed call must say
+// so, nbody_shutdown() must then leave nothing, and the call without injection must then work.  Returns the creating calls the call makes.
+static int sweep(const char* name, const std::function<void()>& setup, const std::function<int()>& call, const std::function<void()>& verify) {
+  for (int k = 1;; ++k) {
+    setup();
+    hip_stub_fail_nth(k);
+    const int rc = call();
+    const bool reached = hip_stub_fail_pending() == 0;
+    hip_stub_fail_nth(0);
+    if (reached && rc == 0) { fprintf(stderr, "neighbors_sanity: %s: creating call %d failed and the call returned 0\n", name, k); exit(1); }
+    if (!reached) {
+      if (rc) { fprintf(stderr, "neighbors_sanity: %s: %d (%s) without an injected failure\n", name, rc, nbody_error_string(rc)); exit(1); }
+      verify();
+      SHUTDOWN();
+      return k - 1;
+    }
+    SHUTDOWN();
+    setup();
+    const int rc2 = call();
+    if (rc2) { fprintf(stderr, "neighbors_sanity: %s: %d (%s) after a failed attempt at creating call %d\n", name, rc2, nbody_error_string(rc2), k); exit(1); }
+    verify();
+    SHUTDOWN();
+  }
+}
+
+int main() {
+  const bool three_devices = getenv("STUB_DEVICES") && atoi(getenv("STUB_DEVICES")) >= 3;
+  {
+    float one[4] = {0, 0, 0, 0}, d[1] = {5};
+    double oned[4] = {0, 0, 0, 0}, dd[1] = {5};
+    int i[2] = {5, 5}, c[1] = {5};
+    CHECK(nbody_neighbors_rows(0, 1, i, d, 1.f, c) == NBODY_ERR_NOT_INIT && nbody_neighbors_rows_d(0, 1, i, dd, 1.0, c) == NBODY_ERR_NOT_INIT);
+    CHECK(nbody_nearest(one, 1, nullptr, i, d, 1.f, c) == NBODY_ERR_NOT_INIT && nbody_nearest_d(oned, 1, nullptr, i, dd, 1.0, c) == NBODY_ERR_NOT_INIT);
+    CHECK(nbody_closest_pair(i, i + 1, d) == NBODY_ERR_NOT_INIT && nbody_closest_pair_d(i, i + 1, dd) == NBODY_ERR_NOT_INIT);
+    CHECK(i[0] == 5 && i[1] == 5 && c[0] == 5 && d[0] == 5 && dd[0] == 5);
+  }
+
+  // ---- one block, six blocks with a short last one; one device and three with ragged slices (5200 = 1733 + 1733 + 1734, 1000 = 333 + 333 + 334) ----
+  for (int n : {1, 1000, 5200}) {
+    shapes<float>(n, 1);
+    if (three_devices && n >= 3) shapes<float>(n, 3);
+  }
+  shapes<double>(5200, 1);
+  if (three_devices) shapes<double>(1000, 3);
+
+  // ---- the batched path: 5000 queries x 6 chunks x 12 B = 360 kB against 0.05 MB: batches of 512 (fp32), of 512 at 16 B too (fp64) ----
+  for (int ngpus : {1, 3}) {
+    if (ngpus > 1 && !three_devices) continue;
+    Case<float> c(5200, 5000);
+    c.open(ngpus);
+    for (const char* split : {(const char*)nullptr, "4", "6"}) {
+      set_env(split, "0.05");
+      c.run_all();
+    }
+    set_env(nullptr, "0");    // not one workgroup's queries fit: no split
+    c.run_all();
+    set_env("5", "0");
+    c.run_all();
+    set_env(nullptr, "0.05");
+    c.run_pair();
+    SHUTDOWN();
+  }
+  {
+    Case<double> c(5200, 1000);
+    c.open(1);
+    set_env(nullptr, "0.05");
+    c.run_all();
+    SHUTDOWN();
+  }
+  set_env(nullptr, nullptr);
+
+  // ---- the argument checks: nothing is written, the context stays usable ----
+  {
+    Case<float> c(5200, 300);
+    c.open(three_devices ? 3 : 1);
+    float* pts = c.pts.data();
+    c.mark();
+    int* I = c.idx.data(); float* D = c.d2.data(); int* N = c.cnt.data();
+    CHECK(nbody_neighbors_rows(0, 300, nullptr, nullptr, 1.f, nullptr) == NBODY_ERR_ARG);
+    CHECK(nbody_neighbors_rows(-1, 300, I, D, 1.f, N) == NBODY_ERR_ARG);
+    CHECK(nbody_neighbors_rows(0, 0, I, D, 1.f, N) == NBODY_ERR_ARG);
+    CHECK(nbody_neighbors_rows(0, -4, I, D, 1.f, N) == NBODY_ERR_ARG);
+    CHECK(nbody_neighbors_rows(5200, 1, I, D, 1.f, N) == NBODY_ERR_ARG);
+    CHECK(nbody_neighbors_rows(5000, 201, I, D, 1.f, N) == NBODY_ERR_ARG);
+    CHECK(nbody_neighbors_rows(1 << 30, 1 << 30, I, D, 1.f, N) == NBODY_ERR_ARG);
+    CHECK(nbody_nearest(nullptr, 300, nullptr, I, D, 1.f, N) == NBODY_ERR_ARG);
+    CHECK(nbody_nearest(pts, 0, nullptr, I, D, 1.f, N) == NBODY_ERR_ARG);
+    CHECK(nbody_nearest(pts, -1, nullptr, I, D, 1.f, N) == NBODY_ERR_ARG);
+    CHECK(nbody_nearest(pts, 300, nullptr, nullptr, nullptr, 1.f, nullptr) == NBODY_ERR_ARG);
+    for (int bad : {5200, -2, 1 << 30}) {
+      std::vector<int> sk = c.skip;
+      sk[299] = bad;
+      CHECK(nbody_nearest(pts, 300, sk.data(), I, D, 1.f, N) == NBODY_ERR_ARG);
+    }
+    CHECK(nbody_closest_pair(nullptr, nullptr, nullptr) == NBODY_ERR_ARG);
+    std::vector<double> pd(1200, 0.0), dd(300, 5.0);
+    CHECK(nbody_nearest_d(pd.data(), 300, nullptr, I, dd.data(), 1.0, N) == NBODY_ERR_STATE);
+    CHECK(nbody_neighbors_rows_d(0, 300, I, dd.data(), 1.0, N) == NBODY_ERR_STATE && nbody_closest_pair_d(I, I + 1, dd.data()) == NBODY_ERR_STATE);
+    CHECK(dd[0] == 5.0 && dd[299] == 5.0);
+    for (size_t k = 0; k < c.idx.size(); ++k) CHECK(c.idx[k] == -77 && c.d2[k] == -77.f && c.cnt[k] == -77);
+    std::vector<int> edge = c.skip;
+    edge[0] = 5199; edge[299] = 0;
+    OK(nbody_nearest(pts, 300, edge.data(), I, nullptr, 1.f, nullptr));
+    CHECK(c.d2[0] == -77.f && c.cnt[0] == -77 && c.idx[0] != -77);
+    c.run_all();
+    SHUTDOWN();
+    Case<double> d(1000, 10);
+    d.open(1);
+    CHECK(nbody_nearest(pts, 10, nullptr, I, D, 1.f, N) == NBODY_ERR_STATE && nbody_neighbors_rows(0, 10, I, D, 1.f, N) == NBODY_ERR_STATE);
+    CHECK(nbody_closest_pair(I, I + 1, D) == NBODY_ERR_STATE);
+    d.run_all();
+    d.run_pair();
+    SHUTDOWN();
+  }
+
+  // ---- the failure paths: every allocating call of a call, one device and three, split (scratch) and not ----
+  for (int ngpus : {1, 3}) {
+    if (ngpus > 1 && !three_devices) continue;
+    Case<float> c(5200, 700);
+    set_env("3", nullptr);
+    int made = sweep("nbody_nearest split", [&] { c.open(ngpus); }, [&] { return nbody_nearest(c.pts.data(), c.m, c.skip.data(), c.idx.data(), c.d2.data(), 1.f, c.cnt.data()); },
+                     [&] { c.run_points(true, true, true, true, 1.f); });
+    CHECK(made == 6 * ngpus);   // points, skip, idx, d2, count, scratch per device
+    made = sweep("nbody_neighbors_rows split", [&] { c.open(ngpus); }, [&] { return nbody_neighbors_rows(0, 5200, c.idx.data(), c.d2.data(), 1.f, nullptr); },
+                 [&] { c.run_rows(0, 5200, true, true, false, 1.f); });
+    CHECK(made == 3 * ngpus);   // idx, d2, scratch
+    set_env("1", nullptr);
+    made = sweep("nbody_nearest", [&] { c.open(ngpus); }, [&] { return nbody_nearest(c.pts.data(), c.m, nullptr, nullptr, c.d2.data(), 1.f, nullptr); },
+                 [&] { c.run_points(false, false, true, false, 1.f); });
+    CHECK(made == 2 * ngpus);   // points, d2
+    int i, j; float d;
+    made = sweep("nbody_closest_pair", [&] { c.open(ngpus); }, [&] { return nbody_closest_pair(&i, &j, &d); }, [&] { c.run_pair(); });
+    CHECK(made == 3 * ngpus);   // idx, d2, the best pairs
+  }
+  set_env(nullptr, nullptr);
+  printf("neighbors_sanity ok\n");
+  return 0;
+}

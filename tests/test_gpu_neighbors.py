@@ -1,0 +1,416 @@
+"""Nearest neighbour, radius count and closest pair on the device (nbody_neighbors_rows, nbody_nearest, nbody_closest_pair and their
+_d forms; include/nbody.h "nearest neighbour, radius count, closest pair"): every case bit for bit against tests/neighbors_ref.c — idx
+and count equal, d2 the same bits — in both precisions, in every arithmetic, both loop forms, however the work is laid out (source
+split, batches, windows of rows, force configuration, device and process count); no effect on the step; the guards; the C host
+program's --closest-pair line."""
+import ctypes as C
+import os
+import re
+import socket
+import subprocess
+import sys
+import textwrap
+
+import numpy as np
+import pytest
+
+from field_common import make_points, make_skip
+from neighbors_common import bits, make_ref, planted, r2_for, same
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ENV = ("NBODY_NEIGHBORS_SPLIT", "NBODY_NEIGHBORS_SCRATCH_MB", "NBODY_NEIGHBORS_LOOP")
+
+
+@pytest.fixture(scope="module")
+def ref(tmp_path_factory):
+    return make_ref(tmp_path_factory.mktemp("neighbors_ref"))
+
+
+@pytest.fixture(autouse=True)
+def clean_env(monkeypatch):
+    for k in ENV:
+        monkeypatch.delenv(k, raising=False)
+
+
+def windows(n):
+    """(first_row, n_rows): everything, a window across a 64 boundary and across a 256 boundary, the last row alone"""
+    w = [(0, n), (n - 1, 1)]
+    if n > 70:
+        w.append((50, 20))
+    if n > 300:
+        w.append((200, 100))
+    return w
+
+
+@pytest.mark.parametrize("loop", ["1", "2"])
+@pytest.mark.parametrize("fp64", [False, True])
+def test_rows_bit_for_bit(nb, ref, monkeypatch, fp64, loop):
+    monkeypatch.setenv("NBODY_NEIGHBORS_LOOP", loop)
+    dtype = np.float64 if fp64 else np.float32
+    for n in (1, 2, 63, 64, 65, 257, 1000, 1025, 2100):
+        pos, vel = nb.make_bodies(n, dtype=dtype)
+        with nb.NBody(n, fp64=fp64) as eng:
+            eng.upload(pos, vel)
+            for r2 in (None, dtype(0), r2_for(pos, 0.01), r2_for(pos, 0.3), dtype(12.5)):   # counts from 0 to all of the others
+                want = ref.rows(pos, r2=r2)
+                if r2 is not None and r2 == 12.5:
+                    assert np.all(want[2] == n - 1)
+                for first, cnt in windows(n):
+                    got = eng.neighbors(first, cnt, r2=r2)
+                    assert same(got, tuple(None if w is None else w[first:first + cnt] for w in want)), (n, first, cnt, r2)
+            assert same(eng.neighbors(), ref.rows(pos))
+            assert eng.closest_pair()[:2] == ref.closest_pair(pos)[:2] and bits(eng.closest_pair()[2]) == bits(ref.closest_pair(pos)[2]), n
+
+
+def test_bits_do_not_follow_the_arithmetic(nb, ref):
+    n = 2100
+    pos, vel = nb.make_bodies(n)
+    r2 = r2_for(pos, 0.1)
+    want = ref.rows(pos, r2=r2)
+    with nb.NBody(n) as eng:
+        eng.upload(pos, vel)
+        for mode in (nb.ARITH_FMA3, nb.ARITH_REFERENCE, nb.ARITH_STRICT, nb.ARITH_REFERENCE_STRICT):
+            eng.set_option(nb.OPT_ARITH, mode)
+            assert same(eng.neighbors(r2=r2), want), mode
+
+
+@pytest.mark.parametrize("fp64", [False, True])
+def test_points_form(nb, ref, fp64):
+    n = 2100
+    dtype = np.float64 if fp64 else np.float32
+    pos, vel = nb.make_bodies(n, dtype=dtype)
+    r2 = r2_for(pos, 0.05)
+    with nb.NBody(n, fp64=fp64) as eng:
+        eng.upload(pos, vel)
+        for m in (1, 255, 256, 257):
+            pts, on = make_points(nb, pos, m)   # on bodies 0, 5, N - 1; between the bodies; 1.5 x: outside the cube
+            pts[-1, :3] = 50.0                  # and far outside
+            spread = ((np.arange(m) * 997) % n).astype(np.int32)   # skip indices across all blocks: the compare window spans the sources
+            for skip in (None, make_skip(n, m, on), spread):
+                for rr in (None, r2):
+                    assert same(eng.nearest(pts, skip, r2=rr), ref.points(pos, pts, skip, r2=rr)), (m, skip is not None, rr)
+            assert same(eng.nearest(np.ascontiguousarray(pts[:, :3])), ref.points(pos, pts))   # (m, 3) points are padded to words
+        got = eng.nearest(pts[:3])
+        assert list(got[0]) == on and np.all(bits(got[1]) == 0)   # a point on a body without a skip: that body at +0
+        assert same(eng.nearest(pos, np.arange(n, dtype=np.int32), r2=r2), eng.neighbors(r2=r2))
+
+
+@pytest.mark.parametrize("loop", ["1", "2"])
+@pytest.mark.parametrize("fp64", [False, True])
+def test_ties_and_specials(nb, ref, monkeypatch, fp64, loop):
+    monkeypatch.setenv("NBODY_NEIGHBORS_LOOP", loop)
+    dtype = np.float64 if fp64 else np.float32
+    n = 2100
+    pos = planted(nb, n, dtype)
+    vel = np.zeros_like(pos)
+    h2 = dtype(2.0 ** -24)
+    with nb.NBody(n, fp64=fp64) as eng:
+        eng.upload(pos, vel)
+        for split in (None, "3"):   # three chunks of one block: the tie at 1024 sits in another chunk than 63's other ties
+            if split:
+                monkeypatch.setenv("NBODY_NEIGHBORS_SPLIT", split)
+            idx, d2, cnt = got = eng.neighbors(r2=h2)
+            assert same(got, ref.rows(pos, r2=h2)), split
+            assert (idx[3], idx[70], idx[900]) == (70, 3, 3) and np.all(bits(d2[[3, 70, 900]]) == 0)
+            assert idx[63] == 64 and d2[63] == h2 and list(cnt[[63, 64, 65, 500, 1024]]) == [4, 1, 1, 1, 1]
+            assert idx[200] == -1 and np.isposinf(d2[200]) and cnt[200] == 0 and not np.any(idx == 200)
+            pts = pos[[3, 63, 200, 63]].copy()
+            pts[2, :3] = 4.0
+            sk = np.array([3, 63, -1, 64], np.int32)
+            assert same(eng.nearest(pts, sk, r2=h2), ref.points(pos, pts, sk, r2=h2)), split
+            assert list(eng.nearest(pts, sk)[0]) == [70, 64, 63, 63]
+            assert eng.closest_pair()[:2] == (3, 70) and bits(eng.closest_pair()[2]) == 0
+    one = pos[:1]
+    with nb.NBody(1, fp64=fp64) as eng:
+        eng.upload(one, vel[:1])
+        idx, d2, cnt = eng.neighbors(r2=dtype(1e30))
+        assert idx[0] == -1 and np.isposinf(d2[0]) and cnt[0] == 0
+        i, j, d = eng.closest_pair()
+        assert (i, j) == (-1, -1) and np.isposinf(d)
+        assert eng.nearest(one)[0][0] == 0 and eng.nearest(one, np.zeros(1, np.int32))[0][0] == -1
+
+
+def test_bits_do_not_depend_on_the_source_split_or_the_batches(nb, ref, monkeypatch):
+    n, m = 5000, 700   # five blocks
+    pos, vel = nb.make_bodies(n)
+    pts, on = make_points(nb, pos, m)
+    skip = make_skip(n, m, on)
+    r2 = r2_for(pos, 0.1)
+    want = (ref.points(pos, pts, r2=r2), ref.points(pos, pts, skip, r2=r2), ref.rows(pos, 100, m, r2=r2))
+    with nb.NBody(n) as eng:
+        eng.upload(pos, vel)
+        calls = lambda: (eng.nearest(pts, r2=r2), eng.nearest(pts, skip, r2=r2), eng.neighbors(100, m, r2=r2))
+        for loop in ("1", "2"):
+            monkeypatch.setenv("NBODY_NEIGHBORS_LOOP", loop)
+            for split in (None, "1", "2", "3", "64"):
+                if split:
+                    monkeypatch.setenv("NBODY_NEIGHBORS_SPLIT", split)
+                for g_, w in zip(calls(), want):
+                    assert same(g_, w), (loop, split)
+                assert same(eng.nearest(pts, skip), want[1][:2] + (None,)), (loop, split)
+            # 700 queries x 5 chunks x 12 B = 42 kB against a bound of 0.02 MB: batches of 256 queries
+            monkeypatch.setenv("NBODY_NEIGHBORS_SCRATCH_MB", "0.02")
+            for split in ("5", None):
+                if split:
+                    monkeypatch.setenv("NBODY_NEIGHBORS_SPLIT", split)
+                else:
+                    monkeypatch.delenv("NBODY_NEIGHBORS_SPLIT")
+                for g_, w in zip(calls(), want):
+                    assert same(g_, w), (loop, "batches", split)
+            monkeypatch.setenv("NBODY_NEIGHBORS_SPLIT", "5")
+            monkeypatch.setenv("NBODY_NEIGHBORS_SCRATCH_MB", "0")   # not even one workgroup's queries fit: no split
+            assert same(calls()[1], want[1]), loop
+            monkeypatch.delenv("NBODY_NEIGHBORS_SPLIT")
+            monkeypatch.delenv("NBODY_NEIGHBORS_SCRATCH_MB")
+
+
+def test_bits_do_not_depend_on_the_queries_beside_a_query_or_the_force_configuration(nb, ref):
+    n, m = 5000, 700
+    pos, vel = nb.make_bodies(n)
+    pts, on = make_points(nb, pos, m)
+    skip = make_skip(n, m, on)
+    r2 = r2_for(pos, 0.1)
+    perm = np.random.default_rng(5).permutation(m)
+    with nb.NBody(n) as eng:
+        eng.upload(pos, vel)
+        a = eng.nearest(pts, skip, r2=r2)
+        rows = eng.neighbors(r2=r2)
+        assert same(a, ref.points(pos, pts, skip, r2=r2)) and same(rows, ref.rows(pos, r2=r2))
+        for sel in (slice(0, 1), slice(100, 357), slice(699, 700), slice(63, 129), perm):
+            assert same(eng.nearest(pts[sel], skip[sel], r2=r2), tuple(v[sel] for v in a)), sel
+        for key, val, default in ((nb.OPT_VARIANT, nb.VARIANT_SMEM, nb.VARIANT_AUTO), (nb.OPT_VARIANT, nb.VARIANT_LDS, nb.VARIANT_AUTO),
+                                  (nb.OPT_VARIANT, nb.VARIANT_READLANE, nb.VARIANT_AUTO), (nb.OPT_JSUB, 3, 0), (nb.OPT_JSLICES, 3, 0),
+                                  (nb.OPT_WSPLIT, 1, -1), (nb.OPT_WSPLIT, 16, -1), (nb.OPT_SUM_ORDER, nb.SUM_SEQ, nb.SUM_BLOCKED),
+                                  (nb.OPT_SUM_ORDER, nb.SUM_FPGA16, nb.SUM_BLOCKED)):
+            eng.set_option(key, val)
+            assert same(eng.nearest(pts, skip, r2=r2), a) and same(eng.neighbors(r2=r2), rows), (key, val)
+            eng.set_option(key, default)
+
+
+def test_bits_do_not_depend_on_the_device_count(nb, ref, monkeypatch):
+    monkeypatch.setenv("NBODY_OVERSUBSCRIBE", "1")
+    n, m = 1500, 300   # 1500 = 500 x 3: slices that end inside a 64-source window and inside a workgroup's rows
+    pos, vel = nb.make_bodies(n)
+    pts, on = make_points(nb, pos, m)
+    skip = make_skip(n, m, on)
+    r2 = r2_for(pos, 0.1)
+    res = {}
+    for ngpus in (1, 3):
+        with nb.NBody(n, ngpus=ngpus) as eng:
+            eng.upload(pos, vel)
+            # after a drift on the device each local holds only its own slice's new positions: the pass brings the rest first
+            eng.integrate(pos.copy(), vel.copy(), 0.01)
+            res[ngpus] = (eng.neighbors(r2=r2), eng.neighbors(450, 600, r2=r2), eng.nearest(pts, skip, r2=r2), eng.closest_pair(),
+                          eng.download()[0])
+    now = res[1][4]
+    assert same((now,), (res[3][4],)) and not same((now,), (pos,)), "the two states differ, or no drift happened"
+    want = ref.rows(now, r2=r2)
+    assert same(res[1][0], want)
+    for k in (1, 3):
+        assert same(res[k][0], want), k
+        assert same(res[k][1], tuple(w[450:1050] for w in want)), k   # a window across both device boundaries: global indices
+        assert same(res[k][2], ref.points(now, pts, skip, r2=r2)), k
+        assert res[k][3][:2] == ref.closest_pair(now)[:2] and bits(res[k][3][2]) == bits(ref.closest_pair(now)[2]), k
+
+
+WORKER = textwrap.dedent("""
+    import os, sys
+    import numpy as np
+    sys.path.insert(0, {root!r})
+    sys.path.insert(0, os.path.join({root!r}, "tests"))
+    import torch
+    import mini_nbody_amd as nb
+    import mini_nbody_amd.distributed as D
+    from field_common import make_points, make_skip
+    rank, world, local = D.init_process_group("gloo")
+    n = {n}
+    eng = D.make_engine(n, transport="host")
+    pos, vel = nb.make_bodies(n, seed=33)
+    eng.upload(pos, vel)
+    eng.step(0.01, 3)
+    m = (300, 41)[rank]
+    pts, on = make_points(nb, pos, m, seed=50 + rank)
+    r2 = np.float32(0.05)
+    idx, d2, cnt = eng.nearest(pts, make_skip(n, m, on), r2=r2)
+    ridx, rd2, rcnt = eng.neighbors(r2=r2)                      # this rank's own rows
+    pair = eng.closest_pair()
+    p, v = eng.download()
+    np.savez({out!r} + "_%d.npz" % rank, idx=idx, d2=d2, cnt=cnt, ridx=ridx, rd2=rd2, rcnt=rcnt, pair_ij=np.array(pair[:2]),
+             pair_d2=np.array([pair[2]], np.float32), first=np.array([eng.config["first_body"], eng.config["n_local"]]), pos=p)
+    eng.close()
+    import torch.distributed as dist
+    dist.barrier(); dist.destroy_process_group()
+""")
+
+
+def test_two_processes_host_transport_equal_one_process(nb, ref, tmp_path):
+    n, world = 1500, 2
+    out = str(tmp_path / "nbr")
+    script = tmp_path / "worker.py"
+    script.write_text(WORKER.format(root=ROOT, n=n, out=out))
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    procs = []
+    for r in range(world):
+        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
+                   MASTER_PORT=str(port), NBODY_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
+        procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
+    for p in procs:
+        o, _ = p.communicate(timeout=300)
+        assert p.returncode == 0, o.decode()[-3000:]
+    got = [np.load(out + "_%d.npz" % r) for r in range(world)]
+    now = got[0]["pos"]
+    assert same((now,), (got[1]["pos"],))
+    pos = nb.make_bodies(n, seed=33)[0]
+    r2 = np.float32(0.05)
+    want_rows = ref.rows(now, r2=r2)
+    want_pair = ref.closest_pair(now)
+    covered = 0
+    for r, m in enumerate((300, 41)):
+        g_ = got[r]
+        pts, on = make_points(nb, pos, m, seed=50 + r)
+        assert same((g_["idx"], g_["d2"], g_["cnt"]), ref.points(now, pts, make_skip(n, m, on), r2=r2)), r
+        first, cnt = (int(v) for v in g_["first"])
+        assert same((g_["ridx"], g_["rd2"], g_["rcnt"]), tuple(w[first:first + cnt] for w in want_rows)), r   # global indices
+        covered += cnt
+        assert tuple(int(v) for v in g_["pair_ij"]) == want_pair[:2] and bits(g_["pair_d2"][0]) == bits(want_pair[2]), r
+    assert covered == n
+    with nb.NBody(n) as one:   # ... and equal to one GPU
+        one.upload(now, np.zeros_like(now))
+        i, j, d = one.closest_pair()
+        assert (i, j) == want_pair[:2] and bits(d) == bits(want_pair[2])
+
+
+@pytest.mark.parametrize("fp64", [False, True])
+def test_closest_pair_n16384(nb, ref, fp64):
+    n = 16384
+    pos, vel = nb.make_bodies(n, dtype=np.float64 if fp64 else np.float32)
+    wi, wj, wd = ref.closest_pair(pos)
+    rows = ref.rows(pos)
+    assert rows[0][wi] == wj and bits(rows[1].min()) == bits(wd)   # the pair scan and the rows scan agree
+    with nb.NBody(n, fp64=fp64) as eng:
+        eng.upload(pos, vel)
+        i, j, d = eng.closest_pair()
+        assert (i, j) == (wi, wj) and bits(d) == bits(wd)
+        assert same(eng.neighbors(), rows)
+
+
+def test_rows_n65536(nb, ref, monkeypatch):
+    """the window re-walk and many workgroups are live here"""
+    n = 65536
+    pos, vel = nb.make_bodies(n)
+    r2 = np.float32(1e-3)
+    with nb.NBody(n) as eng:
+        eng.upload(pos, vel)
+        for first in (0, n // 2 - 256, n - 512):
+            want = ref.rows(pos, first, 512, r2=r2)
+            for loop in ("1", "2"):
+                monkeypatch.setenv("NBODY_NEIGHBORS_LOOP", loop)
+                assert same(eng.neighbors(first, 512, r2=r2), want), (first, loop)
+                assert same(eng.neighbors(first, 512), want[:2] + (None,)), (first, loop)
+
+
+def run_steps(nb, n, pos, vel, plan, graph, probe, timing=False):
+    pts, on = make_points(nb, pos, 300)
+    with nb.NBody(n) as eng:
+        eng.set_option(nb.OPT_GRAPH, graph)
+        if timing:
+            eng.set_option(nb.OPT_TIMING, 1)
+        eng.upload(pos, vel)
+        for k in plan:
+            eng.step(0.01, k)
+            if probe:
+                eng.neighbors(r2=np.float32(0.01))
+                eng.nearest(pts, make_skip(n, 300, on))
+                eng.closest_pair()
+        p, v = eng.download()
+        launches = eng.kernel_time()[1] if timing else None
+    return p, v, launches
+
+
+def test_neighbor_calls_leave_the_step_untouched(nb, monkeypatch):
+    n = 1500   # two blocks: a forced split takes the scratch and combine path between the steps too
+    pos, vel = nb.make_bodies(n)
+    for plan, graph, timing in (([1] * 12, 0, False), ([64, 64, 6, 64], 1, False), ([3, 5, 2], 0, True)):
+        monkeypatch.delenv("NBODY_NEIGHBORS_SPLIT", raising=False)
+        a = run_steps(nb, n, pos, vel, plan, graph, False, timing)
+        for split in (None, "2"):
+            if split:
+                monkeypatch.setenv("NBODY_NEIGHBORS_SPLIT", split)
+            b = run_steps(nb, n, pos, vel, plan, graph, True, timing)
+            assert same(a[:2], b[:2]), (plan, graph)
+            assert a[2] == b[2], "neighbour launches were counted by nbody_kernel_time"
+
+
+def test_guards(nb):
+    lib, E = nb._lib.load(), nb._lib
+    f32, f64, ip = C.POINTER(C.c_float), C.POINTER(C.c_double), lambda a: a.ctypes.data_as(C.POINTER(C.c_int))
+    pts, pts64 = np.zeros((4, 4), np.float32), np.zeros((4, 4), np.float64)
+    idx, cnt = np.full(4, 7, np.int32), np.full(4, 7, np.int32)
+    d2, d264 = np.full(4, 7, np.float32), np.full(4, 7, np.float64)
+    sk = np.array([-1, 0, 3, 2], np.int32)
+    calls32 = (lambda: lib.nbody_neighbors_rows(0, 4, ip(idx), d2.ctypes.data_as(f32), 1.0, ip(cnt)),
+               lambda: lib.nbody_nearest(pts.ctypes.data_as(f32), 4, ip(sk), ip(idx), d2.ctypes.data_as(f32), 1.0, ip(cnt)),
+               lambda: lib.nbody_closest_pair(ip(idx), ip(idx[1:]), d2.ctypes.data_as(f32)))
+    calls64 = (lambda: lib.nbody_neighbors_rows_d(0, 4, ip(idx), d264.ctypes.data_as(f64), 1.0, ip(cnt)),
+               lambda: lib.nbody_nearest_d(pts64.ctypes.data_as(f64), 4, ip(sk), ip(idx), d264.ctypes.data_as(f64), 1.0, ip(cnt)),
+               lambda: lib.nbody_closest_pair_d(ip(idx), ip(idx[1:]), d264.ctypes.data_as(f64)))
+    untouched = lambda: np.all(idx == 7) and np.all(cnt == 7) and np.all(d2 == 7) and np.all(d264 == 7)
+    with nb.Mailbox(capacity=1024, faithful=False) as mb:
+        mb.serve(True, clock_khz=300000)
+        try:
+            assert [c() for c in calls32 + calls64] == [E.ERR_STATE] * 6
+        finally:
+            mb.serve(False)
+        assert untouched()
+    n = 100
+    pos, vel = nb.make_bodies(n)
+    with nb.NBody(n) as eng:
+        eng.upload(pos, vel)
+        assert [c() for c in calls64] == [E.ERR_STATE] * 3 and untouched()
+        i_, d_, c_, x = ip(idx), d2.ctypes.data_as(f32), ip(cnt), pts.ctypes.data_as(f32)
+        assert lib.nbody_neighbors_rows(0, 4, None, None, 1.0, None) == E.ERR_ARG
+        for first, rows in ((-1, 4), (0, 0), (0, -2), (97, 4), (100, 1), (0, 101), (1 << 30, 1 << 30)):
+            assert lib.nbody_neighbors_rows(first, rows, i_, d_, 1.0, c_) == E.ERR_ARG, (first, rows)
+        assert lib.nbody_nearest(None, 4, None, i_, d_, 1.0, c_) == E.ERR_ARG
+        assert lib.nbody_nearest(x, 0, None, i_, d_, 1.0, c_) == E.ERR_ARG
+        assert lib.nbody_nearest(x, -3, None, i_, d_, 1.0, c_) == E.ERR_ARG
+        assert lib.nbody_nearest(x, 4, None, None, None, 1.0, None) == E.ERR_ARG
+        for bad in (n, -2, 1 << 30):
+            sk[:] = (-1, 0, bad, n - 1)
+            assert lib.nbody_nearest(x, 4, ip(sk), i_, d_, 1.0, c_) == E.ERR_ARG, bad
+        assert lib.nbody_closest_pair(None, None, None) == E.ERR_ARG
+        assert untouched()
+        sk[:] = (-1, 0, n - 1, n - 1)
+        assert lib.nbody_nearest(x, 4, ip(sk), i_, None, 1.0, None) == 0 and not np.any(idx == 7) and np.all(d2 == 7) and np.all(cnt == 7)
+        assert lib.nbody_neighbors_rows(96, 4, None, d_, 1.0, None) == 0 and not np.any(d2 == 7) and np.all(cnt == 7)
+        assert lib.nbody_neighbors_rows(96, 4, None, None, 100.0, c_) == 0 and np.all(cnt == n - 1)
+        assert lib.nbody_closest_pair(None, i_, None) == 0 and idx[0] == eng.closest_pair()[1]
+    with nb.NBody(n, fp64=True) as eng:
+        eng.upload(pos.astype(np.float64), vel.astype(np.float64))
+        assert [c() for c in calls32] == [E.ERR_STATE] * 3 and [c() for c in calls64] == [0] * 3
+
+
+def test_c_host_program_closest_pair_line(nb, ref):
+    exe = os.path.join(ROOT, "build", "nbody")
+    n, iters = 4096, 3
+    for flags, fp64 in (([], False), (["--fp64"], True)):
+        r = subprocess.run([exe, str(n), str(iters), "--closest-pair"] + flags, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stdout + r.stderr
+        lines = re.findall(r"^closest pair: (-?\d+) (-?\d+) d2 (\S+)$", r.stdout, flags=re.M)
+        assert len(lines) == 1, r.stdout
+        plain = subprocess.run([exe, str(n), str(iters)] + flags, capture_output=True, text=True, timeout=300)
+        assert plain.returncode == 0 and "closest" not in plain.stdout
+        strip = lambda text: [ln for ln in text.splitlines() if "Billion Interactions" not in ln and not ln.startswith("closest pair")]
+        assert strip(r.stdout) == strip(plain.stdout)   # nothing else changes (the rate line carries a time)
+        dtype = np.float64 if fp64 else np.float32
+        pos, vel = nb.make_bodies(n, dtype=dtype)
+        with nb.NBody(n, fp64=fp64) as eng:
+            eng.upload(pos, vel)
+            eng.step(float(np.float32(0.01)), iters)   # the program's dt is the binary32 0.01 in fp64 contexts too
+            now = eng.download()[0]
+        wi, wj, wd = ref.closest_pair(now)
+        assert (int(lines[0][0]), int(lines[0][1])) == (wi, wj) and dtype(float(lines[0][2])) == wd

@@ -960,20 +960,20 @@ int nbody_download(BodySystem* host) { NB_REFUSE_WHILE_SERVED(); if (!host) retu
 int nbody_upload_d(const BodySystemD* host) { NB_REFUSE_WHILE_SERVED(); if (!host) return NBODY_ERR_ARG; if (g.init && !g.fp64) return NBODY_ERR_STATE; return upload_impl(host->pos, host->vel); }
 int nbody_download_d(BodySystemD* host) { NB_REFUSE_WHILE_SERVED(); if (!host) return NBODY_ERR_ARG; if (g.init && !g.fp64) return NBODY_ERR_STATE; return download_impl(host->pos, host->vel); }
 
-int bodyForce(float* pos, float* vel, float dt, int n) { NB_REFUSE_WHILE_SERVED(); if (g.init && g.fp64) return NBODY_ERR_STATE; return body_force_impl(pos, vel, dt, (double)dt, n); }
-int integrate(float* pos, const float* vel, float dt, int n) { NB_REFUSE_WHILE_SERVED(); if (g.init && g.fp64) return NBODY_ERR_STATE; return integrate_impl(pos, vel, dt, (double)dt, n); }
-int bodyForce_d(double* pos, double* vel, double dt, int n) { NB_REFUSE_WHILE_SERVED(); if (g.init && !g.fp64) return NBODY_ERR_STATE; return body_force_impl(pos, vel, (float)dt, dt, n); }
-int integrate_d(double* pos, const double* vel, double dt, int n) { NB_REFUSE_WHILE_SERVED(); if (g.init && !g.fp64) return NBODY_ERR_STATE; return integrate_impl(pos, vel, (float)dt, dt, n); }
+int bodyForce(float* pos, float* vel, float dt, int n) { NB_ENTER(0); return body_force_impl(pos, vel, dt, (double)dt, n); }
+int integrate(float* pos, const float* vel, float dt, int n) { NB_ENTER(0); return integrate_impl(pos, vel, dt, (double)dt, n); }
+int bodyForce_d(double* pos, double* vel, double dt, int n) { NB_ENTER(1); return body_force_impl(pos, vel, (float)dt, dt, n); }
+int integrate_d(double* pos, const double* vel, double dt, int n) { NB_ENTER(1); return integrate_impl(pos, vel, (float)dt, dt, n); }
 
-int nbody_step(float dt, int nsteps) { NB_REFUSE_WHILE_SERVED(); if (g.init && g.fp64) return NBODY_ERR_STATE; return step_impl(dt, (double)dt, nsteps); }
-int nbody_step_d(double dt, int nsteps) { NB_REFUSE_WHILE_SERVED(); if (g.init && !g.fp64) return NBODY_ERR_STATE; return step_impl((float)dt, dt, nsteps); }
+int nbody_step(float dt, int nsteps) { NB_ENTER(0); return step_impl(dt, (double)dt, nsteps); }
+int nbody_step_d(double dt, int nsteps) { NB_ENTER(1); return step_impl((float)dt, dt, nsteps); }
 int nbody_sync(void) { NB_REFUSE_WHILE_SERVED(); if (!g.init) return NBODY_ERR_NOT_INIT; return sync_all(); }
 
-int nbody_forces(const float* pos_words, float* force_words, int n) { NB_REFUSE_WHILE_SERVED(); if (g.init && g.fp64) return NBODY_ERR_STATE; return forces_impl(pos_words, force_words, n); }
-int nbody_forces_d(const double* pos_words, double* force_words, int n) { NB_REFUSE_WHILE_SERVED(); if (g.init && !g.fp64) return NBODY_ERR_STATE; return forces_impl(pos_words, force_words, n); }
+int nbody_forces(const float* pos_words, float* force_words, int n) { NB_ENTER(0); return forces_impl(pos_words, force_words, n); }
+int nbody_forces_d(const double* pos_words, double* force_words, int n) { NB_ENTER(1); return forces_impl(pos_words, force_words, n); }
 
-int nbody_forces_rows(int first_row, int n_rows, float* force_words) { NB_REFUSE_WHILE_SERVED(); if (g.init && g.fp64) return NBODY_ERR_STATE; return forces_rows_impl(first_row, n_rows, force_words); }
-int nbody_forces_rows_d(int first_row, int n_rows, double* force_words) { NB_REFUSE_WHILE_SERVED(); if (g.init && !g.fp64) return NBODY_ERR_STATE; return forces_rows_impl(first_row, n_rows, force_words); }
+int nbody_forces_rows(int first_row, int n_rows, float* force_words) { NB_ENTER(0); return forces_rows_impl(first_row, n_rows, force_words); }
+int nbody_forces_rows_d(int first_row, int n_rows, double* force_words) { NB_ENTER(1); return forces_rows_impl(first_row, n_rows, force_words); }
 
 int nbody_kernel_time(double* ms_total, long long* launches, int reset) { NB_REFUSE_WHILE_SERVED();
   if (!g.init) return NBODY_ERR_NOT_INIT;

@@ -1,0 +1,89 @@
+// diag_pass.hpp — what the diagnostic passes (energy, field, neighbours) share, stated once: the two launch constants their hosts and
+// kernels agree on and, for device code, the pair arithmetic of the potential and the lane / wave preamble of a one-query-per-lane
+// kernel.  energy_args.hpp, field_args.hpp and neighbors_args.hpp include it.  Like them it stays apart from the force path's hashed
+// source (nbody_args.hpp, nbody_kernels.hpp, kernels.hip, force_loop_gfx950.inc), of which it reads nbody_args.hpp (kSoftBits) only.
+// The kernels' loops are different computations and stay in their files.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace nbd {
+
+constexpr int kSrcBlock = 1024;   // sources per block: a level-1 sum of the potential and the field, the unit of a split launch's chunks
+constexpr int kLanes = 256;       // lanes per workgroup, one row, point or query each
+
+}  // namespace nbd
+
+#ifdef __HIP__
+#include "nbody_args.hpp"
+
+namespace nbd {
+
+constexpr int kRef = 1, kStrict = 2;   // bits of NBODY_ARITH_*: the reference's d2 roundings, the strict 1/sqrt
+
+__device__ __forceinline__ float fma_of(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fma_of(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
+template <typename T>
+__device__ __forceinline__ T soft() { return (T)__builtin_bit_cast(float, nbk::kSoftBits); }   // the force's eps (S/dzsoft.vhd:177)
+
+// THE statement of (|d|^2 + eps)^(-1/2) for the diagnostic passes, from the three differences, with the force's d2 (nbody_kernels.hpp
+// pair_f32): 3 v_fma (FMA3) or the reference's five roundings, then 1 v_rsq_f32.  Strict: the IEEE definition the library's strict
+// 1/sqrt is proved equal to (nbody_strict_proof).
+template <int ARITH>
+__device__ __forceinline__ float inv_dist(float dx, float dy, float dz, float eps) {
+  float d2;
+  if constexpr (ARITH & kRef) {
+    const float sxy = dx * dx + dy * dy;             // S/dxy.vhd:113-122 (compiled with -ffp-contract=off)
+    const float sz = __builtin_fmaf(dz, dz, eps);    // S/dzsoft.vhd:201-202
+    d2 = sxy + sz;                                   // S/dxyz_soft.vhd:149-150
+  } else {
+    d2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, __builtin_fmaf(dz, dz, eps)));
+  }
+  if constexpr (ARITH & kStrict) return (float)(1.0 / __builtin_sqrt((double)d2));
+  else return __builtin_amdgcn_rsqf(d2);             // 1 ulp; d2 >= eps is never subnormal
+}
+// fp64 (one d2 form, as the force's pair_f64): the v_rsq_f64 seed y refined to full precision by one third-order step,
+// with e = 1 - d2 y^2:  d2^(-1/2) = y (1 - e)^(-1/2) = y + y e (1/2 + 3/8 e) + O(e^3);  strict: IEEE sqrt and divide
+template <int ARITH>
+__device__ __forceinline__ double inv_dist(double dx, double dy, double dz, double eps) {
+  const double d2 = __builtin_fma(dx, dx, __builtin_fma(dy, dy, __builtin_fma(dz, dz, eps)));
+  if constexpr (ARITH & kStrict) {
+    return 1.0 / __builtin_sqrt(d2);
+  } else {
+    const double y = __builtin_amdgcn_rsq(d2);
+    const double e = __builtin_fma(-d2, y * y, 1.0);
+    return __builtin_fma(y * e, __builtin_fma(e, 0.375, 0.5), y);
+  }
+}
+
+// One query per lane, kLanes per workgroup: query p of the launch's m.  Lanes beyond m stay in the wave-uniform loops clamped to the
+// last query (pc) and store nothing (live).
+struct Lane { int p; bool live; int pc; };
+__device__ __forceinline__ Lane lane_of(int m) {
+  const int p = (int)blockIdx.x * kLanes + (int)threadIdx.x;
+  const bool live = p < m;
+  return {p, live, live ? p : m - 1};
+}
+
+// [lo, hi]: the lowest and highest excluded source index (sk; < 0: none) among the wave's 64 lanes, wave-uniform — only the aligned
+// 64-source windows that overlap it have to compare j with sk.  [kNoSkipLo, -1], which no window overlaps, when no lane excludes anything.
+constexpr int kNoSkipLo = 0x7fffffff;
+struct SkipWindow { int lo, hi; };
+__device__ __forceinline__ SkipWindow wave_skip_window(int sk) {
+  int lo = sk < 0 ? kNoSkipLo : sk, hi = sk;
+  for (int off = 32; off > 0; off >>= 1) {
+    lo = min(lo, __shfl_xor(lo, off, 64));
+    hi = max(hi, __shfl_xor(hi, off, 64));
+  }
+  return {__builtin_amdgcn_readfirstlane(lo), __builtin_amdgcn_readfirstlane(hi)};
+}
+
+// blocks [b0, b1) of chunk blockIdx.y of a launch whose sources are split into chunks of chunk_blocks whole blocks
+struct Blocks { int b0, b1; };
+__device__ __forceinline__ Blocks chunk_of(int chunk_blocks, int n_blocks) {
+  const int b0 = (int)blockIdx.y * chunk_blocks;
+  return {b0, min(b0 + chunk_blocks, n_blocks)};
+}
+
+}  // namespace nbd
+#endif  // __HIP__

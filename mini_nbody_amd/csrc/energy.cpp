@@ -1,10 +1,10 @@
 // energy.cpp — nbody_energy and nbody_potential_rows(_d): the energy pass (energy.hip) over the state on the device.  Host C++ only.
-// Flow: reconfigure(), complete_positions() (the other slices, as nbody_forces_rows brings them), one pass per local on its compute
-// stream, then the ranks' eight fp64 values added in rank order.  Processes exchange those values through the transport they use for
-// positions (allgather_rank_words), never a reduction, so every rank adds the same numbers in the same order.
+// Flow (query_pass.hpp): reconfigure(), complete_positions() (the other slices, as nbody_forces_rows brings them), one pass per local
+// on its compute stream, then the ranks' eight fp64 values added in rank order.  Processes exchange those values through the transport
+// they use for positions (gather_rank_words), never a reduction, so every rank adds the same numbers in the same order.
 // The pass reads pos[cur] and vel and writes only the Local's en_* buffers: positions, velocities, arrival counters, partial forces,
 // the captured step graph and the force-kernel timer stay as they were.
-#include "nbody_internal.hpp"
+#include "query_pass.hpp"
 #include "energy_args.hpp"
 
 using namespace nbe;
@@ -50,18 +50,7 @@ int energy_impl(double* out) {
   NBC(complete_positions());
   for (int l = 0; l < g.nlocal; ++l) NBC(launch_energy(g.loc[l], 0, g.loc[l].n_local, true));
   std::vector<double> all((size_t)g.nranks * kEnergyWords, 0.0);
-  if (g.multiprocess && g.nranks > 1) {
-    Local& L = g.loc[0];
-    NBC(allgather_rank_words(L, L.en_tot, all.data(), kEnergyWords * (int)sizeof(double)));
-  } else {
-    for (int l = 0; l < g.nlocal; ++l) {
-      Local& L = g.loc[l];
-      HIPC(hipSetDevice(L.device));
-      const size_t off = (size_t)L.rank * kEnergyWords;
-      HIPC(hipStreamSynchronize(L.compute));   // then a blocking copy into the caller's pageable memory, as the other entry points do
-      HIPC(hipMemcpy(all.data() + off, L.en_tot.as<double>() + off, kEnergyWords * sizeof(double), hipMemcpyDeviceToHost));
-    }
-  }
+  NBC(gather_rank_words(&Local::en_tot, all.data(), kEnergyWords * (int)sizeof(double)));
   for (int q = 0; q < kEnergyWords; ++q) {
     double s = 0.0;
     for (int r = 0; r < g.nranks; ++r) s += all[(size_t)r * kEnergyWords + q];   // rank order
@@ -77,16 +66,8 @@ int potential_rows_impl(int first_row, int n_rows, void* phi) {
   NBC(w.open(first_row, n_rows));
   NBC(reconfigure());
   NBC(complete_positions());
-  const size_t es = g.fp64 ? sizeof(double) : sizeof(float);
-  for (int l = 0; l < g.nlocal; ++l) {
-    Local& L = g.loc[l];
-    int r0, cnt;
-    if (!w.rows_of(L, &r0, &cnt)) continue;
-    NBC(launch_energy(L, r0, cnt, false));
-    HIPC(hipStreamSynchronize(L.compute));
-    HIPC(hipMemcpy((char*)phi + (size_t)(L.first + r0 - w.g0) * es, L.en_phi, (size_t)cnt * es, hipMemcpyDeviceToHost));
-  }
-  return NBODY_OK;
+  return run_on_locals([&](int l) { return rows_of(w, l); }, [&](Local& L, const Range& r) { return launch_energy(L, r.first, r.cnt, false); },
+                       [&](Local& L, const Range& r) { return copy_out(phi, r.out, L.en_phi, r.cnt, elem_bytes()); });
 }
 
 }  // namespace
@@ -98,12 +79,10 @@ using namespace nbi;
 extern "C" {
 
 int nbody_energy(double* out) { NB_REFUSE_WHILE_SERVED(); return energy_impl(out); }
-int nbody_potential_rows(int first_row, int n_rows, float* phi) { NB_REFUSE_WHILE_SERVED();
-  if (g.init && g.fp64) return NBODY_ERR_STATE;
+int nbody_potential_rows(int first_row, int n_rows, float* phi) { NB_ENTER(0);
   return potential_rows_impl(first_row, n_rows, phi);
 }
-int nbody_potential_rows_d(int first_row, int n_rows, double* phi) { NB_REFUSE_WHILE_SERVED();
-  if (g.init && !g.fp64) return NBODY_ERR_STATE;
+int nbody_potential_rows_d(int first_row, int n_rows, double* phi) { NB_ENTER(1);
   return potential_rows_impl(first_row, n_rows, phi);
 }
 

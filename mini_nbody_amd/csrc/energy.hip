@@ -1,8 +1,7 @@
 // energy.hip — the energy pass's device code: the all-pairs potential phi_i of every row and the per-workgroup fp64 partial sums of
 // {T, U, P, L}, then one small launch that adds the partials (energy_args.hpp states the order, include/nbody.h the definitions).
-// Compiles on its own; device.hip puts it into the library's one code object next to kernels.hip.  Reads nbody_args.hpp (f4, d4,
-// kSoftBits) and nothing else of the force path: nbody_kernels.hpp is the force path's hashed source, so the few lines of pair
-// arithmetic the potential needs are restated here, rounding for rounding.  gfx950 only.
+// Compiles on its own; device.hip puts it into the library's one code object next to kernels.hip.  Reads nbody_args.hpp (f4, d4)
+// and nothing else of the force path; the pair arithmetic of the potential is diag_pass.hpp's inv_dist.  gfx950 only.
 #include <hip/hip_runtime.h>
 
 #include "../../include/nbody.h"
@@ -11,46 +10,11 @@
 
 using namespace nbk;
 using namespace nbe;
+using namespace nbd;
 
 #define NBE_HIDDEN __attribute__((visibility("hidden")))
 
 namespace {
-
-constexpr int kRef = 1, kStrict = 2;   // bits of NBODY_ARITH_*: the reference's d2 roundings, the strict 1/sqrt
-
-// 1/sqrt(|r_j - r_i|^2 + eps) with the force's d2 (nbody_kernels.hpp pair_f32): 3 v_sub, 3 v_fma (FMA3), 1 v_rsq_f32.
-// Strict: the IEEE definition the library's strict 1/sqrt is proved equal to (nbody_strict_proof).
-template <int ARITH>
-__device__ __forceinline__ float inv_dist(float xj, float yj, float zj, float xi, float yi, float zi, float eps) {
-  const float dx = xj - xi, dy = yj - yi, dz = zj - zi;
-  float d2;
-  if constexpr (ARITH & kRef) {
-    const float sxy = dx * dx + dy * dy;             // S/dxy.vhd:113-122 (compiled with -ffp-contract=off)
-    const float sz = __builtin_fmaf(dz, dz, eps);    // S/dzsoft.vhd:201-202
-    d2 = sxy + sz;                                   // S/dxyz_soft.vhd:149-150
-  } else {
-    d2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, __builtin_fmaf(dz, dz, eps)));
-  }
-  if constexpr (ARITH & kStrict) return (float)(1.0 / __builtin_sqrt((double)d2));
-  else return __builtin_amdgcn_rsqf(d2);             // 1 ulp; d2 >= eps is never subnormal
-}
-// fp64 (one d2 form, as the force's pair_f64): the v_rsq_f64 seed y refined to full precision by one third-order step,
-// with e = 1 - d2 y^2:  d2^(-1/2) = y (1 - e)^(-1/2) = y + y e (1/2 + 3/8 e) + O(e^3);  strict: IEEE sqrt and divide
-template <int ARITH>
-__device__ __forceinline__ double inv_dist(double xj, double yj, double zj, double xi, double yi, double zi, double eps) {
-  const double dx = xj - xi, dy = yj - yi, dz = zj - zi;
-  const double d2 = __builtin_fma(dx, dx, __builtin_fma(dy, dy, __builtin_fma(dz, dz, eps)));
-  if constexpr (ARITH & kStrict) {
-    return 1.0 / __builtin_sqrt(d2);
-  } else {
-    const double y = __builtin_amdgcn_rsq(d2);
-    const double e = __builtin_fma(-d2, y * y, 1.0);
-    return __builtin_fma(y * e, __builtin_fma(e, 0.375, 0.5), y);
-  }
-}
-
-template <typename T>
-__device__ __forceinline__ T soft() { return (T)__builtin_bit_cast(float, kSoftBits); }   // the force's eps (S/dzsoft.vhd:177)
 
 // One row per lane, kEnergyRows rows per workgroup, every lane walks all N sources in kEnergyBlock blocks.  Sources arrive with
 // wave-uniform scalar loads (address space 4, as force_smem_f32).  The self pair is skipped by a wave-uniform branch: only the one or two
@@ -80,20 +44,20 @@ __global__ void __launch_bounds__(kEnergyRows) energy_kernel(EnergyArgs a) {
 #pragma unroll 8
         for (int k = 0; k < 64; ++k) {
           const V4 p = src[j + k];
-          s += inv_dist<ARITH>(p.x, p.y, p.z, me.x, me.y, me.z, eps);
+          s += inv_dist<ARITH>(p.x - me.x, p.y - me.y, p.z - me.z, eps);
         }
       } else {
 #pragma unroll 8
         for (int k = 0; k < 64; ++k) {
           const V4 p = src[j + k];
-          const T t = inv_dist<ARITH>(p.x, p.y, p.z, me.x, me.y, me.z, eps);
+          const T t = inv_dist<ARITH>(p.x - me.x, p.y - me.y, p.z - me.z, eps);
           s += (j + k == i) ? (T)0 : t;
         }
       }
     }
     for (; j < b1; ++j) {   // the last block's tail (N not a multiple of 64)
       const V4 p = src[j];
-      const T t = inv_dist<ARITH>(p.x, p.y, p.z, me.x, me.y, me.z, eps);
+      const T t = inv_dist<ARITH>(p.x - me.x, p.y - me.y, p.z - me.z, eps);
       s += (j == i) ? (T)0 : t;
     }
     l2 += (double)s;

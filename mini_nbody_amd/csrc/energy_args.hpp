@@ -11,10 +11,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "diag_pass.hpp"
+
 namespace nbe {
 
-constexpr int kEnergyBlock = 1024;   // sources per level-1 block
-constexpr int kEnergyRows = 256;     // rows per workgroup = per partial of the totals
+constexpr int kEnergyBlock = nbd::kSrcBlock;   // sources per level-1 block
+constexpr int kEnergyRows = nbd::kLanes;        // rows per workgroup = per partial of the totals
 constexpr int kEnergyWords = 8;      // {T, U, Px, Py, Pz, Lx, Ly, Lz} = NBODY_ENERGY_*
 
 struct EnergyArgs {

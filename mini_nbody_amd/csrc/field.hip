@@ -1,8 +1,7 @@
 // field.hip — the field pass's device code: acceleration and potential of the N bodies on the device at m arbitrary points
 // (field_args.hpp states the order, include/nbody.h the definitions).  Compiles on its own; device.hip puts it into the library's one
-// code object after kernels.hip and energy.hip.  Reads nbody_args.hpp (f4, d4, kSoftBits, NB_CONST) and nothing else of the force path:
-// nbody_kernels.hpp is the force path's hashed source, so the pair arithmetic is restated here, rounding for rounding — d2 and 1/sqrt
-// as energy.hip's inv_dist, the cube and the three fma as the force's pair_f32 / pair_f64.  gfx950 only.
+// code object after kernels.hip and energy.hip.  Reads nbody_args.hpp (f4, d4, NB_CONST) and nothing else of the force path: d2 and
+// 1/sqrt are diag_pass.hpp's inv_dist, the potential's; the cube and the three fma follow the force's pair_f32 / pair_f64.  gfx950 only.
 #include <hip/hip_runtime.h>
 
 #include "../../include/nbody.h"
@@ -11,44 +10,11 @@
 
 using namespace nbk;
 using namespace nbf;
+using namespace nbd;
 
 #define NBF_HIDDEN __attribute__((visibility("hidden")))
 
 namespace {
-
-constexpr int kFRef = 1, kFStrict = 2;   // bits of NBODY_ARITH_*: the reference's d2 roundings, the strict 1/sqrt
-
-// (|d|^2 + eps)^(-1/2) from the differences: fp32 3 v_fma (FMA3) or the reference's five roundings, 1 v_rsq_f32; strict: the IEEE value
-template <int ARITH>
-__device__ __forceinline__ float inv_of(float dx, float dy, float dz, float eps) {
-  float d2;
-  if constexpr (ARITH & kFRef) {
-    const float sxy = dx * dx + dy * dy;             // S/dxy.vhd:113-122 (compiled with -ffp-contract=off)
-    const float sz = __builtin_fmaf(dz, dz, eps);    // S/dzsoft.vhd:201-202
-    d2 = sxy + sz;                                   // S/dxyz_soft.vhd:149-150
-  } else {
-    d2 = __builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, __builtin_fmaf(dz, dz, eps)));
-  }
-  if constexpr (ARITH & kFStrict) return (float)(1.0 / __builtin_sqrt((double)d2));
-  else return __builtin_amdgcn_rsqf(d2);             // 1 ulp; d2 >= eps is never subnormal
-}
-// fp64: the fma-contracted d2; the v_rsq_f64 seed y refined by the energy pass's third-order step (e = 1 - d2 y^2); strict: IEEE
-template <int ARITH>
-__device__ __forceinline__ double inv_of(double dx, double dy, double dz, double eps) {
-  const double d2 = __builtin_fma(dx, dx, __builtin_fma(dy, dy, __builtin_fma(dz, dz, eps)));
-  if constexpr (ARITH & kFStrict) {
-    return 1.0 / __builtin_sqrt(d2);
-  } else {
-    const double y = __builtin_amdgcn_rsq(d2);
-    const double e = __builtin_fma(-d2, y * y, 1.0);
-    return __builtin_fma(y * e, __builtin_fma(e, 0.375, 0.5), y);
-  }
-}
-__device__ __forceinline__ float fma_t(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double fma_t(double a, double b, double c) { return __builtin_fma(a, b, c); }
-
-template <typename T>
-__device__ __forceinline__ T field_soft() { return (T)__builtin_bit_cast(float, kSoftBits); }   // the force's eps (S/dzsoft.vhd:177)
 
 // the four level-1 accumulators of one point
 template <typename T>
@@ -58,10 +24,10 @@ struct Acc { T ax, ay, az, s; };
 template <int ARITH, bool CMP, typename T, typename V4>
 __device__ __forceinline__ void pair(const V4 p, const V4 me, T eps, int j, int sk, Acc<T>& c) {
   const T dx = p.x - me.x, dy = p.y - me.y, dz = p.z - me.z;
-  const T inv = inv_of<ARITH>(dx, dy, dz, eps);
+  const T inv = inv_dist<ARITH>(dx, dy, dz, eps);
   const T inv2 = inv * inv;
   const T inv3 = inv * inv2;
-  const T ax = fma_t(dx, inv3, c.ax), ay = fma_t(dy, inv3, c.ay), az = fma_t(dz, inv3, c.az), s = c.s + inv;
+  const T ax = fma_of(dx, inv3, c.ax), ay = fma_of(dy, inv3, c.ay), az = fma_of(dz, inv3, c.az), s = c.s + inv;
   if (CMP && j == sk) return;
   c.ax = ax; c.ay = ay; c.az = az; c.s = s;
 }
@@ -79,26 +45,18 @@ __device__ __forceinline__ void store_out(const FieldArgs& a, int p, double ax, 
 // 3 fma, 1 rsq, 2 mul, 3 fma and 1 add per pair.
 template <typename T, typename V4, int ARITH, bool SKIP>
 __global__ void __launch_bounds__(kFieldPoints) field_kernel(FieldArgs a) {
-  const int p = (int)blockIdx.x * kFieldPoints + (int)threadIdx.x;
-  const bool live = p < a.m;
-  const int pc = live ? p : a.m - 1;
+  const auto [p, live, pc] = lane_of(a.m);
   const V4 me = ((const V4*)a.points)[pc];
-  int sk = -1, wlo = 0x7fffffff, whi = -1;
+  int sk = -1, wlo = kNoSkipLo, whi = -1;
   if constexpr (SKIP) {
     sk = a.skip[pc];
-    int lo = sk < 0 ? 0x7fffffff : sk, hi = sk;
-    for (int off = 32; off > 0; off >>= 1) {
-      lo = min(lo, __shfl_xor(lo, off, 64));
-      hi = max(hi, __shfl_xor(hi, off, 64));
-    }
-    wlo = __builtin_amdgcn_readfirstlane(lo);
-    whi = __builtin_amdgcn_readfirstlane(hi);
+    const SkipWindow win = wave_skip_window(sk);
+    wlo = win.lo; whi = win.hi;
   }
-  const T eps = field_soft<T>();
+  const T eps = soft<T>();
   const NB_CONST V4* src = (const NB_CONST V4*)(uintptr_t)a.src;
   T* sc = (T*)a.scratch;
-  const int blk0 = (int)blockIdx.y * a.chunk_blocks;
-  const int blk1 = min(blk0 + a.chunk_blocks, a.n_blocks);
+  const auto [blk0, blk1] = chunk_of(a.chunk_blocks, a.n_blocks);
   double l2x = 0.0, l2y = 0.0, l2z = 0.0, l2s = 0.0;
   for (int blk = blk0; blk < blk1; ++blk) {
     const int b0 = blk * kFieldBlock;
@@ -156,13 +114,13 @@ namespace nbl {
 NBF_HIDDEN int launch_field_kernel(int fp64, int arith, hipStream_t st, int chunks, const FieldArgs& a) {
   if (a.m <= 0 || chunks < 1 || (chunks > 1 && !a.scratch)) return (int)hipErrorInvalidValue;
   if (fp64) {   // fp64 contexts have one d2 form: REFERENCE = FMA3, REFERENCE_STRICT = STRICT
-    if (arith & kFStrict) launch_field_one<double, d4, kFStrict>(st, chunks, a);
+    if (arith & kStrict) launch_field_one<double, d4, kStrict>(st, chunks, a);
     else launch_field_one<double, d4, 0>(st, chunks, a);
   } else {
     switch (arith) {
-      case NBODY_ARITH_REFERENCE: launch_field_one<float, f4, kFRef>(st, chunks, a); break;
-      case NBODY_ARITH_STRICT: launch_field_one<float, f4, kFStrict>(st, chunks, a); break;
-      case NBODY_ARITH_REFERENCE_STRICT: launch_field_one<float, f4, kFRef | kFStrict>(st, chunks, a); break;
+      case NBODY_ARITH_REFERENCE: launch_field_one<float, f4, kRef>(st, chunks, a); break;
+      case NBODY_ARITH_STRICT: launch_field_one<float, f4, kStrict>(st, chunks, a); break;
+      case NBODY_ARITH_REFERENCE_STRICT: launch_field_one<float, f4, kRef | kStrict>(st, chunks, a); break;
       default: launch_field_one<float, f4, 0>(st, chunks, a); break;
     }
   }

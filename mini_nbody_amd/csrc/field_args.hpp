@@ -11,10 +11,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "diag_pass.hpp"
+
 namespace nbf {
 
-constexpr int kFieldBlock = 1024;    // sources per level-1 block (= the potential's)
-constexpr int kFieldPoints = 256;    // points per workgroup, one per lane
+constexpr int kFieldBlock = nbd::kSrcBlock;   // sources per level-1 block (the potential's)
+constexpr int kFieldPoints = nbd::kLanes;     // points per workgroup, one per lane
 
 struct FieldArgs {
   const void* src;      // all N source words (16-B or 32-B {x, y, z, w}), ascending

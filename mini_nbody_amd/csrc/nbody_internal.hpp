@@ -3,6 +3,9 @@
 //   context.cpp   the context: options, launch configuration, buffers, the step and its HIP graph, state transfer, the strict gate
 //   comm.cpp      RCCL (resolved with dlopen), the transfer plans, the all-gather of a step, probes and self-tests
 //   mailbox.cpp   the reference's mailbox: RAM images, one request, the service thread
+//   diag_pass.hpp  what the three diagnostic passes below share on the device: the potential's pair arithmetic, the lane and wave
+//                  preamble of a one-query-per-lane kernel, the block and workgroup sizes (read by their *_args.hpp)
+//   query_pass.hpp what they share on the host: ranges over the locals, upload, the split's batches, launch-then-copy-back, the ranks' words
 //   energy.hip    the energy pass's kernels (energy_args.hpp: its argument block and launch functions)
 //   energy.cpp    nbody_energy, nbody_potential_rows(_d): the energy pass on every local and the sum over the ranks
 //   field.hip     the field pass's kernels (field_args.hpp: its argument block and launch functions)
@@ -49,6 +52,8 @@ extern std::atomic<int> g_last_line;
 // While nbody_mailbox_serve(1, .) is in effect the service thread owns the context: every entry point that launches, copies or
 // reconfigures answers NBODY_ERR_STATE (nbody_get_info, nbody_error_string, nbody_mailbox_rams, nbody_mailbox_serve and nbody_shutdown do not)
 #define NB_REFUSE_WHILE_SERVED() do { if (::nbi::mailbox_serving()) return NBODY_ERR_STATE; } while (0)
+// ... and an entry point that exists in two precisions — is_d = 0: the float form, 1: the _d form — answers it on a context of the other
+#define NB_ENTER(is_d) do { NB_REFUSE_WHILE_SERVED(); if (::nbi::g.init && (::nbi::g.fp64 != 0) != ((is_d) != 0)) return NBODY_ERR_STATE; } while (0)
 #define HIPC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { NB_MARK(); return (int)e_; } } while (0)
 #define NBC(expr) do { int e_ = (expr); if (e_ != NBODY_OK) return e_; } while (0)
 #define NCCLC(expr) do { ncclResult_t r_ = (expr); if (r_ != ncclSuccess) { NB_MARK(); return 2000 + (int)r_; } } while (0)
@@ -120,12 +125,10 @@ struct Local {
   DevMem en_part;                      // energy pass (energy.cpp): per-workgroup fp64 partials of {T, U, P, L} ...
   DevMem en_tot;                       // ... the ranks' totals, 8 doubles at word `rank` (all P after an all-gather) ...
   DevMem en_phi;                       // ... and phi of the rows asked for (context precision)
-  DevMem fd_points, fd_skip;           // field pass (field.cpp): this local's range of the caller's points and skip indices ...
-  DevMem fd_accel, fd_phi;             // ... their outputs (context precision) ...
-  DevMem fd_scratch;                   // ... and the per-block level-1 sums of a launch whose sources are split (field_args.hpp)
-  DevMem nb_points, nb_skip;           // neighbour pass (neighbors.cpp): this local's range of the caller's points and skip indices ...
-  DevMem nb_idx, nb_d2, nb_count;      // ... the queries' outputs (d2 in the context precision) ...
-  DevMem nb_scratch;                   // ... the chunks' results of a launch whose sources are split (neighbors_args.hpp) ...
+  DevMem q_points, q_skip;             // field and neighbour pass (query_pass.hpp): this local's range of the caller's points and skip indices ...
+  DevMem q_scratch;                    // ... and what a launch whose sources are split leaves for its combine (field_args.hpp, neighbors_args.hpp)
+  DevMem fd_accel, fd_phi;             // field pass (field.cpp): the points' outputs (context precision)
+  DevMem nb_idx, nb_d2, nb_count;      // neighbour pass (neighbors.cpp): the queries' outputs (d2 in the context precision) ...
   DevMem nb_best;                      // ... and the ranks' closest pairs, one BestPair at word `rank` (all P after an all-gather)
   int cur = 0;
   bool all_present = true;             // pos[cur] holds every slice

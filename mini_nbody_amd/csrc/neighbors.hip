@@ -12,13 +12,12 @@
 
 using namespace nbk;
 using namespace nbn;
+using namespace nbd;
 
 #define NBN_HIDDEN __attribute__((visibility("hidden")))
 
 namespace {
 
-__device__ __forceinline__ float nbn_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
-__device__ __forceinline__ double nbn_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 // the IEEE minimum of b and a d2 (a NaN d2 gives b): one v_min; both operands are results of arithmetic, so nothing is re-quieted
 __device__ __forceinline__ float nbn_min(float b, float d2) { return __builtin_fminf(b, d2); }
 __device__ __forceinline__ double nbn_min(double b, double d2) { return __builtin_fmin(b, d2); }
@@ -31,7 +30,7 @@ __device__ __forceinline__ T nbn_nan() { return (T)__builtin_nanf(""); }
 template <bool CMP, typename T, typename V4>
 __device__ __forceinline__ T nbn_d2(const V4 p, const V4 me, int j, int sk) {
   const T dx = p.x - me.x, dy = p.y - me.y, dz = p.z - me.z;
-  const T d2 = nbn_fma(dx, dx, nbn_fma(dy, dy, dz * dz));
+  const T d2 = fma_of(dx, dx, fma_of(dy, dy, dz * dz));
   if (CMP) return j == sk ? nbn_nan<T>() : d2;
   return d2;
 }
@@ -83,25 +82,17 @@ __device__ __forceinline__ void window64(const NB_CONST V4* src, const V4 me, in
 // 64 queries compare j with it (a wave-uniform branch) — in the rows form the one or two windows that hold the wave's own rows.
 template <typename T, typename V4, bool SKIP, bool COUNT, int LOOP>
 __global__ void __launch_bounds__(kNbQueries) neighbors_kernel(NeighborsArgs a) {
-  const int p = (int)blockIdx.x * kNbQueries + (int)threadIdx.x;
-  const bool live = p < a.m;
-  const int pc = live ? p : a.m - 1;
+  const auto [p, live, pc] = lane_of(a.m);
   const V4 me = a.points ? ((const V4*)a.points)[pc] : ((const V4*)a.src)[a.first + pc];
-  int sk = -1, wlo = 0x7fffffff, whi = -1;
+  int sk = -1, wlo = kNoSkipLo, whi = -1;
   if constexpr (SKIP) {
     sk = a.points ? a.skip[pc] : a.first + pc;
-    int lo = sk < 0 ? 0x7fffffff : sk, hi = sk;
-    for (int off = 32; off > 0; off >>= 1) {
-      lo = min(lo, __shfl_xor(lo, off, 64));
-      hi = max(hi, __shfl_xor(hi, off, 64));
-    }
-    wlo = __builtin_amdgcn_readfirstlane(lo);
-    whi = __builtin_amdgcn_readfirstlane(hi);
+    const SkipWindow win = wave_skip_window(sk);
+    wlo = win.lo; whi = win.hi;
   }
   const T r2 = (T)a.r2;
   const NB_CONST V4* src = (const NB_CONST V4*)(uintptr_t)a.src;
-  const int blk0 = (int)blockIdx.y * a.chunk_blocks;
-  const int blk1 = min(blk0 + a.chunk_blocks, a.n_blocks);
+  const auto [blk0, blk1] = chunk_of(a.chunk_blocks, a.n_blocks);
   const int s0 = blk0 * kNbBlock;
   const int s1 = min(blk1 * kNbBlock, a.n_src);
   Near<T> c = {nbn_inf<T>(), -1, 0};

@@ -10,10 +10,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "diag_pass.hpp"
+
 namespace nbn {
 
-constexpr int kNbBlock = 1024;     // sources per block: chunks are whole blocks (= the field pass's)
-constexpr int kNbQueries = 256;    // queries per workgroup, one per lane
+constexpr int kNbBlock = nbd::kSrcBlock;   // sources per block: chunks are whole blocks
+constexpr int kNbQueries = nbd::kLanes;    // queries per workgroup, one per lane
 // the hot loop's form (same results): SCAN carries (best, index) through every pair; WINDOW keeps only the minimum per aligned
 // 64-source window and walks a window again when a lane of the wave improved in it
 enum { kNbLoopScan = 1, kNbLoopWindow = 2 };

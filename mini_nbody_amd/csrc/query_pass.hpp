@@ -1,0 +1,124 @@
+// query_pass.hpp — the host side that the diagnostic passes share (energy.cpp, field.cpp, neighbors.cpp; host C++ only): a call brings
+// rows or points, every local takes a contiguous range of them, launches on its compute stream — in batches over a split of the
+// sources when the pass asks for one — and the results are copied back once the stream has drained.  A pass says what differs: which
+// range a local gets, what to launch, which outputs go where, and its own split rule (a SplitPlan).
+// The points, skip indices and split scratch of a call live in one set of buffers per Local (q_points, q_skip, q_scratch), whichever
+// pass runs: every call drains the streams it used before it returns, so no two calls ever use them at once.
+#pragma once
+#include "nbody_internal.hpp"
+#include "diag_pass.hpp"
+
+namespace nbi {
+
+// Workgroups a launch should have before its sources stop being split, in units of the CU count (see choose_chunks): the starting
+// value, not measured yet (tools/field_rate.py and tools/neighbors_rate.py time the passes with and without the split).
+constexpr int kQueryFill = 2;
+
+inline long long env_ll(const char* name, long long dflt) {
+  const char* e = getenv(name);
+  return e && *e ? atoll(e) : dflt;
+}
+
+inline size_t elem_bytes() { return g.fp64 ? sizeof(double) : sizeof(float); }
+inline int source_blocks() { return (g.n + nbd::kSrcBlock - 1) / nbd::kSrcBlock; }
+
+// C, the number of source chunks (grid.y) of a launch of `queries` queries over n_blocks blocks.  forced >= 1 (the pass's *_SPLIT
+// variable): min(forced, n_blocks).  Auto: 1 when the queries alone give kQueryFill workgroups per CU, else the smallest number of
+// chunks that does.
+inline int choose_chunks(long long forced, int queries, int n_blocks) {
+  if (forced >= 1) return (int)std::min<long long>(forced, n_blocks);
+  const long long groups = ((long long)queries + nbd::kLanes - 1) / nbd::kLanes;
+  const long long want = (long long)kQueryFill * std::max(1, g.cu_count);
+  if (groups >= want) return 1;
+  return (int)std::min<long long>((want + groups - 1) / groups, n_blocks);
+}
+
+// How a local's launch is cut: grid.y = chunks chunks of chunk_blocks whole blocks (no empty chunk), `batch` queries per launch.
+// Each pass has its own rule (field.cpp: field_split, neighbors.cpp: neighbors_split); both fall back to no_split.
+struct SplitPlan { int chunks, chunk_blocks, batch; };
+inline SplitPlan no_split(int cnt, int n_blocks) { return {1, n_blocks, cnt}; }
+
+// launch(b0, m) for the batches [b0, b0 + m) of a local's cnt queries
+template <typename Launch>
+int for_batches(int cnt, const SplitPlan& plan, Launch&& launch) {
+  for (int b0 = 0; b0 < cnt; b0 += plan.batch) NBC(launch(b0, std::min(plan.batch, cnt - b0)));
+  return NBODY_OK;
+}
+
+// null (nothing is left out) or m indices with -1 <= skip[p] < N
+inline int check_skip(const int* skip, int m) {
+  if (skip)
+    for (int p = 0; p < m; ++p)
+      if (skip[p] < -1 || skip[p] >= g.n) return NBODY_ERR_ARG;
+  return NBODY_OK;
+}
+
+// A local's share of a call: cnt rows of its slice or points of the call from `first`, whose results go to element `out` of the
+// caller's arrays (cnt <= 0: the local has no part in the call)
+struct Range { int first, cnt, out; };
+// m points in contiguous ranges over the locals (one local in an nbody_init_rank context: all of this rank's points)
+inline Range points_of(int m, int l) {
+  const int p0 = (int)((long long)m * l / g.nlocal), p1 = (int)((long long)m * (l + 1) / g.nlocal);
+  return {p0, p1 - p0, p0};
+}
+// the rows of a window (as nbody_forces_rows takes it) that lie in local l's slice
+inline Range rows_of(const RowWindow& w, int l) {
+  const Local& L = g.loc[l];
+  int r0, cnt;
+  if (!w.rows_of(L, &r0, &cnt)) return {0, 0, 0};
+  return {r0, cnt, L.first + r0 - w.g0};
+}
+
+// points [p0, p0 + cnt) of the call and their skip indices (or null) into L's q_points / q_skip (L's device is current)
+inline int upload_queries(Local& L, const void* points, const int* skip, int p0, int cnt) {
+  const size_t wb = word_bytes();
+  NBC(L.q_points.ensure((size_t)cnt * wb));
+  HIPC(hipMemcpy(L.q_points, (const char*)points + (size_t)p0 * wb, (size_t)cnt * wb, hipMemcpyHostToDevice));
+  if (skip) {
+    NBC(L.q_skip.ensure((size_t)cnt * sizeof(int)));
+    HIPC(hipMemcpy(L.q_skip, skip + p0, (size_t)cnt * sizeof(int), hipMemcpyHostToDevice));
+  }
+  return NBODY_OK;
+}
+
+// cnt elements of `elem` bytes from the start of dev into element `at` of the caller's array (null: not asked for)
+inline int copy_out(void* host, int at, const DevMem& dev, int cnt, size_t elem) {
+  if (host) HIPC(hipMemcpy((char*)host + (size_t)at * elem, dev, (size_t)cnt * elem, hipMemcpyDeviceToHost));
+  return NBODY_OK;
+}
+
+// The two phases of a call, range_of(l) being local l's part in it: launch(L, range) on every local that has one, then per local its
+// stream drained and copy_back(L, range): blocking copies into the caller's pageable memory, as the other entry points do
+template <typename RangeOf, typename Launch, typename CopyBack>
+int run_on_locals(RangeOf&& range_of, Launch&& launch, CopyBack&& copy_back) {
+  for (int l = 0; l < g.nlocal; ++l) {
+    const Range r = range_of(l);
+    if (r.cnt > 0) NBC(launch(g.loc[l], r));
+  }
+  for (int l = 0; l < g.nlocal; ++l) {
+    Local& L = g.loc[l];
+    const Range r = range_of(l);
+    if (r.cnt <= 0) continue;
+    HIPC(hipSetDevice(L.device));
+    HIPC(hipStreamSynchronize(L.compute));
+    NBC(copy_back(L, r));
+  }
+  return NBODY_OK;
+}
+
+// Word `rank` (bytes_per_rank, written on the compute stream) of every rank's L.*buf into host_words[0 .. P): processes exchange the
+// words through the transport they use for positions (allgather_rank_words), never a reduction; one process reads each local's own
+// word.  The caller folds them in rank order.
+inline int gather_rank_words(DevMem Local::*buf, void* host_words, int bytes_per_rank) {
+  if (g.multiprocess && g.nranks > 1) return allgather_rank_words(g.loc[0], g.loc[0].*buf, host_words, bytes_per_rank);
+  for (int l = 0; l < g.nlocal; ++l) {
+    Local& L = g.loc[l];
+    const size_t off = (size_t)L.rank * (size_t)bytes_per_rank;
+    HIPC(hipSetDevice(L.device));
+    HIPC(hipStreamSynchronize(L.compute));
+    HIPC(hipMemcpy((char*)host_words + off, (L.*buf).as<char>() + off, (size_t)bytes_per_rank, hipMemcpyDeviceToHost));
+  }
+  return NBODY_OK;
+}
+
+}  // namespace nbi

@@ -3,37 +3,16 @@
 // AddressSanitizer + UBSan.  What it checks is the host's logic: the division of the points over the devices, the upload and copy-back
 // offsets, the choice of the source split, the scratch size and the batches, the argument checks, lifetimes at shutdown and the
 // failure paths.  field_stub.cpp states the values expected here.
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
-#include <functional>
-#include <vector>
-
-#include "../../include/nbody.h"
-
-extern "C" long hip_stub_live(int kind);               // hip_stub.cpp: outstanding 0 device allocations, 1 pinned, 2 events, 3 streams, 4 graphs, 5 graph execs
-extern "C" void hip_stub_fail_nth(int k);              // the k-th creating call from now fails once (0: disarm)
-extern "C" int hip_stub_fail_pending(void);            // > 0: the armed failure has not been reached
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "field_sanity: line %d: %s\n", __LINE__, #cond); exit(1); } } while (0)
-#define OK(call) do { int rc_ = (call); if (rc_) { fprintf(stderr, "field_sanity: line %d: %s = %d (%s)\n", __LINE__, #call, rc_, nbody_error_string(rc_)); exit(1); } } while (0)
-
-static void shutdown_at(int line) {
-  nbody_shutdown();
-  for (int kind = 0; kind < 6; ++kind)
-    if (hip_stub_live(kind)) { fprintf(stderr, "field_sanity: line %d: %ld of kind %d live after nbody_shutdown\n", line, hip_stub_live(kind), kind); exit(1); }
-}
-#define SHUTDOWN() shutdown_at(__LINE__)
+#define SANITY_NAME "field_sanity"
+#include "sanity_common.hpp"
 
 static void set_env(const char* split, const char* scratch_mb) {
   if (split) setenv("NBODY_FIELD_SPLIT", split, 1); else unsetenv("NBODY_FIELD_SPLIT");
   if (scratch_mb) setenv("NBODY_FIELD_SCRATCH_MB", scratch_mb, 1); else unsetenv("NBODY_FIELD_SCRATCH_MB");
 }
 
-template <typename T> int upload(std::vector<T>& pos, std::vector<T>& vel);
-template <> int upload<float>(std::vector<float>& pos, std::vector<float>& vel) { BodySystem b = {pos.data(), vel.data()}; return nbody_upload(&b); }
-template <> int upload<double>(std::vector<double>& pos, std::vector<double>& vel) { BodySystemD b = {pos.data(), vel.data()}; return nbody_upload_d(&b); }
 static int field(const float* p, int m, const int* sk, float* a, float* phi) { return nbody_field(p, m, sk, a, phi); }
 static int field(const double* p, int m, const int* sk, double* a, double* phi) { return nbody_field_d(p, m, sk, a, phi); }
 
@@ -92,31 +71,6 @@ static void shapes(int n, int ngpus) {
     SHUTDOWN();
   }
   set_env(nullptr, nullptr);
-}
-
-// the k-th creating call inside `call` fails, k = 1, 2, ... until the call no longer reaches the armed failure: a failed call must say
-// so, nbody_shutdown() must then leave nothing, and the call without injection must then work.  Returns the creating calls the call makes.
-static int sweep(const char* name, const std::function<void()>& setup, const std::function<int()>& call, const std::function<void()>& verify) {
-  for (int k = 1;; ++k) {
-    setup();
-    hip_stub_fail_nth(k);
-    const int rc = call();
-    const bool reached = hip_stub_fail_pending() == 0;
-    hip_stub_fail_nth(0);
-    if (reached && rc == 0) { fprintf(stderr, "field_sanity: %s: creating call %d failed and the call returned 0\n", name, k); exit(1); }
-    if (!reached) {
-      if (rc) { fprintf(stderr, "field_sanity: %s: %d (%s) without an injected failure\n", name, rc, nbody_error_string(rc)); exit(1); }
-      verify();
-      SHUTDOWN();
-      return k - 1;
-    }
-    SHUTDOWN();
-    setup();
-    const int rc2 = call();
-    if (rc2) { fprintf(stderr, "field_sanity: %s: %d (%s) after a failed attempt at creating call %d\n", name, rc2, nbody_error_string(rc2), k); exit(1); }
-    verify();
-    SHUTDOWN();
-  }
 }
 
 int main() {

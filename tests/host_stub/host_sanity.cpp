@@ -7,19 +7,13 @@
 #include <string.h>
 
 #include <atomic>
-#include <functional>
 #include <thread>
 #include <vector>
 
-#include "../../include/nbody.h"
+#define SANITY_NAME "host_sanity"
+#include "sanity_common.hpp"
 
 extern "C" void hip_stub_lose_next_completion(void);   // hip_stub.cpp
-extern "C" long hip_stub_live(int kind);               // outstanding: 0 device allocations, 1 pinned, 2 events, 3 streams, 4 graphs, 5 graph execs
-extern "C" void hip_stub_fail_nth(int k);              // the k-th creating call from now fails once (0: disarm)
-extern "C" int hip_stub_fail_pending(void);            // > 0: the armed failure has not been reached
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "host_sanity: line %d: %s\n", __LINE__, #cond); exit(1); } } while (0)
-#define OK(call) do { int rc_ = (call); if (rc_) { fprintf(stderr, "host_sanity: line %d: %s = %d (%s)\n", __LINE__, #call, rc_, nbody_error_string(rc_)); exit(1); } } while (0)
 
 static void bodies(std::vector<float>& p, int n, unsigned seed) {
   p.resize((size_t)n * 4);
@@ -28,14 +22,6 @@ static void bodies(std::vector<float>& p, int n, unsigned seed) {
 }
 
 static long long info(int key) { long long v = -1; OK(nbody_get_info(key, &v)); return v; }
-
-// nbody_shutdown() leaves nothing of any kind behind
-static void shutdown_at(int line) {
-  nbody_shutdown();
-  for (int kind = 0; kind < 6; ++kind)
-    if (hip_stub_live(kind)) { fprintf(stderr, "host_sanity: line %d: %ld of kind %d live after nbody_shutdown\n", line, hip_stub_live(kind), kind); exit(1); }
-}
-#define SHUTDOWN() shutdown_at(__LINE__)
 
 // nbody_energy and nbody_potential_rows(_d) on the uploaded state, against what the stub's energy pass writes (hip_stub.cpp energy()):
 // phi of body i = x_i - i; totals {n / 2, n, sum of vel.x, 4n, 5n, 6n, 7n, 8n}.  Windows: all rows, one across the first two slices of a
@@ -60,33 +46,6 @@ static void check_energy(int n, const std::vector<T>& pos, const std::vector<T>&
   CHECK(potential_rows(n - 1, 2, buf) == NBODY_ERR_ARG && potential_rows(-1, 1, buf) == NBODY_ERR_ARG && potential_rows(0, 0, buf) == NBODY_ERR_ARG);
 }
 
-// One entry point under creation-failure injection.  `setup` brings a fresh context to the point before the call (no injection), `call`
-// is the call, `verify` checks its results.  k = 1, 2, 3, ...: the k-th creating call (hipMalloc, hipHostMalloc, hipEventCreate*,
-// hipStreamCreate*, hipGraphInstantiate) inside `call` fails, until the call no longer reaches the armed failure.  Every k is walked, the
-// timer rings' 2 x 2 x 256 events per local included (no stride).  A failed call must say so, nbody_shutdown() must then leave nothing,
-// and the same call without injection must then work.  Returns the number of creating calls the call makes.
-static int sweep(const char* name, const std::function<void()>& setup, const std::function<int()>& call, const std::function<void()>& verify) {
-  for (int k = 1;; ++k) {
-    setup();
-    hip_stub_fail_nth(k);
-    const int rc = call();
-    const bool reached = hip_stub_fail_pending() == 0;
-    hip_stub_fail_nth(0);
-    if (reached && rc == 0) { fprintf(stderr, "host_sanity: %s: creating call %d failed and the call returned 0\n", name, k); exit(1); }
-    if (!reached) {
-      if (rc) { fprintf(stderr, "host_sanity: %s: %d (%s) without an injected failure\n", name, rc, nbody_error_string(rc)); exit(1); }
-      verify();
-      SHUTDOWN();
-      return k - 1;
-    }
-    SHUTDOWN();
-    setup();
-    OK(call());
-    verify();
-    SHUTDOWN();
-  }
-}
-
 // the bodies of seeds (1, 2) uploaded and stepped `steps` times (or, step_now = false, the context as the caller stepped it):
 // positions and velocities back as {pos, vel}
 static std::vector<float> stepped(int n, int steps, bool step_now = true) {
@@ -101,7 +60,8 @@ static std::vector<float> stepped(int n, int steps, bool step_now = true) {
   return out;
 }
 
-// the failure paths of everything that creates a resource: see sweep()
+// the failure paths of everything that creates a resource: sweep() (sanity_common.hpp) walks every creating call of an entry point,
+// the timer rings' 2 x 2 x 256 events per local included
 static void failure_sweeps(bool three_devices) {
   const int n = 200, n3 = 100;   // n3: ragged over three devices (34, 33, 33)
   std::vector<float> pos, vel;

@@ -3,46 +3,31 @@
 // energy.cpp) against tests/host_stub/hip_stub.cpp and neighbors_stub.cpp under AddressSanitizer + UBSan.  What it checks is the host's
 // logic: the rows of a window and the division of the points over the devices, the upload and copy-back offsets, the choice of the
 // source split, the scratch size and the batches, the argument checks, the closest pair over the devices, lifetimes at shutdown and
-// the failure paths.  neighbors_stub.cpp states the values expected here.
+// the failure paths.  neighbors_stub.cpp states the values expected here.  field.cpp and field_stub.cpp are linked too, for the
+// nbody_field calls between neighbour calls on one context (the two passes share their query buffers).
 #include <math.h>
-#include <stdio.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include <algorithm>
-#include <functional>
-#include <vector>
 
-#include "../../include/nbody.h"
+#define SANITY_NAME "neighbors_sanity"
+#include "sanity_common.hpp"
 
-extern "C" long hip_stub_live(int kind);               // hip_stub.cpp: outstanding 0 device allocations, 1 pinned, 2 events, 3 streams, 4 graphs, 5 graph execs
-extern "C" void hip_stub_fail_nth(int k);              // the k-th creating call from now fails once (0: disarm)
-extern "C" int hip_stub_fail_pending(void);            // > 0: the armed failure has not been reached
-
-#define CHECK(cond) do { if (!(cond)) { fprintf(stderr, "neighbors_sanity: line %d: %s\n", __LINE__, #cond); exit(1); } } while (0)
-#define OK(call) do { int rc_ = (call); if (rc_) { fprintf(stderr, "neighbors_sanity: line %d: %s = %d (%s)\n", __LINE__, #call, rc_, nbody_error_string(rc_)); exit(1); } } while (0)
-
-static void shutdown_at(int line) {
-  nbody_shutdown();
-  for (int kind = 0; kind < 6; ++kind)
-    if (hip_stub_live(kind)) { fprintf(stderr, "neighbors_sanity: line %d: %ld of kind %d live after nbody_shutdown\n", line, hip_stub_live(kind), kind); exit(1); }
-}
-#define SHUTDOWN() shutdown_at(__LINE__)
+extern "C" long neighbors_stub_combines(void);   // neighbors_stub.cpp: combine launches so far, one per batch of a split launch
 
 static void set_env(const char* split, const char* scratch_mb) {
   if (split) setenv("NBODY_NEIGHBORS_SPLIT", split, 1); else unsetenv("NBODY_NEIGHBORS_SPLIT");
   if (scratch_mb) setenv("NBODY_NEIGHBORS_SCRATCH_MB", scratch_mb, 1); else unsetenv("NBODY_NEIGHBORS_SCRATCH_MB");
 }
 
-template <typename T> int upload(std::vector<T>& pos, std::vector<T>& vel);
-template <> int upload<float>(std::vector<float>& pos, std::vector<float>& vel) { BodySystem b = {pos.data(), vel.data()}; return nbody_upload(&b); }
-template <> int upload<double>(std::vector<double>& pos, std::vector<double>& vel) { BodySystemD b = {pos.data(), vel.data()}; return nbody_upload_d(&b); }
 static int rows(int f, int n, int* i, float* d, float r2, int* c) { return nbody_neighbors_rows(f, n, i, d, r2, c); }
 static int rows(int f, int n, int* i, double* d, double r2, int* c) { return nbody_neighbors_rows_d(f, n, i, d, r2, c); }
 static int nearest(const float* p, int m, const int* sk, int* i, float* d, float r2, int* c) { return nbody_nearest(p, m, sk, i, d, r2, c); }
 static int nearest(const double* p, int m, const int* sk, int* i, double* d, double r2, int* c) { return nbody_nearest_d(p, m, sk, i, d, r2, c); }
 static int pair(int* i, int* j, float* d) { return nbody_closest_pair(i, j, d); }
 static int pair(int* i, int* j, double* d) { return nbody_closest_pair_d(i, j, d); }
+static int field(const float* p, int m, const int* sk, float* a, float* phi) { return nbody_field(p, m, sk, a, phi); }
+static int field(const double* p, int m, const int* sk, double* a, double* phi) { return nbody_field_d(p, m, sk, a, phi); }
 
 // small integers everywhere: every value of neighbors_stub.cpp is exact in either precision
 template <typename T>
@@ -108,6 +93,23 @@ struct Case {
     OK(pair(nullptr, &j2, (T*)nullptr));
     CHECK(j2 == bj);
   }
+  // nbody_field at the first `count` points, with skip, against what field_stub.cpp makes of them
+  void run_field(int count) {
+    std::vector<T> acc((size_t)count * 4 + 4, (T)-77), phi((size_t)count + 1, (T)-77);
+    OK(field(pts.data(), count, skip.data(), acc.data(), phi.data()));
+    const int nb = (n + 1023) / 1024;
+    for (int p = 0; p < count; ++p) {
+      double ax = 0.0, ay = 0.0, az = 0.0;
+      for (int b = 0; b < nb; ++b) {
+        ax += (double)(T)(pos[4 * (size_t)b * 1024] - pts[4 * (size_t)p]);
+        ay += (double)(T)(pts[4 * (size_t)p + 1] + (T)b);
+        az += (double)(T)((T)skip[(size_t)p] + (b == nb - 1 ? pos[4 * (size_t)(n - 1)] : (T)0));
+      }
+      CHECK(acc[4 * (size_t)p] == (T)ax && acc[4 * (size_t)p + 1] == (T)ay && acc[4 * (size_t)p + 2] == (T)az && acc[4 * (size_t)p + 3] == (T)0);
+      CHECK(phi[(size_t)p] == (T)(0.0 - (double)nb * (double)p));
+    }
+    CHECK(acc[4 * (size_t)count] == (T)-77 && phi[(size_t)count] == (T)-77);   // nothing beyond
+  }
   void run_all() {
     run_points(false, true, true, true, (T)1);
     run_points(true, true, true, true, (T)0);
@@ -139,29 +141,29 @@ static void shapes(int n, int ngpus) {
   }
 }
 
-// the k-th creating call inside `call` fails, k = 1, 2, ... until the call no longer reaches the armed failure: a failed call must say
-// so, nbody_shutdown() must then leave nothing, and the call without injection must then work.  Returns the creating calls the call makes.
-static int sweep(const char* name, const std::function<void()>& setup, const std::function<int()>& call, const std::function<void()>& verify) {
-  for (int k = 1;; ++k) {
-    setup();
-    hip_stub_fail_nth(k);
-    const int rc = call();
-    const bool reached = hip_stub_fail_pending() == 0;
-    hip_stub_fail_nth(0);
-    if (reached && rc == 0) { fprintf(stderr, "neighbors_sanity: %s: creating call %d failed and the call returned 0\n", name, k); exit(1); }
-    if (!reached) {
-      if (rc) { fprintf(stderr, "neighbors_sanity: %s: %d (%s) without an injected failure\n", name, rc, nbody_error_string(rc)); exit(1); }
-      verify();
-      SHUTDOWN();
-      return k - 1;
-    }
-    SHUTDOWN();
-    setup();
-    const int rc2 = call();
-    if (rc2) { fprintf(stderr, "neighbors_sanity: %s: %d (%s) after a failed attempt at creating call %d\n", name, rc2, nbody_error_string(rc2), k); exit(1); }
-    verify();
-    SHUTDOWN();
+// The field pass between neighbour calls on one context: both keep their points, skip indices and split scratch in the Local's q_*
+// buffers (query_pass.hpp), so each call meets buffers the other pass sized.  N = 2100: three blocks, a tail that is no multiple of 64.
+// m = 700 over three chunks against 0.02 MB = 20971 B of scratch.  One device: fp32 takes 36 B a query, 582 fit, batches of 512 + 188;
+// fp64 takes 48 B, 436 fit, batches of 256 + 256 + 188.  Three devices: 233 or 234 queries each, fewer than one workgroup's 256, so
+// each device's queries go as one split batch (a bound that cut them would fit no whole workgroup, which means no split at all).
+// The count of combine launches (one per split batch) says that the split and the batches happened.  Then m = 257 field points (85
+// or 86 a device; their per-block sums are the larger scratch) and m = 5000.
+template <typename T>
+static void interleaved(int ngpus) {
+  unsetenv("NBODY_FIELD_SPLIT"); unsetenv("NBODY_FIELD_SCRATCH_MB");
+  Case<T> c(2100, 5000);
+  c.open(ngpus);
+  const long batches = ngpus > 1 ? ngpus : sizeof(T) == 4 ? 2 : 3;
+  for (int round = 0; round < 2; ++round) {
+    set_env("3", "0.02");
+    const long before = neighbors_stub_combines();
+    c.run_points(true, true, true, true, (T)1, 0, 700);
+    CHECK(neighbors_stub_combines() - before == batches);
+    set_env(nullptr, nullptr);
+    c.run_field(257);
+    c.run_points(true, true, true, true, (T)1);
   }
+  SHUTDOWN();
 }
 
 int main() {
@@ -252,6 +254,13 @@ int main() {
     d.run_all();
     d.run_pair();
     SHUTDOWN();
+  }
+
+  // ---- the buffers shared with the field pass ----
+  for (int ngpus : {1, 3}) {
+    if (ngpus > 1 && !three_devices) continue;
+    interleaved<float>(ngpus);
+    interleaved<double>(ngpus);
   }
 
   // ---- the failure paths: every allocating call of a call, one device and three, split (scratch) and not ----

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <limits>
 
 #include "../../mini_nbody_amd/csrc/neighbors_args.hpp"
@@ -86,7 +87,12 @@ void best(const T* d2, const int* idx, int rows, int first, BestPair* out) {
   *out = b;
 }
 
+std::atomic<long> g_combines{0};
+
 }  // namespace
+
+// combine launches so far: one per batch of a split launch, none when the sources are not split
+extern "C" long neighbors_stub_combines(void) { return g_combines.load(); }
 
 namespace nbl {
 int launch_neighbors_kernel(int fp64, int loop, hipStream_t, const nbn::NeighborsArgs& a) {
@@ -99,6 +105,7 @@ int launch_neighbors_kernel(int fp64, int loop, hipStream_t, const nbn::Neighbor
 }
 int launch_neighbors_combine_kernel(int fp64, hipStream_t, const nbn::NeighborsArgs& a) {
   if (a.m <= 0 || !a.scratch || a.chunks < 1) return (int)hipErrorInvalidValue;
+  g_combines.fetch_add(1);
   if (fp64) combine<double>(a); else combine<float>(a);
   return 0;
 }

@@ -414,3 +414,43 @@ def test_c_host_program_closest_pair_line(nb, ref):
             now = eng.download()[0]
         wi, wj, wd = ref.closest_pair(now)
         assert (int(lines[0][0]), int(lines[0][1])) == (wi, wj) and dtype(float(lines[0][2])) == wd
+
+
+@pytest.mark.parametrize("fp64", [False, True])
+def test_interleaved_with_the_field_pass(nb, monkeypatch, fp64):
+    """The neighbour and the field pass keep their points, skip indices and split scratch in the same buffers of the context: on one
+    context (one device), twice over — nearest at 700 points over three chunks against 0.02 MB = 20971 B of scratch (fp32: 36 B a
+    query, 582 fit, batches of 512 + 188; fp64: 48 B, 436 fit, batches of 256 + 256 + 188), the field at 257 points, nearest at 5000
+    points — every result the bits of the same call on a fresh context that never ran the other pass.  N = 2100: three blocks, a
+    tail that is no multiple of 64."""
+    for k in ("NBODY_FIELD_SPLIT", "NBODY_FIELD_SCRATCH_MB"):
+        monkeypatch.delenv(k, raising=False)
+    n = 2100
+    dtype = np.float64 if fp64 else np.float32
+    pos, vel = nb.make_bodies(n, dtype=dtype)
+    r2 = r2_for(pos, 0.05)
+    pts = {m: make_points(nb, pos, m)[0] for m in (257, 700, 5000)}
+    skip = {m: ((np.arange(m) * 997) % n).astype(np.int32) for m in pts}
+
+    def nearest_small(eng):
+        monkeypatch.setenv("NBODY_NEIGHBORS_SPLIT", "3")
+        monkeypatch.setenv("NBODY_NEIGHBORS_SCRATCH_MB", "0.02")
+        got = eng.nearest(pts[700], skip[700], r2=r2)
+        monkeypatch.delenv("NBODY_NEIGHBORS_SPLIT")
+        monkeypatch.delenv("NBODY_NEIGHBORS_SCRATCH_MB")
+        return got
+
+    calls = (nearest_small, lambda eng: eng.field(pts[257], skip[257]), lambda eng: eng.nearest(pts[5000], skip[5000], r2=r2))
+
+    def run(which):
+        with nb.NBody(n, fp64=fp64) as eng:
+            eng.upload(pos, vel)
+            return [calls[k](eng) if k in which else None for _ in range(2) for k in range(3)]
+
+    mixed, only_nearest, only_field = run((0, 1, 2)), run((0, 2)), run((1,))
+    for k in (0, 2, 3, 5):
+        assert same(mixed[k], only_nearest[k]), k
+    for k in (1, 4):
+        assert same(mixed[k], only_field[k]), k   # (accel, phi): the same bits
+        assert np.all(np.isfinite(mixed[k][0])) and np.all(np.isfinite(mixed[k][1]))
+    assert np.all(mixed[0][0] >= 0) and np.all(mixed[2][0] >= 0) and np.all(mixed[0][0] != skip[700])

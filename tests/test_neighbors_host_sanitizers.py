@@ -4,8 +4,9 @@ in for the HIP runtime ("device" memory is malloc'd, so ASan sees every offset t
 for neighbors.hip (predictable values pushed through the real NeighborsArgs: chunk bounds, the chunks' scratch layout, the combine,
 the best-pair reduction), and tests/host_stub/neighbors_sanity.cpp drives the C-ABI: m and row counts 1, 255, 256, 257, 5000 over one
 and three stub devices with ragged slices, row windows that straddle devices, the source split forced and automatic, the batched path,
-skip present and absent, each output NULL in turn, every NBODY_ERR_ARG case, the closest pair over three devices, and the failure
-sweep (the k-th allocating call fails: the call says so, nothing is live after nbody_shutdown, the same call then works)."""
+skip present and absent, each output NULL in turn, every NBODY_ERR_ARG case, the closest pair over three devices, nbody_field calls
+(field.cpp, tests/host_stub/field_stub.cpp) between nbody_nearest calls on one context, whose query buffers the two passes share, and
+the failure sweep (the k-th allocating call fails: the call says so, nothing is live after nbody_shutdown, the same call then works)."""
 import os
 import shutil
 import subprocess
@@ -14,8 +15,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CXX = "/opt/rocm/lib/llvm/bin/clang++"
-SRC = [os.path.join(ROOT, "mini_nbody_amd", "csrc", f) for f in ("context.cpp", "comm.cpp", "mailbox.cpp", "energy.cpp", "neighbors.cpp")] + \
-      [os.path.join(ROOT, "tests", "host_stub", f) for f in ("hip_stub.cpp", "neighbors_stub.cpp", "neighbors_sanity.cpp")]
+SRC = [os.path.join(ROOT, "mini_nbody_amd", "csrc", f) for f in ("context.cpp", "comm.cpp", "mailbox.cpp", "energy.cpp", "neighbors.cpp", "field.cpp")] + \
+      [os.path.join(ROOT, "tests", "host_stub", f) for f in ("hip_stub.cpp", "neighbors_stub.cpp", "field_stub.cpp", "neighbors_sanity.cpp")]
 
 
 @pytest.mark.skipif(shutil.which("make") is None, reason="no toolchain")

@@ -440,12 +440,10 @@ int nbody_comm_probe(long long bytes, int when, double* comm_ms, double* force_m
   NBC(ensure_full_scratch(L));
   Event ev[6];
   for (Event& x : ev) HIPC(hipEventCreate(x.put()));
-  const Finish fin = {false, false, true};
-  auto force_pass = [&](hipEvent_t begin, hipEvent_t end) -> int {
+  auto timed_pass = [&](hipEvent_t begin, hipEvent_t end) -> int {
     if (begin) HIPC(hipEventRecord(begin, L.compute));
     TicketGuard guard;
-    NBC(launch_force(L, 0, L.n_local, g.cfg.nslices - 1, g.cfg.nslices, fin, 0.f, 0.0));
-    NBC(launch_combine(L, 0, L.n_local, fin, 0.f, 0.0));
+    NBC(force_pass(problem_of(L), L, 0, L.n_local, {false, false, true}));
     guard.done();
     HIPC(hipEventRecord(end, L.compute));
     return NBODY_OK;
@@ -457,15 +455,15 @@ int nbody_comm_probe(long long bytes, int when, double* comm_ms, double* force_m
     return NBODY_OK;
   };
   hipEvent_t from = ev[0];
-  if (when == 1) { NBC(comm_step()); NBC(force_pass(ev[2], ev[3])); }
-  else if (when == 2) { NBC(force_pass(ev[2], ev[3])); NBC(comm_step()); }
+  if (when == 1) { NBC(comm_step()); NBC(timed_pass(ev[2], ev[3])); }
+  else if (when == 2) { NBC(timed_pass(ev[2], ev[3])); NBC(comm_step()); }
   else if (when >= 3) {
-    NBC(force_pass(nullptr, ev[4]));                       // pass A; ev[4] = "own slice ready"
+    NBC(timed_pass(nullptr, ev[4]));                       // pass A; ev[4] = "own slice ready"
     HIPC(hipStreamWaitEvent(L.comm, ev[4], 0));
     if (when == 4) HIPC(hipEventRecord(L.ev_comm_go, L.comm));
     NBC(comm_step());
     if (when == 4) HIPC(hipStreamWaitEvent(L.compute, L.ev_comm_go, 0));
-    NBC(force_pass(ev[2], ev[3]));                       // pass B
+    NBC(timed_pass(ev[2], ev[3]));                       // pass B
     from = ev[4];
   } else NBC(comm_step());
   NBC(sync_all());

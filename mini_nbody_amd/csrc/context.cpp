@@ -27,6 +27,8 @@ inline int rows_per_wg(int R, int wsplit) { return wsplit > 1 ? 64 : kBlock * R;
 int blocks_for(int rows, int R, int wsplit) { const int w = rows_per_wg(R, wsplit); return (rows + w - 1) / w; }
 // words between two segments' partial sums: the launch's rows rounded up to 64 (ForceArgs::part_stride)
 inline size_t part_stride(int rows) { return ((size_t)rows + 63) / 64 * 64; }
+// the CU count the launch rules reckon with (a context whose device reported none: an MI355X's)
+inline int cus_or_default(int cu_count) { return cu_count > 0 ? cu_count : 256; }
 
 }  // namespace
 
@@ -36,9 +38,12 @@ inline size_t part_stride(int rows) { return ((size_t)rows + 63) / 64 * 64; }
 // cutting the sources into pieces so that a launch has >= 16k workgroups adds ~8 % (load balance across the 256 CUs).
 LaunchConfig resolve_config(int n, int nranks, int fp64, const Options& opt, int cu_count) {
   LaunchConfig c;
+  const int cus = cus_or_default(cu_count);
   const long long wb = fp64 ? 32 : 16;   // bytes per body word
   // the largest slice (ceil(N / P)): every rank of a multi-process job resolves the same segmentation from it
   const int n_local = std::max(1, (n + nranks - 1) / nranks);
+  // few rows: a rank's bodies fill at most half the CUs with 64-row workgroups (n_local <= 8192)
+  const bool few_rows = (n_local + 63) / 64 <= cus / 2;
   c.nslices = nranks > 1 ? nranks : (opt.jslices > 0 ? opt.jslices : 1);
   // AUTO: the hand-scheduled ISA loop (+6 % over hipcc's schedule of the same operations, profiles/r01_sweep_isa.txt)
   c.variant = opt.variant == NBODY_VARIANT_AUTO ? NBODY_VARIANT_ISA : opt.variant;
@@ -60,13 +65,12 @@ LaunchConfig resolve_config(int n, int nranks, int fp64, const Options& opt, int
   // automatic: wherever it exists, except for NBODY_SUM_SEQ in fp32, whose meaning is ONE sequential sum per segment (what a CPU
   // nbody.c does); fp64 contexts, which always sum sequentially and have 29 bits to spare, take the split
   const bool auto_split = fp64 || opt.sum_order != NBODY_SUM_SEQ;
-  // ... with 16 waves per workgroup where a rank's bodies fill at most half the CUs with 64-row workgroups (n_local <= 8192):
+  // ... with 16 waves per workgroup where few_rows holds:
   // there a step is latency and the 16-wave form needs the fewest global partial sums for the same number of waves (measured
   // per step, profiles/r03_small_n.md: N = 2048 7.5 us against 9.1 with 4 waves, N = 4096 9.7 / 10.2, N = 8192 22.0 / 22.1; from
   // N = 16384 up the two are level in fp32 and 4 waves win by 4 % in fp64, so 4 it is)
-  const int cus_ = cu_count > 0 ? cu_count : 256;
   // (one-rank contexts only: 8 virtual ranks of 8192 bodies each ran 2335 G pairs/s with 16 waves, 2553 with 4)
-  const int auto_ws = (!fp64 && c.nslices == 1 && (n_local + 63) / 64 <= cus_ / 2) ? 16 : 4;
+  const int auto_ws = (!fp64 && c.nslices == 1 && few_rows) ? 16 : 4;
   c.wsplit = !can_split ? 1 : (opt.wsplit == 4 || opt.wsplit == 16) ? opt.wsplit : (opt.wsplit < 0 && auto_split) ? auto_ws : 1;
   // The FPGA order's "split" is of another kind: its sixteen partial sums per row go to the sixteen waves of a workgroup
   // (force_fpga16w_f32) — the same chains, rotation and tree, hence the same bits as one lane holding all sixteen (NBODY_OPT_WSPLIT 1,
@@ -83,14 +87,13 @@ LaunchConfig resolve_config(int n, int nranks, int fp64, const Options& opt, int
   //   small: the step is latency, not issue: ~2 workgroups per CU (N = 4096: 32 segments 16.0 us per step, 16: 18.4,
   //     64: 19.4; N = 8192: 16 segments 27.2, 64: 31.8) and the sums added by a second small kernel — in one launch the
   //     hand-off is exposed (N = 4096: 22.7 us, N = 8192: 36.4).
-  const int cus = cu_count > 0 ? cu_count : 256;
   const int blocks = blocks_for(n_local, R, 1);   // in workgroups of 256*R rows: `sub` below counts pieces of a slice as round 2 did
   // "small" = the latency regime: fp32: where the 16-wave workgroups are the automatic choice (n_local <= 8192); between there
   // and N = 16384 round 2's small-launch rule (2 workgroups per CU, combine kernel) measured 21-30 % behind the large-launch one
   // (profiles/r03_sweep_boundary_n*.txt: N = 12288 59.5 us per step against 41.6); fp64, which has no 16-wave regime: never
   // (small-launch rule against large: N = 512 13.7 / 12.8 us per step, 1024: 14.4 / 13.0, 2048: 15.5 / 13.6, 4096: 24.6 / 19.9,
   //  8192: 63.6 / 49.6, 12288: 130.8 / 97.6)
-  const bool small = fp64 ? false : (n_local + 63) / 64 <= cus / 2;
+  const bool small = !fp64 && few_rows;
   int sub = opt.jsub;
   if (sub == 0) {
     // workgroups per launch-slice: the step's launches together have 128 (2) per CU whatever the rank count, so that
@@ -186,17 +189,17 @@ void drop_step_graph() {
   g.graph_cur = -1;
 }
 
-int ensure_partial(Local& L, int nseg) {
+int ensure_partial(Local& L, int rows, int nseg) {
   HIPC(hipSetDevice(L.device));
   bool moved = false;
-  const int rc = L.partial.ensure(((size_t)nseg * part_stride(L.n_local) + 64) * word_bytes(), false, &moved);
+  const int rc = L.partial.ensure(((size_t)nseg * part_stride(rows) + 64) * word_bytes(), false, &moved);
   if (moved) drop_step_graph();   // captured launches hold the old buffer's address (a mailbox request of another size may be what grows it)
   return rc;
 }
 
 TicketGuard::~TicketGuard() { if (!ok) g.tickets_dirty = true; }
 
-// every counter as allocated (a mailbox request may have switched n_local), stream-ordered with the kernels that use them
+// every counter as allocated, stream-ordered with the kernels that use them
 int zero_tickets() {
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
@@ -212,11 +215,10 @@ int reconfigure() {
   const bool changed = next != g.cfg || g.tickets_dirty;
   g.cfg = next;
   if (changed) drop_step_graph();
-  for (int l = 0; l < g.nlocal; ++l) NBC(ensure_partial(g.loc[l], g.cfg.nseg));
+  for (int l = 0; l < g.nlocal; ++l) NBC(ensure_partial(g.loc[l], g.loc[l].n_local, g.cfg.nseg));
   // the arrival counters are zero between steps by construction (the last arriver resets its own); a change of
   // the row-block shape is the one moment to re-zero them all
   if (changed) NBC(zero_tickets());
-  g.view = {g.n, g.loc[0].n_local, g.cfg};
   return NBODY_OK;
 }
 
@@ -256,9 +258,9 @@ namespace {
 inline bool isa_phase_is_diag(int ph) { return ph >= 2; }
 
 // how a launch finishes its rows: directly (one segment), by the last-arriving workgroup, or by combine_kernel
-inline int finish_mode() { return g.cfg.nseg == 1 ? kFinishDirect : (g.cfg.fuse ? kFinishLast : kFinishStore); }
+inline int finish_mode(const LaunchConfig& cfg) { return cfg.nseg == 1 ? kFinishDirect : (cfg.fuse ? kFinishLast : kFinishStore); }
 
-void fill_args(Local& L, ForceArgs& a, int row0, int row_count, const Finish& fin, float dt, double dt64, const Redirect* rd) {
+void fill_args(const Problem& p, Local& L, ForceArgs& a, int row0, int row_count, const Finish& fin, const Redirect* rd) {
   memset(&a, 0, sizeof(a));
   a.src = L.pos[L.cur];
   a.rows = word_ptr(L.pos[L.cur], (size_t)L.first);
@@ -268,39 +270,39 @@ void fill_args(Local& L, ForceArgs& a, int row0, int row_count, const Finish& fi
   a.pos_next_rows = word_ptr(L.pos[L.cur ^ 1], (size_t)L.first);
   a.force_out = fin.store_force ? (rd && rd->force_dst ? rd->force_dst : L.force) : nullptr;
   a.tickets = L.tickets.as<unsigned>();
-  a.n_src = g.n; a.n_rows = L.n_local; a.row0 = row0; a.row_count = row_count;
-  a.nslices = g.cfg.nslices; a.sub = g.cfg.sub; a.nseg = g.cfg.nseg;
-  a.finish = finish_mode();
+  a.n_src = p.n; a.n_rows = p.n_local; a.row0 = row0; a.row_count = row_count;
+  a.nslices = p.cfg.nslices; a.sub = p.cfg.sub; a.nseg = p.cfg.nseg;
+  a.finish = finish_mode(p.cfg);
   a.do_kick = fin.kick; a.do_drift = fin.drift;
   a.sum_block = (!g.fp64 && g.opt.sum_order == NBODY_SUM_BLOCKED) ? g.opt.sum_block : 0;
   a.fpga16 = g.opt.sum_order == NBODY_SUM_FPGA16;
-  a.wsplit = g.cfg.wsplit;
+  a.wsplit = p.cfg.wsplit;
   a.part_stride = (int)part_stride(row_count);
-  a.dt = dt; a.dt64 = dt64;
+  a.dt = fin.dt; a.dt64 = fin.dt64;
 }
 
 }  // namespace
 
-bool takes_rows16(int row_count) {
-  if (g.fp64 || g.opt.sum_order != NBODY_SUM_FPGA16 || g.cfg.wsplit != 16 || g.cfg.nseg != 1 || g.opt.variant == NBODY_VARIANT_SMEM) return false;
+bool takes_rows16(const LaunchConfig& cfg, int row_count) {
+  if (g.fp64 || g.opt.sum_order != NBODY_SUM_FPGA16 || cfg.wsplit != 16 || cfg.nseg != 1 || g.opt.variant == NBODY_VARIANT_SMEM) return false;
   static const int force_rows16 = [] { const char* e = getenv("NBODY_FPGA_ROWS16"); return (e && *e) ? atoi(e) : -1; }();
-  const int cus = g.cu_count > 0 ? g.cu_count : 256;
-  return force_rows16 > 0 || (force_rows16 < 0 && (long long)row_count < 64LL * cus);
+  return force_rows16 > 0 || (force_rows16 < 0 && (long long)row_count < 64LL * cus_or_default(g.cu_count));
 }
 
-// Launch the force kernel of local L for rows [row0, row0+row_count) against `nsl` source slices
+// Launch the force kernel of problem p on local L for rows [row0, row0+row_count) against `nsl` source slices
 // starting at slice_start and descending (ring arrival order).  A step may take several launches (own slice, then
 // arrived slices); the rows are finished when the LAST of a row block's nseg segments has been summed.
-int launch_force(Local& L, int row0, int row_count, int slice_start, int nsl, const Finish& fin, float dt, double dt64, const Redirect* rd) {
+int launch_force(const Problem& p, Local& L, int row0, int row_count, int slice_start, int nsl, const Finish& fin, const Redirect* rd) {
   if (row_count <= 0 || nsl <= 0) return NBODY_OK;
   HIPC(hipSetDevice(L.device));
+  const LaunchConfig& cfg = p.cfg;
   ForceArgs a;
-  fill_args(L, a, row0, row_count, fin, dt, dt64, rd);
+  fill_args(p, L, a, row0, row_count, fin, rd);
   a.slice_start = slice_start;
-  const int R = g.cfg.R;
-  dim3 grid(blocks_for(row_count, R, g.cfg.wsplit), nsl * g.cfg.sub, 1);
+  const int R = cfg.R;
+  dim3 grid(blocks_for(row_count, R, cfg.wsplit), nsl * cfg.sub, 1);
   // few waves per SIMD and short pieces: the scalar loads are no longer hidden by other waves
-  const int cus = g.cu_count > 0 ? g.cu_count : 256;
+  const int cus = cus_or_default(g.cu_count);
   // XCD-aware placement of segments (block_segment): needs a multiple of 8 segment rows in the launch, or 1/2/4 of them and a
   // row-block count the 8 / rows XCDs of a segment can deal evenly.  Automatic: for launches whose source set is larger than one
   // XCD's L2 share (N = 1M on one GPU: sources fetched once per XCD, 477 MB of memory-side traffic per step
@@ -312,12 +314,12 @@ int launch_force(Local& L, int row0, int row_count, int slice_start, int nsl, co
   // (r03, wall clock per step: 16384 waves in the launch (N = 16384) 68.0 us with the long buffers against 69.5, 20480 waves
   //  101.7 / 102.9, 24576 waves 144.2 / 142.2, 32768 waves 249.6 / 246.6: the switch sits at 88 waves per CU)
   a.long_buffers = g.opt.long_buffers < 0 ? ((long long)grid.x * grid.y * (wg_threads(a.wsplit) / 64) < 88LL * cus ? 1 : 0) : g.opt.long_buffers;
-  nbl::KernelSel sel = {g.fp64, g.cfg.variant, R, g.opt.arith, g.tile, g.opt.isa_phase, g.opt.variant != NBODY_VARIANT_SMEM ? 1 : 0, 0, 0};
+  nbl::KernelSel sel = {g.fp64, cfg.variant, R, g.opt.arith, g.tile, g.opt.isa_phase, g.opt.variant != NBODY_VARIANT_SMEM ? 1 : 0, 0, 0};
   // The FPGA order with ONE segment (the mailbox's faithful mode) in a launch that would leave CUs idle with 64 rows per workgroup:
   // sixteen rows x sixteen chains per workgroup instead (force_fpga16r_f32) — the same bits from four times the workgroups.  Up to four
   // 16-row workgroups per CU (rows < 64 x CUs: there the 64-row form fills every CU too, with a quarter of the source fetches).
   // NBODY_FPGA_ROWS16 = 0 / 1 overrides (A/B).
-  if (takes_rows16(row_count)) {
+  if (takes_rows16(cfg, row_count)) {
     sel.fpga_rows16 = 1;
     grid = dim3((row_count + 15) / 16, 1, 1);
     a.xcd_map = 0;
@@ -325,7 +327,7 @@ int launch_force(Local& L, int row0, int row_count, int slice_start, int nsl, co
   }
   // optional occupancy cap: k workgroups (= k waves per SIMD) per CU by giving each 160 KiB / k of dynamic LDS
   if (g.opt.waves_per_simd > 0 && g.opt.waves_per_simd < 8) {
-    const size_t static_lds = (g.cfg.variant == NBODY_VARIANT_LDS ? (size_t)g.tile * 32 : 0) + (a.wsplit > 1 ? (size_t)(a.wsplit - 1) * 64 * word_bytes() : 0) +
+    const size_t static_lds = (cfg.variant == NBODY_VARIANT_LDS ? (size_t)g.tile * 32 : 0) + (a.wsplit > 1 ? (size_t)(a.wsplit - 1) * 64 * word_bytes() : 0) +
                               ((a.fpga16 && a.wsplit == 16 && sel.fpga_lds) ? (size_t)32 * 1024 : 0);
     // (a workgroup of WS waves holds WS / 4 wave slots per SIMD: the cap is on workgroups per CU = waves_per_simd / (WS / 4))
     const size_t budget = (size_t)(160 * 1024) / (size_t)g.opt.waves_per_simd;
@@ -339,13 +341,18 @@ int launch_force(Local& L, int row0, int row_count, int slice_start, int nsl, co
 }
 
 // the two-launch form (NBODY_OPT_FUSE_COMBINE = 0): after the step's last force launch, add the partials
-int launch_combine(Local& L, int row0, int row_count, const Finish& fin, float dt, double dt64, const Redirect* rd) {
-  if (row_count <= 0 || finish_mode() != kFinishStore) return NBODY_OK;
+int launch_combine(const Problem& p, Local& L, int row0, int row_count, const Finish& fin, const Redirect* rd) {
+  if (row_count <= 0 || finish_mode(p.cfg) != kFinishStore) return NBODY_OK;
   HIPC(hipSetDevice(L.device));
   ForceArgs c;
-  fill_args(L, c, row0, row_count, fin, dt, dt64, rd);
+  fill_args(p, L, c, row0, row_count, fin, rd);
   HIPC((hipError_t)nbl::launch_combine_kernel(g.fp64, L.compute, dim3((row_count + kBlock - 1) / kBlock), c));
   return NBODY_OK;
+}
+
+int force_pass(const Problem& p, Local& L, int row0, int row_count, const Finish& fin, const Redirect* rd) {
+  NBC(launch_force(p, L, row0, row_count, p.cfg.nslices - 1, p.cfg.nslices, fin, rd));
+  return launch_combine(p, L, row0, row_count, fin, rd);
 }
 
 namespace {
@@ -363,7 +370,7 @@ int wait_for_slice(Local& L, hipEvent_t ev) {
 int enqueue_step(float dt, double dt64) {
   TicketGuard guard;
   const int P = g.nranks;
-  const Finish fin = {true, true, false};
+  const Finish fin = {true, true, false, dt, dt64};
   const bool need_gather = !g.loc[0].all_present;
   if (need_gather && g.opt.overlap) {
     // The own-slice kernels run while the other slices travel on the second stream.  Device-side transports (RCCL,
@@ -374,7 +381,7 @@ int enqueue_step(float dt, double dt64) {
     g.comm_go_armed = false;
     if (!host_staged) NBC(enqueue_gather(g.loc[0].cur));
     if (g.comm_go_armed) HIPC(hipStreamWaitEvent(g.loc[0].compute, g.loc[0].ev_comm_go, 0));   // RCCL transport: see enqueue_gather
-    for (int l = 0; l < g.nlocal; ++l) NBC(launch_force(g.loc[l], 0, g.loc[l].n_local, g.loc[l].rank, 1, fin, dt, dt64));
+    for (int l = 0; l < g.nlocal; ++l) NBC(launch_force(problem_of(g.loc[l]), g.loc[l], 0, g.loc[l].n_local, g.loc[l].rank, 1, fin));
     if (host_staged) NBC(enqueue_gather(g.loc[0].cur));
   }
   for (int l = 0; l < g.nlocal; ++l) {
@@ -384,26 +391,27 @@ int enqueue_step(float dt, double dt64) {
       // gather first, then one launch over everything
       if (l == 0) NBC(enqueue_gather(L.cur));
     }
+    const Problem p = problem_of(L);
     if (P == 1) {
-      NBC(launch_force(L, 0, L.n_local, g.cfg.nslices - 1, g.cfg.nslices, fin, dt, dt64));
+      NBC(launch_force(p, L, 0, L.n_local, p.cfg.nslices - 1, p.cfg.nslices, fin));
     } else if (!need_gather) {
-      NBC(launch_force(L, 0, L.n_local, L.rank, P, fin, dt, dt64));
+      NBC(launch_force(p, L, 0, L.n_local, L.rank, P, fin));
     } else if (g.opt.overlap == 2) {
       // one launch per arriving slice, each released by that slice's event (ring arrival order)
       for (int s = 1; s < P; ++s) {
         NBC(wait_for_slice(L, L.ev_gather[s]));
-        NBC(launch_force(L, 0, L.n_local, ring_slice(L.rank, s), 1, fin, dt, dt64));
+        NBC(launch_force(p, L, 0, L.n_local, ring_slice(L.rank, s), 1, fin));
       }
     } else if (g.opt.overlap) {
       // the other slices in one launch once they have all arrived (N = 1M, P = 8: 14 MiB of transfers against
       // ~3.7 ms of own-slice work already running; what is not hidden shows up in nbody_comm_time)
       NBC(wait_for_slice(L, L.ev_gather[P - 1]));
-      NBC(launch_force(L, 0, L.n_local, ring_slice(L.rank, 1), P - 1, fin, dt, dt64));
+      NBC(launch_force(p, L, 0, L.n_local, ring_slice(L.rank, 1), P - 1, fin));
     } else {
       NBC(wait_for_slice(L, L.ev_gather[P - 1]));
-      NBC(launch_force(L, 0, L.n_local, L.rank, P, fin, dt, dt64));
+      NBC(launch_force(p, L, 0, L.n_local, L.rank, P, fin));
     }
-    NBC(launch_combine(L, 0, L.n_local, fin, dt, dt64));
+    NBC(launch_combine(p, L, 0, L.n_local, fin));
     // "own slice of pos[cur^1] written": what the next step's transfers wait for.  With one rank nothing does, and inside a
     // captured graph the record would be a node between two kernels.
     if (P > 1) HIPC(hipEventRecord(L.ev_own_ready, L.compute));
@@ -550,9 +558,7 @@ int forces_on_device(const RowWindow& w) {
     Local& L = g.loc[l];
     int r0, cnt;
     if (!w.rows_of(L, &r0, &cnt)) continue;
-    const Finish fin = {false, false, true};
-    NBC(launch_force(L, r0, cnt, g.cfg.nslices - 1, g.cfg.nslices, fin, 0.f, 0.0));
-    NBC(launch_combine(L, r0, cnt, fin, 0.f, 0.0));
+    NBC(force_pass(problem_of(L), L, r0, cnt, {false, false, true}));
   }
   NBC(sync_all());
   return guard.done();
@@ -622,9 +628,7 @@ int body_force_impl(void* pos, void* vel, float dt, double dt64, int n) {
   TicketGuard guard;
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
-    const Finish fin = {true, false, true};
-    NBC(launch_force(L, 0, L.n_local, g.cfg.nslices - 1, g.cfg.nslices, fin, dt, dt64));
-    NBC(launch_combine(L, 0, L.n_local, fin, dt, dt64));
+    NBC(force_pass(problem_of(L), L, 0, L.n_local, {true, false, true, dt, dt64}));
   }
   NBC(sync_all());
   guard.done();
@@ -878,15 +882,15 @@ int nbody_get_info(int key, long long* value) {
   if (!g.init) return NBODY_ERR_NOT_INIT;
   const Local& L = g.loc[0];
   switch (key) {
-    case NBODY_INFO_N: *value = g.view.n; break;
-    case NBODY_INFO_N_LOCAL: *value = g.view.n_local; break;
+    case NBODY_INFO_N: *value = g.n; break;
+    case NBODY_INFO_N_LOCAL: *value = L.n_local; break;
     case NBODY_INFO_FIRST_BODY: *value = L.first; break;
     case NBODY_INFO_RANK: *value = L.rank; break;
     case NBODY_INFO_NRANKS: *value = g.nranks; break;
-    case NBODY_INFO_VARIANT: *value = g.view.cfg.variant; break;
-    case NBODY_INFO_IBLOCK: *value = g.view.cfg.R; break;
-    case NBODY_INFO_JSUB: *value = g.view.cfg.sub; break;
-    case NBODY_INFO_NSEG: *value = g.view.cfg.nseg; break;
+    case NBODY_INFO_VARIANT: *value = g.cfg.variant; break;
+    case NBODY_INFO_IBLOCK: *value = g.cfg.R; break;
+    case NBODY_INFO_JSUB: *value = g.cfg.sub; break;
+    case NBODY_INFO_NSEG: *value = g.cfg.nseg; break;
     case NBODY_INFO_DEVICE: *value = L.device; break;
     case NBODY_INFO_CU_COUNT: *value = g.cu_count; break;
     case NBODY_INFO_CLOCK_KHZ: *value = g.clock_khz; break;
@@ -897,15 +901,15 @@ int nbody_get_info(int key, long long* value) {
     case NBODY_INFO_SUM_BLOCK: *value = (!g.fp64 && g.opt.sum_order == NBODY_SUM_BLOCKED) ? g.opt.sum_block : 0; break;
     case NBODY_INFO_LAUNCHES_PER_STEP: {
       const int force = g.nranks == 1 ? 1 : (g.opt.overlap == 2 ? g.nranks : (g.opt.overlap ? 2 : 1));
-      *value = force + ((g.view.cfg.nseg > 1 && !g.view.cfg.fuse) ? 1 : 0);   // (finish_mode() of the context's own configuration)
+      *value = force + (finish_mode(g.cfg) == kFinishStore ? 1 : 0);
       break;
     }
     case NBODY_INFO_HAS_COMM: *value = L.comm_h ? 1 : 0; break;
-    case NBODY_INFO_WSPLIT: *value = g.view.cfg.wsplit; break;
+    case NBODY_INFO_WSPLIT: *value = g.cfg.wsplit; break;
     case NBODY_INFO_ISA_PHASE: *value = g.opt.isa_phase; break;
     case NBODY_INFO_LONG_BUFFERS: *value = g.opt.long_buffers; break;
     case NBODY_INFO_XCD_MAP: *value = g.opt.xcd_map; break;
-    case NBODY_INFO_FUSE_COMBINE: *value = g.view.cfg.fuse; break;
+    case NBODY_INFO_FUSE_COMBINE: *value = g.cfg.fuse; break;
     case NBODY_INFO_COMM_FORM: *value = g.nranks > 1 ? resolved_comm_form() : -1; break;
     case NBODY_INFO_COMM_PRIORITY: *value = g.comm_priority; break;
     case NBODY_INFO_MAILBOX_SERVED: *value = mailbox_served(); break;
@@ -975,37 +979,25 @@ int nbody_forces_d(const double* pos_words, double* force_words, int n) { NB_ENT
 int nbody_forces_rows(int first_row, int n_rows, float* force_words) { NB_ENTER(0); return forces_rows_impl(first_row, n_rows, force_words); }
 int nbody_forces_rows_d(int first_row, int n_rows, double* force_words) { NB_ENTER(1); return forces_rows_impl(first_row, n_rows, force_words); }
 
-int nbody_kernel_time(double* ms_total, long long* launches, int reset) { NB_REFUSE_WHILE_SERVED();
+// the summed spans of one of the locals' timers (locals run concurrently: the slowest device's) and how many they were
+static int timer_total(EventTimer Local::*timer, double* ms_total, long long* count, int reset) {
   if (!g.init) return NBODY_ERR_NOT_INIT;
   double ms = 0.0; long long n = 0;
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
+    EventTimer& T = L.*timer;
     HIPC(hipSetDevice(L.device));
-    NBC(timer_drain(L.kern, 0));
-    ms = std::max(ms, L.kern.ms);   // locals run concurrently: report the slowest device
-    n += L.kern.n;
-    if (reset) { L.kern.ms = 0.0; L.kern.n = 0; }
+    NBC(timer_drain(T, 0));
+    ms = std::max(ms, T.ms);
+    n += T.n;
+    if (reset) { T.ms = 0.0; T.n = 0; }
   }
   if (ms_total) *ms_total = ms;
-  if (launches) *launches = n;
+  if (count) *count = n;
   return NBODY_OK;
 }
-
-int nbody_comm_time(double* wait_ms_total, long long* waits, int reset) { NB_REFUSE_WHILE_SERVED();
-  if (!g.init) return NBODY_ERR_NOT_INIT;
-  double ms = 0.0; long long n = 0;
-  for (int l = 0; l < g.nlocal; ++l) {
-    Local& L = g.loc[l];
-    HIPC(hipSetDevice(L.device));
-    NBC(timer_drain(L.wait, 0));
-    ms = std::max(ms, L.wait.ms);
-    n += L.wait.n;
-    if (reset) { L.wait.ms = 0.0; L.wait.n = 0; }
-  }
-  if (wait_ms_total) *wait_ms_total = ms;
-  if (waits) *waits = n;
-  return NBODY_OK;
-}
+int nbody_kernel_time(double* ms_total, long long* launches, int reset) { NB_REFUSE_WHILE_SERVED(); return timer_total(&Local::kern, ms_total, launches, reset); }
+int nbody_comm_time(double* wait_ms_total, long long* waits, int reset) { NB_REFUSE_WHILE_SERVED(); return timer_total(&Local::wait, wait_ms_total, waits, reset); }
 
 int nbody_device_ptr(int which, void** ptr, size_t* bytes) { NB_REFUSE_WHILE_SERVED();
   if (!g.init) return NBODY_ERR_NOT_INIT;

@@ -21,8 +21,9 @@ namespace nbi {
 namespace {
 
 // One context serves requests of ANY NUM_PTS up to its capacity, as the RTL samples NUM_PTS with every BEGIN (:180-186) against a RAM
-// sized once (:45).  The buffers are sized for the capacity; a request switches N and the launch configuration for its own duration
-// (resolve_config is host arithmetic) and leaves the context's N, options and captured step graph as they were.
+// sized once (:45).  The buffers are sized for the capacity; a request resolves a launch configuration for its own NUM_PTS
+// (resolve_config is host arithmetic) and launches its force pass for that Problem: the context's N, configuration, options and captured
+// step graph are not written, so nbody_get_info may read them from the caller's thread while the service thread works.
 constexpr int kMailboxMaxPoints = 32767;   // ram_depth - 1, S/top_level.vhd:45
 
 // the mailbox's two RAMs as the PS sees them (S/top_level.vhd:100-117, 148-163): pinned host memory the device reads (RAM A)
@@ -64,27 +65,6 @@ int mailbox_rams() {   // RAM A and RAM B: capacity + 1 words each (+ slack), pi
   return NBODY_OK;
 }
 
-// N and the launch configuration of a one-rank context switched for the duration of one request.  What nbody_get_info reports is the
-// CONTEXT's configuration (Global::view, published by reconfigure()), which a request never touches.
-struct ActiveN {
-  bool armed = false;
-  Global::View saved;   // the context's own {n, n_local, cfg}
-  int enter(int n_new) {
-    Local& L = g.loc[0];
-    saved = {g.n, L.n_local, g.cfg};
-    armed = true;
-    g.n = n_new; L.n_local = n_new;
-    g.cfg = resolve_config(n_new, g.nranks, g.fp64, g.opt, g.cu_count);
-    NBC(ensure_partial(L, g.cfg.nseg));
-    if (g.tickets_dirty) NBC(zero_tickets());   // a failed launch sequence left arrival counters part-counted (TicketGuard)
-    return NBODY_OK;
-  }
-  ~ActiveN() {
-    if (!armed) return;
-    g.n = saved.n; g.loc[0].n_local = saved.n_local; g.cfg = saved.cfg;
-  }
-};
-
 // completion of everything on `stream` as the HOST sees it: polled for the first 200 us (a request at the mailbox's sizes takes 7-500 us
 // of device time and an interrupt-driven wait adds tens of us of wake-up), then a blocking wait
 int wait_stream(hipStream_t stream) {
@@ -122,7 +102,8 @@ int wait_seq(hipStream_t stream, unsigned seq) {
 
 // the launches of one request on the compute stream: RAM A's read port (which starts the tick count), the force pass storing into RAM B
 // (and its combine), and — device-written completion — the one-wave launch that rewrites word 0
-int mailbox_launches(Local& L, int num_pts, bool done_by_device, unsigned seq, int clock_khz) {
+int mailbox_launches(const Problem& p, Local& L, bool done_by_device, unsigned seq, int clock_khz) {
+  const int num_pts = p.n;
   // RAM B's write port: the force launch (or its combine) stores {Fx, Fy, Fz, 0} of body k at word k itself — row k - 1 of the launch
   // goes to force_dst[k - 1] and force_dst is word 1 —; word 0 and the words beyond N are never written       S/compute_store.vhd:213, 221-242
   Redirect rd = {(char*)mb_b_dev + 16};
@@ -130,11 +111,9 @@ int mailbox_launches(Local& L, int num_pts, bool done_by_device, unsigned seq, i
   // bodies are words 1..N                                              S/top_level.vhd:55, 206-208
   // A handful of bodies in the faithful mode: the 16-row kernel reads RAM A itself (its tile loads ARE the PCIe reads) and stamps the tick
   // count's start; everything else goes through the ingest launch, which reads RAM A once for all workgroups (into pos[cur]).
-  if (done_by_device && num_pts <= mb_direct_max && takes_rows16(num_pts)) { rd.src_direct = (const char*)mb_a_dev + 16; rd.t0_stamp = t0; }
+  if (done_by_device && num_pts <= mb_direct_max && takes_rows16(p.cfg, num_pts)) { rd.src_direct = (const char*)mb_a_dev + 16; rd.t0_stamp = t0; }
   else HIPC((hipError_t)nbl::launch_ingest_kernel(L.compute, L.pos[L.cur], (const char*)mb_a_dev + 16, num_pts, done_by_device ? t0 : nullptr));
-  const Finish fin = {false, false, true};
-  NBC(launch_force(L, 0, num_pts, g.cfg.nslices - 1, g.cfg.nslices, fin, 0.f, 0.0, &rd));
-  NBC(launch_combine(L, 0, num_pts, fin, 0.f, 0.0, &rd));
+  NBC(force_pass(p, L, 0, num_pts, {false, false, true}, &rd));
   if (!done_by_device) return NBODY_OK;
   HIPC((hipError_t)nbl::launch_mailbox_done_kernel(L.compute, mb_a_dev, mb_seq_dev, t0, seq, (unsigned)clock_khz, (unsigned)mb_rt_khz));
   return NBODY_OK;
@@ -146,8 +125,9 @@ int mailbox_request(const void* ram_a, void* ram_b, int num_pts, int clock_khz, 
   *device_done = false;
   HIPC(hipSetDevice(L.device));
   NBC(mailbox_rams());
-  ActiveN scope;
-  NBC(scope.enter(num_pts));
+  const Problem p = {num_pts, num_pts, resolve_config(num_pts, g.nranks, g.fp64, g.opt, g.cu_count)};
+  NBC(ensure_partial(L, num_pts, p.cfg.nseg));
+  if (g.tickets_dirty) NBC(zero_tickets());   // a failed launch sequence left arrival counters part-counted (TicketGuard)
   // RAM A: the library's own pinned image is read in place; any other host buffer is copied into it first
   if (ram_a != g.mb.a) memcpy(g.mb.a.as<char>() + 16, (const char*)ram_a + 16, (size_t)num_pts * 16);
   L.all_present = true;
@@ -155,7 +135,7 @@ int mailbox_request(const void* ram_a, void* ram_b, int num_pts, int clock_khz, 
   const unsigned seq = by_device ? ++mb_seq_next : 0u;
   if (by_device && ram_a != g.mb.a) g.mb.a.as<uint32_t>()[0] = 1u;   // (the device clears THIS image's BEGIN; the caller's word 0 follows below)
   TicketGuard guard;   // up to the request's completion
-  const int rc = mailbox_launches(L, num_pts, by_device, seq, clock_khz);
+  const int rc = mailbox_launches(p, L, by_device, seq, clock_khz);
   if (rc) {
     if (by_device) { (void)hipStreamSynchronize(L.compute); --mb_seq_next; }   // nothing of this request may still be writing when word 0 is rewritten
     return rc;
@@ -268,7 +248,7 @@ int nbody_mailbox_open(int capacity, int faithful) {
   OpenGuard guard;
   NBC(mailbox_rams());
   // the partial sums of the largest segmentation any request can resolve to (64 segments), so that no request allocates
-  NBC(ensure_partial(g.loc[0], 64));
+  NBC(ensure_partial(g.loc[0], capacity, 64));
   if (faithful) {
     // the PL block's own bits: its rounding points (S/dxy.vhd:113-122, S/dzsoft.vhd:201-202, S/dxyz_soft.vhd:149-150) with 1/sqrt rounded
     // once — after this device has proved that 1/sqrt —, its sixteen partial sums, rotation and adder tree (S/fxyz.vhd:129-184,

@@ -1,8 +1,9 @@
 // nbody_internal.hpp — what the parts of libnbody_hip.so share (none of it crosses the C-ABI of include/nbody.h):
 //   kernels.hip   the nbk kernels (nbody_kernels.hpp) and the thin launch functions that pick an instantiation (namespace nbl)
-//   context.cpp   the context: options, launch configuration, buffers, the step and its HIP graph, state transfer, the strict gate
+//   context.cpp   the context: options, launch configuration, buffers, the force pass (a function of the Problem it is given), the step
+//                 and its HIP graph, state transfer, the strict gate
 //   comm.cpp      RCCL (resolved with dlopen), the transfer plans, the all-gather of a step, probes and self-tests
-//   mailbox.cpp   the reference's mailbox: RAM images, one request, the service thread
+//   mailbox.cpp   the reference's mailbox: RAM images, one request (a force pass over a Problem of the request's own N), the service thread
 //   diag_pass.hpp  what the three diagnostic passes below share on the device: the potential's pair arithmetic, the lane and wave
 //                  preamble of a one-query-per-lane kernel, the block and workgroup sizes (read by their *_args.hpp)
 //   query_pass.hpp what they share on the host: ranges over the locals, upload, the split's batches, launch-then-copy-back, the ranks' words
@@ -147,8 +148,8 @@ struct Options {
   int wsplit = -1;
 };
 
-// what happens to the force of a row once all its segments are summed
-struct Finish { bool kick, drift, store_force; };
+// what happens to the force of a row once all its segments are summed, and the time step of a kick or drift
+struct Finish { bool kick, drift, store_force; float dt = 0.f; double dt64 = 0.0; };
 
 // what one launch reads and writes instead of the context's buffers (a mailbox request); none by default
 struct Redirect {
@@ -166,6 +167,10 @@ struct LaunchConfig {
   }
   bool operator!=(const LaunchConfig& o) const { return !(*this == o); }
 };
+
+// What a force pass works on: n sources, a local that owns n_local rows of them, and the launch configuration resolved for that.  The
+// context's own passes take {g.n, L.n_local, g.cfg} (problem_of); a mailbox request makes one of its NUM_PTS and touches none of the three.
+struct Problem { int n = 0, n_local = 0; LaunchConfig cfg; };
 
 typedef int (*host_gather_fn)(void* user, void* host_words, int n_total, int word_bytes, int rank, int nranks);
 
@@ -193,10 +198,9 @@ struct Global {
   int cu_count = 0, clock_khz = 0;
   int comm_priority = 0;          // HIP priority of the transfer streams (0 = default)
   long long steps_done = 0;
-  // The CONTEXT's N and resolved configuration as nbody_get_info reports them: published by reconfigure(), never touched by a mailbox
-  // request (which switches n, n_local and cfg for its own duration) — so the caller's thread may read them while the service thread works
-  struct View { int n = 0, n_local = 0; LaunchConfig cfg; } view;
 };
+// Who writes what: n in init_common, Local::n_local in describe_local, cfg in reconfigure() — none of them while the mailbox's service
+// thread runs (NB_REFUSE_WHILE_SERVED), and a mailbox request writes none of them: nbody_get_info may read all three from any thread.
 // The context is never destroyed: it is allocated once and its handles are released by nbody_shutdown() alone.  A process that exits
 // without nbody_shutdown() therefore frees nothing and makes no HIP call after main() returns (static destructors may run after the HIP
 // runtime's own teardown).
@@ -217,8 +221,8 @@ inline int ring_slice(int rank, int s) { int q = (rank - s) % g.nranks; return q
 inline size_t ticket_words(int n_local) { return ((size_t)(n_local + 63) / 64 + 32 + 63) / 64 * 64; }
 
 // A sequence of force launches that fails part-way leaves arrival counters at a partial count: the next launch would combine early.
-// Every such sequence (a step, forces_on_device, bodyForce, the comm probe's force pass, a mailbox request up to its completion) holds
-// a TicketGuard; any way out before done() marks the counters dirty, and the next upload, reconfigure() or mailbox request re-zeroes
+// Every caller of such a sequence (a step, forces_on_device, bodyForce, the comm probe, a mailbox request up to its completion) holds
+// a TicketGuard around it; any way out before done() marks the counters dirty, and the next upload, reconfigure() or mailbox request re-zeroes
 // them (zero_tickets) before it launches anything.
 struct TicketGuard {
   bool ok = false;
@@ -237,18 +241,20 @@ struct RowWindow {
 // ---- context.cpp ----
 LaunchConfig resolve_config(int n, int nranks, int fp64, const Options& opt, int cu_count);
 int reconfigure();
-int ensure_partial(Local& L, int nseg);   // partial sums for nseg segments of L's rows
+int ensure_partial(Local& L, int rows, int nseg);   // partial sums for nseg segments of a launch of `rows` rows on L
 int zero_tickets();                       // every local's arrival counters, and the dirty mark off (TicketGuard sets it)
 void drop_step_graph();
 int timer_begin(EventTimer& T, hipStream_t stream, int* slot);
 int timer_end(EventTimer& T, hipStream_t stream, int slot);
 int timer_drain(EventTimer& T, int keep);
-// the force kernel of local L for rows [row0, row0 + row_count) against `nsl` source slices starting at slice_start and descending
-int launch_force(Local& L, int row0, int row_count, int slice_start, int nsl, const Finish& fin, float dt, double dt64,
-                 const Redirect* rd = nullptr);
-int launch_combine(Local& L, int row0, int row_count, const Finish& fin, float dt, double dt64, const Redirect* rd = nullptr);
-// launch_force would take the 16-row FPGA kernel (force_fpga16r_f32) for a launch of row_count rows in the configuration as it stands
-bool takes_rows16(int row_count);
+inline Problem problem_of(const Local& L) { return {g.n, L.n_local, g.cfg}; }   // the context's own problem on local L
+// the force kernel of problem p on local L for rows [row0, row0 + row_count) against `nsl` source slices starting at slice_start and descending
+int launch_force(const Problem& p, Local& L, int row0, int row_count, int slice_start, int nsl, const Finish& fin, const Redirect* rd = nullptr);
+int launch_combine(const Problem& p, Local& L, int row0, int row_count, const Finish& fin, const Redirect* rd = nullptr);
+// one whole force pass: launch_force over all of p's slices, then launch_combine
+int force_pass(const Problem& p, Local& L, int row0, int row_count, const Finish& fin, const Redirect* rd = nullptr);
+// launch_force would take the 16-row FPGA kernel (force_fpga16r_f32) for a launch of row_count rows in configuration cfg
+bool takes_rows16(const LaunchConfig& cfg, int row_count);
 int sync_all();
 int complete_positions();
 int forces_impl(const void* pos_words, void* force_words, int n);

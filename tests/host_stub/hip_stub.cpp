@@ -7,7 +7,7 @@
 // launch's segments of (r_j - r_i), float or double, segment by segment) through the REAL data flow of a launch: ForceArgs, segment
 // bounds, per-segment partial sums, one arrival counter per 64 rows, ascending combine, apply (store / kick / drift), the mailbox's
 // ingest and device-written completion.  The energy pass writes values a test can predict from what it reads (see energy()).  It says nothing about the kernels' arithmetic (the GPU tests do); it checks the host's logic:
-// buffer sizes, offsets, state switching per request, the service thread's hand-over, the guard, lifetimes.
+// buffer sizes, offsets, a request's own N beside the context's, the service thread's hand-over, the guard, lifetimes.
 // For the failure paths: hip_stub_live(kind) counts what is outstanding of each kind of resource, and hip_stub_fail_nth(k) makes the k-th
 // creating call from now fail once, with hipErrorOutOfMemory and nothing created.
 #include <hip/hip_runtime.h>

@@ -132,7 +132,7 @@ def test_default_arithmetic_mailbox_is_within_tolerance(nb):
 
 
 def test_requests_inside_an_nbody_init_context_leave_it_as_it_was(nb, oracle_fast):
-    """Any one-GPU fp32 context is a mailbox of capacity n.  A request of another size switches N for its own duration only: the
+    """Any one-GPU fp32 context is a mailbox of capacity n.  A request of another size launches for its own N: the
     context's N, options and captured step graph survive, and after a fresh upload the step loop gives the bits it gave before."""
     n = 1000
     pos, vel = nb.make_bodies(n, seed=5)
@@ -323,7 +323,7 @@ def test_num_pts_1_2_3_are_answered_a_stated_departure_from_the_rtl(nb, oracle_f
 def test_the_served_context_is_guarded_against_the_callers_thread(nb):
     """While nbody_mailbox_serve(1, .) is in effect the service thread owns the context: every entry point that
     launches, copies or reconfigures answers NBODY_ERR_STATE, and nbody_get_info reports the CONTEXT's N and configuration — never the N a
-    request has switched in for its own duration.  A second thread hammers both while 10^4 served requests of alternating sizes stay
+    request is being launched for.  A second thread hammers both while 10^4 served requests of alternating sizes stay
     bit-exact."""
     L = nb._lib
     lib = L.load()

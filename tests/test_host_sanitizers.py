@@ -11,8 +11,8 @@ failure paths (the stub fails the k-th creating call of every entry point that a
 live after nbody_shutdown, the same call then works; and nothing is live after any nbody_shutdown of the harness), and
 the SERVED mailbox with a second thread hammering nbody_get_info and the refused entry points ("a TSan build of a
 host-only stub of the serve loop").
-What this checks is the host's logic — buffer sizes and offsets (ASan sees every index the host computed), the per-request switch of
-N, the service thread's hand-over, the guard, lifetimes at shutdown; the kernels' arithmetic is the GPU tests' business."""
+What this checks is the host's logic — buffer sizes and offsets (ASan sees every index the host computed), a request's force pass
+over its own N beside a context that keeps its own, the service thread's hand-over, the guard, lifetimes at shutdown; the kernels' arithmetic is the GPU tests' business."""
 import os
 import shutil
 import subprocess

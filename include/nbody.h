@@ -2,7 +2,7 @@
  *
  * Plain C99: pointers, ints, floats.  No HIP, torch or C++ types cross this
  * boundary.  The library behind it is hand-written HIP for gfx950
- * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, field.hip, neighbors.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, field.cpp, neighbors.cpp); there is
+ * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, field.hip, neighbors.hip, knn.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, field.cpp, neighbors.cpp, knn.cpp); there is
  * no CPU fallback: every entry
  * point fails with NBODY_ERR_NO_DEVICE when no GPU is usable.
  *
@@ -416,6 +416,39 @@ int nbody_nearest(const float *points, int m, const int *skip, int *idx, float *
 int nbody_nearest_d(const double *points, int m, const int *skip, int *idx, double *d2, double r2, int *count);
 int nbody_closest_pair(int *i, int *j, float *d2);
 int nbody_closest_pair_d(int *i, int *j, double *d2);
+
+/* ---- k nearest neighbours: which k bodies are nearest, and how far away the k-th is (not in the reference) ----
+ * The dual of the section above: a local density k / r_k^3, softening or time steps from the k-th neighbour's distance, interpolation
+ * stencils, linking lengths.  Queries, skip and d2 are exactly the neighbour pass's: in the context precision T, for every body j,
+ *   dx = xj - x;  dy = yj - y;  dz = zj - z;   d2_j = fma(dx, dx, fma(dy, dy, dz * dz))
+ * no softening, independent of NBODY_OPT_ARITH, every operation IEEE-exact.
+ * A CANDIDATE is a non-skipped j with d2_j < +inf: a NaN d2_j is never listed, nor is one that overflowed to +inf.  For a query and
+ * 1 <= k <= NBODY_KNN_MAX the result is the first k candidates in ascending (d2_j, j) order, a total order — what an ascending scan
+ * over j arrives at that starts from k entries (d2 = +inf, idx = -1), puts a candidate behind every entry with d2 <= its own and drops
+ * the last entry.  Entry 0 is the nearest.  With fewer than k candidates the remaining entries are idx = -1, d2 = +inf.  A coincident
+ * distinct body is listed at +0.
+ * Entry r of any k equals entry r of any larger k, and entry 0 equals nbody_neighbors_rows / nbody_nearest.  A selection is exact: the
+ * values depend on the N positions, the query, its skip and k alone — not on the number of queries, on where the query stands, on the
+ * launch shape (NBODY_KNN_SPLIT below), on the arithmetic, on the force configuration or on the device or rank count.  No atomics: two
+ * calls return identical values.
+ * idx, d2: m (n_rows) x k values, row-major: entry r of query p at [p * k + r]; either may be NULL, not both.
+ * nbody_knn_rows(_d): the queries are the bodies themselves, each excluding itself; rows exactly as in nbody_forces_rows and
+ *   nbody_neighbors_rows.  The idx returned are always GLOBAL body indices.
+ * nbody_knn(_d): the queries are m caller points; points, skip and the division over the devices as in nbody_nearest.  nbody_init_rank:
+ *   every rank asks for its own points, m and k may differ between ranks.
+ * Both bring the other slices' positions first (collective in nbody_init_rank contexts) and, like their siblings, leave positions,
+ * velocities, the arrival counters, the captured step graph and the force-kernel timer as they were.
+ * Environment, read on every call: NBODY_KNN_SPLIT = c >= 1 walks the sources in min(c, blocks of 1024) chunks side by side (unset or 0:
+ * chosen from the number of queries and the CU count); NBODY_KNN_SCRATCH_MB (default 256, fractions allowed) bounds the k * 8 (fp64:
+ * k * 12) bytes per query and chunk a split launch stores, larger calls go in consecutive batches of queries.  Same values in every case.
+ * NBODY_ERR_NOT_INIT without a context; NBODY_ERR_ARG, checked before anything is launched or written, for both outputs NULL, k < 1,
+ * k > NBODY_KNN_MAX, a bad row range, points == NULL, m < 1 or a skip value outside [-1, N); NBODY_ERR_STATE for the other precision's
+ * entry point or while the mailbox is served. */
+#define NBODY_KNN_MAX 32
+int nbody_knn_rows(int first_row, int n_rows, int k, int *idx, float *d2);
+int nbody_knn_rows_d(int first_row, int n_rows, int k, int *idx, double *d2);
+int nbody_knn(const float *points, int m, const int *skip, int k, int *idx, float *d2);
+int nbody_knn_d(const double *points, int m, const int *skip, int k, int *idx, double *d2);
 
 #ifdef __cplusplus
 }

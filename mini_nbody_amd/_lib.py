@@ -24,6 +24,8 @@ COMM_RING, COMM_ALLGATHER, COMM_AUTO, COMM_DIRECT = 0, 1, 2, 3
 
 (ENERGY_KINETIC, ENERGY_POTENTIAL, ENERGY_PX, ENERGY_PY, ENERGY_PZ, ENERGY_LX, ENERGY_LY, ENERGY_LZ, ENERGY_WORDS) = range(9)
 
+KNN_MAX = 32   # NBODY_KNN_MAX
+
 ERR_NOT_INIT, ERR_ARG, ERR_NO_DEVICE, ERR_RCCL_LOAD, ERR_STATE, ERR_UNSUPPORTED = 1001, 1002, 1003, 1004, 1005, 1006
 
 # every symbol include/nbody.h declares (tests/test_abi.py checks the library exports exactly these)
@@ -37,6 +39,7 @@ SYMBOLS = [
     "nbody_rsqrt_selftest", "nbody_rsqrt_strict", "nbody_strict_proof", "nbody_mailbox_open", "nbody_mailbox_rams",
     "nbody_mailbox_serve", "nbody_energy", "nbody_potential_rows", "nbody_potential_rows_d", "nbody_field", "nbody_field_d",
     "nbody_neighbors_rows", "nbody_neighbors_rows_d", "nbody_nearest", "nbody_nearest_d", "nbody_closest_pair", "nbody_closest_pair_d",
+    "nbody_knn_rows", "nbody_knn_rows_d", "nbody_knn", "nbody_knn_d",
 ]
 
 
@@ -96,6 +99,8 @@ def load():
         "nbody_nearest": [fp, i, C.POINTER(i), C.POINTER(i), fp, f, C.POINTER(i)],
         "nbody_nearest_d": [dp, i, C.POINTER(i), C.POINTER(i), dp, d, C.POINTER(i)],
         "nbody_closest_pair": [C.POINTER(i), C.POINTER(i), fp], "nbody_closest_pair_d": [C.POINTER(i), C.POINTER(i), dp],
+        "nbody_knn_rows": [i, i, i, C.POINTER(i), fp], "nbody_knn_rows_d": [i, i, i, C.POINTER(i), dp],
+        "nbody_knn": [fp, i, C.POINTER(i), i, C.POINTER(i), fp], "nbody_knn_d": [dp, i, C.POINTER(i), i, C.POINTER(i), dp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -226,6 +226,50 @@ class NBody:
         L.check((self.lib.nbody_closest_pair_d if self.fp64 else self.lib.nbody_closest_pair)(C.byref(i), C.byref(j), C.byref(d2)))
         return i.value, j.value, self.dtype(d2.value)
 
+    def _knn_out(self, m, k):
+        k = int(k)
+        if not 1 <= k <= L.KNN_MAX:
+            raise ValueError("k must be in 1..%d" % L.KNN_MAX)
+        ct = C.c_double if self.fp64 else C.c_float
+        idx, d2 = np.empty((m, k), np.int32), np.empty((m, k), self.dtype)
+        return idx, d2, (k, idx.ctypes.data_as(C.POINTER(C.c_int)), d2.ctypes.data_as(C.POINTER(ct)))
+
+    def knn(self, k, first_row=0, n_rows=None):
+        """(idx, d2), each (n_rows, k), of n_rows bodies from first_row (rows as in forces_rows; default: all of them) from the state on
+        the device (nbody_knn_rows): per body the k nearest other bodies in ascending (d2, index) order — idx their GLOBAL indices
+        (int32; -1 where there are fewer than k), d2 their plain squared distances in the context precision (no softening; +inf there).
+        1 <= k <= 32.  Column 0 is neighbors().  Collective in a multi-rank job."""
+        if n_rows is None:
+            n_rows = self.info(L.INFO_N_LOCAL if self._by_rank else L.INFO_N) - int(first_row)
+        if int(n_rows) < 1:
+            raise ValueError("expected at least one row")
+        idx, d2, out = self._knn_out(int(n_rows), k)
+        fn = self.lib.nbody_knn_rows_d if self.fp64 else self.lib.nbody_knn_rows
+        L.check(fn(int(first_row), int(n_rows), *out))
+        return idx, d2
+
+    def knn_at(self, points, k, skip=None):
+        """(idx, d2), each (m, k), as knn(), of the bodies on the device at arbitrary points (nbody_knn).  points: (m, 4) words or
+        (m, 3) in the context dtype; skip: None or m ints, each -1 or the global index of a body to leave out for that point.  A
+        point on a body without a skip lists that body first at d2 = 0.  Column 0 is nearest()."""
+        p = np.asarray(points, self.dtype)
+        if p.ndim != 2 or p.shape[1] not in (3, 4) or len(p) < 1:
+            raise ValueError("expected an (m, 4) or (m, 3) array of %s, m >= 1" % np.dtype(self.dtype).name)
+        if p.shape[1] == 3:
+            p = np.concatenate([p, np.zeros((len(p), 1), self.dtype)], axis=1)
+        p = np.ascontiguousarray(p)
+        m = len(p)
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, np.int32)
+            if sk.shape != (m,):
+                raise ValueError("skip must hold one index per point")
+        idx, d2, out = self._knn_out(m, k)
+        ct = C.c_double if self.fp64 else C.c_float
+        fn = self.lib.nbody_knn_d if self.fp64 else self.lib.nbody_knn
+        L.check(fn(p.ctypes.data_as(C.POINTER(ct)), m, sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None, *out))
+        return idx, d2
+
     def comm_selftest(self):
         """Push a patterned array through the RCCL calls of the multi-GPU path (all-gather + one ring step); returns
         the bytes this rank received.  Needs the communicator of NBody(..., rank=, nranks=, uid=)."""

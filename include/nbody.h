@@ -450,6 +450,43 @@ int nbody_knn_rows_d(int first_row, int n_rows, int k, int *idx, double *d2);
 int nbody_knn(const float *points, int m, const int *skip, int k, int *idx, float *d2);
 int nbody_knn_d(const double *points, int m, const int *skip, int k, int *idx, double *d2);
 
+/* ---- friends-of-friends groups: which bodies belong together at a linking length (not in the reference) ----
+ * The sections above answer a question about one body or one point; this one is about the system: halos, clumps, bound-pair candidates,
+ * "is the system still one piece".  The pair predicate is the neighbour pass's d2 in the context precision T,
+ *   dx = xj - xi;  dy = yj - yi;  dz = zj - zi;   d2_ij = fma(dx, dx, fma(dy, dy, dz * dz))
+ * no softening, independent of NBODY_OPT_ARITH, every operation IEEE-exact; it is symmetric bit for bit.
+ * Bodies i != j are LINKED when d2_ij <= b2; b2 is the linking length already squared, in T, as r2 is for the radius count.  A NaN d2
+ * links nothing, so a NaN body is a group of one; coincident bodies (d2 = +0) are linked for every b2 >= 0.  A GROUP is a connected
+ * component of the link graph.
+ *   group[i]   the lowest global body index in i's group; group[i] == i for exactly one body per group.  N ints, or NULL.
+ *   n_groups   the number of such bodies.  May be NULL (group and n_groups not both).
+ *   rounds     the number of link passes the call ran, a diagnostic: the same for two identical calls and for every launch shape.
+ *              May be NULL.
+ * The result is a property of the N positions and b2 alone: it does not depend on the launch shape (NBODY_FOF_SPLIT below), on the
+ * rounds taken, on the force configuration or on the device or rank count.  No atomics: two calls return identical values.
+ * How: the all-pairs work runs on the device, the O(N) bookkeeping on the host.  The host keeps a union-find whose root is the lowest
+ * index, L[i] = find(i).  A round uploads L, the link pass gives every active row i the lowest FOREIGN label among its friends,
+ *   m_i = min{ L[j] : d2_ij <= b2 and L[j] != L[i] }   (INT_MAX: none; the self pair drops out by its label),
+ * and the host unites i with m_i.  A round in which no row reports is the last.  Every group that is not yet a whole component has a
+ * row that reports, so the incomplete groups at least halve per round: rounds <= ceil(log2 N) + 1, a hard cap of the host loop
+ * (NBODY_ERR_STATE beyond it; nothing on the device spins or polls).  A group none of whose rows reported is finished: later rounds
+ * walk only the rows of the groups that did report.
+ * Cost, in the pass's current form: the rows are ALL N global rows whatever the context, divided in contiguous ranges over the
+ * process's devices; every device holds all positions, gets the whole L and returns its rows' m.  In an nbody_init_rank job every rank
+ * therefore walks all N rows on its own device and returns the same values: the call is collective only because the other slices'
+ * positions are brought first, labels are not exchanged between processes, and P ranks do P times the work of one.
+ * Like its siblings the call leaves positions, velocities, the arrival counters, the captured step graph and the force-kernel timer
+ * as they were.
+ * Environment, read on every call: NBODY_FOF_SPLIT = c >= 1 walks the sources in min(c, blocks of 1024) chunks side by side (unset or 0:
+ * chosen from the number of active rows and the CU count); NBODY_FOF_SCRATCH_MB (default 256, fractions allowed) bounds the 4 bytes per
+ * row and chunk a split launch stores, larger rounds go in consecutive batches of rows; NBODY_FOF_ALL_ROWS = 1 walks every row in every
+ * round.  Same group and rounds in every case.
+ * NBODY_ERR_NOT_INIT without a context; NBODY_ERR_ARG, checked before anything is launched or written, for both outputs NULL, b2 NaN
+ * or b2 < 0 (b2 = +inf is legal: every non-NaN body in one group); NBODY_ERR_STATE for the other precision's entry point or while the
+ * mailbox is served. */
+int nbody_fof(float b2, int *group, int *n_groups, int *rounds);
+int nbody_fof_d(double b2, int *group, int *n_groups, int *rounds);
+
 #ifdef __cplusplus
 }
 #endif

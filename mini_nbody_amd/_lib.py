@@ -39,7 +39,7 @@ SYMBOLS = [
     "nbody_rsqrt_selftest", "nbody_rsqrt_strict", "nbody_strict_proof", "nbody_mailbox_open", "nbody_mailbox_rams",
     "nbody_mailbox_serve", "nbody_energy", "nbody_potential_rows", "nbody_potential_rows_d", "nbody_field", "nbody_field_d",
     "nbody_neighbors_rows", "nbody_neighbors_rows_d", "nbody_nearest", "nbody_nearest_d", "nbody_closest_pair", "nbody_closest_pair_d",
-    "nbody_knn_rows", "nbody_knn_rows_d", "nbody_knn", "nbody_knn_d",
+    "nbody_knn_rows", "nbody_knn_rows_d", "nbody_knn", "nbody_knn_d", "nbody_fof", "nbody_fof_d",
 ]
 
 
@@ -101,6 +101,7 @@ def load():
         "nbody_closest_pair": [C.POINTER(i), C.POINTER(i), fp], "nbody_closest_pair_d": [C.POINTER(i), C.POINTER(i), dp],
         "nbody_knn_rows": [i, i, i, C.POINTER(i), fp], "nbody_knn_rows_d": [i, i, i, C.POINTER(i), dp],
         "nbody_knn": [fp, i, C.POINTER(i), i, C.POINTER(i), fp], "nbody_knn_d": [dp, i, C.POINTER(i), i, C.POINTER(i), dp],
+        "nbody_fof": [f, C.POINTER(i), C.POINTER(i), C.POINTER(i)], "nbody_fof_d": [d, C.POINTER(i), C.POINTER(i), C.POINTER(i)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

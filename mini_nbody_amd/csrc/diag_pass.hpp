@@ -1,6 +1,6 @@
-// diag_pass.hpp — what the diagnostic passes (energy, field, neighbours, k nearest neighbours) share, stated once: the two launch constants their hosts and
+// diag_pass.hpp — what the diagnostic passes (energy, field, neighbours, k nearest neighbours, friends-of-friends) share, stated once: the two launch constants their hosts and
 // kernels agree on and, for device code, the pair arithmetic of the potential and the lane / wave preamble of a one-query-per-lane
-// kernel.  energy_args.hpp, field_args.hpp, neighbors_args.hpp and knn_args.hpp include it.  Like them it stays apart from the force path's hashed
+// kernel.  energy_args.hpp, field_args.hpp, neighbors_args.hpp, knn_args.hpp and fof_args.hpp include it.  Like them it stays apart from the force path's hashed
 // source (nbody_args.hpp, nbody_kernels.hpp, kernels.hip, force_loop_gfx950.inc), of which it reads nbody_args.hpp (kSoftBits) only.
 // The kernels' loops are different computations and stay in their files.
 #pragma once

@@ -1,4 +1,4 @@
-// query_pass.hpp — the host side that the diagnostic passes share (energy.cpp, field.cpp, neighbors.cpp, knn.cpp; host C++ only): a call brings
+// query_pass.hpp — the host side that the diagnostic passes share (energy.cpp, field.cpp, neighbors.cpp, knn.cpp, fof.cpp; host C++ only): a call brings
 // rows or points, every local takes a contiguous range of them, launches on its compute stream — in batches over a split of the
 // sources when the pass asks for one — and the results are copied back once the stream has drained.  A pass says what differs: which
 // range a local gets, what to launch, which outputs go where, and its own split rule (a SplitPlan).
@@ -34,7 +34,7 @@ inline int choose_chunks(long long forced, int queries, int n_blocks) {
 }
 
 // How a local's launch is cut: grid.y = chunks chunks of chunk_blocks whole blocks (no empty chunk), `batch` queries per launch.
-// Each pass has its own rule (field.cpp: field_split, neighbors.cpp: neighbors_split, knn.cpp: knn_split); all fall back to no_split.
+// Each pass has its own rule (field.cpp: field_split, neighbors.cpp: neighbors_split, knn.cpp: knn_split, fof.cpp: fof_split); all fall back to no_split.
 struct SplitPlan { int chunks, chunk_blocks, batch; };
 inline SplitPlan no_split(int cnt, int n_blocks) { return {1, n_blocks, cnt}; }
 

@@ -31,6 +31,7 @@ class NBody:
             L.check(self.lib.nbody_init_rank(self.n, int(self.fp64), int(tile), int(rank), int(nranks), buf))
         self._by_rank = rank is not None   # rows are those of this rank's slice (nbody_init_rank)
         self._open = True
+        self.fof_rounds = None             # link passes of the last fof() call
 
     # ---- options / info ----
     def set_option(self, key, value):
@@ -269,6 +270,22 @@ class NBody:
         fn = self.lib.nbody_knn_d if self.fp64 else self.lib.nbody_knn
         L.check(fn(p.ctypes.data_as(C.POINTER(ct)), m, sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None, *out))
         return idx, d2
+
+    def fof(self, b2):
+        """(group, n_groups): the friends-of-friends groups of the state on the device at the linking length whose SQUARE is b2, in
+        the context precision (nbody_fof).  Bodies with plain squared distance d2 <= b2 are linked, a group is a connected component;
+        group: (N,) int32, the lowest GLOBAL body index of every body's group over all N bodies, n_groups the number of groups
+        (numpy.bincount(group) gives their sizes).  b2 = inf is legal.  The number of link passes the call ran is left in
+        self.fof_rounds.  Collective in a multi-rank job; every rank gets the same values."""
+        b2 = float(self.dtype(b2))
+        if not b2 >= 0:
+            raise ValueError("b2 must be a squared length: not NaN, not negative")
+        group = np.empty(self.n, np.int32)
+        n_groups, rounds = C.c_int(), C.c_int()
+        fn = self.lib.nbody_fof_d if self.fp64 else self.lib.nbody_fof
+        L.check(fn(b2, group.ctypes.data_as(C.POINTER(C.c_int)), C.byref(n_groups), C.byref(rounds)))
+        self.fof_rounds = rounds.value
+        return group, n_groups.value
 
     def comm_selftest(self):
         """Push a patterned array through the RCCL calls of the multi-GPU path (all-gather + one ring step); returns

@@ -113,7 +113,14 @@ enum { NBODY_ARITH_FMA3 = 0,       /* d2 = fma(dx,dx,fma(dy,dy,fma(dz,dz,eps))):
        NBODY_ARITH_STRICT = 2,     /* FMA3 with 1/sqrt rounded once from an fp64 evaluation instead of v_rsq_f32 (1 ulp):
                                       every operation is then IEEE-exact and the result is bit-identical to the CPU oracle.
                                       In an fp64 context: 1/sqrt as IEEE sqrt and divide instead of v_rsq_f64 + one third-order
-                                      step — bit-identical to the oracle's fp64 evaluation in the configured summation order */
+                                      step — bit-identical to the oracle's fp64 evaluation in the configured summation order.
+                                      DOMAIN of the timed fp64 FORCE (NBODY_ARITH_FMA3 in an fp64 context: bodyForce_d, nbody_step_d,
+                                      nbody_forces_d, nbody_forces_rows_d): the squares of the coordinate differences must not overflow
+                                      binary64 (|difference| below about 1.3e154).  Beyond that d2 = +inf, the seed is 0, the step's
+                                      e = fma(-inf, 0, 1) is NaN and the pair contributes NaN, to every row that sees it, where
+                                      NBODY_ARITH_STRICT contributes exactly +0: NBODY_ARITH_STRICT has no such limit.  The fp32 timed
+                                      mode has none either (v_rsq_f32(inf) = 0, inv3 = 0), nor have the fp64 diagnostic passes below
+                                      (energy, potential, field), which return the seed when it is 0. */
        NBODY_ARITH_REFERENCE_STRICT = 3 /* REFERENCE roundings + strict 1/sqrt (fp64 contexts have ONE d2 form — the fma-contracted one,
                                            as the oracle's fp64 evaluation — so there REFERENCE = FMA3 and REFERENCE_STRICT = STRICT) */ };
 enum { NBODY_SUM_SEQ = 0,          /* one accumulator per segment, sources ascending (S/top_level.vhd:233-254) */

@@ -43,7 +43,9 @@ __device__ __forceinline__ float inv_dist(float dx, float dy, float dz, float ep
   else return __builtin_amdgcn_rsqf(d2);             // 1 ulp; d2 >= eps is never subnormal
 }
 // fp64 (one d2 form, as the force's pair_f64): the v_rsq_f64 seed y refined to full precision by one third-order step,
-// with e = 1 - d2 y^2:  d2^(-1/2) = y (1 - e)^(-1/2) = y + y e (1/2 + 3/8 e) + O(e^3);  strict: IEEE sqrt and divide
+// with e = 1 - d2 y^2:  d2^(-1/2) = y (1 - e)^(-1/2) = y + y e (1/2 + 3/8 e) + O(e^3);  strict: IEEE sqrt and divide.
+// A square that overflows gives d2 = +inf and y = +0, where e = fma(-inf, 0, 1) is NaN: the seed itself is the answer then (+0, as
+// the strict form and v_rsq_f32 give).  y == 0 for no finite d2 (d2 >= eps) and not for a NaN d2, which stays NaN.
 template <int ARITH>
 __device__ __forceinline__ double inv_dist(double dx, double dy, double dz, double eps) {
   const double d2 = __builtin_fma(dx, dx, __builtin_fma(dy, dy, __builtin_fma(dz, dz, eps)));
@@ -52,7 +54,8 @@ __device__ __forceinline__ double inv_dist(double dx, double dy, double dz, doub
   } else {
     const double y = __builtin_amdgcn_rsq(d2);
     const double e = __builtin_fma(-d2, y * y, 1.0);
-    return __builtin_fma(y * e, __builtin_fma(e, 0.375, 0.5), y);
+    const double r = __builtin_fma(y * e, __builtin_fma(e, 0.375, 0.5), y);
+    return y == 0.0 ? y : r;
   }
 }
 

@@ -76,18 +76,23 @@ def make_skip(n, m, on):
     return sk
 
 
-def numpy_field(pos, points, skip=None):
-    """the definition in plain numpy fp64: sums over all j (skip left out), no stated order"""
+def numpy_field(pos, points, skip=None, mags=False):
+    """the definition in plain numpy fp64: sums over all j (skip left out, whatever it holds), no stated order.  mags: also the sums
+    of the magnitudes of the acceleration's terms, (m, 3) — the scale an error of a sum that cancels is measured against"""
     p, x = pos[:, :3].astype(np.float64), points[:, :3].astype(np.float64)
-    acc, phi = np.zeros((len(x), 4)), np.zeros(len(x))
-    for k in range(len(x)):
-        d = p - x[k]
-        inv = 1.0 / np.sqrt((d * d).sum(1) + EPS)
-        if skip is not None and skip[k] >= 0:
-            inv[skip[k]] = 0.0
-        acc[k, :3] = (d * (inv ** 3)[:, None]).sum(0)
-        phi[k] = -inv.sum()
-    return acc, phi
+    acc, phi, mag = np.zeros((len(x), 4)), np.zeros(len(x)), np.zeros((len(x), 3))
+    with np.errstate(all="ignore"):
+        for k in range(len(x)):
+            d = p - x[k]
+            inv = 1.0 / np.sqrt((d * d).sum(1) + EPS)
+            term = d * (inv ** 3)[:, None]
+            if skip is not None and skip[k] >= 0:
+                inv[skip[k]] = 0.0
+                term[skip[k]] = 0.0
+            acc[k, :3] = term.sum(0)
+            mag[k] = np.abs(term).sum(0)
+            phi[k] = -inv.sum()
+    return (acc, phi, mag) if mags else (acc, phi)
 
 
 def row_rel(got, want):

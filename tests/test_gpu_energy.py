@@ -1,7 +1,7 @@
 """Energy, momentum and per-body potential of the state on the device (nbody_energy, nbody_potential_rows(_d); include/nbody.h
 "energy and potential"): phi_i bit for bit against tests/potential_ref.c in the strict modes, within the north_star tolerance in the
 timed arithmetic, the same bits however the context is configured or sharded, totals against an fp64 evaluation of the downloaded
-state, no effect on the step, the physics of a circular orbit, the mailbox guard and the C host program's --energy lines."""
+state and bit for bit against the header's summation order, all of it on the hostile system of specials_common.py too, no effect on the step, the physics of a circular orbit, the mailbox guard and the C host program's --energy lines."""
 import ctypes as C
 import os
 import re
@@ -12,6 +12,9 @@ import textwrap
 
 import numpy as np
 import pytest
+
+from field_common import numpy_field
+from specials_common import SIZES, VARIANTS, hostile_system, near, same_nan, within
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,6 +39,21 @@ class Ref:
         nr = len(pos) - r0 if nr is None else nr
         out = np.empty(nr, np.float64)
         self.lib.potential_f64(pos.ctypes.data_as(C.c_void_p), len(pos), r0, nr, out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def totals(self, pos, vel, slices, ref=False):
+        """{T, U, Px, Py, Pz, Lx, Ly, Lz} in the header's order; slices: the ranks' (first, count)"""
+        sl = np.ascontiguousarray(slices, np.int32).reshape(-1, 2)
+        out = np.empty(8, np.float64)
+        if pos.dtype == np.float32:
+            pos, vel = np.ascontiguousarray(pos, np.float32), np.ascontiguousarray(vel, np.float32)
+            rc = self.lib.energy_totals_f32(pos.ctypes.data_as(C.c_void_p), vel.ctypes.data_as(C.c_void_p), len(pos),
+                                            sl.ctypes.data_as(C.c_void_p), len(sl), int(ref), out.ctypes.data_as(C.c_void_p))
+        else:
+            pos, vel = np.ascontiguousarray(pos, np.float64), np.ascontiguousarray(vel, np.float64)
+            rc = self.lib.energy_totals_f64(pos.ctypes.data_as(C.c_void_p), vel.ctypes.data_as(C.c_void_p), len(pos),
+                                            sl.ctypes.data_as(C.c_void_p), len(sl), out.ctypes.data_as(C.c_void_p))
+        assert rc == 0
         return out
 
 
@@ -328,3 +346,96 @@ def test_c_host_program_energy_lines(nb):
         e, t, u = (float(x) for x in line[1:])
         for got, ref_ in ((e, w["total"]), (t, w["kinetic"]), (u, w["potential"])):
             assert abs(got - ref_) <= 1e-6 * abs(ref_), (line, w)
+
+
+# ---- the hostile system (specials_common.py): what a uniform cloud never shows the pass ----
+
+def planted_ranges(n):
+    """the whole system and sub-ranges that start and end on the planted rows"""
+    r = [(0, n), (10, 2), (11, 12), (22, 2), (40, 2), (41, 23), (63, 2), (64, 1), (n - 1, 1), (n - 7, 7)]
+    if n > 1028:
+        r += [(1023, 1), (1023, 2), (1024, 5), (1020, 9), (1024, n - 1024), (1028, n - 1028)]
+    return r
+
+
+def strict_phi(ref, pos, r0, nr, reference=False):
+    return ref.phi64(pos, r0, nr) if pos.dtype == np.float64 else ref.phi32(pos, r0, nr, ref=reference)
+
+
+@pytest.mark.parametrize("arith", ["strict", "reference_strict", "fp64_strict"])
+def test_hostile_system_rows_strict_bit_for_bit(nb, ref, arith):
+    fp64 = arith == "fp64_strict"
+    dtype = np.float64 if fp64 else np.float32
+    mode = nb.ARITH_REFERENCE_STRICT if arith == "reference_strict" else nb.ARITH_STRICT
+    for n in SIZES:
+        with nb.NBody(n, fp64=fp64) as eng:
+            eng.set_option(nb.OPT_ARITH, mode)
+            for variant in VARIANTS:
+                pos, vel, far = hostile_system(nb, n, dtype, variant)
+                eng.upload(pos, vel)
+                want = strict_phi(ref, pos, 0, n, mode == nb.ARITH_REFERENCE_STRICT)
+                if variant == "nan":
+                    assert np.all(np.isnan(want))
+                else:
+                    assert np.all(np.isfinite(want))       # an overflowing square and an infinity are +0 in a sum of 1/sqrt
+                for r0, nr in planted_ranges(n):
+                    got = eng.potential_rows(r0, nr)
+                    assert same_nan(got, want[r0:r0 + nr]), (n, variant, r0, nr, r0 + np.flatnonzero(got != want[r0:r0 + nr])[:8])
+
+
+@pytest.mark.parametrize("fp64", [False, True])
+def test_hostile_system_rows_timed_arithmetic(nb, ref, fp64):
+    """The timed arithmetic on the hostile system: (a) phi_i and the eight totals finite exactly where the strict references are, in
+    every variant; (c) on the near rows (every |coordinate| <= 2, not a far-away body) |phi - phi64| <= TOL |phi64| against the plain
+    numpy binary64 evaluation, TOL = 1e-5 (binary32, the north_star tolerance) or 1e-12 (binary64, test_fp64_rows' bar).  The strict
+    references sit at <= 1.6e-6 and <= 2.8e-15 in that measure (tests/test_specials_reference.py, which requires 3e-6 and 1e-13).
+    Measured on an MI355X, worst over sizes and variants: binary32 1.5e-6, binary64 2.8e-15."""
+    dtype = np.float64 if fp64 else np.float32
+    tol = 1e-12 if fp64 else 1e-5
+    for n in SIZES:
+        rows_skip = np.arange(n, dtype=np.int32)
+        with nb.NBody(n, fp64=fp64) as eng:
+            for variant in VARIANTS:
+                pos, vel, far = hostile_system(nb, n, dtype, variant)
+                eng.upload(pos, vel)
+                keep = near(pos, far)
+                p64 = numpy_field(pos, pos, rows_skip)[1]
+                for mode in (nb.ARITH_FMA3,) if fp64 else (nb.ARITH_FMA3, nb.ARITH_REFERENCE):
+                    eng.set_option(nb.OPT_ARITH, mode)
+                    want = strict_phi(ref, pos, 0, n, mode == nb.ARITH_REFERENCE)
+                    got = eng.potential_rows(0, n)
+                    assert np.array_equal(np.isfinite(got), np.isfinite(want)), (n, variant, mode, np.flatnonzero(np.isfinite(got) != np.isfinite(want))[:8])
+                    with np.errstate(all="ignore"):
+                        print("timed %s n=%d %s arith %d: phi %.3e on %d near rows" % (np.dtype(dtype).name, n, variant, mode,
+                              np.nanmax(np.abs(got[keep] - p64[keep]) / np.abs(p64[keep]), initial=0.0), keep.sum()))
+                    assert within(got[keep], p64[keep], tol * np.abs(p64[keep])), (n, variant, mode)
+                    for r0, nr in planted_ranges(n):
+                        assert same_nan(eng.potential_rows(r0, nr), got[r0:r0 + nr]), (n, variant, mode, r0, nr)
+                    e = bits(eng.energy()).view(np.float64)
+                    w = ref.totals(pos, vel, [(0, n)], ref=(mode == nb.ARITH_REFERENCE))
+                    assert np.array_equal(np.isfinite(e), np.isfinite(w)), (n, variant, mode, e, w)
+                eng.set_option(nb.OPT_ARITH, nb.ARITH_FMA3)
+
+
+@pytest.mark.parametrize("ngpus", [1, 3])
+@pytest.mark.parametrize("arith", ["strict", "reference_strict", "fp64_strict"])
+def test_totals_bit_for_bit_in_the_documented_order(nb, ref, arith, ngpus, monkeypatch):
+    """T, U, P, L in the order include/nbody.h fixes — a rank's rows in groups of 256 from its first body, ascending rows, groups
+    ascending, T and U halved, ranks in rank order — restated by tests/potential_ref.c energy_totals_*: the eight values bit for bit
+    (NaN for NaN in the "nan" variant) on one device and on three, whose slices are mini_nbody_amd/sharding.py's."""
+    from mini_nbody_amd.sharding import slice_bounds
+    monkeypatch.setenv("NBODY_OVERSUBSCRIBE", "1")
+    fp64 = arith == "fp64_strict"
+    dtype = np.float64 if fp64 else np.float32
+    mode = nb.ARITH_REFERENCE_STRICT if arith == "reference_strict" else nb.ARITH_STRICT
+    for n in SIZES + (3000,):
+        slices = [(f0, f1 - f0) for f0, f1 in (slice_bounds(q, n, ngpus) for q in range(ngpus))]
+        with nb.NBody(n, fp64=fp64, ngpus=ngpus) as eng:
+            eng.set_option(nb.OPT_ARITH, mode)
+            systems = [("cloud",) + nb.make_bodies(n, dtype=dtype)] if n == 3000 else [(v,) + hostile_system(nb, n, dtype, v)[:2] for v in VARIANTS]
+            for variant, pos, vel in systems:
+                eng.upload(pos, vel)
+                got = bits(eng.energy()).view(np.float64)
+                want = ref.totals(pos, vel, slices, ref=(mode == nb.ARITH_REFERENCE_STRICT))
+                assert same_nan(got, want), (n, variant, ngpus, got, want)
+                assert np.isnan(want).sum() == (6 if variant == "nan" else 0), (n, variant, want)   # all but Px, Py

@@ -1,6 +1,8 @@
 """Acceleration and potential at arbitrary points (nbody_field(_d); include/nbody.h "field at arbitrary points"): bit for bit against
 tests/field_ref.c in the strict modes, within the project's tolerances in the timed arithmetic, phi with the point's own body skipped
-equal to nbody_potential_rows in EVERY arithmetic, the same bits however the work is laid out (source split, batches, sub-ranges,
+equal to nbody_potential_rows in EVERY arithmetic, all of it again on the hostile system of specials_common.py (coincident bodies on
+the window and block edges, underflow, overflow, subnormal cubes, signed zeros, infinity, NaN, skip indices on every loop edge), the
+same bits however the work is laid out (source split, batches, sub-ranges,
 force configuration, device and process count), no effect on the step, the force as the gradient of the potential, the guards and the
 C host program's --field line."""
 import ctypes as C
@@ -14,7 +16,8 @@ import textwrap
 import numpy as np
 import pytest
 
-from field_common import FieldRef, compile_ref, make_points, make_skip, row_rel
+from field_common import FieldRef, compile_ref, make_points, make_skip, numpy_field, row_rel
+from specials_common import POINT_COUNTS, SIZES, VARIANTS, hostile_points, hostile_system, nan_row, near, same_nan, special_row, within
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -384,3 +387,107 @@ def test_c_host_program_field_line(nb):
     got = [float(v) for v in lines[0][1:]]
     for g_, w in zip(got, want):
         assert abs(g_ - w) <= 1e-12 * abs(w), (got, want)
+
+
+# ---- the hostile system (specials_common.py): what a uniform cloud never shows the pass ----
+
+def bits_of(a):
+    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
+
+
+def check_specials_directly(a, p, pts, skip, n, variant, what, planted=0):
+    """What include/nbody.h promises without any reference: a skipped body leaves no trace ("for j == skip[p] all four keep their
+    values"), so a finite point that skips the NaN, inf or overflow body has a finite field (planted: how many such points there must
+    be); and a NaN body poisons every point that does not skip it."""
+    special = special_row(n, variant)
+    sk = np.full(len(pts), -1, np.int32) if skip is None else skip
+    if special is not None:
+        clean = near(pts) & (sk == special)
+        assert clean.sum() >= planted, what
+        for out in (a[:, :3] if a is not None else None, p):
+            assert out is None or np.all(np.isfinite(out[clean])), what
+    if variant == "nan":
+        dirty = sk != nan_row(n)
+        for out in (a[:, :3] if a is not None else None, p):
+            assert out is None or np.all(np.isnan(out[dirty])), what
+
+
+@pytest.mark.parametrize("arith", ["strict", "reference_strict", "fp64_strict"])
+def test_hostile_system_strict_bit_for_bit(nb, ref, arith, monkeypatch):
+    """every variant, size and point count, with and without skip, both outputs and each alone, the one-launch form and the scratch +
+    combine form (NBODY_FIELD_SPLIT unset, 1, 2, 3): bit for bit tests/field_ref.c, whose `continue` on j == skip is the definition"""
+    fp64 = arith == "fp64_strict"
+    dtype = np.float64 if fp64 else np.float32
+    mode = nb.ARITH_REFERENCE_STRICT if arith == "reference_strict" else nb.ARITH_STRICT
+    for n in SIZES:
+        with nb.NBody(n, fp64=fp64) as eng:
+            eng.set_option(nb.OPT_ARITH, mode)
+            for variant in VARIANTS:
+                pos, vel, far = hostile_system(nb, n, dtype, variant)
+                eng.upload(pos, vel)
+                for m in POINT_COUNTS:
+                    pts, hsk = hostile_points(nb, pos, m, variant)
+                    for skip in (None, hsk):
+                        wa, wp = ref.f64(pos, pts, skip) if fp64 else ref.f32(pos, pts, skip, ref=(mode == nb.ARITH_REFERENCE_STRICT))
+                        what = (n, variant, m, skip is not None)
+                        planted = 2 if skip is not None and m >= 65 else 0
+                        check_specials_directly(wa, wp, pts, skip, n, variant, what, planted)     # the reference itself keeps the promise
+                        for split in (None, "1", "2", "3"):
+                            if split is None:
+                                monkeypatch.delenv("NBODY_FIELD_SPLIT", raising=False)
+                            else:
+                                monkeypatch.setenv("NBODY_FIELD_SPLIT", split)
+                            a, p = eng.field(pts, skip)
+                            assert same_nan(a, wa), what + (split, np.flatnonzero((bits_of(a) != bits_of(wa)).any(1))[:8])
+                            assert same_nan(p, wp), what + (split, np.flatnonzero(bits_of(p) != bits_of(wp))[:8])
+                            assert np.all(bits_of(a[:, 3]) == 0)
+                            check_specials_directly(a, p, pts, skip, n, variant, what + (split,), planted)
+                            a1, none = eng.field(pts, skip, potential=False)
+                            assert none is None and same_nan(a1, wa), what + (split,)
+                            none, p1 = eng.field(pts, skip, accel=False)
+                            assert none is None and same_nan(p1, wp), what + (split,)
+
+
+@pytest.mark.parametrize("fp64", [False, True])
+def test_hostile_system_timed_arithmetic(nb, ref, fp64):
+    """The timed arithmetic (v_rsq_f32; the v_rsq_f64 seed + one third-order step) on the hostile system:
+    (a) finite exactly where the strict reference is finite, in every variant — rows, points, with and without skip;
+    (b) phi of points = pos, skip = arange(n) is potential_rows(0, n), NaN for NaN and bit for bit elsewhere, in every arithmetic;
+    (c) on the near rows and points (every |coordinate| <= 2, not a far-away body): |a - a64| <= TOL sum_j |term_j| per component and
+        |phi - phi64| <= TOL |phi64| against the plain numpy binary64 evaluation, TOL = 1e-5 (binary32) or 1e-12 (binary64).
+    The far-away rows are held to (a) and (b) only: there the strict binary32 arithmetic is itself tens of percent off binary64 (a cube
+    of one or two bits).  The strict references sit at <= 1.6e-6 (binary32) and <= 4.7e-15 (binary64) in the measure of (c), worst over
+    sizes and variants (tests/test_specials_reference.py, which requires 3e-6 and 1e-13).  Measured on an MI355X, worst over sizes,
+    variants and point sets: binary32 accel 1.6e-6, phi 1.6e-6; binary64 accel 4.7e-15, phi 2.8e-15."""
+    dtype = np.float64 if fp64 else np.float32
+    tol = 1e-12 if fp64 else TOL
+    modes = (nb.ARITH_FMA3, nb.ARITH_STRICT) if fp64 else (nb.ARITH_FMA3, nb.ARITH_REFERENCE, nb.ARITH_STRICT, nb.ARITH_REFERENCE_STRICT)
+    for n in SIZES:
+        rows_skip = np.arange(n, dtype=np.int32)
+        with nb.NBody(n, fp64=fp64) as eng:
+            for variant in VARIANTS:
+                pos, vel, far = hostile_system(nb, n, dtype, variant)
+                eng.upload(pos, vel)
+                for mode in modes:                                                   # (b)
+                    eng.set_option(nb.OPT_ARITH, mode)
+                    a, p = eng.field(pos, rows_skip)
+                    assert same_nan(p, eng.potential_rows(0, n)), (n, variant, mode)
+                pts, hsk = hostile_points(nb, pos, 300, variant)
+                for x, skip, keep in ((pos, rows_skip, near(pos, far)), (pts, hsk, near(pts)), (pts, None, near(pts))):
+                    a64, p64, mag = numpy_field(pos, x, skip, mags=True)
+                    for mode in (nb.ARITH_FMA3,) if fp64 else (nb.ARITH_FMA3, nb.ARITH_REFERENCE):
+                        eng.set_option(nb.OPT_ARITH, mode)
+                        what = (n, variant, mode, len(x), skip is not None)
+                        wa, wp = ref.f64(pos, x, skip) if fp64 else ref.f32(pos, x, skip, ref=(mode == nb.ARITH_REFERENCE))
+                        a, p = eng.field(x, skip)
+                        assert np.array_equal(np.isfinite(a), np.isfinite(wa)), what + (np.flatnonzero((np.isfinite(a) != np.isfinite(wa)).any(1))[:8],)   # (a)
+                        assert np.array_equal(np.isfinite(p), np.isfinite(wp)), what + (np.flatnonzero(np.isfinite(p) != np.isfinite(wp))[:8],)
+                        check_specials_directly(a, p, x, skip, n, variant, what, 2 if x is pts and skip is not None else 0)
+                        with np.errstate(all="ignore"):                              # (c)
+                            ea = np.nanmax(np.abs(a[keep, :3] - a64[keep, :3]) / mag[keep], initial=0.0)
+                            ep = np.nanmax(np.abs(p[keep] - p64[keep]) / np.abs(p64[keep]), initial=0.0)
+                        print("timed %s n=%d %s arith %d, %d of %d near, skip=%s: accel %.3e phi %.3e"
+                              % (np.dtype(dtype).name, n, variant, mode, keep.sum(), len(x), skip is not None, ea, ep))
+                        assert within(a[keep, :3], a64[keep, :3], tol * mag[keep]), what
+                        assert within(p[keep], p64[keep], tol * np.abs(p64[keep])), what
+                eng.set_option(nb.OPT_ARITH, nb.ARITH_FMA3)

@@ -14,7 +14,8 @@ all: lib host oracle microbench
 # The library = ONE device code object (device.hip: the force path's kernels.hip — the nbk kernels + the launch functions that pick an
 # instantiation, ~45 s of hipcc — the energy pass's energy.hip, the field pass's field.hip, the neighbour pass's neighbors.hip, the k-nearest-neighbour pass's knn.hip and the friends-of-friends pass's fof.hip) and eight
 # host-only C++ files (context, comm, mailbox, energy, field, neighbors, knn, fof: seconds each) behind csrc/nbody_internal.hpp.  A host-side edit relinks in seconds.
-# The five diagnostic passes share csrc/diag_pass.hpp (device code and the sizes their hosts read) and csrc/query_pass.hpp (host only).
+# The five diagnostic passes share csrc/diag_pass.hpp (device code — the distance passes' pair distance and query preamble included — the sizes
+# their hosts read and the guard of a split launch) and csrc/query_pass.hpp (host only: the flow of a call and the distance passes' split rule).
 HOSTFLAGS := -O2 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function
 OBJ      := build/obj
 KERNEL_SRC := $(CSRC)/kernels.hip $(CSRC)/nbody_kernels.hpp $(CSRC)/nbody_args.hpp $(CSRC)/force_loop_gfx950.inc
@@ -22,7 +23,7 @@ HOST_HDR := $(CSRC)/nbody_internal.hpp $(CSRC)/nbody_args.hpp $(CSRC)/query_pass
 HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o $(OBJ)/energy.o $(OBJ)/field.o $(OBJ)/neighbors.o $(OBJ)/knn.o $(OBJ)/fof.o
 # the energy diagnostics' device code (energy.hip, seconds of hipcc on its own) reads nbody_args.hpp and changes nothing of the force path's
 # hashed source (KERNEL_SRC); device.hip compiles it with kernels.hip into the library's one code object.  Its host side is energy.cpp, one
-# of HOST_OBJ.  What it shares with the three passes below is diag_pass.hpp, which is no part of the hashed source either.
+# of HOST_OBJ.  What it shares with the four passes below is diag_pass.hpp, which is no part of the hashed source either.
 ENERGY_SRC := $(CSRC)/energy.hip $(CSRC)/energy_args.hpp
 # the field pass (acceleration and potential at arbitrary points) in the same way: field.hip beside energy.hip, field.cpp one of HOST_OBJ
 FIELD_SRC := $(CSRC)/field.hip $(CSRC)/field_args.hpp

@@ -1,7 +1,9 @@
 // diag_pass.hpp — what the diagnostic passes (energy, field, neighbours, k nearest neighbours, friends-of-friends) share, stated once: the two launch constants their hosts and
-// kernels agree on and, for device code, the pair arithmetic of the potential and the lane / wave preamble of a one-query-per-lane
-// kernel.  energy_args.hpp, field_args.hpp, neighbors_args.hpp, knn_args.hpp and fof_args.hpp include it.  Like them it stays apart from the force path's hashed
-// source (nbody_args.hpp, nbody_kernels.hpp, kernels.hip, force_loop_gfx950.inc), of which it reads nbody_args.hpp (kSoftBits) only.
+// kernels agree on and the guard of a launch over split sources; for device code, the pair arithmetic of the potential, the plain
+// squared distance of the three distance passes (neighbours, k nearest neighbours, friends-of-friends) and the preamble of a
+// one-query-per-lane kernel: the lane, the wave's skip window, the chunk's sources.
+// energy_args.hpp, field_args.hpp, neighbors_args.hpp, knn_args.hpp and fof_args.hpp include it.  Like them it stays apart from the force path's hashed
+// source (nbody_args.hpp, nbody_kernels.hpp, kernels.hip, force_loop_gfx950.inc), of which it reads nbody_args.hpp (kSoftBits, NB_CONST) only.
 // The kernels' loops are different computations and stay in their files.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -10,6 +12,17 @@ namespace nbd {
 
 constexpr int kSrcBlock = 1024;   // sources per block: a level-1 sum of the potential and the field, the unit of a split launch's chunks
 constexpr int kLanes = 256;       // lanes per workgroup, one row, point or query each
+
+// What a launch over split sources refuses, for any argument block with the geometry members m, first, n_src, n_blocks, chunk_blocks,
+// chunks and scratch: no query, chunks that need scratch and have none, chunks that do not cover the blocks, an empty last chunk, and
+// (indexed_by_first: query p is source first + p) a window outside the sources.  Every host split rule normalises to "no empty
+// chunk" (query_pass.hpp), so none of this is reachable through include/nbody.h: it guards the launch functions themselves.
+template <class A>
+inline bool bad_source_split(const A& a, bool indexed_by_first) {
+  if (a.m <= 0 || a.chunks < 1 || a.chunk_blocks < 1 || (a.chunks > 1 && !a.scratch)) return true;
+  if ((long long)a.chunks * a.chunk_blocks < a.n_blocks || (long long)(a.chunks - 1) * a.chunk_blocks >= a.n_blocks) return true;
+  return indexed_by_first && (a.first < 0 || a.first > a.n_src - a.m);
+}
 
 }  // namespace nbd
 
@@ -22,6 +35,14 @@ constexpr int kRef = 1, kStrict = 2;   // bits of NBODY_ARITH_*: the reference's
 
 __device__ __forceinline__ float fma_of(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fma_of(double a, double b, double c) { return __builtin_fma(a, b, c); }
+// the IEEE minimum of b and a d2 (a NaN d2 gives b): one v_min (two pairs in one v_min3, fp32); both operands are results of
+// arithmetic, so nothing is re-quieted
+__device__ __forceinline__ float min_of(float b, float d2) { return __builtin_fminf(b, d2); }
+__device__ __forceinline__ double min_of(double b, double d2) { return __builtin_fmin(b, d2); }
+template <typename T>
+__device__ __forceinline__ T inf_of() { return (T)__builtin_huge_valf(); }
+template <typename T>
+__device__ __forceinline__ T nan_of() { return (T)__builtin_nanf(""); }
 
 template <typename T>
 __device__ __forceinline__ T soft() { return (T)__builtin_bit_cast(float, nbk::kSoftBits); }   // the force's eps (S/dzsoft.vhd:177)
@@ -59,6 +80,21 @@ __device__ __forceinline__ double inv_dist(double dx, double dy, double dz, doub
   }
 }
 
+// THE statement of the plain squared distance of a pair, the distance passes' d2: 3 sub, 1 mul, 2 fma.  No softening, one form per
+// precision whatever NBODY_OPT_ARITH says, every operation IEEE-exact (their files are compiled with contraction off).
+template <typename T, typename V4>
+__device__ __forceinline__ T plain_d2(const V4 p, const V4 me) {
+  const T dx = p.x - me.x, dy = p.y - me.y, dz = p.z - me.z;
+  return fma_of(dx, dx, fma_of(dy, dy, dz * dz));
+}
+// CMP: the excluded body's (j == sk) d2 becomes a quiet NaN, which is below nothing: neither chosen, counted nor listed
+template <bool CMP, typename T, typename V4>
+__device__ __forceinline__ T plain_d2(const V4 p, const V4 me, int j, int sk) {
+  const T d2 = plain_d2<T, V4>(p, me);
+  if (CMP) return j == sk ? nan_of<T>() : d2;
+  return d2;
+}
+
 // One query per lane, kLanes per workgroup: query p of the launch's m.  Lanes beyond m stay in the wave-uniform loops clamped to the
 // last query (pc) and store nothing (live).
 struct Lane { int p; bool live; int pc; };
@@ -69,16 +105,22 @@ __device__ __forceinline__ Lane lane_of(int m) {
 }
 
 // [lo, hi]: the lowest and highest excluded source index (sk; < 0: none) among the wave's 64 lanes, wave-uniform — only the aligned
-// 64-source windows that overlap it have to compare j with sk.  [kNoSkipLo, -1], which no window overlaps, when no lane excludes anything.
+// 64-source windows that overlap it have to compare j with sk.  [kNoSkipLo, -1], which no window overlaps, when no lane excludes
+// anything, and without a look at the lanes in a kernel's SKIP = false form (whose sk is -1).
 constexpr int kNoSkipLo = 0x7fffffff;
-struct SkipWindow { int lo, hi; };
+struct SkipWindow { int sk, lo, hi; };
+template <bool SKIP>
 __device__ __forceinline__ SkipWindow wave_skip_window(int sk) {
-  int lo = sk < 0 ? kNoSkipLo : sk, hi = sk;
-  for (int off = 32; off > 0; off >>= 1) {
-    lo = min(lo, __shfl_xor(lo, off, 64));
-    hi = max(hi, __shfl_xor(hi, off, 64));
+  if constexpr (SKIP) {
+    int lo = sk < 0 ? kNoSkipLo : sk, hi = sk;
+    for (int off = 32; off > 0; off >>= 1) {
+      lo = min(lo, __shfl_xor(lo, off, 64));
+      hi = max(hi, __shfl_xor(hi, off, 64));
+    }
+    return {sk, __builtin_amdgcn_readfirstlane(lo), __builtin_amdgcn_readfirstlane(hi)};
+  } else {
+    return {-1, kNoSkipLo, -1};
   }
-  return {__builtin_amdgcn_readfirstlane(lo), __builtin_amdgcn_readfirstlane(hi)};
 }
 
 // blocks [b0, b1) of chunk blockIdx.y of a launch whose sources are split into chunks of chunk_blocks whole blocks
@@ -86,6 +128,29 @@ struct Blocks { int b0, b1; };
 __device__ __forceinline__ Blocks chunk_of(int chunk_blocks, int n_blocks) {
   const int b0 = (int)blockIdx.y * chunk_blocks;
   return {b0, min(b0 + chunk_blocks, n_blocks)};
+}
+// and its sources [s0, s1), for any argument block with n_src, n_blocks and chunk_blocks
+struct Sources { int s0, s1; };
+template <class A>
+__device__ __forceinline__ Sources chunk_sources(const A& a) {
+  const auto [b0, b1] = chunk_of(a.chunk_blocks, a.n_blocks);
+  return {b0 * kSrcBlock, min(b1 * kSrcBlock, a.n_src)};
+}
+// the sources (or their labels) for wave-uniform scalar loads: address space 4
+template <typename V>
+__device__ __forceinline__ const NB_CONST V* scalar_src(const void* p) { return (const NB_CONST V*)(uintptr_t)p; }
+
+// The preamble of a distance query (lane pc), for any argument block with src, points, skip, first, n_src, n_blocks and chunk_blocks:
+// the query point — points[pc], or in the rows form (a.points == null) source a.first + pc, which leaves itself out; SKIP: the
+// excluded index and the wave's window of them — the sources and the chunk's range of them.
+template <typename V4>
+struct Query { V4 me; int sk, wlo, whi; const NB_CONST V4* src; int s0, s1; };
+template <typename V4, bool SKIP, class A>
+__device__ __forceinline__ Query<V4> query_of(const A& a, int pc) {
+  const V4 me = a.points ? ((const V4*)a.points)[pc] : ((const V4*)a.src)[a.first + pc];
+  const auto [sk, wlo, whi] = wave_skip_window<SKIP>(!SKIP ? -1 : a.points ? a.skip[pc] : a.first + pc);
+  const auto [s0, s1] = chunk_sources(a);
+  return {me, sk, wlo, whi, scalar_src<V4>(a.src), s0, s1};
 }
 
 }  // namespace nbd

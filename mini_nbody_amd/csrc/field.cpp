@@ -15,11 +15,12 @@ namespace nbi {
 namespace {
 
 // The field pass's split: the scratch is per BLOCK, so its size per point does not depend on the number of chunks; the points whose
-// per-block sums fit the scratch bound go together, in whole workgroups, and the chunks are chosen anew for such a batch.
+// per-block sums fit the scratch bound go together, in whole workgroups, and the chunks are chosen anew for such a batch.  A different
+// rule from query_pass.hpp's chunk_split, and it reads its MB bound as an integer (env_ll) where that one takes fractions (atof).
 SplitPlan field_split(int cnt, int n_blocks, size_t es) {
   const long long forced = env_ll("NBODY_FIELD_SPLIT", 0);
   const long long bound = std::max<long long>(0, env_ll("NBODY_FIELD_SCRATCH_MB", 256)) << 20;
-  const long long fit = bound / (long long)field_scratch_bytes(1, (size_t)n_blocks, es) / kFieldPoints * kFieldPoints;
+  const long long fit = bound / (long long)field_scratch_bytes(1, (size_t)n_blocks, es) / nbd::kLanes * nbd::kLanes;
   int batch = cnt;
   if (choose_chunks(forced, cnt, n_blocks) > 1 && fit < cnt) batch = (int)fit;   // (fit < 256: batch = 0, no split)
   const int chunks = batch > 0 ? choose_chunks(forced, batch, n_blocks) : 1;

@@ -38,29 +38,24 @@ __device__ __forceinline__ void store_out(const FieldArgs& a, int p, double ax, 
   if (a.phi) ((T*)a.phi)[p] = (T)(0.0 - s);
 }
 
-// One point per lane, kFieldPoints points per workgroup; workgroup (x, y) walks the blocks of chunk y for the points of x.  Sources
+// One point per lane, kLanes points per workgroup; workgroup (x, y) walks the blocks of chunk y for the points of x.  Sources
 // arrive with wave-uniform scalar loads (address space 4, as energy_kernel).  Lanes beyond m stay in the wave-uniform loops clamped to
 // the last point and store nothing.  SKIP: only the aligned 64-source windows that overlap [lowest, highest] skip index of the wave's
 // 64 points compare j with skip (a wave-uniform branch); every other window, and every window of the SKIP = false form, is 3 sub,
 // 3 fma, 1 rsq, 2 mul, 3 fma and 1 add per pair.
 template <typename T, typename V4, int ARITH, bool SKIP>
-__global__ void __launch_bounds__(kFieldPoints) field_kernel(FieldArgs a) {
+__global__ void __launch_bounds__(kLanes) field_kernel(FieldArgs a) {
   const auto [p, live, pc] = lane_of(a.m);
   const V4 me = ((const V4*)a.points)[pc];
-  int sk = -1, wlo = kNoSkipLo, whi = -1;
-  if constexpr (SKIP) {
-    sk = a.skip[pc];
-    const SkipWindow win = wave_skip_window(sk);
-    wlo = win.lo; whi = win.hi;
-  }
+  const auto [sk, wlo, whi] = wave_skip_window<SKIP>(SKIP ? a.skip[pc] : -1);
   const T eps = soft<T>();
-  const NB_CONST V4* src = (const NB_CONST V4*)(uintptr_t)a.src;
+  const NB_CONST V4* src = scalar_src<V4>(a.src);
   T* sc = (T*)a.scratch;
   const auto [blk0, blk1] = chunk_of(a.chunk_blocks, a.n_blocks);
   double l2x = 0.0, l2y = 0.0, l2z = 0.0, l2s = 0.0;
   for (int blk = blk0; blk < blk1; ++blk) {
-    const int b0 = blk * kFieldBlock;
-    const int b1 = min(b0 + kFieldBlock, a.n_src);
+    const int b0 = blk * kSrcBlock;
+    const int b1 = min(b0 + kSrcBlock, a.n_src);
     Acc<T> c = {(T)0, (T)0, (T)0, (T)0};
     int j = b0;
     for (; j + 64 <= b1; j += 64) {
@@ -87,8 +82,8 @@ __global__ void __launch_bounds__(kFieldPoints) field_kernel(FieldArgs a) {
 
 // level 2 from the stored per-block sums: blocks ascending, fp64, one point per lane (a wave reads 64 consecutive values per word)
 template <typename T, typename V4>
-__global__ void __launch_bounds__(kFieldPoints) field_combine(FieldArgs a) {
-  const int p = (int)blockIdx.x * kFieldPoints + (int)threadIdx.x;
+__global__ void __launch_bounds__(kLanes) field_combine(FieldArgs a) {
+  const int p = (int)blockIdx.x * kLanes + (int)threadIdx.x;
   if (p >= a.m) return;
   const T* sc = (const T*)a.scratch;
   const size_t m = (size_t)a.m;
@@ -102,9 +97,9 @@ __global__ void __launch_bounds__(kFieldPoints) field_combine(FieldArgs a) {
 
 template <typename T, typename V4, int ARITH>
 void launch_field_one(hipStream_t st, int chunks, const FieldArgs& a) {
-  const dim3 grid((a.m + kFieldPoints - 1) / kFieldPoints, chunks);
-  if (a.skip) hipLaunchKernelGGL((field_kernel<T, V4, ARITH, true>), grid, dim3(kFieldPoints), 0, st, a);
-  else hipLaunchKernelGGL((field_kernel<T, V4, ARITH, false>), grid, dim3(kFieldPoints), 0, st, a);
+  const dim3 grid((a.m + kLanes - 1) / kLanes, chunks);
+  if (a.skip) hipLaunchKernelGGL((field_kernel<T, V4, ARITH, true>), grid, dim3(kLanes), 0, st, a);
+  else hipLaunchKernelGGL((field_kernel<T, V4, ARITH, false>), grid, dim3(kLanes), 0, st, a);
 }
 
 }  // namespace
@@ -129,9 +124,9 @@ NBF_HIDDEN int launch_field_kernel(int fp64, int arith, hipStream_t st, int chun
 
 NBF_HIDDEN int launch_field_combine_kernel(int fp64, hipStream_t st, const FieldArgs& a) {
   if (a.m <= 0 || !a.scratch) return (int)hipErrorInvalidValue;
-  const dim3 grid((a.m + kFieldPoints - 1) / kFieldPoints);
-  if (fp64) hipLaunchKernelGGL((field_combine<double, d4>), grid, dim3(kFieldPoints), 0, st, a);
-  else hipLaunchKernelGGL((field_combine<float, f4>), grid, dim3(kFieldPoints), 0, st, a);
+  const dim3 grid((a.m + kLanes - 1) / kLanes);
+  if (fp64) hipLaunchKernelGGL((field_combine<double, d4>), grid, dim3(kLanes), 0, st, a);
+  else hipLaunchKernelGGL((field_combine<float, f4>), grid, dim3(kLanes), 0, st, a);
   return (int)hipGetLastError();
 }
 

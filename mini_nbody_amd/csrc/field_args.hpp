@@ -2,7 +2,7 @@
 // functions of field.hip.  Like energy_args.hpp it stays apart from nbody_args.hpp, the force path's hashed kernel source.
 //
 // The order of every sum (include/nbody.h, "field at arbitrary points") is fixed by N alone and is the potential's:
-//   level 1  sources in blocks of kFieldBlock consecutive bodies; per block four accumulators from +0 in ascending j in the context
+//   level 1  sources in blocks of nbd::kSrcBlock consecutive bodies; per block four accumulators from +0 in ascending j in the context
 //            precision: ax = fma(dx, inv3, ax), ay, az likewise, s = s + inv; j == skip[p] leaves all four as they are;
 //   level 2  the blocks' four sums converted to fp64 and added in ascending block order from zero: accel = (T){A}, phi = (T)(0 - S).
 // Level 2 happens in registers when one workgroup walks every block of its points (grid.y = 1, scratch == null).  When the sources are
@@ -15,9 +15,6 @@
 
 namespace nbf {
 
-constexpr int kFieldBlock = nbd::kSrcBlock;   // sources per level-1 block (the potential's)
-constexpr int kFieldPoints = nbd::kLanes;     // points per workgroup, one per lane
-
 struct FieldArgs {
   const void* src;      // all N source words (16-B or 32-B {x, y, z, w}), ascending
   const void* points;   // [m] words {x, y, z, ignored} of this launch's points
@@ -28,7 +25,7 @@ struct FieldArgs {
                         // (b * 4 + q) * m + p, q = {ax, ay, az, s}, so that a wave's 64 stores of one (b, q) are contiguous
   int n_src;            // N
   int m;                // points of this launch
-  int n_blocks;         // ceil(N / kFieldBlock)
+  int n_blocks;         // ceil(N / nbd::kSrcBlock)
   int chunk_blocks;     // blocks per chunk: workgroup (x, y) walks blocks [y * chunk_blocks, min((y + 1) * chunk_blocks, n_blocks))
 };
 
@@ -39,7 +36,7 @@ inline size_t field_scratch_bytes(size_t m, size_t n_blocks, size_t elem) { retu
 
 namespace nbl {
 // both return a hipError_t as int (0 = launched).  arith: NBODY_ARITH_* (fp64 contexts: strict or not).
-// grid = (ceil(m / kFieldPoints), chunks); chunks > 1 needs a.scratch and is followed by launch_field_combine_kernel
+// grid = (ceil(m / nbd::kLanes), chunks); chunks > 1 needs a.scratch and is followed by launch_field_combine_kernel
 int launch_field_kernel(int fp64, int arith, hipStream_t stream, int chunks, const nbf::FieldArgs& a);
 // level 2 of every point of the launch from a.scratch: blocks ascending in fp64, then accel and phi
 int launch_field_combine_kernel(int fp64, hipStream_t stream, const nbf::FieldArgs& a);

@@ -25,23 +25,6 @@ namespace nbi {
 
 namespace {
 
-// The pass's split, as neighbors_split: the scratch is per CHUNK, so the chunks are chosen from the local's rows and normalised first;
-// the rows whose chunk minima fit the scratch bound then go together, in whole workgroups.
-SplitPlan fof_split(int cnt, int n_blocks) {
-  const long long forced = env_ll("NBODY_FOF_SPLIT", 0);
-  const char* mb = getenv("NBODY_FOF_SCRATCH_MB");
-  const double bound = std::max(0.0, mb && *mb ? atof(mb) : 256.0) * 1048576.0;
-  const int asked = choose_chunks(forced, cnt, n_blocks);
-  if (asked <= 1) return no_split(cnt, n_blocks);
-  const int chunk_blocks = (n_blocks + asked - 1) / asked;
-  const int chunks = (n_blocks + chunk_blocks - 1) / chunk_blocks;   // no empty chunk
-  const double fit = bound / (double)fof_scratch_bytes(1, (size_t)chunks);
-  int batch = cnt;
-  if (fit < (double)cnt) batch = (int)fit / kFoRows * kFoRows;
-  if (batch <= 0) return no_split(cnt, n_blocks);   // not one workgroup's rows fit
-  return {chunks, chunk_blocks, batch};
-}
-
 // One round's link pass on local L over r.cnt active rows — entries [r.first, r.first + r.cnt) of `active` (uploaded), or with
 // active == null the bodies of those indices themselves — against the labels `label` (uploaded), the m_i left in fo_min for the copy back
 int launch_fof(Local& L, const int* label, const int* active, const Range& r, double b2) {
@@ -55,23 +38,17 @@ int launch_fof(Local& L, const int* label, const int* active, const Range& r, do
   }
   NBC(L.fo_min.ensure((size_t)r.cnt * sizeof(int)));
   const int n_blocks = source_blocks();
-  const SplitPlan plan = fof_split(r.cnt, n_blocks);
+  const SplitPlan plan = chunk_split("NBODY_FOF_SPLIT", "NBODY_FOF_SCRATCH_MB", r.cnt, n_blocks, fof_scratch_bytes(1, 1));
   if (plan.chunks > 1) NBC(L.q_scratch.ensure(fof_scratch_bytes((size_t)plan.batch, (size_t)plan.chunks)));
   return for_batches(r.cnt, plan, [&](int b0, int m) {
     FofArgs a;
     memset(&a, 0, sizeof(a));
-    a.src = L.pos[L.cur];
+    fill_sources(a, L, plan, n_blocks, m, active ? 0 : r.first + b0);
     a.label = L.fo_label.as<int>();
     a.rows = active ? L.fo_rows.as<int>() + b0 : nullptr;
     a.out = L.fo_min.as<int>() + b0;
     a.scratch = plan.chunks > 1 ? L.q_scratch.as<int>() : nullptr;
     a.b2 = b2;
-    a.n_src = g.n;
-    a.m = m;
-    a.first = active ? 0 : r.first + b0;
-    a.n_blocks = n_blocks;
-    a.chunk_blocks = plan.chunk_blocks;
-    a.chunks = plan.chunks;
     HIPC((hipError_t)nbl::launch_fof_kernel(g.fp64, L.compute, a));
     if (plan.chunks > 1) HIPC((hipError_t)nbl::launch_fof_combine_kernel(L.compute, a));
     return NBODY_OK;

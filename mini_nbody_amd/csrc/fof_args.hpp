@@ -4,7 +4,7 @@
 //
 // One link pass (include/nbody.h, "friends-of-friends groups") gives every row i of the launch the lowest FOREIGN label among its
 // friends: m_i = min{ L[j] : d2_ij <= b2 and L[j] != L[i] }, kFoNone when there is none.  An integer minimum is exact, so no order has
-// to be defended: when the sources are split over grid.y chunks of whole kFoBlock-source blocks, every workgroup stores its chunk's
+// to be defended: when the sources are split over grid.y chunks of whole nbd::kSrcBlock-source blocks, every workgroup stores its chunk's
 // minimum and fof_combine takes the minimum over the chunks — the same values for every number of chunks.  The union-find that turns the
 // m_i into groups runs on the host (fof.cpp).
 #pragma once
@@ -14,9 +14,7 @@
 
 namespace nbg {
 
-constexpr int kFoBlock = nbd::kSrcBlock;   // sources per block: chunks are whole blocks
-constexpr int kFoRows = nbd::kLanes;       // rows per workgroup, one per lane
-constexpr int kFoNone = 0x7fffffff;        // INT_MAX: no friend with a foreign label
+constexpr int kFoNone = 0x7fffffff;   // INT_MAX: no friend with a foreign label
 
 struct FofArgs {
   const void* src;      // all N source words (16-B or 32-B {x, y, z, w}), ascending
@@ -29,7 +27,7 @@ struct FofArgs {
   int n_src;            // N
   int m;                // rows of this launch
   int first;            // rows == null: global index of row 0
-  int n_blocks;         // ceil(N / kFoBlock)
+  int n_blocks;         // ceil(N / nbd::kSrcBlock)
   int chunk_blocks;     // blocks per chunk: workgroup (x, y) walks blocks [y * chunk_blocks, min((y + 1) * chunk_blocks, n_blocks))
   int chunks;           // grid.y = ceil(n_blocks / chunk_blocks): no empty chunk
 };
@@ -40,7 +38,7 @@ inline size_t fof_scratch_bytes(size_t m, size_t chunks) { return m * chunks * s
 }  // namespace nbg
 
 namespace nbl {
-// both return a hipError_t as int (0 = launched).  grid = (ceil(m / kFoRows), a.chunks); a.chunks > 1 needs a.scratch and is followed by
+// both return a hipError_t as int (0 = launched; nbd::bad_source_split says what is refused).  grid = (ceil(m / nbd::kLanes), a.chunks); a.chunks > 1 is followed by
 // launch_fof_combine_kernel
 int launch_fof_kernel(int fp64, hipStream_t stream, const nbg::FofArgs& a);
 // every row of the launch from a.scratch: the minimum over the chunks into a.out

@@ -15,23 +15,6 @@ namespace {
 
 struct Want { bool idx, d2; int k; };
 
-// The pass's split, as neighbors_split: the scratch is per CHUNK, so the chunks are chosen from the local's queries and normalised
-// first; the queries whose chunk lists (k entries each) fit the scratch bound then go together, in whole workgroups.
-SplitPlan knn_split(int cnt, int n_blocks, int k, size_t es) {
-  const long long forced = env_ll("NBODY_KNN_SPLIT", 0);
-  const char* mb = getenv("NBODY_KNN_SCRATCH_MB");
-  const double bound = std::max(0.0, mb && *mb ? atof(mb) : 256.0) * 1048576.0;
-  const int asked = choose_chunks(forced, cnt, n_blocks);
-  if (asked <= 1) return no_split(cnt, n_blocks);
-  const int chunk_blocks = (n_blocks + asked - 1) / asked;
-  const int chunks = (n_blocks + chunk_blocks - 1) / chunk_blocks;   // no empty chunk
-  const double fit = bound / (double)knn_scratch_bytes(1, (size_t)chunks, (size_t)k, es);
-  int batch = cnt;
-  if (fit < (double)cnt) batch = (int)fit / kKnQueries * kKnQueries;
-  if (batch <= 0) return no_split(cnt, n_blocks);   // not one workgroup's queries fit
-  return {chunks, chunk_blocks, batch};
-}
-
 // r.cnt queries on local L — points [r.first, r.first + r.cnt) of the call (uploaded), or with points == null rows
 // [r.first, r.first + r.cnt) of L's slice — with the outputs left in kn_idx / kn_d2 ([r.cnt][k]) for the copy back
 int launch_knn(Local& L, const void* points, const int* skip, const Range& r, const Want& w) {
@@ -41,24 +24,18 @@ int launch_knn(Local& L, const void* points, const int* skip, const Range& r, co
   if (w.idx) NBC(L.kn_idx.ensure((size_t)r.cnt * k * sizeof(int)));
   if (w.d2) NBC(L.kn_d2.ensure((size_t)r.cnt * k * es));
   const int n_blocks = source_blocks();
-  const SplitPlan plan = knn_split(r.cnt, n_blocks, w.k, es);
+  const SplitPlan plan = chunk_split("NBODY_KNN_SPLIT", "NBODY_KNN_SCRATCH_MB", r.cnt, n_blocks, knn_scratch_bytes(1, 1, k, es));
   if (plan.chunks > 1) NBC(L.q_scratch.ensure(knn_scratch_bytes((size_t)plan.batch, (size_t)plan.chunks, k, es)));
   return for_batches(r.cnt, plan, [&](int b0, int m) {
     KnnArgs a;
     memset(&a, 0, sizeof(a));
-    a.src = L.pos[L.cur];
+    fill_sources(a, L, plan, n_blocks, m, points ? 0 : L.first + r.first + b0);
     a.points = points ? L.q_points.as<char>() + (size_t)b0 * wb : nullptr;
     a.skip = points && skip ? L.q_skip.as<int>() + b0 : nullptr;
     a.idx = w.idx ? L.kn_idx.as<int>() + (size_t)b0 * k : nullptr;
     a.d2 = w.d2 ? L.kn_d2.as<char>() + (size_t)b0 * k * es : nullptr;
     a.scratch = plan.chunks > 1 ? L.q_scratch.as<void>() : nullptr;
-    a.n_src = g.n;
-    a.m = m;
     a.k = w.k;
-    a.first = points ? 0 : L.first + r.first + b0;
-    a.n_blocks = n_blocks;
-    a.chunk_blocks = plan.chunk_blocks;
-    a.chunks = plan.chunks;
     HIPC((hipError_t)nbl::launch_knn_kernel(g.fp64, L.compute, a));
     if (plan.chunks > 1) HIPC((hipError_t)nbl::launch_knn_combine_kernel(g.fp64, L.compute, a));
     return NBODY_OK;

@@ -1,9 +1,8 @@
 // knn.hip — the k-nearest-neighbour pass's device code: per query the first k of the N bodies on the device in ascending (d2, j) order
 // (knn_args.hpp states the rule, include/nbody.h the definition) and the combine of a split launch.  Compiles on its own; device.hip
 // puts it into the library's one code object after neighbors.hip.  Reads diag_pass.hpp and nbody_args.hpp (f4, d4, NB_CONST) and
-// nothing else of the force path.  d2 is the neighbour pass's: the plain squared distance fma(dx, dx, fma(dy, dy, dz * dz)), no
-// softening, one form per precision whatever NBODY_OPT_ARITH says, every operation IEEE-exact (the file is compiled with contraction
-// off).  No atomics, no LDS.  gfx950 only.
+// nothing else of the force path.  d2 is the neighbour pass's: diag_pass.hpp's plain_d2, the plain squared distance; the file is
+// compiled with contraction off.  No atomics, no LDS.  gfx950 only.
 #include <hip/hip_runtime.h>
 
 #include "../../include/nbody.h"
@@ -20,23 +19,6 @@ static_assert(kKnMax == NBODY_KNN_MAX, "the header's limit is the largest list c
 
 namespace {
 
-// the IEEE minimum of b and a d2 (a NaN d2 gives b): one v_min
-__device__ __forceinline__ float knn_min(float b, float d2) { return __builtin_fminf(b, d2); }
-__device__ __forceinline__ double knn_min(double b, double d2) { return __builtin_fmin(b, d2); }
-template <typename T>
-__device__ __forceinline__ T knn_inf() { return (T)__builtin_huge_valf(); }
-template <typename T>
-__device__ __forceinline__ T knn_nan() { return (T)__builtin_nanf(""); }
-
-// d2 of one pair: 3 sub, 1 mul, 2 fma.  CMP: the excluded body's d2 becomes NaN, which is below nothing and so never listed
-template <bool CMP, typename T, typename V4>
-__device__ __forceinline__ T knn_d2(const V4 p, const V4 me, int j, int sk) {
-  const T dx = p.x - me.x, dy = p.y - me.y, dz = p.z - me.z;
-  const T d2 = fma_of(dx, dx, fma_of(dy, dy, dz * dz));
-  if (CMP) return j == sk ? knn_nan<T>() : d2;
-  return d2;
-}
-
 // What a lane carries: K (d2, idx) pairs in registers, ascending.  K is a compile-time capacity and every element index below is a
 // constant after unrolling: an array indexed at run time would go to scratch memory.  The k entries of the query are the LAST k slots;
 // the K - k slots before them hold (-inf, -1), which every candidate goes behind and which therefore never move.  So d[K - 1] is the
@@ -48,7 +30,7 @@ struct KList {
   __device__ __forceinline__ void init(int k) {
 #pragma unroll
     for (int s = 0; s < K; ++s) {
-      d[s] = s < K - k ? -knn_inf<T>() : knn_inf<T>();
+      d[s] = s < K - k ? -inf_of<T>() : inf_of<T>();
       i[s] = -1;
     }
   }
@@ -77,29 +59,19 @@ template <bool CMP, typename T, typename V4>
 __device__ __forceinline__ T knn_window_min(const NB_CONST V4* src, const V4 me, int j, int sk, T kth) {
   T wmin = kth;
 #pragma unroll 8
-  for (int k = 0; k < 64; ++k) wmin = knn_min(wmin, knn_d2<CMP, T, V4>(src[j + k], me, j + k, sk));
+  for (int k = 0; k < 64; ++k) wmin = min_of(wmin, plain_d2<CMP, T, V4>(src[j + k], me, j + k, sk));
   return wmin;
 }
 
-// One query per lane, kKnQueries queries per workgroup; workgroup (x, y) walks the blocks of chunk y for the queries of x.  Sources
+// One query per lane, kLanes queries per workgroup; workgroup (x, y) walks the blocks of chunk y for the queries of x.  Sources
 // arrive with wave-uniform scalar loads (address space 4, as neighbors_kernel).  Lanes beyond m stay in the wave-uniform loops clamped
 // to the last query and store nothing.  SKIP: the rows form (a.points == null: query p is source a.first + p and leaves itself out)
 // and the points form with a skip array; only the aligned 64-source windows that overlap [lowest, highest] excluded index of the
 // wave's 64 queries compare j with it.
 template <typename T, typename V4, bool SKIP, int K>
-__global__ void __launch_bounds__(kKnQueries) knn_kernel(KnnArgs a) {
+__global__ void __launch_bounds__(kLanes) knn_kernel(KnnArgs a) {
   const auto [p, live, pc] = lane_of(a.m);
-  const V4 me = a.points ? ((const V4*)a.points)[pc] : ((const V4*)a.src)[a.first + pc];
-  int sk = -1, wlo = kNoSkipLo, whi = -1;
-  if constexpr (SKIP) {
-    sk = a.points ? a.skip[pc] : a.first + pc;
-    const SkipWindow win = wave_skip_window(sk);
-    wlo = win.lo; whi = win.hi;
-  }
-  const NB_CONST V4* src = (const NB_CONST V4*)(uintptr_t)a.src;
-  const auto [blk0, blk1] = chunk_of(a.chunk_blocks, a.n_blocks);
-  const int s0 = blk0 * kKnBlock;
-  const int s1 = min(blk1 * kKnBlock, a.n_src);
+  const auto [me, sk, wlo, whi, src, s0, s1] = query_of<V4, SKIP>(a, pc);
   const int k = a.k;
   KList<T, K> c;
   c.init(k);
@@ -119,7 +91,7 @@ __global__ void __launch_bounds__(kKnQueries) knn_kernel(KnnArgs a) {
     if (!walk) continue;
 #pragma unroll 1
     for (int q = 0; q < cnt; ++q) {
-      const T d2 = knn_d2<SKIP, T, V4>(src[j + q], me, j + q, sk);
+      const T d2 = plain_d2<SKIP, T, V4>(src[j + q], me, j + q, sk);
       if (__ballot(d2 < c.kth()) != 0) c.insert(d2, j + q);
     }
   }
@@ -151,8 +123,8 @@ __global__ void __launch_bounds__(kKnQueries) knn_kernel(KnnArgs a) {
 // the chunks of a split launch in ascending order, each chunk's entries in ascending order, through the same insertion; one query per
 // lane (a wave reads 64 consecutive values).  A chunk's padding (+inf, -1) is below nothing and is never inserted.
 template <typename T, int K>
-__global__ void __launch_bounds__(kKnQueries) knn_combine(KnnArgs a) {
-  const int p = (int)blockIdx.x * kKnQueries + (int)threadIdx.x;
+__global__ void __launch_bounds__(kLanes) knn_combine(KnnArgs a) {
+  const int p = (int)blockIdx.x * kLanes + (int)threadIdx.x;
   if (p >= a.m) return;
   const T* sd = (const T*)knn_scratch_d2(a);
   const int* si = knn_scratch_idx(a, sizeof(T));
@@ -179,7 +151,7 @@ __global__ void __launch_bounds__(kKnQueries) knn_combine(KnnArgs a) {
 
 template <typename T, typename V4, int K>
 void launch_knn_one(hipStream_t st, const KnnArgs& a) {
-  const dim3 grid((a.m + kKnQueries - 1) / kKnQueries, a.chunks), block(kKnQueries);
+  const dim3 grid((a.m + kLanes - 1) / kLanes, a.chunks), block(kLanes);
   if (!a.points || a.skip) hipLaunchKernelGGL((knn_kernel<T, V4, true, K>), grid, block, 0, st, a);
   else hipLaunchKernelGGL((knn_kernel<T, V4, false, K>), grid, block, 0, st, a);
 }
@@ -196,7 +168,7 @@ void launch_knn_of(hipStream_t st, const KnnArgs& a) {
 
 template <typename T>
 void launch_knn_combine_of(hipStream_t st, const KnnArgs& a) {
-  const dim3 grid((a.m + kKnQueries - 1) / kKnQueries), block(kKnQueries);
+  const dim3 grid((a.m + kLanes - 1) / kLanes), block(kLanes);
   switch (knn_capacity(a.k)) {
     case 4: hipLaunchKernelGGL((knn_combine<T, 4>), grid, block, 0, st, a); break;
     case 8: hipLaunchKernelGGL((knn_combine<T, 8>), grid, block, 0, st, a); break;
@@ -210,9 +182,7 @@ void launch_knn_combine_of(hipStream_t st, const KnnArgs& a) {
 namespace nbl {
 
 NBQ_HIDDEN int launch_knn_kernel(int fp64, hipStream_t st, const KnnArgs& a) {
-  if (a.m <= 0 || a.k < 1 || a.k > kKnMax || a.chunks < 1 || a.chunk_blocks < 1 || (a.chunks > 1 && !a.scratch)) return (int)hipErrorInvalidValue;
-  if ((long long)a.chunks * a.chunk_blocks < a.n_blocks || (!a.points && (a.first < 0 || a.first > a.n_src - a.m))) return (int)hipErrorInvalidValue;
-  if (!a.scratch && !a.idx && !a.d2) return (int)hipErrorInvalidValue;
+  if (bad_source_split(a, !a.points) || a.k < 1 || a.k > kKnMax || (!a.scratch && !a.idx && !a.d2)) return (int)hipErrorInvalidValue;
   if (fp64) launch_knn_of<double, d4>(st, a);
   else launch_knn_of<float, f4>(st, a);
   return (int)hipGetLastError();

@@ -5,7 +5,7 @@
 // The result of a query (include/nbody.h, "k nearest neighbours") is the first k candidates in ascending (d2, j) order: a selection, so
 // it is exact and no order of evaluation has to be defended.  It is what an ascending scan over the sources arrives at that starts from
 // k entries (+inf, -1), puts a candidate behind every entry with d2 <= its own and drops the last entry.  When the sources are split
-// over grid.y chunks of whole kKnBlock-source blocks, every workgroup stores its chunk's k entries and knn_combine pushes the chunks'
+// over grid.y chunks of whole nbd::kSrcBlock-source blocks, every workgroup stores its chunk's k entries and knn_combine pushes the chunks'
 // entries, chunks ascending and entries ascending, through the same insertion: lower chunks hold lower j, so the tie rule is kept and
 // every number of chunks gives the same values.
 #pragma once
@@ -15,9 +15,7 @@
 
 namespace nbq {
 
-constexpr int kKnBlock = nbd::kSrcBlock;   // sources per block: chunks are whole blocks
-constexpr int kKnQueries = nbd::kLanes;    // queries per workgroup, one per lane
-constexpr int kKnMax = 32;                 // = NBODY_KNN_MAX: the largest list a lane carries in registers
+constexpr int kKnMax = 32;   // = NBODY_KNN_MAX: the largest list a lane carries in registers
 
 // the list capacities the kernels are instantiated for; a launch takes the smallest one >= k
 constexpr int knn_capacity(int k) { return k <= 4 ? 4 : k <= 8 ? 8 : k <= 16 ? 16 : 32; }
@@ -34,7 +32,7 @@ struct KnnArgs {
   int m;                // queries of this launch
   int k;                // entries per query, 1 .. kKnMax
   int first;            // rows form: global index of query 0
-  int n_blocks;         // ceil(N / kKnBlock)
+  int n_blocks;         // ceil(N / nbd::kSrcBlock)
   int chunk_blocks;     // blocks per chunk: workgroup (x, y) walks blocks [y * chunk_blocks, min((y + 1) * chunk_blocks, n_blocks))
   int chunks;           // grid.y = ceil(n_blocks / chunk_blocks): no empty chunk
 };
@@ -53,7 +51,7 @@ __host__ __device__ inline size_t knn_scratch_at(const KnnArgs& a, int c, int r,
 }  // namespace nbq
 
 namespace nbl {
-// both return a hipError_t as int (0 = launched).  grid = (ceil(m / kKnQueries), a.chunks); a.chunks > 1 needs a.scratch and is followed
+// both return a hipError_t as int (0 = launched; nbd::bad_source_split says what is refused).  grid = (ceil(m / nbd::kLanes), a.chunks); a.chunks > 1 is followed
 // by launch_knn_combine_kernel.  The list capacity is knn_capacity(a.k)
 int launch_knn_kernel(int fp64, hipStream_t stream, const nbq::KnnArgs& a);
 // every query of the launch from a.scratch: chunks ascending, their entries ascending, the same insertion; then idx and d2

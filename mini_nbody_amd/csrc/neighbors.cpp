@@ -23,23 +23,6 @@ constexpr int kNbDefaultLoop = kNbLoopWindow;
 
 struct Want { bool idx, d2, count; double r2; };
 
-// The neighbour pass's split: the scratch is per CHUNK, so the chunks are chosen from the local's queries and normalised first; the
-// queries whose chunk results fit the scratch bound then go together, in whole workgroups.
-SplitPlan neighbors_split(int cnt, int n_blocks, size_t es) {
-  const long long forced = env_ll("NBODY_NEIGHBORS_SPLIT", 0);
-  const char* mb = getenv("NBODY_NEIGHBORS_SCRATCH_MB");
-  const double bound = std::max(0.0, mb && *mb ? atof(mb) : 256.0) * 1048576.0;
-  const int asked = choose_chunks(forced, cnt, n_blocks);
-  if (asked <= 1) return no_split(cnt, n_blocks);
-  const int chunk_blocks = (n_blocks + asked - 1) / asked;
-  const int chunks = (n_blocks + chunk_blocks - 1) / chunk_blocks;   // no empty chunk
-  const double fit = bound / (double)neighbors_scratch_bytes(1, (size_t)chunks, es);
-  int batch = cnt;
-  if (fit < (double)cnt) batch = (int)fit / kNbQueries * kNbQueries;
-  if (batch <= 0) return no_split(cnt, n_blocks);   // not one workgroup's queries fit
-  return {chunks, chunk_blocks, batch};
-}
-
 // r.cnt queries on local L — points [r.first, r.first + r.cnt) of the call (uploaded), or with points == null rows
 // [r.first, r.first + r.cnt) of L's slice — with the outputs left in nb_idx / nb_d2 / nb_count for the copy back
 int launch_neighbors(Local& L, const void* points, const int* skip, const Range& r, const Want& w) {
@@ -52,12 +35,12 @@ int launch_neighbors(Local& L, const void* points, const int* skip, const Range&
   const int n_blocks = source_blocks();
   const long long asked_loop = env_ll("NBODY_NEIGHBORS_LOOP", 0);   // 1: the scan, 2: the window form (same results), else the default
   const int loop = asked_loop == kNbLoopScan || asked_loop == kNbLoopWindow ? (int)asked_loop : kNbDefaultLoop;
-  const SplitPlan plan = neighbors_split(r.cnt, n_blocks, es);
+  const SplitPlan plan = chunk_split("NBODY_NEIGHBORS_SPLIT", "NBODY_NEIGHBORS_SCRATCH_MB", r.cnt, n_blocks, neighbors_scratch_bytes(1, 1, es));
   if (plan.chunks > 1) NBC(L.q_scratch.ensure(neighbors_scratch_bytes((size_t)plan.batch, (size_t)plan.chunks, es)));
   return for_batches(r.cnt, plan, [&](int b0, int m) {
     NeighborsArgs a;
     memset(&a, 0, sizeof(a));
-    a.src = L.pos[L.cur];
+    fill_sources(a, L, plan, n_blocks, m, points ? 0 : L.first + r.first + b0);
     a.points = points ? L.q_points.as<char>() + (size_t)b0 * wb : nullptr;
     a.skip = points && skip ? L.q_skip.as<int>() + b0 : nullptr;
     a.idx = w.idx ? L.nb_idx.as<int>() + b0 : nullptr;
@@ -65,12 +48,6 @@ int launch_neighbors(Local& L, const void* points, const int* skip, const Range&
     a.count = w.count ? L.nb_count.as<int>() + b0 : nullptr;
     a.scratch = plan.chunks > 1 ? L.q_scratch.as<void>() : nullptr;
     a.r2 = w.count ? w.r2 : 0.0;
-    a.n_src = g.n;
-    a.m = m;
-    a.first = points ? 0 : L.first + r.first + b0;
-    a.n_blocks = n_blocks;
-    a.chunk_blocks = plan.chunk_blocks;
-    a.chunks = plan.chunks;
     HIPC((hipError_t)nbl::launch_neighbors_kernel(g.fp64, loop, L.compute, a));
     if (plan.chunks > 1) HIPC((hipError_t)nbl::launch_neighbors_combine_kernel(g.fp64, L.compute, a));
     return NBODY_OK;

@@ -1,9 +1,8 @@
 // neighbors.hip — the neighbour pass's device code: per query the nearest of the N bodies on the device, its squared distance and the
 // number of bodies within a radius (neighbors_args.hpp states the rule, include/nbody.h the definitions), the combine of a split launch
 // and the fixed-order reduction of a device's rows to its closest pair.  Compiles on its own; device.hip puts it into the library's
-// one code object after field.hip.  Reads nbody_args.hpp (f4, d4, NB_CONST) and nothing else of the force path.  d2 is the plain
-// squared distance, fma(dx, dx, fma(dy, dy, dz * dz)): no softening, one form per precision whatever NBODY_OPT_ARITH says, every
-// operation IEEE-exact (the file is compiled with contraction off).  gfx950 only.
+// one code object after field.hip.  Reads nbody_args.hpp (f4, d4, NB_CONST) and nothing else of the force path.  d2 is
+// diag_pass.hpp's plain_d2, the plain squared distance; the file is compiled with contraction off.  gfx950 only.
 #include <hip/hip_runtime.h>
 
 #include "../../include/nbody.h"
@@ -18,23 +17,6 @@ using namespace nbd;
 
 namespace {
 
-// the IEEE minimum of b and a d2 (a NaN d2 gives b): one v_min; both operands are results of arithmetic, so nothing is re-quieted
-__device__ __forceinline__ float nbn_min(float b, float d2) { return __builtin_fminf(b, d2); }
-__device__ __forceinline__ double nbn_min(double b, double d2) { return __builtin_fmin(b, d2); }
-template <typename T>
-__device__ __forceinline__ T nbn_inf() { return (T)__builtin_huge_valf(); }
-template <typename T>
-__device__ __forceinline__ T nbn_nan() { return (T)__builtin_nanf(""); }
-
-// d2 of one pair: 3 sub, 1 mul, 2 fma.  CMP: the excluded body's d2 becomes NaN, which is neither chosen nor counted
-template <bool CMP, typename T, typename V4>
-__device__ __forceinline__ T nbn_d2(const V4 p, const V4 me, int j, int sk) {
-  const T dx = p.x - me.x, dy = p.y - me.y, dz = p.z - me.z;
-  const T d2 = fma_of(dx, dx, fma_of(dy, dy, dz * dz));
-  if (CMP) return j == sk ? nbn_nan<T>() : d2;
-  return d2;
-}
-
 // what a lane carries: the ascending scan's state
 template <typename T>
 struct Near { T best; int idx, cnt; };
@@ -42,7 +24,7 @@ struct Near { T best; int idx, cnt; };
 // the statement of record: one pair of the ascending scan that replaces on strict < (compare, two selects; compare and add for the count)
 template <bool CMP, bool COUNT, typename T, typename V4>
 __device__ __forceinline__ void scan_pair(const V4 p, const V4 me, int j, int sk, T r2, Near<T>& c) {
-  const T d2 = nbn_d2<CMP, T, V4>(p, me, j, sk);
+  const T d2 = plain_d2<CMP, T, V4>(p, me, j, sk);
   const bool less = d2 < c.best;
   c.best = less ? d2 : c.best;
   c.idx = less ? j : c.idx;
@@ -58,8 +40,8 @@ __device__ __forceinline__ void window64(const NB_CONST V4* src, const V4 me, in
   T wmin = c.best;
 #pragma unroll 8
   for (int k = 0; k < 64; ++k) {
-    const T d2 = nbn_d2<CMP, T, V4>(src[j + k], me, j + k, sk);
-    wmin = nbn_min(wmin, d2);
+    const T d2 = plain_d2<CMP, T, V4>(src[j + k], me, j + k, sk);
+    wmin = min_of(wmin, d2);
     if (COUNT) c.cnt += d2 <= r2 ? 1 : 0;
   }
   const bool improved = wmin < c.best;
@@ -67,7 +49,7 @@ __device__ __forceinline__ void window64(const NB_CONST V4* src, const V4 me, in
     int widx = -1;
 #pragma unroll 8
     for (int k = 63; k >= 0; --k) {
-      const T d2 = nbn_d2<CMP, T, V4>(src[j + k], me, j + k, sk);
+      const T d2 = plain_d2<CMP, T, V4>(src[j + k], me, j + k, sk);
       widx = d2 == wmin ? j + k : widx;
     }
     c.idx = improved ? widx : c.idx;
@@ -75,27 +57,17 @@ __device__ __forceinline__ void window64(const NB_CONST V4* src, const V4 me, in
   }
 }
 
-// One query per lane, kNbQueries queries per workgroup; workgroup (x, y) walks the blocks of chunk y for the queries of x.  Sources
+// One query per lane, kLanes queries per workgroup; workgroup (x, y) walks the blocks of chunk y for the queries of x.  Sources
 // arrive with wave-uniform scalar loads (address space 4, as field_kernel).  Lanes beyond m stay in the wave-uniform loops clamped to
 // the last query and store nothing.  SKIP: the rows form (a.points == null: query p is source a.first + p and leaves itself out) and
 // the points form with a skip array; only the aligned 64-source windows that overlap [lowest, highest] excluded index of the wave's
 // 64 queries compare j with it (a wave-uniform branch) — in the rows form the one or two windows that hold the wave's own rows.
 template <typename T, typename V4, bool SKIP, bool COUNT, int LOOP>
-__global__ void __launch_bounds__(kNbQueries) neighbors_kernel(NeighborsArgs a) {
+__global__ void __launch_bounds__(kLanes) neighbors_kernel(NeighborsArgs a) {
   const auto [p, live, pc] = lane_of(a.m);
-  const V4 me = a.points ? ((const V4*)a.points)[pc] : ((const V4*)a.src)[a.first + pc];
-  int sk = -1, wlo = kNoSkipLo, whi = -1;
-  if constexpr (SKIP) {
-    sk = a.points ? a.skip[pc] : a.first + pc;
-    const SkipWindow win = wave_skip_window(sk);
-    wlo = win.lo; whi = win.hi;
-  }
+  const auto [me, sk, wlo, whi, src, s0, s1] = query_of<V4, SKIP>(a, pc);
   const T r2 = (T)a.r2;
-  const NB_CONST V4* src = (const NB_CONST V4*)(uintptr_t)a.src;
-  const auto [blk0, blk1] = chunk_of(a.chunk_blocks, a.n_blocks);
-  const int s0 = blk0 * kNbBlock;
-  const int s1 = min(blk1 * kNbBlock, a.n_src);
-  Near<T> c = {nbn_inf<T>(), -1, 0};
+  Near<T> c = {inf_of<T>(), -1, 0};
   int j = s0;
   for (; j + 64 <= s1; j += 64) {
     if (!SKIP || j + 63 < wlo || j > whi) {
@@ -130,13 +102,13 @@ __global__ void __launch_bounds__(kNbQueries) neighbors_kernel(NeighborsArgs a) 
 
 // the chunks of a split launch in ascending order: strict <, counts added; one query per lane (a wave reads 64 consecutive values)
 template <typename T>
-__global__ void __launch_bounds__(kNbQueries) neighbors_combine(NeighborsArgs a) {
-  const int p = (int)blockIdx.x * kNbQueries + (int)threadIdx.x;
+__global__ void __launch_bounds__(kLanes) neighbors_combine(NeighborsArgs a) {
+  const int p = (int)blockIdx.x * kLanes + (int)threadIdx.x;
   if (p >= a.m) return;
   const T* sd = (const T*)scratch_d2(a);
   const int* si = scratch_idx(a, sizeof(T));
   const int* sn = scratch_count(a, sizeof(T));
-  Near<T> c = {nbn_inf<T>(), -1, 0};
+  Near<T> c = {inf_of<T>(), -1, 0};
   for (int y = 0; y < a.chunks; ++y) {
     const size_t w = (size_t)y * (size_t)a.m + (size_t)p;
     const T d2 = sd[w];
@@ -151,13 +123,13 @@ __global__ void __launch_bounds__(kNbQueries) neighbors_combine(NeighborsArgs a)
 // the closest pair of a device's rows: lane t takes rows t, t + 256, ... ascending with strict <, lane 0 then the 256 lanes' bests by
 // (d2, row).  One workgroup, no atomics.  The lowest row that reaches the smallest d2 is the pair's i and its neighbour the pair's j.
 template <typename T>
-__global__ void __launch_bounds__(kNbQueries) neighbors_best(const T* d2, const int* idx, int rows, int first, BestPair* out) {
-  __shared__ double sd[kNbQueries];
-  __shared__ int sr[kNbQueries];
+__global__ void __launch_bounds__(kLanes) neighbors_best(const T* d2, const int* idx, int rows, int first, BestPair* out) {
+  __shared__ double sd[kLanes];
+  __shared__ int sr[kLanes];
   const int t = (int)threadIdx.x;
-  T best = nbn_inf<T>();
+  T best = inf_of<T>();
   int row = -1;
-  for (int r = t; r < rows; r += kNbQueries) {
+  for (int r = t; r < rows; r += kLanes) {
     const T v = d2[r];
     if (v < best) { best = v; row = r; }
   }
@@ -165,9 +137,9 @@ __global__ void __launch_bounds__(kNbQueries) neighbors_best(const T* d2, const 
   sr[t] = row;
   __syncthreads();
   if (t != 0) return;
-  double b = (double)nbn_inf<T>();
+  double b = (double)inf_of<T>();
   int br = -1;
-  for (int q = 0; q < kNbQueries; ++q) {
+  for (int q = 0; q < kLanes; ++q) {
     if (sr[q] >= 0 && (sd[q] < b || (sd[q] == b && sr[q] < br))) { b = sd[q]; br = sr[q]; }
   }
   out->d2 = b;
@@ -177,7 +149,7 @@ __global__ void __launch_bounds__(kNbQueries) neighbors_best(const T* d2, const 
 
 template <typename T, typename V4, int LOOP>
 void launch_neighbors_one(hipStream_t st, const NeighborsArgs& a) {
-  const dim3 grid((a.m + kNbQueries - 1) / kNbQueries, a.chunks), block(kNbQueries);
+  const dim3 grid((a.m + kLanes - 1) / kLanes, a.chunks), block(kLanes);
   const bool skip = !a.points || a.skip;
   if (skip && a.count) hipLaunchKernelGGL((neighbors_kernel<T, V4, true, true, LOOP>), grid, block, 0, st, a);
   else if (skip) hipLaunchKernelGGL((neighbors_kernel<T, V4, true, false, LOOP>), grid, block, 0, st, a);
@@ -190,8 +162,7 @@ void launch_neighbors_one(hipStream_t st, const NeighborsArgs& a) {
 namespace nbl {
 
 NBN_HIDDEN int launch_neighbors_kernel(int fp64, int loop, hipStream_t st, const NeighborsArgs& a) {
-  if (a.m <= 0 || a.chunks < 1 || a.chunk_blocks < 1 || (a.chunks > 1 && !a.scratch)) return (int)hipErrorInvalidValue;
-  if ((long long)a.chunks * a.chunk_blocks < a.n_blocks || (!a.points && (a.first < 0 || a.first > a.n_src - a.m))) return (int)hipErrorInvalidValue;
+  if (bad_source_split(a, !a.points)) return (int)hipErrorInvalidValue;
   if (fp64) {
     if (loop == kNbLoopScan) launch_neighbors_one<double, d4, kNbLoopScan>(st, a);
     else launch_neighbors_one<double, d4, kNbLoopWindow>(st, a);
@@ -204,16 +175,16 @@ NBN_HIDDEN int launch_neighbors_kernel(int fp64, int loop, hipStream_t st, const
 
 NBN_HIDDEN int launch_neighbors_combine_kernel(int fp64, hipStream_t st, const NeighborsArgs& a) {
   if (a.m <= 0 || !a.scratch || a.chunks < 1) return (int)hipErrorInvalidValue;
-  const dim3 grid((a.m + kNbQueries - 1) / kNbQueries);
-  if (fp64) hipLaunchKernelGGL((neighbors_combine<double>), grid, dim3(kNbQueries), 0, st, a);
-  else hipLaunchKernelGGL((neighbors_combine<float>), grid, dim3(kNbQueries), 0, st, a);
+  const dim3 grid((a.m + kLanes - 1) / kLanes);
+  if (fp64) hipLaunchKernelGGL((neighbors_combine<double>), grid, dim3(kLanes), 0, st, a);
+  else hipLaunchKernelGGL((neighbors_combine<float>), grid, dim3(kLanes), 0, st, a);
   return (int)hipGetLastError();
 }
 
 NBN_HIDDEN int launch_neighbors_best_kernel(int fp64, hipStream_t st, const void* d2, const int* idx, int rows, int first, BestPair* out) {
   if (rows < 0 || !out || (rows > 0 && (!d2 || !idx))) return (int)hipErrorInvalidValue;
-  if (fp64) hipLaunchKernelGGL((neighbors_best<double>), dim3(1), dim3(kNbQueries), 0, st, (const double*)d2, idx, rows, first, out);
-  else hipLaunchKernelGGL((neighbors_best<float>), dim3(1), dim3(kNbQueries), 0, st, (const float*)d2, idx, rows, first, out);
+  if (fp64) hipLaunchKernelGGL((neighbors_best<double>), dim3(1), dim3(kLanes), 0, st, (const double*)d2, idx, rows, first, out);
+  else hipLaunchKernelGGL((neighbors_best<float>), dim3(1), dim3(kLanes), 0, st, (const float*)d2, idx, rows, first, out);
   return (int)hipGetLastError();
 }
 

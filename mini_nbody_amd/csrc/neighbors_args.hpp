@@ -4,7 +4,7 @@
 //
 // The result of a query (include/nbody.h, "nearest neighbour, radius count, closest pair") is a minimum and an integer count, both exact,
 // so no order has to be defended: an ascending scan over the sources from (d2 = +inf, idx = -1, count = 0) that replaces on strict <.
-// When the sources are split over grid.y chunks of whole kNbBlock-source blocks, every workgroup stores its chunk's {d2, idx, count}
+// When the sources are split over grid.y chunks of whole nbd::kSrcBlock-source blocks, every workgroup stores its chunk's {d2, idx, count}
 // and neighbors_combine takes the chunks in ascending order by the same rule (strict <, counts added): the same values for every
 // number of chunks.
 #pragma once
@@ -14,8 +14,6 @@
 
 namespace nbn {
 
-constexpr int kNbBlock = nbd::kSrcBlock;   // sources per block: chunks are whole blocks
-constexpr int kNbQueries = nbd::kLanes;    // queries per workgroup, one per lane
 // the hot loop's form (same results): SCAN carries (best, index) through every pair; WINDOW keeps only the minimum per aligned
 // 64-source window and walks a window again when a lane of the wave improved in it
 enum { kNbLoopScan = 1, kNbLoopWindow = 2 };
@@ -33,7 +31,7 @@ struct NeighborsArgs {
   int n_src;            // N
   int m;                // queries of this launch
   int first;            // rows form: global index of query 0
-  int n_blocks;         // ceil(N / kNbBlock)
+  int n_blocks;         // ceil(N / nbd::kSrcBlock)
   int chunk_blocks;     // blocks per chunk: workgroup (x, y) walks blocks [y * chunk_blocks, min((y + 1) * chunk_blocks, n_blocks))
   int chunks;           // grid.y = ceil(n_blocks / chunk_blocks): no empty chunk
 };
@@ -52,7 +50,7 @@ struct BestPair { double d2; int i, j; };
 }  // namespace nbn
 
 namespace nbl {
-// all return a hipError_t as int (0 = launched).  grid = (ceil(m / kNbQueries), a.chunks); a.chunks > 1 needs a.scratch and is followed
+// all return a hipError_t as int (0 = launched; nbd::bad_source_split says what is refused).  grid = (ceil(m / nbd::kLanes), a.chunks); a.chunks > 1 is followed
 // by launch_neighbors_combine_kernel.  loop: kNbLoopScan or kNbLoopWindow
 int launch_neighbors_kernel(int fp64, int loop, hipStream_t stream, const nbn::NeighborsArgs& a);
 // every query of the launch from a.scratch: chunks ascending, strict <, counts added, then idx, d2 and count

@@ -1,7 +1,8 @@
 // query_pass.hpp — the host side that the diagnostic passes share (energy.cpp, field.cpp, neighbors.cpp, knn.cpp, fof.cpp; host C++ only): a call brings
 // rows or points, every local takes a contiguous range of them, launches on its compute stream — in batches over a split of the
 // sources when the pass asks for one — and the results are copied back once the stream has drained.  A pass says what differs: which
-// range a local gets, what to launch, which outputs go where, and its own split rule (a SplitPlan).
+// range a local gets, what to launch, which outputs go where, and which of the two split rules (a SplitPlan) it follows: chunk_split
+// here, for the three distance passes whose scratch is per chunk, or field.cpp's field_split, whose scratch is per block.
 // The points, skip indices and split scratch of a call live in one set of buffers per Local (q_points, q_skip, q_scratch), whichever
 // pass runs: every call drains the streams it used before it returns, so no two calls ever use them at once.
 #pragma once
@@ -34,9 +35,41 @@ inline int choose_chunks(long long forced, int queries, int n_blocks) {
 }
 
 // How a local's launch is cut: grid.y = chunks chunks of chunk_blocks whole blocks (no empty chunk), `batch` queries per launch.
-// Each pass has its own rule (field.cpp: field_split, neighbors.cpp: neighbors_split, knn.cpp: knn_split, fof.cpp: fof_split); all fall back to no_split.
+// Two rules make one, chunk_split below and field.cpp's field_split; both fall back to no_split.
 struct SplitPlan { int chunks, chunk_blocks, batch; };
 inline SplitPlan no_split(int cnt, int n_blocks) { return {1, n_blocks, cnt}; }
+
+// The split of the neighbour, k-nearest-neighbour and friends-of-friends passes, whose scratch is per CHUNK (bytes_per_query_chunk of
+// it for every query and chunk): the chunks are chosen from the local's cnt queries — split_env forces their number — and normalised
+// first; the queries whose chunk results fit the bound of scratch_mb_env (MB, fractions allowed; 256 when unset) then go together, in
+// whole workgroups.
+inline SplitPlan chunk_split(const char* split_env, const char* scratch_mb_env, int cnt, int n_blocks, size_t bytes_per_query_chunk) {
+  const long long forced = env_ll(split_env, 0);
+  const char* mb = getenv(scratch_mb_env);
+  const double bound = std::max(0.0, mb && *mb ? atof(mb) : 256.0) * 1048576.0;
+  const int asked = choose_chunks(forced, cnt, n_blocks);
+  if (asked <= 1) return no_split(cnt, n_blocks);
+  const int chunk_blocks = (n_blocks + asked - 1) / asked;
+  const int chunks = (n_blocks + chunk_blocks - 1) / chunk_blocks;   // no empty chunk
+  const double fit = bound / (double)((size_t)chunks * bytes_per_query_chunk);
+  int batch = cnt;
+  if (fit < (double)cnt) batch = (int)fit / nbd::kLanes * nbd::kLanes;
+  if (batch <= 0) return no_split(cnt, n_blocks);   // not one workgroup's queries fit
+  return {chunks, chunk_blocks, batch};
+}
+
+// the sources and the geometry members of a distance pass's argument block (diag_pass.hpp's bad_source_split names them) for a launch
+// of m queries on local L under plan; first: the global index of query 0 where the queries are rows
+template <class A>
+void fill_sources(A& a, const Local& L, const SplitPlan& plan, int n_blocks, int m, int first) {
+  a.src = L.pos[L.cur];
+  a.n_src = g.n;
+  a.m = m;
+  a.first = first;
+  a.n_blocks = n_blocks;
+  a.chunk_blocks = plan.chunk_blocks;
+  a.chunks = plan.chunks;
+}
 
 // launch(b0, m) for the batches [b0, b0 + m) of a local's cnt queries
 template <typename Launch>

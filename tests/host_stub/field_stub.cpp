@@ -24,7 +24,7 @@ void block_sums(const nbf::FieldArgs& a, int p, int b, T out[4]) {
   const V* src = (const V*)a.src;
   const V me = ((const V*)a.points)[p];
   const int sk = a.skip ? a.skip[p] : -1;
-  out[0] = src[(size_t)b * nbf::kFieldBlock].x - me.x;
+  out[0] = src[(size_t)b * nbd::kSrcBlock].x - me.x;
   out[1] = me.y + (T)b;
   out[2] = (T)sk + (b == a.n_blocks - 1 ? src[a.n_src - 1].x : (T)0);
   out[3] = me.w;

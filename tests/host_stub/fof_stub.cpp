@@ -32,8 +32,8 @@ void link(const FofArgs& a) {
     const V me = src[i];
     const int mine = a.label[i];
     for (int y = 0; y < a.chunks; ++y) {
-      const int s0 = y * a.chunk_blocks * kFoBlock;
-      const int s1 = std::min(std::min((y + 1) * a.chunk_blocks, a.n_blocks) * kFoBlock, a.n_src);
+      const int s0 = y * a.chunk_blocks * nbd::kSrcBlock;
+      const int s1 = std::min(std::min((y + 1) * a.chunk_blocks, a.n_blocks) * nbd::kSrcBlock, a.n_src);
       int m = kFoNone;
       for (int j = s0; j < s1; ++j) {
         const T dx = src[j].x - me.x, dy = src[j].y - me.y, dz = src[j].z - me.z;
@@ -54,10 +54,8 @@ extern "C" long fof_stub_listed(void) { return g_listed.load(); }
 
 namespace nbl {
 int launch_fof_kernel(int fp64, hipStream_t, const nbg::FofArgs& a) {
-  if (a.m <= 0 || !a.src || !a.label || !a.out || a.chunks < 1 || a.chunk_blocks < 1 || (a.chunks > 1 && !a.scratch)) return (int)hipErrorInvalidValue;
-  if ((long long)a.chunks * a.chunk_blocks < a.n_blocks || (long long)(a.chunks - 1) * a.chunk_blocks >= a.n_blocks) return (int)hipErrorInvalidValue;
-  if (a.n_blocks != (a.n_src + nbg::kFoBlock - 1) / nbg::kFoBlock || !(a.b2 >= 0.0)) return (int)hipErrorInvalidValue;
-  if (!a.rows && (a.first < 0 || a.first > a.n_src - a.m)) return (int)hipErrorInvalidValue;
+  if (nbd::bad_source_split(a, !a.rows) || !a.src || !a.label || !a.out) return (int)hipErrorInvalidValue;
+  if (a.n_blocks != (a.n_src + nbd::kSrcBlock - 1) / nbd::kSrcBlock || !(a.b2 >= 0.0)) return (int)hipErrorInvalidValue;
   if (a.rows)
     for (int p = 0; p < a.m; ++p)
       if (a.rows[p] < 0 || a.rows[p] >= a.n_src || (p > 0 && a.rows[p] <= a.rows[p - 1])) return (int)hipErrorInvalidValue;

@@ -44,7 +44,7 @@ void block(const KnnArgs& a, int p, int b, List<T>& c) {
   const V* src = (const V*)a.src;
   const V q = a.points ? ((const V*)a.points)[p] : src[a.first + p];
   const int sk = a.points ? (a.skip ? a.skip[p] : -1) : a.first + p;
-  const int b0 = b * kKnBlock, len = std::min(kKnBlock, a.n_src - b0);
+  const int b0 = b * nbd::kSrcBlock, len = std::min(nbd::kSrcBlock, a.n_src - b0);
   const int j = b0 + ((int)q.w + b) % len;
   const T d = src[j].x - q.x, d2 = d < 0 ? -d : d;
   if (j != sk) c.push(d2, j);
@@ -99,9 +99,7 @@ extern "C" long knn_stub_combines(void) { return g_combines.load(); }
 
 namespace nbl {
 int launch_knn_kernel(int fp64, hipStream_t, const nbq::KnnArgs& a) {
-  if (a.m <= 0 || a.k < 1 || a.k > nbq::kKnMax || a.chunks < 1 || a.chunk_blocks < 1 || (a.chunks > 1 && !a.scratch)) return (int)hipErrorInvalidValue;
-  if ((long long)a.chunks * a.chunk_blocks < a.n_blocks || (long long)(a.chunks - 1) * a.chunk_blocks >= a.n_blocks) return (int)hipErrorInvalidValue;
-  if (!a.points && (a.first < 0 || a.first > a.n_src - a.m)) return (int)hipErrorInvalidValue;
+  if (nbd::bad_source_split(a, !a.points) || a.k < 1 || a.k > nbq::kKnMax) return (int)hipErrorInvalidValue;
   if (!a.scratch && !a.idx && !a.d2) return (int)hipErrorInvalidValue;
   if (fp64) knn<double>(a); else knn<float>(a);
   return 0;

@@ -33,7 +33,7 @@ void block(const NeighborsArgs& a, int p, int b, Near<T>& c) {
   const V* src = (const V*)a.src;
   const V q = a.points ? ((const V*)a.points)[p] : src[a.first + p];
   const int sk = a.points ? (a.skip ? a.skip[p] : -1) : a.first + p;
-  const int b0 = b * kNbBlock, len = std::min(kNbBlock, a.n_src - b0);
+  const int b0 = b * nbd::kSrcBlock, len = std::min(nbd::kSrcBlock, a.n_src - b0);
   const int j = b0 + ((int)q.w + b) % len;
   const T d = src[j].x - q.x, d2 = d < 0 ? -d : d;
   if (j != sk && d2 < c.best) { c.best = d2; c.idx = j; }
@@ -96,9 +96,7 @@ extern "C" long neighbors_stub_combines(void) { return g_combines.load(); }
 
 namespace nbl {
 int launch_neighbors_kernel(int fp64, int loop, hipStream_t, const nbn::NeighborsArgs& a) {
-  if (a.m <= 0 || a.chunks < 1 || a.chunk_blocks < 1 || (a.chunks > 1 && !a.scratch)) return (int)hipErrorInvalidValue;
-  if ((long long)a.chunks * a.chunk_blocks < a.n_blocks || (long long)(a.chunks - 1) * a.chunk_blocks >= a.n_blocks) return (int)hipErrorInvalidValue;
-  if (!a.points && (a.first < 0 || a.first > a.n_src - a.m)) return (int)hipErrorInvalidValue;
+  if (nbd::bad_source_split(a, !a.points)) return (int)hipErrorInvalidValue;
   if (loop != nbn::kNbLoopScan && loop != nbn::kNbLoopWindow) return (int)hipErrorInvalidValue;
   if (fp64) neighbors<double>(a); else neighbors<float>(a);
   return 0;

@@ -1,4 +1,4 @@
-// field_sanity.cpp — TEST INFRASTRUCTURE (tests/test_field_host_sanitizers.py): drives nbody_field(_d) of the library's host code
+// field_sanity.cpp — TEST INFRASTRUCTURE (tests/test_host_sanitizers.py): drives nbody_field(_d) of the library's host code
 // (field.cpp beside context.cpp, comm.cpp, mailbox.cpp, energy.cpp) against tests/host_stub/hip_stub.cpp and field_stub.cpp under
 // AddressSanitizer + UBSan.  What it checks is the host's logic: the division of the points over the devices, the upload and copy-back
 // offsets, the choice of the source split, the scratch size and the batches, the argument checks, lifetimes at shutdown and the

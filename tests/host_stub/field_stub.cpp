@@ -1,4 +1,4 @@
-// field_stub.cpp — TEST INFRASTRUCTURE (tests/test_field_host_sanitizers.py): a host-only stand-in for the launch functions of field.hip,
+// field_stub.cpp — TEST INFRASTRUCTURE (tests/test_host_sanitizers.py): a host-only stand-in for the launch functions of field.hip,
 // linked beside hip_stub.cpp so that field.cpp runs on a machine without a GPU under AddressSanitizer / UBSan.  hip_stub.cpp's streams
 // are synchronous and the field pass is never captured, so both functions execute at launch.
 // The stand-in pushes values a test can predict through the REAL FieldArgs — chunk bounds, the per-block scratch layout, the combine's

@@ -1,4 +1,4 @@
-// fof_stub.cpp — TEST INFRASTRUCTURE (tests/test_fof_host_sanitizers.py): a host-only stand-in for the launch functions of fof.hip,
+// fof_stub.cpp — TEST INFRASTRUCTURE (tests/test_host_sanitizers.py): a host-only stand-in for the launch functions of fof.hip,
 // linked beside hip_stub.cpp so that fof.cpp runs on a machine without a GPU under AddressSanitizer / UBSan.  hip_stub.cpp's streams
 // are synchronous and the pass is never captured, so both functions execute at launch.
 // The stand-in computes the REAL m of include/nbody.h — per row the lowest foreign label among the bodies with d2 <= b2 — from the REAL

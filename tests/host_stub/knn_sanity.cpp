@@ -1,4 +1,4 @@
-// knn_sanity.cpp — TEST INFRASTRUCTURE (tests/test_knn_host_sanitizers.py): drives nbody_knn_rows and nbody_knn (and their _d forms) of
+// knn_sanity.cpp — TEST INFRASTRUCTURE (tests/test_host_sanitizers.py): drives nbody_knn_rows and nbody_knn (and their _d forms) of
 // the library's host code (knn.cpp beside context.cpp, comm.cpp, mailbox.cpp, energy.cpp, field.cpp, neighbors.cpp) against
 // tests/host_stub/hip_stub.cpp and knn_stub.cpp under AddressSanitizer + UBSan.  What it checks is the host's logic: the rows of a
 // window and the division of the points over the devices, the upload and copy-back offsets of [m][k] outputs, the choice of the source

@@ -1,4 +1,4 @@
-// knn_stub.cpp — TEST INFRASTRUCTURE (tests/test_knn_host_sanitizers.py): a host-only stand-in for the launch functions of knn.hip,
+// knn_stub.cpp — TEST INFRASTRUCTURE (tests/test_host_sanitizers.py): a host-only stand-in for the launch functions of knn.hip,
 // linked beside hip_stub.cpp so that knn.cpp runs on a machine without a GPU under AddressSanitizer / UBSan.  hip_stub.cpp's streams
 // are synchronous and the pass is never captured, so both functions execute at launch.
 // The stand-in pushes values a test can predict through the REAL KnnArgs — chunk bounds, the chunks' scratch layout [chunk][r][m], the

@@ -1,4 +1,4 @@
-// neighbors_sanity.cpp — TEST INFRASTRUCTURE (tests/test_neighbors_host_sanitizers.py): drives nbody_neighbors_rows, nbody_nearest and
+// neighbors_sanity.cpp — TEST INFRASTRUCTURE (tests/test_host_sanitizers.py): drives nbody_neighbors_rows, nbody_nearest and
 // nbody_closest_pair (and their _d forms) of the library's host code (neighbors.cpp beside context.cpp, comm.cpp, mailbox.cpp,
 // energy.cpp) against tests/host_stub/hip_stub.cpp and neighbors_stub.cpp under AddressSanitizer + UBSan.  What it checks is the host's
 // logic: the rows of a window and the division of the points over the devices, the upload and copy-back offsets, the choice of the

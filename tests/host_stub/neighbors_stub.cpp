@@ -1,4 +1,4 @@
-// neighbors_stub.cpp — TEST INFRASTRUCTURE (tests/test_neighbors_host_sanitizers.py): a host-only stand-in for the launch functions of
+// neighbors_stub.cpp — TEST INFRASTRUCTURE (tests/test_host_sanitizers.py): a host-only stand-in for the launch functions of
 // neighbors.hip, linked beside hip_stub.cpp so that neighbors.cpp runs on a machine without a GPU under AddressSanitizer / UBSan.
 // hip_stub.cpp's streams are synchronous and the neighbour pass is never captured, so all three functions execute at launch.
 // The stand-in pushes values a test can predict through the REAL NeighborsArgs — chunk bounds, the chunks' scratch layout, the combine's

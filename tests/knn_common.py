@@ -1,12 +1,13 @@
 """What the knn tests (test_knn_abi.py, test_gpu_knn.py) share: tests/knn_ref.c compiled as the field tests compile field_ref.c, bit
-comparison of (idx, d2) pairs and a plain numpy fp64 brute force.  bits and planted come from neighbors_common, make_points and
-make_skip from field_common."""
+comparison of (idx, d2) pairs and a plain numpy fp64 brute force.  bits and same come from pass_common, planted from neighbors_common,
+make_points and make_skip from field_common."""
 import ctypes as C
 
 import numpy as np
 
 from field_common import compile_ref, make_points, make_skip  # noqa: F401
-from neighbors_common import bits, planted  # noqa: F401
+from neighbors_common import planted  # noqa: F401
+from pass_common import bits, same  # noqa: F401
 
 KS = (1, 2, 3, 4, 5, 8, 9, 16, 17, 31, 32)   # both sides of every list capacity the kernels are built for (4, 8, 16, 32)
 
@@ -44,17 +45,6 @@ class KnnRef:
 
 def make_ref(tmp_dir):
     return KnnRef(compile_ref(tmp_dir, "knn_ref"))
-
-
-def same(got, want):
-    """(idx, d2) pairs: the same shapes and dtypes, idx equal, d2 the same bits"""
-    if len(got) != len(want):
-        return False
-    for g, w in zip(got, want):
-        g, w = np.asarray(g), np.asarray(w)
-        if g.shape != w.shape or g.dtype != w.dtype or not np.array_equal(bits(g), bits(w)):
-            return False
-    return True
 
 
 def numpy_knn(pos, queries, skip, k):

@@ -1,10 +1,12 @@
 """What the neighbour tests (test_neighbors_abi.py, test_gpu_neighbors.py) share: tests/neighbors_ref.c compiled as the field tests
-compile field_ref.c, bit comparison, a plain numpy fp64 brute force and the planted systems (duplicates, ties, a NaN body)."""
+compile field_ref.c, bit comparison (bits and same, from pass_common), a plain numpy fp64 brute force and the planted systems
+(duplicates, ties, a NaN body)."""
 import ctypes as C
 
 import numpy as np
 
 from field_common import compile_ref
+from pass_common import bits, same  # noqa: F401
 
 
 class NeighborsRef:
@@ -52,24 +54,6 @@ class NeighborsRef:
 
 def make_ref(tmp_dir):
     return NeighborsRef(compile_ref(tmp_dir, "neighbors_ref"))
-
-
-def bits(a):
-    a = np.asarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
-
-
-def same(got, want):
-    """(idx, d2, count) triples: idx and count equal, d2 the same bits (count may be None in both)"""
-    for g, w in zip(got, want):
-        if g is None or w is None:
-            if not (g is None and w is None):
-                return False
-            continue
-        g, w = np.asarray(g), np.asarray(w)
-        if g.shape != w.shape or g.dtype != w.dtype or not np.array_equal(bits(g), bits(w)):
-            return False
-    return True
 
 
 def numpy_neighbors(pos, queries, skip):

@@ -4,25 +4,11 @@ depends on the transfer form AND the rank.  What must hold: the slowest rank's t
 another form is faster by more than the margin, ragged slice lengths drop the all-gather form, and the engine is left configured
 with the choice."""
 import json
-import os
-import socket
-import subprocess
-import sys
-import textwrap
 
-import pytest
+from ranks_common import run_ranks, worker_source
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-WORKER = textwrap.dedent("""
-    import json, os, sys, time
-    sys.path.insert(0, {root!r})
-    import torch.distributed as dist
-    import mini_nbody_amd as nb
-    import mini_nbody_amd.distributed as D
+WORKER = """
     L = nb._lib
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     cost = {cost!r}          # {{form name: [seconds per step on rank 0, on rank 1]}}
     names = {{L.COMM_ALLGATHER: "allgather", L.COMM_DIRECT: "direct", L.COMM_RING: "ring"}}
 
@@ -42,20 +28,12 @@ WORKER = textwrap.dedent("""
     e = Stub()
     best, ms = D.autotune_comm(e, 0.01, steps=2, margin={margin}, restore={restore!r})
     json.dump({{"best": best, "ms": ms, "left": [names[e.opt[L.OPT_COMM]], e.opt[L.OPT_OVERLAP]], "log": e.log}}, open({out!r} + "%d.json" % rank, "w"))
-    dist.barrier(); dist.destroy_process_group()
-""")
+"""
 
 
 def run(tmp_path, cost, n=1000, margin=0.01, fail=None, restore=None):
-    s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     out = str(tmp_path / "r")
-    script = tmp_path / "w.py"
-    script.write_text(WORKER.format(root=ROOT, cost=cost, n=n, margin=margin, out=out, fail=fail, restore=restore))
-    procs = [subprocess.Popen([sys.executable, str(script)], env=dict(os.environ, RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port)),
-                              stdout=subprocess.PIPE, stderr=subprocess.STDOUT) for r in range(2)]
-    for p in procs:
-        o, _ = p.communicate(timeout=300)
-        assert p.returncode == 0, o.decode()[-2000:]
+    run_ranks(tmp_path, worker_source(WORKER, engine=None, cost=cost, n=n, margin=margin, out=out, fail=fail, restore=restore), 2, 300, tag="w")
     return [json.load(open(out + "%d.json" % r)) for r in range(2)]
 
 

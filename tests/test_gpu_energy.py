@@ -5,15 +5,14 @@ state and bit for bit against the header's summation order, all of it on the hos
 import ctypes as C
 import os
 import re
-import socket
 import subprocess
-import sys
-import textwrap
 
 import numpy as np
 import pytest
 
+import pass_common
 from field_common import numpy_field
+from ranks_common import run_ranks, shared_gpu_env, worker_source
 from specials_common import SIZES, VARIANTS, hostile_system, near, same_nan, within
 
 pytestmark = pytest.mark.gpu
@@ -79,7 +78,8 @@ def fp64_totals(ref, pos, vel):
 
 
 def bits(e):
-    return np.array([e["kinetic"], e["potential"], *e["momentum"], *e["angular_momentum"]]).view(np.uint64)
+    """the eight totals of an energy() result as binary64 words"""
+    return pass_common.bits(np.array([e["kinetic"], e["potential"], *e["momentum"], *e["angular_momentum"]]))
 
 
 @pytest.mark.parametrize("arith", ["strict", "reference_strict"])
@@ -158,10 +158,7 @@ def test_phi_bits_do_not_depend_on_the_force_configuration(nb):
     with nb.NBody(n) as eng:
         eng.upload(pos, vel)
         base, ebase = eng.potential_rows(0, n), bits(eng.energy())
-        for key, val, default in ((nb.OPT_VARIANT, nb.VARIANT_SMEM, nb.VARIANT_AUTO), (nb.OPT_VARIANT, nb.VARIANT_LDS, nb.VARIANT_AUTO),
-                                  (nb.OPT_VARIANT, nb.VARIANT_READLANE, nb.VARIANT_AUTO), (nb.OPT_JSUB, 3, 0), (nb.OPT_JSLICES, 3, 0),
-                                  (nb.OPT_WSPLIT, 1, -1), (nb.OPT_WSPLIT, 16, -1), (nb.OPT_SUM_ORDER, nb.SUM_SEQ, nb.SUM_BLOCKED),
-                                  (nb.OPT_SUM_ORDER, nb.SUM_FPGA16, nb.SUM_BLOCKED)):
+        for key, val, default in pass_common.FORCE_CONFIGS:
             eng.set_option(key, val)
             got = eng.potential_rows(0, n)
             assert np.array_equal(got.view(np.uint32), base.view(np.uint32)), (key, val)
@@ -193,16 +190,7 @@ def test_phi_bits_do_not_depend_on_the_device_count(nb, monkeypatch):
             assert np.all(np.abs(e[k] - e1[k]) <= 1e-12 * np.abs(e1[k]).sum()), (ngpus, k)
 
 
-WORKER = textwrap.dedent("""
-    import os, sys
-    import numpy as np
-    sys.path.insert(0, {root!r})
-    import torch
-    import mini_nbody_amd as nb
-    import mini_nbody_amd.distributed as D
-    rank, world, local = D.init_process_group("gloo")
-    n = {n}
-    eng = D.make_engine(n, transport="host")
+WORKER = """
     eng.set_option(nb.OPT_JSUB, 2)
     pos, vel = nb.make_bodies(n, seed=33)
     eng.upload(pos, vel)
@@ -216,29 +204,13 @@ WORKER = textwrap.dedent("""
     if rank == 0:
         np.save({out!r} + "_pos.npy", p)
         open({out!r} + "_wsplit.txt", "w").write(str(eng.config["wsplit"]))
-    eng.close()
-    import torch.distributed as dist
-    dist.barrier(); dist.destroy_process_group()
-""")
+"""
 
 
 def test_two_processes_host_transport_equal_one_process(nb, tmp_path, monkeypatch):
     n, world = 6007, 2
     out = str(tmp_path / "en")
-    script = tmp_path / "worker.py"
-    script.write_text(WORKER.format(root=ROOT, n=n, out=out))
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), NBODY_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    for p in procs:
-        o, _ = p.communicate(timeout=300)
-        assert p.returncode == 0, o.decode()[-3000:]
+    run_ranks(tmp_path, worker_source(WORKER, n=n, out=out), world, 300, env_of=shared_gpu_env)
     monkeypatch.setenv("NBODY_OVERSUBSCRIBE", "1")
     pos, vel = nb.make_bodies(n, seed=33)
     with nb.NBody(n, ngpus=world) as one:
@@ -257,29 +229,13 @@ def test_two_processes_host_transport_equal_one_process(nb, tmp_path, monkeypatc
     assert np.array_equal(got_phi.view(np.uint32), phi.view(np.uint32))
 
 
-def run_steps(nb, n, pos, vel, plan, graph, probe, timing=False):
-    with nb.NBody(n) as eng:
-        eng.set_option(nb.OPT_GRAPH, graph)
-        if timing:
-            eng.set_option(nb.OPT_TIMING, 1)
-        eng.upload(pos, vel)
-        for k in plan:
-            eng.step(0.01, k)
-            if probe:
-                eng.energy()
-                eng.potential_rows(0, n)
-                eng.potential_rows(n // 3, 7)
-        p, v = eng.download()
-        launches = eng.kernel_time()[1] if timing else None
-    return p, v, launches
-
-
 def test_energy_calls_leave_the_step_untouched(nb):
     n = 1500
     pos, vel = nb.make_bodies(n)
+    probe = lambda eng: (eng.energy(), eng.potential_rows(0, n), eng.potential_rows(n // 3, 7))
     for plan, graph, timing in (([1] * 12, 0, False), ([64, 64, 6, 64], 1, False), ([3, 5, 2], 0, True)):
-        a = run_steps(nb, n, pos, vel, plan, graph, False, timing)
-        b = run_steps(nb, n, pos, vel, plan, graph, True, timing)
+        a = pass_common.run_steps(nb, n, pos, vel, plan, graph, None, timing)
+        b = pass_common.run_steps(nb, n, pos, vel, plan, graph, probe, timing)
         assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)), (plan, graph)
         assert np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)), (plan, graph)
         assert a[2] == b[2], "energy launches were counted by nbody_kernel_time"

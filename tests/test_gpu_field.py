@@ -8,15 +8,14 @@ C host program's --field line."""
 import ctypes as C
 import os
 import re
-import socket
 import subprocess
-import sys
-import textwrap
 
 import numpy as np
 import pytest
 
 from field_common import FieldRef, compile_ref, make_points, make_skip, numpy_field, row_rel
+from pass_common import FORCE_CONFIGS, bits, check_step_untouched, same
+from ranks_common import run_ranks, shared_gpu_env, worker_source
 from specials_common import POINT_COUNTS, SIZES, VARIANTS, hostile_points, hostile_system, nan_row, near, same_nan, special_row, within
 
 pytestmark = pytest.mark.gpu
@@ -27,14 +26,6 @@ TOL = 1e-5   # the project's north_star tolerance (TOL in tests/test_gpu_parity.
 @pytest.fixture(scope="module")
 def ref(tmp_path_factory):
     return FieldRef(compile_ref(tmp_path_factory.mktemp("field_ref"), "field_ref"))
-
-
-def same(a, b):
-    """identical bits (either may be None when the other is)"""
-    if a is None or b is None:
-        return a is None and b is None
-    u = np.uint32 if a.dtype == np.float32 else np.uint64
-    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(u), b.view(u))
 
 
 @pytest.mark.parametrize("arith", ["strict", "reference_strict"])
@@ -156,10 +147,7 @@ def test_bits_do_not_depend_on_the_points_beside_a_point_or_the_force_configurat
             assert same(a1, a[sel]) and same(p1, p[sel]), sel
         a3, p3 = eng.field(np.ascontiguousarray(pts[:, :3]), skip)   # (m, 3) points are padded to words
         assert same(a3, a) and same(p3, p)
-        for key, val, default in ((nb.OPT_VARIANT, nb.VARIANT_SMEM, nb.VARIANT_AUTO), (nb.OPT_VARIANT, nb.VARIANT_LDS, nb.VARIANT_AUTO),
-                                  (nb.OPT_VARIANT, nb.VARIANT_READLANE, nb.VARIANT_AUTO), (nb.OPT_JSUB, 3, 0), (nb.OPT_JSLICES, 3, 0),
-                                  (nb.OPT_WSPLIT, 1, -1), (nb.OPT_WSPLIT, 16, -1), (nb.OPT_SUM_ORDER, nb.SUM_SEQ, nb.SUM_BLOCKED),
-                                  (nb.OPT_SUM_ORDER, nb.SUM_FPGA16, nb.SUM_BLOCKED)):
+        for key, val, default in FORCE_CONFIGS:
             eng.set_option(key, val)
             a1, p1 = eng.field(pts, skip)
             assert same(a1, a) and same(p1, p), (key, val)
@@ -185,18 +173,8 @@ def test_bits_do_not_depend_on_the_device_count(nb, monkeypatch):
         assert same(res[1][k], res[3][k]), k
 
 
-WORKER = textwrap.dedent("""
-    import os, sys
-    import numpy as np
-    sys.path.insert(0, {root!r})
-    sys.path.insert(0, os.path.join({root!r}, "tests"))
-    import torch
-    import mini_nbody_amd as nb
-    import mini_nbody_amd.distributed as D
+WORKER = """
     from field_common import make_points, make_skip
-    rank, world, local = D.init_process_group("gloo")
-    n = {n}
-    eng = D.make_engine(n, transport="host")
     eng.set_option(nb.OPT_JSUB, 2)
     pos, vel = nb.make_bodies(n, seed=33)
     eng.upload(pos, vel)
@@ -210,29 +188,13 @@ WORKER = textwrap.dedent("""
     if rank == 0:
         np.save({out!r} + "_pos.npy", p)
         open({out!r} + "_wsplit.txt", "w").write(str(eng.config["wsplit"]))
-    eng.close()
-    import torch.distributed as dist
-    dist.barrier(); dist.destroy_process_group()
-""")
+"""
 
 
 def test_two_processes_host_transport_equal_one_process(nb, tmp_path, monkeypatch):
     n, world = 6007, 2
     out = str(tmp_path / "fd")
-    script = tmp_path / "worker.py"
-    script.write_text(WORKER.format(root=ROOT, n=n, out=out))
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), NBODY_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    for p in procs:
-        o, _ = p.communicate(timeout=300)
-        assert p.returncode == 0, o.decode()[-3000:]
+    run_ranks(tmp_path, worker_source(WORKER, n=n, out=out), world, 300, env_of=shared_gpu_env)
     monkeypatch.setenv("NBODY_OVERSUBSCRIBE", "1")
     pos, vel = nb.make_bodies(n, seed=33)
     with nb.NBody(n, ngpus=world) as one:
@@ -249,37 +211,11 @@ def test_two_processes_host_transport_equal_one_process(nb, tmp_path, monkeypatc
             assert same(np.load(out + "_%d_phi.npy" % r), phi), r
 
 
-def run_steps(nb, n, pos, vel, plan, graph, probe, timing=False):
-    pts, on = make_points(nb, pos, 300)
-    with nb.NBody(n) as eng:
-        eng.set_option(nb.OPT_GRAPH, graph)
-        if timing:
-            eng.set_option(nb.OPT_TIMING, 1)
-        eng.upload(pos, vel)
-        for k in plan:
-            eng.step(0.01, k)
-            if probe:
-                eng.field(pts)
-                eng.field(pts, make_skip(n, 300, on))
-                eng.field(pts[:7], accel=False)
-        p, v = eng.download()
-        launches = eng.kernel_time()[1] if timing else None
-    return p, v, launches
-
-
 def test_field_calls_leave_the_step_untouched(nb, monkeypatch):
     n = 1500   # two blocks: a forced split takes the scratch and combine path between the steps too
-    pos, vel = nb.make_bodies(n)
-    for plan, graph, timing in (([1] * 12, 0, False), ([64, 64, 6, 64], 1, False), ([3, 5, 2], 0, True)):
-        monkeypatch.delenv("NBODY_FIELD_SPLIT", raising=False)
-        a = run_steps(nb, n, pos, vel, plan, graph, False, timing)
-        for split in (None, "2"):
-            if split:
-                monkeypatch.setenv("NBODY_FIELD_SPLIT", split)
-            b = run_steps(nb, n, pos, vel, plan, graph, True, timing)
-            assert np.array_equal(a[0].view(np.uint32), b[0].view(np.uint32)), (plan, graph)
-            assert np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32)), (plan, graph)
-            assert a[2] == b[2], "field launches were counted by nbody_kernel_time"
+    pts, on = make_points(nb, nb.make_bodies(n)[0], 300)
+    probe = lambda eng: (eng.field(pts), eng.field(pts, make_skip(n, 300, on)), eng.field(pts[:7], accel=False))
+    check_step_untouched(nb, monkeypatch, n, probe, "NBODY_FIELD_SPLIT")
 
 
 def gradient_error(field, x, h):
@@ -391,10 +327,6 @@ def test_c_host_program_field_line(nb):
 
 # ---- the hostile system (specials_common.py): what a uniform cloud never shows the pass ----
 
-def bits_of(a):
-    return a.view(np.uint32 if a.dtype == np.float32 else np.uint64)
-
-
 def check_specials_directly(a, p, pts, skip, n, variant, what, planted=0):
     """What include/nbody.h promises without any reference: a skipped body leaves no trace ("for j == skip[p] all four keep their
     values"), so a finite point that skips the NaN, inf or overflow body has a finite field (planted: how many such points there must
@@ -438,9 +370,9 @@ def test_hostile_system_strict_bit_for_bit(nb, ref, arith, monkeypatch):
                             else:
                                 monkeypatch.setenv("NBODY_FIELD_SPLIT", split)
                             a, p = eng.field(pts, skip)
-                            assert same_nan(a, wa), what + (split, np.flatnonzero((bits_of(a) != bits_of(wa)).any(1))[:8])
-                            assert same_nan(p, wp), what + (split, np.flatnonzero(bits_of(p) != bits_of(wp))[:8])
-                            assert np.all(bits_of(a[:, 3]) == 0)
+                            assert same_nan(a, wa), what + (split, np.flatnonzero((bits(a) != bits(wa)).any(1))[:8])
+                            assert same_nan(p, wp), what + (split, np.flatnonzero(bits(p) != bits(wp))[:8])
+                            assert np.all(bits(a[:, 3]) == 0)
                             check_specials_directly(a, p, pts, skip, n, variant, what + (split,), planted)
                             a1, none = eng.field(pts, skip, potential=False)
                             assert none is None and same_nan(a1, wa), what + (split,)

@@ -3,11 +3,6 @@ integer for integer against tests/fof_ref.c in both precisions, on planted ties 
 however the work is laid out (source split, batches, the active-row list, force configuration, device and process count); against the
 neighbour pass with no CPU statement involved; no effect on the step or on the passes that share the query buffers; the guards."""
 import ctypes as C
-import os
-import socket
-import subprocess
-import sys
-import textwrap
 
 import numpy as np
 import pytest
@@ -16,9 +11,10 @@ import knn_common
 import neighbors_common
 from fof_common import CHAIN_N, b2_for, chain, make_ref, planted, round_bound
 from field_common import make_points, make_skip
+from pass_common import PLANS, check_step_untouched
+from ranks_common import run_ranks, shared_gpu_env, worker_source
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENV = ("NBODY_FOF_SPLIT", "NBODY_FOF_SCRATCH_MB", "NBODY_FOF_ALL_ROWS", "NBODY_KNN_SPLIT", "NBODY_KNN_SCRATCH_MB", "NBODY_NEIGHBORS_SPLIT",
        "NBODY_NEIGHBORS_SCRATCH_MB", "NBODY_NEIGHBORS_LOOP", "NBODY_FIELD_SPLIT", "NBODY_FIELD_SCRATCH_MB")
 SIZES = (1, 2, 5, 63, 64, 65, 257, 1000, 1025, 2100)   # one body, a window edge, a block edge, two blocks with a tail
@@ -169,16 +165,7 @@ def test_values_do_not_depend_on_the_device_count(nb, ref, monkeypatch):
         assert res[1][k][2] == res[3][k][2]
 
 
-WORKER = textwrap.dedent("""
-    import os, sys
-    import numpy as np
-    sys.path.insert(0, {root!r})
-    import torch
-    import mini_nbody_amd as nb
-    import mini_nbody_amd.distributed as D
-    rank, world, local = D.init_process_group("gloo")
-    n = {n}
-    eng = D.make_engine(n, transport="host")
+WORKER = """
     pos, vel = nb.make_bodies(n, seed=33)
     eng.upload(pos, vel)
     eng.step(0.01, 3)
@@ -186,30 +173,14 @@ WORKER = textwrap.dedent("""
     rounds = eng.fof_rounds
     p, v = eng.download()
     np.savez({out!r} + "_%d.npz" % rank, group=group, meta=np.array([n_groups, rounds]), pos=p)
-    eng.close()
-    import torch.distributed as dist
-    dist.barrier(); dist.destroy_process_group()
-""")
+"""
 
 
 def test_two_processes_host_transport_equal_one_process(nb, ref, tmp_path):
     n, world = 1500, 2
     b2 = float(b2_for(n, 0.9))
     out = str(tmp_path / "fof")
-    script = tmp_path / "worker.py"
-    script.write_text(WORKER.format(root=ROOT, n=n, out=out, b2=b2))
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), NBODY_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    for p in procs:
-        o, _ = p.communicate(timeout=300)
-        assert p.returncode == 0, o.decode()[-3000:]
+    run_ranks(tmp_path, worker_source(WORKER, n=n, out=out, b2=b2), world, 300, env_of=shared_gpu_env)
     got = [np.load(out + "_%d.npz" % r) for r in range(world)]
     now = got[0]["pos"]
     assert np.array_equal(now.view(np.uint32), got[1]["pos"].view(np.uint32))
@@ -243,34 +214,10 @@ def test_cross_checks_against_the_neighbour_pass(nb, fp64):
                 assert n_groups == int((group == me).sum())
 
 
-def run_steps(nb, n, pos, vel, plan, graph, b2, timing=False):
-    with nb.NBody(n) as eng:
-        eng.set_option(nb.OPT_GRAPH, graph)
-        if timing:
-            eng.set_option(nb.OPT_TIMING, 1)
-        eng.upload(pos, vel)
-        for k in plan:
-            eng.step(0.01, k)
-            if b2 is not None:
-                eng.fof(b2)
-        p, v = eng.download()
-        launches = eng.kernel_time()[1] if timing else None
-    return p, v, launches
-
-
 def test_fof_calls_leave_the_step_untouched(nb, monkeypatch):
     n = 1500   # two blocks: a forced split takes the scratch and combine path between the steps too
-    pos, vel = nb.make_bodies(n)
     b2 = b2_for(n, 0.9)
-    for plan, graph, timing in (([1] * 6, 0, False), ([64, 64, 6, 64], 1, False), ([3, 5, 2], 0, True)):
-        monkeypatch.delenv("NBODY_FOF_SPLIT", raising=False)
-        a = run_steps(nb, n, pos, vel, plan, graph, None, timing)
-        for split in (None, "2"):
-            if split:
-                monkeypatch.setenv("NBODY_FOF_SPLIT", split)
-            b = run_steps(nb, n, pos, vel, plan, graph, b2, timing)
-            assert knn_common.same(a[:2], b[:2]), (plan, graph)
-            assert a[2] == b[2], "fof launches were counted by nbody_kernel_time"
+    check_step_untouched(nb, monkeypatch, n, lambda eng: eng.fof(b2), "NBODY_FOF_SPLIT", (([1] * 6, 0, False),) + PLANS[1:])
 
 
 def test_interleaved_with_knn_neighbors_and_field(nb, ref, tmp_path_factory, monkeypatch):

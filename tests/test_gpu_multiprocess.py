@@ -3,27 +3,20 @@ rendezvous over gloo, nbody_init_rank(), positions exchanged every step through 
 (nbody_set_host_gather) — i.e. everything the 8-GPU job does except that the slices travel through host memory
 instead of RCCL/xGMI.  Result must equal one process configured with the same segmentation, bit for bit."""
 import os
-import socket
 import subprocess
 import sys
-import textwrap
 
 import numpy as np
 import pytest
 
+from mini_nbody_amd.launcher import free_port
+from ranks_common import run_ranks, shared_gpu_env, worker_source
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
-WORKER = textwrap.dedent("""
-    import os, sys
-    import numpy as np
-    sys.path.insert(0, {root!r})
-    import torch
-    import mini_nbody_amd as nb
-    import mini_nbody_amd.distributed as D
-    rank, world, local = D.init_process_group("gloo")
-    n, steps = {n}, {steps}
-    eng = D.make_engine(n, fp64={fp64}, transport={transport!r})
+WORKER = """
+    steps = {steps}
     eng.set_option(nb.OPT_JSUB, {jsub})
     eng.set_option(nb.OPT_OVERLAP, {overlap})
     if {comm} >= 0:
@@ -42,43 +35,27 @@ WORKER = textwrap.dedent("""
         np.save({out!r} + "_force.npy", f)
     if rank == 0:
         np.save({out!r} + "_pos.npy", p); np.save({out!r} + "_vel.npy", v)
-    eng.close()
-    import torch.distributed as dist
-    dist.barrier(); dist.destroy_process_group()
-""")
+"""
 
 
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+def run_job(tmp_path, tag, world, timeout_s, env_of, local_of=None, **fmt):
+    """WORKER as `world` ranks; -> the stem of the files ranks 0 and world - 1 leave"""
+    out = str(tmp_path / tag)
+    run_ranks(tmp_path, worker_source(WORKER, engine="fp64={fp64}, transport={transport!r}", out=out, **fmt), world, timeout_s, env_of, local_of,
+              tag="worker_" + tag)
+    return out
 
 
-@pytest.mark.parametrize("world,overlap", [(2, 1), (3, 0), (3, 2)])
-def test_two_processes_one_gpu_host_transport(nb, tmp_path, world, overlap):
-    n, steps, jsub = 12000 + 7, 3, 2
-    out = str(tmp_path / "mp")
-    script = tmp_path / "worker.py"
-    script.write_text(WORKER.format(root=ROOT, n=n, steps=steps, jsub=jsub, overlap=overlap, out=out, transport="host", comm=-1, fp64=False))
-    port = free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), NBODY_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    for p in procs:
-        o, _ = p.communicate(timeout=600)
-        assert p.returncode == 0, o.decode()[-3000:]
-    gp, gv = np.load(out + "_pos.npy"), np.load(out + "_vel.npy")
-    pos, vel = nb.make_bodies(n, seed=33)
-    one = nb.NBody(n)
+def check_against_one_gpu(nb, out, n, world, jsub, steps, fp64=False, what=None):
+    """The job's result against ONE process configured with the job's summation order: its slices, its pieces per slice, its waves per
+    workgroup (<out>_wsplit.txt: the engine picks them from a rank's body count, which differs between the job and this one-GPU
+    restatement) — forces, positions and velocities bit for bit."""
+    u = np.uint64 if fp64 else np.uint32
+    pos, vel = nb.make_bodies(n, seed=33, dtype=np.float64 if fp64 else np.float32)
+    one = nb.NBody(n, fp64=fp64)
     try:
         one.set_option(nb.OPT_JSUB, jsub)
         one.set_option(nb.OPT_JSLICES, world)
-        # the summation order of the P-rank job on one GPU: its slices, its pieces per slice, its waves per workgroup (the
-        # engine picks the last from a rank's body count, which differs between the job and this one-GPU restatement)
         one.set_option(nb.OPT_WSPLIT, int(open(out + "_wsplit.txt").read()))
         wf = one.forces(pos)
         one.upload(pos, vel)
@@ -86,9 +63,16 @@ def test_two_processes_one_gpu_host_transport(nb, tmp_path, world, overlap):
         wp, wv = one.download()
     finally:
         one.close()
-    assert np.array_equal(gp.view(np.uint32), wp.view(np.uint32))
-    assert np.array_equal(gv.view(np.uint32), wv.view(np.uint32))
-    assert np.array_equal(np.load(out + "_force.npy").view(np.uint32), wf.view(np.uint32))
+    assert np.array_equal(np.load(out + "_pos.npy").view(u), wp.view(u)), what
+    assert np.array_equal(np.load(out + "_vel.npy").view(u), wv.view(u)), what
+    assert np.array_equal(np.load(out + "_force.npy").view(u), wf.view(u)), what
+
+
+@pytest.mark.parametrize("world,overlap", [(2, 1), (3, 0), (3, 2)])
+def test_two_processes_one_gpu_host_transport(nb, tmp_path, world, overlap):
+    n, steps, jsub = 12000 + 7, 3, 2
+    out = run_job(tmp_path, "mp", world, 600, shared_gpu_env, n=n, steps=steps, jsub=jsub, overlap=overlap, transport="host", comm=-1, fp64=False)
+    check_against_one_gpu(nb, out, n, world, jsub, steps)
 
 
 def test_bench_launches_and_supervises_its_own_workers(tmp_path):
@@ -172,33 +156,9 @@ def test_real_rccl_job_is_bit_identical_to_one_gpu(nb, tmp_path):
 def _one_rccl_job(nb, tmp_path, world, comm_name, overlap):
     comm = {"auto": nb.COMM_AUTO, "ring": nb.COMM_RING, "direct": nb.COMM_DIRECT, "allgather": nb.COMM_ALLGATHER}[comm_name]
     n, steps, jsub = 30000 + 7, 4, 2
-    out = str(tmp_path / ("rccl_%s_%d" % (comm_name, overlap)))
-    script = tmp_path / ("worker_%s_%d.py" % (comm_name, overlap))
-    script.write_text(WORKER.format(root=ROOT, n=n, steps=steps, jsub=jsub, overlap=overlap, out=out, transport="rccl", comm=comm, fp64=False))
-    port = free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), NBODY_DEVICE=str(r), HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    for p in procs:
-        o, _ = p.communicate(timeout=600)
-        assert p.returncode == 0, (comm_name, overlap, o.decode()[-3000:])
-    pos, vel = nb.make_bodies(n, seed=33)
-    one = nb.NBody(n)
-    try:
-        one.set_option(nb.OPT_JSUB, jsub)
-        one.set_option(nb.OPT_JSLICES, world)
-        one.set_option(nb.OPT_WSPLIT, int(open(out + "_wsplit.txt").read()))
-        wf = one.forces(pos)
-        one.upload(pos, vel)
-        one.step(0.01, steps)
-        wp, wv = one.download()
-    finally:
-        one.close()
-    assert np.array_equal(np.load(out + "_pos.npy").view(np.uint32), wp.view(np.uint32)), (comm_name, overlap)
-    assert np.array_equal(np.load(out + "_vel.npy").view(np.uint32), wv.view(np.uint32)), (comm_name, overlap)
-    assert np.array_equal(np.load(out + "_force.npy").view(np.uint32), wf.view(np.uint32)), (comm_name, overlap)
+    out = run_job(tmp_path, "rccl_%s_%d" % (comm_name, overlap), world, 600, lambda r: {"NBODY_DEVICE": str(r), "HSA_ENABLE_IPC_MODE_LEGACY": "0"},
+                  local_of=lambda r: r, n=n, steps=steps, jsub=jsub, overlap=overlap, transport="rccl", comm=comm, fp64=False)
+    check_against_one_gpu(nb, out, n, world, jsub, steps, what=(comm_name, overlap))
 
 
 @pytest.mark.parametrize("virtual_hosts", [False, True])
@@ -235,7 +195,7 @@ def test_bench_under_torch_distributed_run(tmp_path, virtual_hosts):
 def virtual_host_env(rank):
     """several RCCL ranks on ONE device: each poses as a host of its own (RCCL compares host id and bus id before refusing a duplicate GPU)
     and RCCL connects them through its socket transport over loopback"""
-    return {"NCCL_HOSTID": "nbody-virtual-host-%d" % rank, "NCCL_SOCKET_IFNAME": "lo", "NCCL_IB_DISABLE": "1"}
+    return dict(shared_gpu_env(rank), NCCL_HOSTID="nbody-virtual-host-%d" % rank, NCCL_SOCKET_IFNAME="lo", NCCL_IB_DISABLE="1")
 
 
 @pytest.mark.parametrize("world", [2, 3])
@@ -250,38 +210,9 @@ def test_real_rccl_ranks_on_one_gpu_over_loopback(nb, tmp_path, world):
     for comm_name, overlap in forms:
         comm = {"auto": nb.COMM_AUTO, "ring": nb.COMM_RING, "direct": nb.COMM_DIRECT, "allgather": nb.COMM_ALLGATHER}[comm_name]
         n, steps, jsub = 30000 + 7, int(os.environ.get("NBODY_TEST_RCCL_STEPS", "4")), 2      # (a soak sets the step count: profiles/r04_rccl_soak.txt)
-        out = str(tmp_path / ("lo_%s_%d" % (comm_name, overlap)))
-        script = tmp_path / ("worker_%s_%d.py" % (comm_name, overlap))
-        script.write_text(WORKER.format(root=ROOT, n=n, steps=steps, jsub=jsub, overlap=overlap, out=out, transport="rccl", comm=comm, fp64=False))
-        port = free_port()
-        procs = []
-        for r in range(world):
-            env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                       NBODY_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", **virtual_host_env(r))
-            procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-        for p in procs:
-            try:
-                o, _ = p.communicate(timeout=240)
-            except subprocess.TimeoutExpired:
-                for q in procs:
-                    q.kill()
-                raise
-            assert p.returncode == 0, (comm_name, overlap, o.decode()[-3000:])
-        pos, vel = nb.make_bodies(n, seed=33)
-        one = nb.NBody(n)
-        try:
-            one.set_option(nb.OPT_JSUB, jsub)
-            one.set_option(nb.OPT_JSLICES, world)
-            one.set_option(nb.OPT_WSPLIT, int(open(out + "_wsplit.txt").read()))
-            wf = one.forces(pos)
-            one.upload(pos, vel)
-            one.step(0.01, steps)
-            wp, wv = one.download()
-        finally:
-            one.close()
-        assert np.array_equal(np.load(out + "_pos.npy").view(np.uint32), wp.view(np.uint32)), (comm_name, overlap)
-        assert np.array_equal(np.load(out + "_vel.npy").view(np.uint32), wv.view(np.uint32)), (comm_name, overlap)
-        assert np.array_equal(np.load(out + "_force.npy").view(np.uint32), wf.view(np.uint32)), (comm_name, overlap)
+        out = run_job(tmp_path, "lo_%s_%d" % (comm_name, overlap), world, 240, virtual_host_env, n=n, steps=steps, jsub=jsub, overlap=overlap,
+                      transport="rccl", comm=comm, fp64=False)
+        check_against_one_gpu(nb, out, n, world, jsub, steps, what=(comm_name, overlap))
 
 
 def test_bench_rccl_attempt_with_virtual_hosts(tmp_path):
@@ -309,35 +240,5 @@ def test_real_rccl_fp64_job_on_one_gpu_over_loopback(nb, tmp_path):
     """config 5's arithmetic over real RCCL: a two-rank fp64 job (32-byte words through ncclAllGather), ranks sharing the GPU as separate
     virtual hosts — bit-identical to the one-GPU restatement"""
     world, n, steps, jsub = 2, 20000 + 3, 3, 2
-    out = str(tmp_path / "lo64")
-    script = tmp_path / "worker64.py"
-    script.write_text(WORKER.format(root=ROOT, n=n, steps=steps, jsub=jsub, overlap=1, out=out, transport="rccl", comm=nb.COMM_AUTO, fp64=True))
-    port = free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                   NBODY_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", **virtual_host_env(r))
-        procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    for p in procs:
-        try:
-            o, _ = p.communicate(timeout=240)
-        except subprocess.TimeoutExpired:
-            for q in procs:
-                q.kill()
-            raise
-        assert p.returncode == 0, o.decode()[-3000:]
-    pos, vel = nb.make_bodies(n, seed=33, dtype=np.float64)
-    one = nb.NBody(n, fp64=True)
-    try:
-        one.set_option(nb.OPT_JSUB, jsub)
-        one.set_option(nb.OPT_JSLICES, world)
-        one.set_option(nb.OPT_WSPLIT, int(open(out + "_wsplit.txt").read()))
-        wf = one.forces(pos)
-        one.upload(pos, vel)
-        one.step(0.01, steps)
-        wp, wv = one.download()
-    finally:
-        one.close()
-    assert np.array_equal(np.load(out + "_pos.npy").view(np.uint64), wp.view(np.uint64))
-    assert np.array_equal(np.load(out + "_vel.npy").view(np.uint64), wv.view(np.uint64))
-    assert np.array_equal(np.load(out + "_force.npy").view(np.uint64), wf.view(np.uint64))
+    out = run_job(tmp_path, "lo64", world, 240, virtual_host_env, n=n, steps=steps, jsub=jsub, overlap=1, transport="rccl", comm=nb.COMM_AUTO, fp64=True)
+    check_against_one_gpu(nb, out, n, world, jsub, steps, fp64=True)

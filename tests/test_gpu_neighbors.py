@@ -6,16 +6,15 @@ program's --closest-pair line."""
 import ctypes as C
 import os
 import re
-import socket
 import subprocess
-import sys
-import textwrap
 
 import numpy as np
 import pytest
 
 from field_common import make_points, make_skip
 from neighbors_common import bits, make_ref, planted, r2_for, same
+from pass_common import FORCE_CONFIGS, check_step_untouched
+from ranks_common import run_ranks, shared_gpu_env, worker_source
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -179,10 +178,7 @@ def test_bits_do_not_depend_on_the_queries_beside_a_query_or_the_force_configura
         assert same(a, ref.points(pos, pts, skip, r2=r2)) and same(rows, ref.rows(pos, r2=r2))
         for sel in (slice(0, 1), slice(100, 357), slice(699, 700), slice(63, 129), perm):
             assert same(eng.nearest(pts[sel], skip[sel], r2=r2), tuple(v[sel] for v in a)), sel
-        for key, val, default in ((nb.OPT_VARIANT, nb.VARIANT_SMEM, nb.VARIANT_AUTO), (nb.OPT_VARIANT, nb.VARIANT_LDS, nb.VARIANT_AUTO),
-                                  (nb.OPT_VARIANT, nb.VARIANT_READLANE, nb.VARIANT_AUTO), (nb.OPT_JSUB, 3, 0), (nb.OPT_JSLICES, 3, 0),
-                                  (nb.OPT_WSPLIT, 1, -1), (nb.OPT_WSPLIT, 16, -1), (nb.OPT_SUM_ORDER, nb.SUM_SEQ, nb.SUM_BLOCKED),
-                                  (nb.OPT_SUM_ORDER, nb.SUM_FPGA16, nb.SUM_BLOCKED)):
+        for key, val, default in FORCE_CONFIGS:
             eng.set_option(key, val)
             assert same(eng.nearest(pts, skip, r2=r2), a) and same(eng.neighbors(r2=r2), rows), (key, val)
             eng.set_option(key, default)
@@ -214,18 +210,8 @@ def test_bits_do_not_depend_on_the_device_count(nb, ref, monkeypatch):
         assert res[k][3][:2] == ref.closest_pair(now)[:2] and bits(res[k][3][2]) == bits(ref.closest_pair(now)[2]), k
 
 
-WORKER = textwrap.dedent("""
-    import os, sys
-    import numpy as np
-    sys.path.insert(0, {root!r})
-    sys.path.insert(0, os.path.join({root!r}, "tests"))
-    import torch
-    import mini_nbody_amd as nb
-    import mini_nbody_amd.distributed as D
+WORKER = """
     from field_common import make_points, make_skip
-    rank, world, local = D.init_process_group("gloo")
-    n = {n}
-    eng = D.make_engine(n, transport="host")
     pos, vel = nb.make_bodies(n, seed=33)
     eng.upload(pos, vel)
     eng.step(0.01, 3)
@@ -238,29 +224,13 @@ WORKER = textwrap.dedent("""
     p, v = eng.download()
     np.savez({out!r} + "_%d.npz" % rank, idx=idx, d2=d2, cnt=cnt, ridx=ridx, rd2=rd2, rcnt=rcnt, pair_ij=np.array(pair[:2]),
              pair_d2=np.array([pair[2]], np.float32), first=np.array([eng.config["first_body"], eng.config["n_local"]]), pos=p)
-    eng.close()
-    import torch.distributed as dist
-    dist.barrier(); dist.destroy_process_group()
-""")
+"""
 
 
 def test_two_processes_host_transport_equal_one_process(nb, ref, tmp_path):
     n, world = 1500, 2
     out = str(tmp_path / "nbr")
-    script = tmp_path / "worker.py"
-    script.write_text(WORKER.format(root=ROOT, n=n, out=out))
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK="0", MASTER_ADDR="127.0.0.1",
-                   MASTER_PORT=str(port), NBODY_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
-        procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    for p in procs:
-        o, _ = p.communicate(timeout=300)
-        assert p.returncode == 0, o.decode()[-3000:]
+    run_ranks(tmp_path, worker_source(WORKER, n=n, out=out), world, 300, env_of=shared_gpu_env)
     got = [np.load(out + "_%d.npz" % r) for r in range(world)]
     now = got[0]["pos"]
     assert same((now,), (got[1]["pos"],))
@@ -313,36 +283,11 @@ def test_rows_n65536(nb, ref, monkeypatch):
                 assert same(eng.neighbors(first, 512), want[:2] + (None,)), (first, loop)
 
 
-def run_steps(nb, n, pos, vel, plan, graph, probe, timing=False):
-    pts, on = make_points(nb, pos, 300)
-    with nb.NBody(n) as eng:
-        eng.set_option(nb.OPT_GRAPH, graph)
-        if timing:
-            eng.set_option(nb.OPT_TIMING, 1)
-        eng.upload(pos, vel)
-        for k in plan:
-            eng.step(0.01, k)
-            if probe:
-                eng.neighbors(r2=np.float32(0.01))
-                eng.nearest(pts, make_skip(n, 300, on))
-                eng.closest_pair()
-        p, v = eng.download()
-        launches = eng.kernel_time()[1] if timing else None
-    return p, v, launches
-
-
 def test_neighbor_calls_leave_the_step_untouched(nb, monkeypatch):
     n = 1500   # two blocks: a forced split takes the scratch and combine path between the steps too
-    pos, vel = nb.make_bodies(n)
-    for plan, graph, timing in (([1] * 12, 0, False), ([64, 64, 6, 64], 1, False), ([3, 5, 2], 0, True)):
-        monkeypatch.delenv("NBODY_NEIGHBORS_SPLIT", raising=False)
-        a = run_steps(nb, n, pos, vel, plan, graph, False, timing)
-        for split in (None, "2"):
-            if split:
-                monkeypatch.setenv("NBODY_NEIGHBORS_SPLIT", split)
-            b = run_steps(nb, n, pos, vel, plan, graph, True, timing)
-            assert same(a[:2], b[:2]), (plan, graph)
-            assert a[2] == b[2], "neighbour launches were counted by nbody_kernel_time"
+    pts, on = make_points(nb, nb.make_bodies(n)[0], 300)
+    probe = lambda eng: (eng.neighbors(r2=np.float32(0.01)), eng.nearest(pts, make_skip(n, 300, on)), eng.closest_pair())
+    check_step_untouched(nb, monkeypatch, n, probe, "NBODY_NEIGHBORS_SPLIT")
 
 
 def test_guards(nb):

@@ -21,15 +21,12 @@ import pytest
 
 import oracle as O
 from field_common import numpy_field
+from pass_common import bits
 from specials_common import SIZES, VARIANTS as HOSTILE, hostile_system, near, same_nan, within
 
 pytestmark = pytest.mark.gpu
 
 TOL = 1e-5  # north_star: "within 1e-5 relative fp32 tolerance"
-
-
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else np.uint64)
 
 
 def maxnorm_rel(a, b):

@@ -2,27 +2,14 @@
 (mini_nbody_amd/sharding.py — slices, ring exchange, ascending combine, kick, drift) with the oracle as
 the per-segment force function (tests may; the product's force function is the HIP kernel) and real
 torch.distributed send/recv for the ring, and must reproduce the single-process result bit for bit."""
-import os
-import socket
-import subprocess
-import sys
-import textwrap
-
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from ranks_common import run_ranks, worker_source
 
-WORKER = textwrap.dedent("""
-    import os, sys
-    import numpy as np
-    import torch, torch.distributed as dist
-    sys.path.insert(0, {root!r}); sys.path.insert(0, os.path.join({root!r}, "oracle"))
+WORKER = """
     import oracle as O
-    import mini_nbody_amd as nb
     S = nb.sharding
-    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
-    dist.init_process_group("gloo", rank=rank, world_size=world)
     ora = O.Oracle(fast=False)
     n, sub, steps, dt = {n}, {sub}, {steps}, np.float32(0.01)
     pos, vel = nb.make_bodies(n, seed=5)
@@ -50,16 +37,7 @@ WORKER = textwrap.dedent("""
         cur ^= 1
         have_all = world == 1
     np.save({out!r} + "_pos%d.npy" % rank, buf[cur][f0:f1]); np.save({out!r} + "_vel%d.npy" % rank, my_vel)
-    dist.barrier(); dist.destroy_process_group()
-""")
-
-
-def free_port():
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+"""
 
 
 def single_process(nb, oracle, n, P, sub, steps, block):
@@ -74,17 +52,8 @@ def single_process(nb, oracle, n, P, sub, steps, block):
 def test_gloo_ring_matches_single_process(nb, oracle, tmp_path, world, n, sub, block):
     steps = 3
     out = str(tmp_path / "r")
-    script = tmp_path / "worker.py"
-    script.write_text(WORKER.format(root=ROOT, n=n, sub=sub, steps=steps, out=out, block=block))
-    port = free_port()
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port),
-                   OMP_NUM_THREADS="1")
-        procs.append(subprocess.Popen([sys.executable, str(script)], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    for p in procs:
-        o, _ = p.communicate(timeout=300)
-        assert p.returncode == 0, o.decode()[-3000:]
+    run_ranks(tmp_path, worker_source(WORKER, engine=None, n=n, sub=sub, steps=steps, out=out, block=block), world, 300,
+              env_of=lambda r: {"OMP_NUM_THREADS": "1"})
     want_p, want_v = single_process(nb, oracle, n, world, sub, steps, block)
     got_p = np.concatenate([np.load(out + "_pos%d.npy" % r) for r in range(world)])
     got_v = np.concatenate([np.load(out + "_vel%d.npy" % r) for r in range(world)])

@@ -4,6 +4,9 @@
 // gfx950 only.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "nbody_internal.hpp"
 #include "nbody_kernels.hpp"
 
@@ -13,60 +16,81 @@ using namespace nbk;
 
 namespace {
 
-template <typename K>
-int launch_k(K kernel, const nbl::KernelSel& s, hipStream_t stream, dim3 grid, const ForceArgs& a) {
-  if (s.dyn_lds > 64 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-  }
-  hipLaunchKernelGGL(kernel, grid, dim3(wg_threads(a.wsplit)), s.dyn_lds, stream, a);
-  return (int)hipGetLastError();
-}
+// Every force kernel has the signature void(ForceArgs): which one a launch takes is a function of KernelSel and of three fields of
+// ForceArgs (wsplit, fpga16, long_buffers), written once here.  tests/test_force_dispatch.py pins it, fallbacks included.
+using ForceKernel = void (*)(ForceArgs);
 
-template <int R, int ARITH>
-int launch_f32_RA(const nbl::KernelSel& s, hipStream_t st, dim3 grid, const ForceArgs& a) {
-  if constexpr (R == 8) {   // 8 bodies per lane only exists for the SMEM variant
-    return launch_k(force_smem_f32<R, ARITH, 1>, s, st, grid, a);
-  } else {
-    switch (s.variant) {
-      case NBODY_VARIANT_LDS:
-        if (s.tile >= 1024) return launch_k(force_lds_f32<R, ARITH, 1024>, s, st, grid, a);
-        if (s.tile >= 512) return launch_k(force_lds_f32<R, ARITH, 512>, s, st, grid, a);
-        return launch_k(force_lds_f32<R, ARITH, 256>, s, st, grid, a);
-      case NBODY_VARIANT_READLANE:
-        return launch_k(force_readlane_f32<R, ARITH>, s, st, grid, a);
-      default:
-        if constexpr (R == 1) {
-          if (a.wsplit == 16) return launch_k(force_smem_f32<1, ARITH, 16>, s, st, grid, a);
-          if (a.wsplit == 4) return launch_k(force_smem_f32<1, ARITH, 4>, s, st, grid, a);
-        }
-        return launch_k(force_smem_f32<R, ARITH, 1>, s, st, grid, a);
-    }
-  }
+template <int... Cs> using Ints = std::integer_sequence<int, Cs...>;
+// a run-time value as a compile-time constant: f(std::integral_constant<int, C>) for the first C of the list that equals v, for the
+// LAST of the list when none does (the fallback)
+template <int C, int... Rest, typename F>
+ForceKernel on_value(Ints<C, Rest...>, int v, F f) {
+  if constexpr (sizeof...(Rest) == 0) return f(std::integral_constant<int, C>{});
+  else return v == C ? f(std::integral_constant<int, C>{}) : on_value(Ints<Rest...>{}, v, f);
 }
+template <typename F> ForceKernel on_arith(int arith, F f) { return on_value(Ints<NBODY_ARITH_REFERENCE, NBODY_ARITH_STRICT, NBODY_ARITH_REFERENCE_STRICT, 0>{}, arith, f); }
+template <typename F> ForceKernel on_wsplit(int wsplit, F f) { return on_value(Ints<16, 4, 1>{}, wsplit, f); }
+// bodies per lane: 8 only exists in fp32 (and there only for the SMEM kernel, see below)
+template <bool FP64, typename F> ForceKernel on_rows_per_lane(int R, F f) {
+  if constexpr (FP64) return on_value(Ints<1, 2, 4>{}, R, f);
+  else return on_value(Ints<1, 2, 8, 4>{}, R, f);
+}
+template <typename F> ForceKernel on_lds_tile(int tile, F f) { return on_value(Ints<1024, 512, 256>{}, tile >= 1024 ? 1024 : tile >= 512 ? 512 : 256, f); }
+// the forms of the hand-scheduled loops (NBODY_OPT_ISA_PHASE); whatever is not in a list runs the product loop, form 1
+using IsaPhasesF64 = Ints<2, 0, 1>;
+#ifdef NBODY_DIAG_LOOPS   // the diagnostic build only extends the list (NB_DIAG_LOOP_FORMS, nbody_kernels.hpp: some are TIMING-ONLY, WRONG RESULTS)
+#define NB_LIST_FORM(N) N,
+using IsaPhasesF32 = Ints<0, NB_DIAG_LOOP_FORMS(NB_LIST_FORM) 1>;
+#undef NB_LIST_FORM
+#else
+using IsaPhasesF32 = Ints<0, 1>;
+#endif
 
-template <int R>
-int launch_f32_R(const nbl::KernelSel& s, hipStream_t st, dim3 grid, const ForceArgs& a) {
-  switch (s.arith) {
-    case NBODY_ARITH_REFERENCE: return launch_f32_RA<R, 1>(s, st, grid, a);
-    case NBODY_ARITH_STRICT: return launch_f32_RA<R, 2>(s, st, grid, a);
-    case NBODY_ARITH_REFERENCE_STRICT: return launch_f32_RA<R, 3>(s, st, grid, a);
-    default: return launch_f32_RA<R, 0>(s, st, grid, a);
-  }
-}
+// the 16-row FPGA kernel: small launches of ONE segment, sixteen rows x sixteen chains per 256-thread workgroup (grid.x counts 16-row units)
+bool takes_fpga_rows16(const nbl::KernelSel& s, const ForceArgs& a) { return !s.fp64 && a.fpga16 && s.fpga_rows16; }
 
-// the hand-scheduled fp32 loop in form PH (NBODY_OPT_ISA_PHASE), with or without the wave split
-template <int PH>
-int launch_isa_f32(const nbl::KernelSel& s, hipStream_t st, dim3 grid, const ForceArgs& a) {
-  if constexpr (PH <= 1) {   // the 16-wave form exists for the product loop and its placement twin (resolve_config sees to it)
-    if (a.wsplit == 16) return launch_k(force_isa_f32<PH, 16>, s, st, grid, a);
+ForceKernel select_force_kernel(const nbl::KernelSel& s, const ForceArgs& a) {
+  if (s.fp64 && s.variant == NBODY_VARIANT_ISA)
+    return on_value(IsaPhasesF64{}, s.isa_phase, [&](auto PH) {
+      return on_wsplit(a.wsplit, [](auto WS) -> ForceKernel { return force_isa_f64<decltype(PH)::value, decltype(WS)::value>; });
+    });
+  if (s.fp64)   // STRICT = NBODY_ARITH_STRICT / _REFERENCE_STRICT: IEEE 1/sqrt (fp64 has one d2 form: the bit-0 distinction is fp32's)
+    return on_value(Ints<1, 0>{}, (s.arith & 2) ? 1 : 0, [&](auto STRICT) {
+      return on_rows_per_lane<true>(s.R, [&](auto R) -> ForceKernel {
+        constexpr int r = decltype(R)::value, strict = decltype(STRICT)::value;
+        if constexpr (r == 1) return on_wsplit(a.wsplit, [](auto WS) -> ForceKernel { return force_smem_f64<1, decltype(WS)::value, strict>; });
+        else return force_smem_f64<r, 1, strict>;   // the wave split is for one body per lane
+      });
+    });
+  if (a.fpga16)
+    return on_arith(s.arith, [&](auto A) -> ForceKernel {
+      constexpr int arith = decltype(A)::value;
+      if (s.fpga_rows16) return force_fpga16r_f32<arith>;
+      if (a.wsplit != 16) return force_fpga16_f32<arith>;
+      return s.fpga_lds ? force_fpga16w_lds_f32<arith>     // sources staged through LDS (the default of the sixteen-wave form)
+                        : force_fpga16w_f32<arith>;
+    });
+  if (s.variant == NBODY_VARIANT_ISA) {   // one body per lane, fast arithmetic only (resolve_config guarantees both)
+    if (a.long_buffers) return on_wsplit(a.wsplit, [](auto WS) -> ForceKernel { return force_isa_long_f32<decltype(WS)::value>; });
+    return on_value(IsaPhasesF32{}, s.isa_phase, [&](auto PH) {
+      return on_wsplit(a.wsplit, [](auto WS) -> ForceKernel {
+        // the 16-wave form exists for the product loop and its placement twin (resolve_config sees to it)
+        constexpr int ph = decltype(PH)::value, ws = (ph <= 1 || decltype(WS)::value != 16) ? decltype(WS)::value : 1;
+        return force_isa_f32<ph, ws>;
+      });
+    });
   }
-  return a.wsplit == 4 ? launch_k(force_isa_f32<PH, 4>, s, st, grid, a) : launch_k(force_isa_f32<PH, 1>, s, st, grid, a);
-}
-template <int PH>
-int launch_isa_f64(const nbl::KernelSel& s, hipStream_t st, dim3 grid, const ForceArgs& a) {
-  if (a.wsplit == 16) return launch_k(force_isa_f64<PH, 16>, s, st, grid, a);
-  return a.wsplit == 4 ? launch_k(force_isa_f64<PH, 4>, s, st, grid, a) : launch_k(force_isa_f64<PH, 1>, s, st, grid, a);
+  return on_rows_per_lane<false>(s.R, [&](auto R) {
+    return on_arith(s.arith, [&](auto A) -> ForceKernel {
+      constexpr int r = decltype(R)::value, arith = decltype(A)::value;
+      if constexpr (r != 8) {   // 8 bodies per lane only exists for the SMEM variant
+        if (s.variant == NBODY_VARIANT_LDS) return on_lds_tile(s.tile, [](auto TILE) -> ForceKernel { return force_lds_f32<r, arith, decltype(TILE)::value>; });
+        if (s.variant == NBODY_VARIANT_READLANE) return force_readlane_f32<r, arith>;
+      }
+      if constexpr (r == 1) return on_wsplit(a.wsplit, [](auto WS) -> ForceKernel { return force_smem_f32<1, arith, decltype(WS)::value>; });
+      else return force_smem_f32<r, arith, 1>;
+    });
+  });
 }
 
 }  // namespace
@@ -82,99 +106,15 @@ NBL_HIDDEN bool diag_build() {
 }
 
 NBL_HIDDEN int launch_force_kernel(const KernelSel& s, hipStream_t st, dim3 grid, const ForceArgs& a) {
-  const int R = s.R;
-  if (s.fp64 && s.variant == NBODY_VARIANT_ISA) {
-    if (s.isa_phase == 2) return launch_isa_f64<2>(s, st, grid, a);
-    return s.isa_phase == 0 ? launch_isa_f64<0>(s, st, grid, a) : launch_isa_f64<1>(s, st, grid, a);
+  const ForceKernel kernel = select_force_kernel(s, a);
+  const bool rows16 = takes_fpga_rows16(s, a);   // its own block shape; launched without dynamic LDS, hence without the attribute call
+  const size_t dyn_lds = rows16 ? 0 : s.dyn_lds;
+  if (dyn_lds > 64 * 1024) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) return (int)e;
   }
-  if (s.fp64 && (s.arith & 2)) {   // NBODY_ARITH_STRICT / _REFERENCE_STRICT: IEEE 1/sqrt (fp64 has one d2 form: the bit-0 distinction is fp32's)
-    switch (R) {
-      case 1:
-        if (a.wsplit == 16) return launch_k(force_smem_f64<1, 16, 1>, s, st, grid, a);
-        return a.wsplit == 4 ? launch_k(force_smem_f64<1, 4, 1>, s, st, grid, a) : launch_k(force_smem_f64<1, 1, 1>, s, st, grid, a);
-      case 2: return launch_k(force_smem_f64<2, 1, 1>, s, st, grid, a);
-      default: return launch_k(force_smem_f64<4, 1, 1>, s, st, grid, a);
-    }
-  }
-  if (s.fp64) {
-    switch (R) {
-      case 1:
-        if (a.wsplit == 16) return launch_k(force_smem_f64<1, 16>, s, st, grid, a);
-        return a.wsplit == 4 ? launch_k(force_smem_f64<1, 4>, s, st, grid, a) : launch_k(force_smem_f64<1, 1>, s, st, grid, a);
-      case 2: return launch_k(force_smem_f64<2, 1>, s, st, grid, a);
-      default: return launch_k(force_smem_f64<4, 1>, s, st, grid, a);
-    }
-  }
-  if (a.fpga16 && s.fpga_rows16) {   // small launches of ONE segment: sixteen rows x sixteen chains per 256-thread workgroup (grid.x counts 16-row units)
-    switch (s.arith) {
-      case NBODY_ARITH_REFERENCE: hipLaunchKernelGGL(force_fpga16r_f32<1>, grid, dim3(256), 0, st, a); break;
-      case NBODY_ARITH_STRICT: hipLaunchKernelGGL(force_fpga16r_f32<2>, grid, dim3(256), 0, st, a); break;
-      case NBODY_ARITH_REFERENCE_STRICT: hipLaunchKernelGGL(force_fpga16r_f32<3>, grid, dim3(256), 0, st, a); break;
-      default: hipLaunchKernelGGL(force_fpga16r_f32<0>, grid, dim3(256), 0, st, a); break;
-    }
-    return (int)hipGetLastError();
-  }
-  if (a.fpga16 && a.wsplit == 16 && s.fpga_lds) {   // sources staged through LDS (the default of the sixteen-wave form)
-    switch (s.arith) {
-      case NBODY_ARITH_REFERENCE: return launch_k(force_fpga16w_lds_f32<1>, s, st, grid, a);
-      case NBODY_ARITH_STRICT: return launch_k(force_fpga16w_lds_f32<2>, s, st, grid, a);
-      case NBODY_ARITH_REFERENCE_STRICT: return launch_k(force_fpga16w_lds_f32<3>, s, st, grid, a);
-      default: return launch_k(force_fpga16w_lds_f32<0>, s, st, grid, a);
-    }
-  }
-  if (a.fpga16 && a.wsplit == 16) {
-    switch (s.arith) {
-      case NBODY_ARITH_REFERENCE: return launch_k(force_fpga16w_f32<1>, s, st, grid, a);
-      case NBODY_ARITH_STRICT: return launch_k(force_fpga16w_f32<2>, s, st, grid, a);
-      case NBODY_ARITH_REFERENCE_STRICT: return launch_k(force_fpga16w_f32<3>, s, st, grid, a);
-      default: return launch_k(force_fpga16w_f32<0>, s, st, grid, a);
-    }
-  }
-  if (a.fpga16) {
-    switch (s.arith) {
-      case NBODY_ARITH_REFERENCE: return launch_k(force_fpga16_f32<1>, s, st, grid, a);
-      case NBODY_ARITH_STRICT: return launch_k(force_fpga16_f32<2>, s, st, grid, a);
-      case NBODY_ARITH_REFERENCE_STRICT: return launch_k(force_fpga16_f32<3>, s, st, grid, a);
-      default: return launch_k(force_fpga16_f32<0>, s, st, grid, a);
-    }
-  }
-  if (s.variant == NBODY_VARIANT_ISA) {   // one body per lane, fast arithmetic only (resolve_config guarantees both)
-    if (a.long_buffers) {
-      if (a.wsplit == 16) return launch_k(force_isa_long_f32<16>, s, st, grid, a);
-      return a.wsplit == 4 ? launch_k(force_isa_long_f32<4>, s, st, grid, a) : launch_k(force_isa_long_f32<1>, s, st, grid, a);
-    }
-    switch (s.isa_phase) {
-      case 0: return launch_isa_f32<0>(s, st, grid, a);
-#ifdef NBODY_DIAG_LOOPS
-      case 2: return launch_isa_f32<2>(s, st, grid, a);     // 2, 9..13, 16..18: the same operations in other encodings (bit-identical)
-      case 3: return launch_isa_f32<3>(s, st, grid, a);     // 3..8, 14, 15: TIMING-ONLY forms, WRONG RESULTS
-      case 4: return launch_isa_f32<4>(s, st, grid, a);
-      case 5: return launch_isa_f32<5>(s, st, grid, a);
-      case 6: return launch_isa_f32<6>(s, st, grid, a);
-      case 7: return launch_isa_f32<7>(s, st, grid, a);
-      case 8: return launch_isa_f32<8>(s, st, grid, a);
-      case 9: return launch_isa_f32<9>(s, st, grid, a);
-      case 10: return launch_isa_f32<10>(s, st, grid, a);
-      case 11: return launch_isa_f32<11>(s, st, grid, a);
-      case 12: return launch_isa_f32<12>(s, st, grid, a);
-      case 13: return launch_isa_f32<13>(s, st, grid, a);
-      case 14: return launch_isa_f32<14>(s, st, grid, a);
-      case 15: return launch_isa_f32<15>(s, st, grid, a);
-      case 16: return launch_isa_f32<16>(s, st, grid, a);
-      case 17: return launch_isa_f32<17>(s, st, grid, a);
-      case 18: return launch_isa_f32<18>(s, st, grid, a);
-      case 19: return launch_isa_f32<19>(s, st, grid, a);
-      case 20: return launch_isa_f32<20>(s, st, grid, a);
-#endif
-      default: return launch_isa_f32<1>(s, st, grid, a);
-    }
-  }
-  switch (R) {
-    case 1: return launch_f32_R<1>(s, st, grid, a);
-    case 2: return launch_f32_R<2>(s, st, grid, a);
-    case 8: return launch_f32_R<8>(s, st, grid, a);
-    default: return launch_f32_R<4>(s, st, grid, a);
-  }
+  hipLaunchKernelGGL(kernel, grid, dim3(rows16 ? 256 : wg_threads(a.wsplit)), dyn_lds, st, a);
+  return (int)hipGetLastError();
 }
 
 // the two-launch form (NBODY_OPT_FUSE_COMBINE = 0): after the step's last force launch, add the partials

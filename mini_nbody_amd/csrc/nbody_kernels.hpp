@@ -581,15 +581,18 @@ __device__ __forceinline__ void load_rows(const ForceArgs& a, int lane_row, int 
 }
 
 // What a wave works on: its lane's first row and the sources it walks.  WS = 1: the workgroup's 256*R rows, the whole
-// segment.  WS = 4: the workgroup's 64 rows (lane l of every wave owns the same row), piece `wave` of the segment.
-template <int R, int WS>
+// segment.  WS = 4: the workgroup's 64 rows (lane l of every wave owns the same row), piece `wave` of the segment — or, PIECES = false
+// (the FPGA order on sixteen waves, whose wave k walks the sources congruent to k), the whole segment.
+template <int R, int WS, bool PIECES = true>
 __device__ __forceinline__ void wave_work(const ForceArgs& a, int* seg, int* jb, int* je, int* lane_row) {
   int rb;
   block_segment(a, seg, jb, je, &rb);
   if constexpr (WS > 1) {
     static_assert(R == 1, "the wave split is for one body per lane");
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    piece_bounds(*jb, *je, wave, WS, jb, je);
+    if constexpr (PIECES) {
+      const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+      piece_bounds(*jb, *je, wave, WS, jb, je);
+    }
     *lane_row = a.row0 + rb * 64 + (int)(threadIdx.x & 63);
   } else {
     *lane_row = a.row0 + rb * (kBlock * R) + (int)threadIdx.x;
@@ -597,6 +600,16 @@ __device__ __forceinline__ void wave_work(const ForceArgs& a, int* seg, int* jb,
 }
 // LDS words of the wave split's hand-over (3 waves x 64 rows); one dummy word when the kernel does not split
 #define NB_WS_LDS(V4, WS) __shared__ V4 ws_sums[(WS) > 1 ? (WS) - 1 : 1][64]
+// How a force kernel opens: what its wave works on, the softening, the end of the launch's rows and the lane's R rows.  Declares seg,
+// jb, je, lane_row, eps, row_end and me[R] in the kernel's scope (a macro, not a function: the statements stay in the kernel's own body,
+// so what the timed kernels compile to does not hang on how a helper is inlined); the arguments after R are wave_work's
+#define NB_OPEN_ROWS(T, V4, R, ...)                                   \
+  int seg, jb, je, lane_row;                                          \
+  wave_work<R, __VA_ARGS__>(a, &seg, &jb, &je, &lane_row);            \
+  const T eps = (T)soft_f32();                                        \
+  const int row_end = a.row0 + a.row_count;                           \
+  V4 me[R];                                                           \
+  load_rows<T, V4, R>(a, lane_row, row_end, me)
 
 // ---------------------------------------------------------------------------
 // SMEM variant.  The source words are read with scalar loads (8 bodies = two
@@ -606,12 +619,7 @@ __device__ __forceinline__ void wave_work(const ForceArgs& a, int* seg, int* jb,
 template <int R, int ARITH, int WS>
 __global__ void __launch_bounds__(wg_threads(WS)) force_smem_f32(ForceArgs a) {
   NB_WS_LDS(f4, WS);
-  int seg, jb, je, lane_row;
-  wave_work<R, WS>(a, &seg, &jb, &je, &lane_row);
-  const float eps = soft_f32();
-  const int row_end = a.row0 + a.row_count;
-  f4 me[R];
-  load_rows<float, f4, R>(a, lane_row, row_end, me);
+  NB_OPEN_ROWS(float, f4, R, WS);
   Sums<float, R> s;
   s.clear();
   const NB_CONST f4* src = (const NB_CONST f4*)(uintptr_t)a.src;
@@ -658,6 +666,13 @@ __global__ void __launch_bounds__(wg_threads(WS)) force_smem_f32(ForceArgs a) {
 // re-measure the code-placement effect).  LONG = 1: scalar buffers of 8 bodies for launches with few waves per SIMD
 // (small N), where a 4-body buffer's 48 instructions no longer cover the ~280 ns of a scalar load.
 #include "force_loop_gfx950.inc"
+#ifdef NBODY_DIAG_LOOPS
+// `make diag` only (libnbody_hip_diag.so): the forms of the fp32 loop beside 0 and 1 — experiment encodings of the same operations
+// (2, 9..13, 16..20: bit-identical) and TIMING-ONLY forms with WRONG RESULTS (3..8, 14, 15) that price one part of the loop inside
+// the real kernel (tools/gen_force_loop.py, profiles/r02_loop_diagnostics.md).  The product library does not contain them.  This is
+// the one list of them: the kernel body below and the launch's selection (kernels.hip) are generated from it.
+#define NB_DIAG_LOOP_FORMS(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16) X(17) X(18) X(19) X(20)
+#endif
 // SGPR budgets: 81-96 SGPRs leave room for 7 waves per SIMD, <= 80 for 8 (MI355X_MICROARCH.md, "Occupancy API" row).  The
 // product loop's scalars end at s71 (78-79 with VCC etc.: 8 waves); the long-buffer loop holds 64 buffer SGPRs (106: 6-7 waves),
 // which is why it is a kernel of its own.
@@ -695,57 +710,24 @@ __device__ __forceinline__ void force_isa_f32_body(const ForceArgs& a, f4 (*ws_s
                    : [ax] "+v"(ax), [ay] "+v"(ay), [az] "+v"(az), [bx] "+v"(bx), [by] "+v"(by), [bz] "+v"(bz)            \
                    : [xi] "v"(xi), [yi] "v"(yi), [zi] "v"(zi), [eps] "s"(eps), [p] "s"(p), [groups] "s"(groups), [blk] "s"(blk) \
                    : CLOBBERS)
+#ifdef NBODY_DIAG_LOOPS
+    if constexpr (!LONG && PLACEMENT == 15) {   // form 15 reads from LDS: the lanes' own rows stand in for a tile
+      __shared__ f4 diag_tile[64];
+      if (threadIdx.x < 64) diag_tile[threadIdx.x] = me[0];
+      __syncthreads();
+    }
+#endif
     if constexpr (LONG) {   // its own kernel: the 64 buffer SGPRs would cost the product loop its 8th resident wave
       NB_RUN_LOOP(NB_FORCE_LOOP_LONG, NB_FORCE_LOOP_LONG_CLOBBERS);
     } else if constexpr (PLACEMENT == 0) {   // the product loop one 4-byte placement phase off (kept to re-measure that effect)
       NB_RUN_LOOP(NB_FORCE_LOOP_V0, NB_FORCE_LOOP_CLOBBERS);
+    }
 #ifdef NBODY_DIAG_LOOPS
-    // `make diag` only (libnbody_hip_diag.so): experiment encodings of the same operations (2, 9..13, 16..20: bit-identical)
-    // and TIMING-ONLY forms with WRONG RESULTS (3..8, 14, 15) that price one part of the loop inside the real kernel
-    // (tools/gen_force_loop.py, profiles/r02_loop_diagnostics.md).  The product library does not contain them.
-    } else if constexpr (PLACEMENT == 2) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V2, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 3) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V3, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 4) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V4, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 5) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V5, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 6) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V6, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 7) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V7, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 8) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V8, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 9) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V9, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 10) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V10, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 11) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V11, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 12) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V12, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 13) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V13, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 14) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V14, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 15) {
-      __shared__ f4 diag_tile[64];
-      if (threadIdx.x < 64) diag_tile[threadIdx.x] = me[0];
-      __syncthreads();
-      NB_RUN_LOOP(NB_FORCE_LOOP_V15, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 16) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V16, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 17) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V17, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 18) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V18, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 19) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V19, NB_FORCE_LOOP_DIAG_CLOBBERS);
-    } else if constexpr (PLACEMENT == 20) {
-      NB_RUN_LOOP(NB_FORCE_LOOP_V20, NB_FORCE_LOOP_DIAG_CLOBBERS);
+#define NB_DIAG_LOOP_FORM(N) else if constexpr (PLACEMENT == N) { NB_RUN_LOOP(NB_FORCE_LOOP_V##N, NB_FORCE_LOOP_DIAG_CLOBBERS); }
+    NB_DIAG_LOOP_FORMS(NB_DIAG_LOOP_FORM)
+#undef NB_DIAG_LOOP_FORM
 #endif
-    } else {
+    else {
       static_assert(PLACEMENT == 1 || LONG, "this loop form exists in the diagnostic build only (make diag)");
       NB_RUN_LOOP(NB_FORCE_LOOP_V1, NB_FORCE_LOOP_CLOBBERS);
     }
@@ -782,15 +764,10 @@ __global__ void __launch_bounds__(kBlock) force_lds_f32(ForceArgs a) {
   static_assert(TILE % kBlock == 0, "tile is a multiple of the workgroup");
   constexpr int LPT = TILE / kBlock;   // loads per thread per tile
   __shared__ f4 tile[2][TILE];
-  int seg, jb, je, lane_row;
-  wave_work<R, 1>(a, &seg, &jb, &je, &lane_row);
-  const float eps = soft_f32();
-  const f4* src = (const f4*)a.src;
-  const int row_end = a.row0 + a.row_count;
-  f4 me[R];
-  load_rows<float, f4, R>(a, lane_row, row_end, me);
+  NB_OPEN_ROWS(float, f4, R, 1);
   Sums<float, R> s;
   s.clear();
+  const f4* src = (const f4*)a.src;
   const bool blocked = a.sum_block > 0;
   int until_fold = blocked ? a.sum_block : 0x7fffffff;   // sources left in the running block
   const int last = a.n_src - 1;
@@ -847,16 +824,11 @@ __global__ void __launch_bounds__(kBlock) force_lds_f32(ForceArgs a) {
 // amortised over the R bodies of the lane.
 template <int R, int ARITH>
 __global__ void __launch_bounds__(kBlock) force_readlane_f32(ForceArgs a) {
-  int seg, jb, je, lane_row;
-  wave_work<R, 1>(a, &seg, &jb, &je, &lane_row);
-  const float eps = soft_f32();
-  const f4* src = (const f4*)a.src;
-  const int lane = threadIdx.x & 63;
-  const int row_end = a.row0 + a.row_count;
-  f4 me[R];
-  load_rows<float, f4, R>(a, lane_row, row_end, me);
+  NB_OPEN_ROWS(float, f4, R, 1);
   Sums<float, R> s;
   s.clear();
+  const f4* src = (const f4*)a.src;
+  const int lane = threadIdx.x & 63;
   const bool blocked = a.sum_block > 0;
   int until_fold = blocked ? a.sum_block : 0x7fffffff;
   const int last = a.n_src - 1;
@@ -918,12 +890,7 @@ __device__ __forceinline__ void rotate16(float (&p)[16], int rot) {
 
 template <int ARITH>
 __global__ void __launch_bounds__(kBlock) force_fpga16_f32(ForceArgs a) {
-  int seg, jb, je, i;
-  wave_work<1, 1>(a, &seg, &jb, &je, &i);
-  const float eps = soft_f32();
-  const int row_end = a.row0 + a.row_count;
-  f4 me[1];
-  load_rows<float, f4, 1>(a, i, row_end, me);
+  NB_OPEN_ROWS(float, f4, 1, 1);
   float px[16], py[16], pz[16];
 #pragma unroll
   for (int k = 0; k < 16; ++k) px[k] = py[k] = pz[k] = 0.0f;
@@ -989,7 +956,7 @@ __global__ void __launch_bounds__(kBlock) force_fpga16_f32(ForceArgs a) {
   Sums<float, 1> s;
   s.clear();
   s.bx[0] = tree16(px); s.by[0] = tree16(py); s.bz[0] = tree16(pz);
-  finish_rows<float, f4, 1, 1>(seg, i, row_end, me, s, nullptr);
+  finish_rows<float, f4, 1, 1>(seg, lane_row, row_end, me, s, nullptr);
 }
 
 // ---------------------------------------------------------------------------
@@ -1004,16 +971,10 @@ __global__ void __launch_bounds__(kBlock) force_fpga16_f32(ForceArgs a) {
 template <int ARITH>
 __global__ void __launch_bounds__(wg_threads(16), 8) force_fpga16w_f32(ForceArgs a) {
   NB_WS_LDS(f4, 16);
-  int seg, jb, je, rb;
-  block_segment(a, &seg, &jb, &je, &rb);
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int lane_row = a.row0 + rb * 64 + (int)(threadIdx.x & 63);
-  const float eps = soft_f32();
-  const int row_end = a.row0 + a.row_count;
-  f4 me[1];
-  load_rows<float, f4, 1>(a, lane_row, row_end, me);
+  NB_OPEN_ROWS(float, f4, 1, 16, false);
   Sums<float, 1> s;
   s.clear();
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   float px = 0.0f, py = 0.0f, pz = 0.0f;
   const NB_CONST f4* src = (const NB_CONST f4*)(uintptr_t)a.src;
   constexpr int G = 8;
@@ -1053,23 +1014,18 @@ __global__ void __launch_bounds__(wg_threads(16), 8) force_fpga16w_f32(ForceArgs
 // NBODY_VARIANT_SMEM keeps that one selectable; tests: test_fpga16_order, the rtl_n*.json fixtures).  LDS: 2 x 16 KiB + the 15 KiB join.
 // Measured (profiles/r06_mailbox_rate.txt, block C's header): LEVEL with the scalar form at every size — N = 1024 11.3 us either way: the
 // launch was not load-bound but issue-bound inside its sixteen CUs, which is what force_fpga16r_f32 below is for.  Kept as the default because
-// the 16-row kernel shares its tile code and a launch's first loads no longer serialise on the scalar cache.
+// the 16-row kernel stages its sources the same way (its own statement of the tile: four loads per thread, chains by lane) and a launch's
+// first loads no longer serialise on the scalar cache.
 template <int ARITH>
 __global__ void __launch_bounds__(wg_threads(16), 8) force_fpga16w_lds_f32(ForceArgs a) {
   NB_WS_LDS(f4, 16);
   constexpr int TILE = 1024;
   __shared__ f4 tile[2][TILE];
-  int seg, jb, je, rb;
-  block_segment(a, &seg, &jb, &je, &rb);
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int t = (int)threadIdx.x;
-  const int lane_row = a.row0 + rb * 64 + (t & 63);
-  const float eps = soft_f32();
-  const int row_end = a.row0 + a.row_count;
-  f4 me[1];
-  load_rows<float, f4, 1>(a, lane_row, row_end, me);
+  NB_OPEN_ROWS(float, f4, 1, 16, false);
   Sums<float, 1> s;
   s.clear();
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int t = (int)threadIdx.x;
   float px = 0.0f, py = 0.0f, pz = 0.0f;
   const f4* gsrc = (const f4*)a.src;
   const f4 none = {0.f, 0.f, 0.f, 0.f};
@@ -1186,12 +1142,7 @@ __global__ void __launch_bounds__(256) force_fpga16r_f32(ForceArgs a) {
 template <int R, int WS, int STRICT = 0>
 __global__ void __launch_bounds__(wg_threads(WS)) force_smem_f64(ForceArgs a) {
   NB_WS_LDS(d4, WS);
-  int seg, jb, je, lane_row;
-  wave_work<R, WS>(a, &seg, &jb, &je, &lane_row);
-  const double eps = (double)soft_f32();
-  const int row_end = a.row0 + a.row_count;
-  d4 me[R];
-  load_rows<double, d4, R>(a, lane_row, row_end, me);
+  NB_OPEN_ROWS(double, d4, R, WS);
   Sums<double, R> s;
   s.clear();
   const NB_CONST d4* src = (const NB_CONST d4*)(uintptr_t)a.src;
@@ -1222,34 +1173,26 @@ __global__ void __launch_bounds__(wg_threads(WS)) force_smem_f64(ForceArgs a) {
 template <int PLACEMENT, int WS>
 __global__ void __launch_bounds__(wg_threads(WS)) force_isa_f64(ForceArgs a) {
   NB_WS_LDS(d4, WS);
-  int seg, jb, je, i;
-  wave_work<1, WS>(a, &seg, &jb, &je, &i);
-  const double eps = (double)soft_f32();
-  const int row_end = a.row0 + a.row_count;
-  d4 me[1];
-  load_rows<double, d4, 1>(a, i, row_end, me);
+  NB_OPEN_ROWS(double, d4, 1, WS);
   const double xi = me[0].x, yi = me[0].y, zi = me[0].z;
   double ax = 0.0, ay = 0.0, az = 0.0;
   int j = jb;
   const int groups = (je - jb) / NB_FORCE_LOOP_F64_GROUP;
   if (groups > 0) {
     const uint64_t p = (uint64_t)(uintptr_t)a.src + (uint64_t)jb * sizeof(d4);
+#define NB_RUN_LOOP_F64(TEXT)                                                                                        \
+      asm volatile(TEXT                                                                                                  \
+                   : [ax] "+v"(ax), [ay] "+v"(ay), [az] "+v"(az)                                                         \
+                   : [xi] "v"(xi), [yi] "v"(yi), [zi] "v"(zi), [eps] "s"(eps), [p] "s"(p), [groups] "s"(groups)          \
+                   : NB_FORCE_LOOP_F64_CLOBBERS)
     if constexpr (PLACEMENT == 2) {   // experiment: eps and 3/8 from VGPR pairs instead of SGPR pairs
-      asm volatile(NB_FORCE_LOOP_F64_V2
-                   : [ax] "+v"(ax), [ay] "+v"(ay), [az] "+v"(az)
-                   : [xi] "v"(xi), [yi] "v"(yi), [zi] "v"(zi), [eps] "s"(eps), [p] "s"(p), [groups] "s"(groups)
-                   : NB_FORCE_LOOP_F64_CLOBBERS);
+      NB_RUN_LOOP_F64(NB_FORCE_LOOP_F64_V2);
     } else if constexpr (PLACEMENT == 1) {
-      asm volatile(NB_FORCE_LOOP_F64_V1
-                   : [ax] "+v"(ax), [ay] "+v"(ay), [az] "+v"(az)
-                   : [xi] "v"(xi), [yi] "v"(yi), [zi] "v"(zi), [eps] "s"(eps), [p] "s"(p), [groups] "s"(groups)
-                   : NB_FORCE_LOOP_F64_CLOBBERS);
+      NB_RUN_LOOP_F64(NB_FORCE_LOOP_F64_V1);
     } else {
-      asm volatile(NB_FORCE_LOOP_F64_V0
-                   : [ax] "+v"(ax), [ay] "+v"(ay), [az] "+v"(az)
-                   : [xi] "v"(xi), [yi] "v"(yi), [zi] "v"(zi), [eps] "s"(eps), [p] "s"(p), [groups] "s"(groups)
-                   : NB_FORCE_LOOP_F64_CLOBBERS);
+      NB_RUN_LOOP_F64(NB_FORCE_LOOP_F64_V0);
     }
+#undef NB_RUN_LOOP_F64
     j += groups * NB_FORCE_LOOP_F64_GROUP;
   }
   const NB_CONST d4* src = (const NB_CONST d4*)(uintptr_t)a.src;
@@ -1260,7 +1203,7 @@ __global__ void __launch_bounds__(wg_threads(WS)) force_isa_f64(ForceArgs a) {
   Sums<double, 1> s;
   s.clear();
   s.bx[0] = ax; s.by[0] = ay; s.bz[0] = az;
-  finish_rows<double, d4, 1, WS>(seg, i, row_end, me, s, ws_sums);
+  finish_rows<double, d4, 1, WS>(seg, lane_row, row_end, me, s, ws_sums);
 }
 
 // ---------------------------------------------------------------------------

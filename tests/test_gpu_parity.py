@@ -566,9 +566,10 @@ def test_fpga16_order(nb, oracle_fast, engine_factory, wsplit):
     """16 strided partials + pairwise tree, S/fxyz.vhd:129-184, S/final_adder.vhd:88-104 — with the sixteen
     partial sums in one lane (NBODY_OPT_WSPLIT 1, force_fpga16_f32) and on the sixteen waves of a workgroup (16 = the automatic
     choice, force_fpga16w_f32): the same chains, rotation and tree, hence the same bits.  Sizes: below 16 (results without items),
-    ragged tails of every kind, several 64-row workgroups, more than 8 items per chain (the loads-ahead loop) and N = 32767, the
-    mailbox's maximum."""
-    for n in (1, 5, 15, 16, 17, 100, 129, 257, 1031, 4099, 32767):
+    ragged tails of every kind, several 64-row workgroups, more than 8 items per chain (the loads-ahead loop), the edges of the
+    1024-source LDS tile (1023 .. 1025 and 2048, 2049 as one segment through the 16-row kernel; 3072 and 3075, whose three-segment
+    case hands the staged sixteen-wave kernel segments of exactly 1024 and 1025) and N = 32767, the mailbox's maximum."""
+    for n in (1, 5, 15, 16, 17, 100, 129, 257, 1023, 1024, 1025, 1031, 2048, 2049, 3072, 3075, 4099, 32767):
         pos, _ = nb.make_bodies(n, seed=2)
         eng = engine_factory(n)
         eng.set_option(nb.OPT_SUM_ORDER, nb.SUM_FPGA16)

@@ -2,7 +2,7 @@
  *
  * Plain C99: pointers, ints, floats.  No HIP, torch or C++ types cross this
  * boundary.  The library behind it is hand-written HIP for gfx950
- * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, field.hip, neighbors.hip, knn.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, field.cpp, neighbors.cpp, knn.cpp); there is
+ * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, field.hip, neighbors.hip, knn.hip, fof.hip, hist.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, field.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp); there is
  * no CPU fallback: every entry
  * point fails with NBODY_ERR_NO_DEVICE when no GPU is usable.
  *
@@ -493,6 +493,53 @@ int nbody_knn_d(const double *points, int m, const int *skip, int k, int *idx, d
  * mailbox is served. */
 int nbody_fof(float b2, int *group, int *n_groups, int *rounds);
 int nbody_fof_d(double b2, int *group, int *n_groups, int *rounds);
+
+/* ---- radial counts, pair histogram: how many bodies lie in each shell of distance (not in the reference) ----
+ * The sections above say who is nearest and who hangs together; this one says how many: a density profile around a body or a centre,
+ * and the pair counts DD(r) of the whole system, from which the radial distribution function g(r) and the two-point correlation
+ * function follow.  Queries, skip and d2 are exactly the neighbour pass's: in the context precision T, for every body j,
+ *   dx = xj - x;  dy = yj - y;  dz = zj - z;   d2_j = fma(dx, dx, fma(dy, dy, dz * dz))
+ * no softening, independent of NBODY_OPT_ARITH, every operation IEEE-exact.
+ * EDGES: edges2 holds n_bins + 1 squared radii in T, 1 <= n_bins <= NBODY_HIST_MAX_BINS, no NaN, non-decreasing.  Equal neighbours
+ * give an empty bin; edges2[n_bins] = +inf is legal.
+ * THE STATEMENT OF RECORD IS CUMULATIVE: for a query,
+ *   c_b = #{ non-skipped j : d2_j < edges2[b] }   and   counts[b] = c_(b+1) - c_b,
+ * with non-decreasing edges the number of j with edges2[b] <= d2_j < edges2[b+1].  So a NaN d2_j is below nothing and is never
+ * counted; a d2_j that overflowed to +inf is never counted either (it is not below +inf); a coincident distinct body (d2 = +0) falls
+ * in the bin that holds 0.
+ * nbody_radial_counts_rows(_d): the queries are the bodies themselves, each excluding itself; rows exactly as in nbody_forces_rows and
+ *   nbody_neighbors_rows.  counts: n_rows x n_bins ints, row-major: bin b of query p at [p * n_bins + b], as nbody_knn lays out its lists.
+ * nbody_radial_counts(_d): the queries are m caller points; points, skip and the division over the devices as in nbody_nearest.
+ *   nbody_init_rank: every rank asks for its own points, m and n_bins may differ between ranks.
+ * nbody_pair_histogram(_d): pairs[b] is the number of unordered pairs i < j of the whole system in bin b.  d2 is symmetric bit for bit
+ *   (the section above), so pairs[b] is half the sum over all N rows of the rows form's counts[b], and that sum is even.  The per-row
+ *   counts are int32, the totals 64-bit (N = 70 000 already has more than 2^31 pairs).  Every device or rank runs the rows pass over its
+ *   own rows, in batches under the scratch bound below, and adds them on the device to n_bins 64-bit sums; the per-row counts never go
+ *   to the host.  The sums are added in rank order and halved after the sum over the ranks (one rank's own sum may be odd: a pair
+ *   across ranks is counted once per side).  In an nbody_init_rank job it is collective and every rank returns the same values.
+ * The values depend on the N positions, the query, its skip and the edges alone — not on m, on where the query stands, on the launch
+ * shape (NBODY_HIST_SPLIT, NBODY_HIST_LOOP below), on the arithmetic, on the force configuration or on the device or rank count.  A bin
+ * that merges adjacent bins of a finer edge list holds their sum.  nbody_radial_counts* with edges2 = {0, nextafter(r2, +inf)} equals
+ * the neighbour pass's count at r2, for finite r2 >= 0.  The sums are integer sums (the pair histogram's with integer atomics), exact
+ * in every order: two calls return identical values.
+ * All three bring the other slices' positions first (collective in nbody_init_rank contexts) and, like their siblings, leave positions,
+ * velocities, the arrival counters, the captured step graph and the force-kernel timer as they were.
+ * Environment, read on every call: NBODY_HIST_SPLIT = c >= 1 walks the sources in min(c, blocks of 1024) chunks side by side (unset or 0:
+ * chosen from the number of queries and the CU count); NBODY_HIST_SCRATCH_MB (default 256, fractions allowed) bounds the n_bins * 4
+ * bytes per query and chunk a split launch stores, larger calls go in consecutive batches of queries, and it bounds the per-row counts
+ * of nbody_pair_histogram in the same way (never below one workgroup's 256 rows); NBODY_HIST_LOOP = 1 compares every pair with every
+ * edge, 2 first takes the minimum of each aligned window of 64 sources and walks it with the counters only if some query of the wave
+ * has a body below the last edge (unset: 2, and 1 where the last edge is +inf and no window can be left out).  Same values in every case.
+ * NBODY_ERR_NOT_INIT without a context; NBODY_ERR_ARG, checked before anything is launched or written, for a NULL output, edges2 or
+ * points, n_bins < 1 or > NBODY_HIST_MAX_BINS, a NaN or a descending edge, a bad row range, m < 1 or a skip value outside [-1, N);
+ * NBODY_ERR_STATE for the other precision's entry point or while the mailbox is served. */
+#define NBODY_HIST_MAX_BINS 32
+int nbody_radial_counts_rows(int first_row, int n_rows, const float *edges2, int n_bins, int *counts);
+int nbody_radial_counts_rows_d(int first_row, int n_rows, const double *edges2, int n_bins, int *counts);
+int nbody_radial_counts(const float *points, int m, const int *skip, const float *edges2, int n_bins, int *counts);
+int nbody_radial_counts_d(const double *points, int m, const int *skip, const double *edges2, int n_bins, int *counts);
+int nbody_pair_histogram(const float *edges2, int n_bins, long long *pairs);
+int nbody_pair_histogram_d(const double *edges2, int n_bins, long long *pairs);
 
 #ifdef __cplusplus
 }

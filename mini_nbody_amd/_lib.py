@@ -25,6 +25,7 @@ COMM_RING, COMM_ALLGATHER, COMM_AUTO, COMM_DIRECT = 0, 1, 2, 3
 (ENERGY_KINETIC, ENERGY_POTENTIAL, ENERGY_PX, ENERGY_PY, ENERGY_PZ, ENERGY_LX, ENERGY_LY, ENERGY_LZ, ENERGY_WORDS) = range(9)
 
 KNN_MAX = 32   # NBODY_KNN_MAX
+HIST_MAX_BINS = 32   # NBODY_HIST_MAX_BINS
 
 ERR_NOT_INIT, ERR_ARG, ERR_NO_DEVICE, ERR_RCCL_LOAD, ERR_STATE, ERR_UNSUPPORTED = 1001, 1002, 1003, 1004, 1005, 1006
 
@@ -40,6 +41,8 @@ SYMBOLS = [
     "nbody_mailbox_serve", "nbody_energy", "nbody_potential_rows", "nbody_potential_rows_d", "nbody_field", "nbody_field_d",
     "nbody_neighbors_rows", "nbody_neighbors_rows_d", "nbody_nearest", "nbody_nearest_d", "nbody_closest_pair", "nbody_closest_pair_d",
     "nbody_knn_rows", "nbody_knn_rows_d", "nbody_knn", "nbody_knn_d", "nbody_fof", "nbody_fof_d",
+    "nbody_radial_counts_rows", "nbody_radial_counts_rows_d", "nbody_radial_counts", "nbody_radial_counts_d",
+    "nbody_pair_histogram", "nbody_pair_histogram_d",
 ]
 
 
@@ -102,6 +105,10 @@ def load():
         "nbody_knn_rows": [i, i, i, C.POINTER(i), fp], "nbody_knn_rows_d": [i, i, i, C.POINTER(i), dp],
         "nbody_knn": [fp, i, C.POINTER(i), i, C.POINTER(i), fp], "nbody_knn_d": [dp, i, C.POINTER(i), i, C.POINTER(i), dp],
         "nbody_fof": [f, C.POINTER(i), C.POINTER(i), C.POINTER(i)], "nbody_fof_d": [d, C.POINTER(i), C.POINTER(i), C.POINTER(i)],
+        "nbody_radial_counts_rows": [i, i, fp, i, C.POINTER(i)], "nbody_radial_counts_rows_d": [i, i, dp, i, C.POINTER(i)],
+        "nbody_radial_counts": [fp, i, C.POINTER(i), fp, i, C.POINTER(i)],
+        "nbody_radial_counts_d": [dp, i, C.POINTER(i), dp, i, C.POINTER(i)],
+        "nbody_pair_histogram": [fp, i, C.POINTER(C.c_longlong)], "nbody_pair_histogram_d": [dp, i, C.POINTER(C.c_longlong)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

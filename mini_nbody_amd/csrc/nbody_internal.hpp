@@ -4,7 +4,7 @@
 //                 and its HIP graph, state transfer, the strict gate
 //   comm.cpp      RCCL (resolved with dlopen), the transfer plans, the all-gather of a step, probes and self-tests
 //   mailbox.cpp   the reference's mailbox: RAM images, one request (a force pass over a Problem of the request's own N), the service thread
-//   diag_pass.hpp  what the five diagnostic passes below share on the device: the potential's pair arithmetic, the lane and wave
+//   diag_pass.hpp  what the six diagnostic passes below share on the device: the potential's pair arithmetic, the lane and wave
 //                  preamble of a one-query-per-lane kernel, the block and workgroup sizes (read by their *_args.hpp)
 //   query_pass.hpp what they share on the host: ranges over the locals, upload, the split's batches, launch-then-copy-back, the ranks' words
 //   energy.hip    the energy pass's kernels (energy_args.hpp: its argument block and launch functions)
@@ -17,7 +17,9 @@
 //   knn.cpp       nbody_knn_rows(_d), nbody_knn(_d): the k nearest bodies of a row or a point and their squared distances
 //   fof.hip       the friends-of-friends link pass's kernels (fof_args.hpp: its argument block and launch functions)
 //   fof.cpp       nbody_fof(_d): the groups of a linking length, rounds of the link pass under a union-find on the host
-// Only kernels.hip, energy.hip, field.hip, neighbors.hip, knn.hip and fof.hip are device code (a minute of hipcc, as one code object through device.hip);
+//   hist.hip      the radial-count pass's kernels (hist_args.hpp: its argument block and launch functions)
+//   hist.cpp      nbody_radial_counts_rows(_d), nbody_radial_counts(_d), nbody_pair_histogram(_d): bodies per shell of distance, pair counts
+// Only kernels.hip, energy.hip, field.hip, neighbors.hip, knn.hip, fof.hip and hist.hip are device code (a minute of hipcc, as one code object through device.hip);
 // the others are host C++ (seconds).  gfx950 only, no CPU fallback anywhere.
 // Ownership: every stream, event, device and pinned allocation the context uses lives in an owning handle (Stream, Event, DevMem, Pinned,
 // below) that is a member of Global or of one of its Locals; nbody_shutdown() releases them all, and nothing does at process exit (see `g`).
@@ -130,12 +132,14 @@ struct Local {
   DevMem en_part;                      // energy pass (energy.cpp): per-workgroup fp64 partials of {T, U, P, L} ...
   DevMem en_tot;                       // ... the ranks' totals, 8 doubles at word `rank` (all P after an all-gather) ...
   DevMem en_phi;                       // ... and phi of the rows asked for (context precision)
-  DevMem q_points, q_skip;             // field, neighbour and knn pass (query_pass.hpp): this local's range of the caller's points and skip indices ...
-  DevMem q_scratch;                    // ... and what a launch whose sources are split leaves for its combine (field_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp)
+  DevMem q_points, q_skip;             // field, neighbour, knn and radial-count pass (query_pass.hpp): this local's range of the caller's points and skip indices ...
+  DevMem q_scratch;                    // ... and what a launch whose sources are split leaves for its combine (field_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp, hist_args.hpp)
   DevMem fd_accel, fd_phi;             // field pass (field.cpp): the points' outputs (context precision)
   DevMem nb_idx, nb_d2, nb_count;      // neighbour pass (neighbors.cpp): the queries' outputs (d2 in the context precision) ...
   DevMem nb_best;                      // ... and the ranks' closest pairs, one BestPair at word `rank` (all P after an all-gather)
   DevMem kn_idx, kn_d2;                // knn pass (knn.cpp): the queries' outputs, k entries each (d2 in the context precision)
+  DevMem hi_count;                     // radial-count pass (hist.cpp): the queries' counts, n_bins each ...
+  DevMem hi_sums;                      // ... and the ranks' pair-histogram sums, NBODY_HIST_MAX_BINS 64-bit sums at word `rank` (all P after an all-gather)
   DevMem fo_label, fo_rows, fo_min;    // fof pass (fof.cpp): the N labels of a round, this local's range of the active rows and their m_i
   int cur = 0;
   bool all_present = true;             // pos[cur] holds every slice

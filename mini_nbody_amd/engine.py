@@ -287,6 +287,63 @@ class NBody:
         self.fof_rounds = rounds.value
         return group, n_groups.value
 
+    def _hist_edges(self, edges2):
+        e = np.ascontiguousarray(np.asarray(edges2, self.dtype).reshape(-1))
+        if not 2 <= len(e) <= L.HIST_MAX_BINS + 1:
+            raise ValueError("expected 2..%d edges (1..%d bins)" % (L.HIST_MAX_BINS + 1, L.HIST_MAX_BINS))
+        if np.isnan(e).any() or (e[1:] < e[:-1]).any():
+            raise ValueError("edges2 must hold no NaN and must not descend")
+        return e, len(e) - 1, e.ctypes.data_as(C.POINTER(C.c_double if self.fp64 else C.c_float))
+
+    def radial_counts(self, edges2, first_row=0, n_rows=None):
+        """counts, (n_rows, n_bins) int32, of n_rows bodies from first_row (rows as in forces_rows; default: all of them) from the state
+        on the device (nbody_radial_counts_rows): per body the number of other bodies j with edges2[b] <= d2_j < edges2[b + 1], d2 the
+        plain squared distance in the context precision (no softening).  edges2: 2..33 squared radii, cast to the context dtype, no
+        NaN, non-decreasing; the last may be inf.  Collective in a multi-rank job."""
+        e, nb, ep = self._hist_edges(edges2)
+        if n_rows is None:
+            n_rows = self.info(L.INFO_N_LOCAL if self._by_rank else L.INFO_N) - int(first_row)
+        if int(n_rows) < 1:
+            raise ValueError("expected at least one row")
+        counts = np.empty((int(n_rows), nb), np.int32)
+        fn = self.lib.nbody_radial_counts_rows_d if self.fp64 else self.lib.nbody_radial_counts_rows
+        L.check(fn(int(first_row), int(n_rows), ep, nb, counts.ctypes.data_as(C.POINTER(C.c_int))))
+        return counts
+
+    def radial_counts_at(self, points, edges2, skip=None):
+        """counts, (m, n_bins) int32, as radial_counts(), of the bodies on the device around arbitrary points (nbody_radial_counts).
+        points: (m, 4) words or (m, 3) in the context dtype; skip: None or m ints, each -1 or the global index of a body to leave out
+        for that point.  A point on a body without a skip counts that body in the bin that holds 0."""
+        e, nb, ep = self._hist_edges(edges2)
+        p = np.asarray(points, self.dtype)
+        if p.ndim != 2 or p.shape[1] not in (3, 4) or len(p) < 1:
+            raise ValueError("expected an (m, 4) or (m, 3) array of %s, m >= 1" % np.dtype(self.dtype).name)
+        if p.shape[1] == 3:
+            p = np.concatenate([p, np.zeros((len(p), 1), self.dtype)], axis=1)
+        p = np.ascontiguousarray(p)
+        m = len(p)
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, np.int32)
+            if sk.shape != (m,):
+                raise ValueError("skip must hold one index per point")
+        counts = np.empty((m, nb), np.int32)
+        ct = C.c_double if self.fp64 else C.c_float
+        fn = self.lib.nbody_radial_counts_d if self.fp64 else self.lib.nbody_radial_counts
+        L.check(fn(p.ctypes.data_as(C.POINTER(ct)), m, sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None, ep, nb,
+                   counts.ctypes.data_as(C.POINTER(C.c_int))))
+        return counts
+
+    def pair_histogram(self, edges2):
+        """pairs, (n_bins,) int64: the number of unordered pairs i < j of the whole system with edges2[b] <= d2_ij < edges2[b + 1]
+        (nbody_pair_histogram) — DD(r), the numerator of the radial distribution function.  edges2 as in radial_counts().  The rows'
+        counts are added on the device; collective in a multi-rank job, every rank gets the same values."""
+        e, nb, ep = self._hist_edges(edges2)
+        pairs = np.empty(nb, np.int64)
+        fn = self.lib.nbody_pair_histogram_d if self.fp64 else self.lib.nbody_pair_histogram
+        L.check(fn(ep, nb, pairs.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return pairs
+
     def comm_selftest(self):
         """Push a patterned array through the RCCL calls of the multi-GPU path (all-gather + one ring step); returns
         the bytes this rank received.  Needs the communicator of NBody(..., rank=, nranks=, uid=)."""

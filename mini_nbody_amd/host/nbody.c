@@ -8,13 +8,16 @@
  *
  * usage: nbody [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K]
  *              [--sum seq|blocked] [--block K] [--one-launch | --two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16]
- *              [--energy] [--field M] [--closest-pair]
+ *              [--energy] [--field M] [--closest-pair] [--pair-histogram B]
  * --energy: E = T + U, T and U of the state on the device (nbody_energy) before the first iteration and after the last, and the
  * relative drift, outside the timed region.
  * --field M: after the last iteration, acceleration and potential of the state on the device (nbody_field) at M points — the position
  * words of an M-body system of the same initial conditions with seed 4242 — as plain ascending fp64 sums, outside the timed region.
  * --closest-pair: after the last iteration, the two bodies of the state on the device that are closest and their plain squared distance
  * (nbody_closest_pair), outside the timed region.
+ * --pair-histogram B (1 <= B <= 32): after the last iteration, one line "pair histogram: c0 c1 ... c(B-1)", the number of unordered
+ * pairs of the state on the device per bin of squared distance (nbody_pair_histogram), outside the timed region.  The B + 1 edges are
+ * edges2[0] = 0 and edges2[b] = 2^(2 (b - B) + 4) for b >= 1: exact powers of two up to 16 in either precision.
  */
 #define _POSIX_C_SOURCE 199309L
 #include <math.h>
@@ -99,8 +102,30 @@ static int print_closest_pair(int fp64) {
   return 0;
 }
 
+/* the line of --pair-histogram */
+static int print_pair_histogram(int bins, int fp64) {
+  long long pairs[NBODY_HIST_MAX_BINS];
+  int rc;
+  if (!fp64) {
+    float e[NBODY_HIST_MAX_BINS + 1];
+    e[0] = 0.0f;
+    for (int b = 1; b <= bins; ++b) e[b] = ldexpf(1.0f, 2 * (b - bins) + 4);
+    rc = nbody_pair_histogram(e, bins, pairs);
+  } else {
+    double e[NBODY_HIST_MAX_BINS + 1];
+    e[0] = 0.0;
+    for (int b = 1; b <= bins; ++b) e[b] = ldexp(1.0, 2 * (b - bins) + 4);
+    rc = nbody_pair_histogram_d(e, bins, pairs);
+  }
+  if (rc) { fprintf(stderr, "nbody_pair_histogram failed: %s\n", nbody_error_string(rc)); return 1; }
+  printf("pair histogram:");
+  for (int b = 0; b < bins; ++b) printf(" %lld", pairs[b]);
+  printf("\n");
+  return 0;
+}
+
 int main(int argc, char **argv) {
-  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0, closest = 0;
+  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0, closest = 0, pair_hist = 0;
   double e0 = 0.0;
   unsigned long long seed = NBODY_IC_DEFAULT_SEED;
   for (int a = 1; a < argc; ++a) {
@@ -115,6 +140,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--energy")) energy = 1;
     else if (!strcmp(argv[a], "--field") && a + 1 < argc) field = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--closest-pair")) closest = 1;
+    else if (!strcmp(argv[a], "--pair-histogram") && a + 1 < argc) { pair_hist = atoi(argv[++a]); if (pair_hist < 1 || pair_hist > NBODY_HIST_MAX_BINS) { fprintf(stderr, "--pair-histogram needs 1 <= B <= %d\n", NBODY_HIST_MAX_BINS); return 2; } }
     else if (!strcmp(argv[a], "--two-launch")) two_launch = 1;
     else if (!strcmp(argv[a], "--one-launch")) two_launch = 0;
     else if (!strcmp(argv[a], "--overlap") && a + 1 < argc) overlap = atoi(argv[++a]);
@@ -124,7 +150,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--block") && a + 1 < argc) block = atoi(argv[++a]);
     else if (argv[a][0] != '-' && npos == 0) { n = atoi(argv[a]); npos++; }
     else if (argv[a][0] != '-' && npos == 1) { iters = atoi(argv[a]); npos++; }
-    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--closest-pair]\n", argv[0]); return 2; }
+    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--closest-pair] [--pair-histogram B]\n", argv[0]); return 2; }
   }
   if (field < 0) { fprintf(stderr, "--field needs M >= 1\n"); return 2; }
   if (n <= 0 || iters < 2) { fprintf(stderr, "need N > 0 and iters >= 2 (iteration 1 is warm-up)\n"); return 2; }
@@ -175,10 +201,11 @@ int main(int argc, char **argv) {
       total = now_s() - t0;
       CHECK(nbody_download(&p));
     }
-    if ((energy || field || closest) && host_loop) CHECK(nbody_upload(&p));
+    if ((energy || field || closest || pair_hist) && host_loop) CHECK(nbody_upload(&p));
     if (energy && print_energy(iters, &e0, 0)) return 1;
     if (field && print_field(field, 0)) return 1;
     if (closest && print_closest_pair(0)) return 1;
+    if (pair_hist && print_pair_histogram(pair_hist, 0)) return 1;
     double cx = 0, cy = 0, cz = 0;
     for (int i = 0; i < n; ++i) { cx += p.pos[4 * i]; cy += p.pos[4 * i + 1]; cz += p.pos[4 * i + 2]; }
     printf("checksum (sum of positions): %.9g %.9g %.9g\n", cx, cy, cz);
@@ -207,10 +234,11 @@ int main(int argc, char **argv) {
       total = now_s() - t0;
       CHECK(nbody_download_d(&p));
     }
-    if ((energy || field || closest) && host_loop) CHECK(nbody_upload_d(&p));
+    if ((energy || field || closest || pair_hist) && host_loop) CHECK(nbody_upload_d(&p));
     if (energy && print_energy(iters, &e0, 0)) return 1;
     if (field && print_field(field, 1)) return 1;
     if (closest && print_closest_pair(1)) return 1;
+    if (pair_hist && print_pair_histogram(pair_hist, 1)) return 1;
     double cx = 0, cy = 0, cz = 0;
     for (int i = 0; i < n; ++i) { cx += p.pos[4 * i]; cy += p.pos[4 * i + 1]; cz += p.pos[4 * i + 2]; }
     printf("checksum (sum of positions): %.17g %.17g %.17g\n", cx, cy, cz);

@@ -2,7 +2,7 @@
  *
  * Plain C99: pointers, ints, floats.  No HIP, torch or C++ types cross this
  * boundary.  The library behind it is hand-written HIP for gfx950
- * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, field.hip, neighbors.hip, knn.hip, fof.hip, hist.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, field.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp); there is
+ * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, field.hip, tidal.hip, neighbors.hip, knn.hip, fof.hip, hist.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, field.cpp, tidal.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp); there is
  * no CPU fallback: every entry
  * point fails with NBODY_ERR_NO_DEVICE when no GPU is usable.
  *
@@ -382,6 +382,46 @@ int nbody_potential_rows_d(int first_row, int n_rows, double *phi);
  * NULL or a skip value outside [-1, N); NBODY_ERR_STATE for the other precision's entry point or while the mailbox is served. */
 int nbody_field(const float *points, int m, const int *skip, float *accel, float *phi);
 int nbody_field_d(const double *points, int m, const int *skip, double *accel, double *phi);
+
+/* ---- tidal tensor at arbitrary points: the gradient of the field, T = grad a = -grad grad phi (not in the reference) ----
+ * For a point x and the N bodies on the device, unit masses, G = 1, eps the force's softening (bits 0x3089705F):
+ *   d = r_j - x,  inv = (|d|^2 + eps)^(-1/2),  inv2 = inv * inv,  inv3 = inv * inv2,  inv5 = inv3 * inv2
+ *   T_ab(x) = d a_a / d x_b = sum_j ( 3 d_a d_b inv5 - delta_ab inv3 )
+ * over ALL j, as the field's sums; skip[p] = a global body index leaves that body out of point p's sums (-1: nothing), exactly as in
+ * nbody_field.  T is symmetric: the result has six values per point in the order {xx, yy, zz, xy, xz, yz}.  PROPERTY: its trace is
+ * -3 eps sum_j inv5 (Poisson's equation for the softened bodies: negative, and zero only as eps -> 0).  A point that coincides with a
+ * body without skipping it gets +0 from that body off the diagonal and -eps^(-3/2) on it.  What it is for: tidal stretching and tidal
+ * radii, the eigenvalue signature of voids, sheets, filaments and knots, the linearised equations of motion, a time-step or softening
+ * criterion from |T|.
+ * Pair arithmetic follows NBODY_OPT_ARITH exactly as the field's: dx = xj - x (dy, dz likewise), inv as nbody_field states it (d2 in
+ * the FMA3 form or the reference's five roundings; v_rsq_f32 or under a strict mode (float)(1.0 / sqrt((double)d2)); fp64 contexts:
+ * the fma-contracted d2, the refined v_rsq_f64 seed or under a strict mode IEEE sqrt and divide).  Then, in the context precision T,
+ * every operation rounded once:
+ *   inv2 = inv * inv;  inv3 = inv * inv2;  inv5 = inv3 * inv2;  w = (T)3 * inv5;  wx = w * dx;  wy = w * dy;  wz = w * dz
+ *   qxx = fma(wx, dx, qxx)  qyy = fma(wy, dy, qyy)  qzz = fma(wz, dz, qzz)
+ *   qxy = fma(wx, dy, qxy)  qxz = fma(wx, dz, qxz)  qyz = fma(wy, dz, qyz)   s3 = s3 + inv3
+ * ORDER (fixed by N alone; it is the potential's):
+ *   level 1: the sources in blocks of 1024 consecutive bodies; per block the seven accumulators above from +0 in ascending j; for
+ *            j == skip[p] all seven keep their values;
+ *   level 2: the blocks' seven sums converted to fp64 and added in ascending block order from zero; then T_aa = (T)(Q_aa - S3), the
+ *            subtraction in fp64 and rounded once, and T_ab = (T)Q_ab.
+ * The bits of a point's result depend on the N source positions, the point, its skip, the arithmetic and the precision — not on m, on
+ * where the point stands in the array, on the launch shape (NBODY_TIDAL_SPLIT below), on the force configuration or on the device or
+ * rank count.  No atomics: two calls return identical bits.  DOMAIN: the field's; a square that overflows gives inv = 0 and the pair
+ * contributes +0, in every binary32 arithmetic and in both binary64 ones.
+ * points: m words {x, y, z, ignored} in the context precision, host memory.  tensor: m x 6 values.  skip: NULL, or m ints, each -1 or a
+ * global body index in [0, N).  The points are divided over the devices as nbody_field divides them; nbody_init_rank: every rank
+ * evaluates the points IT was given on its own device, the call is collective only because the other slices' positions are brought
+ * first — every rank calls it, m may differ between ranks.  It leaves positions, velocities, the arrival counters, the captured step
+ * graph and the force-kernel timer as they were.
+ * Environment, read on every call: NBODY_TIDAL_SPLIT = k >= 1 walks the sources in min(k, blocks) chunks of whole blocks side by side
+ * (unset or 0: chosen from m and the CU count); NBODY_TIDAL_SCRATCH_MB (default 256) bounds the per-block sums a split launch stores,
+ * larger calls go in consecutive batches of points.  Same bits in every case.
+ * NBODY_ERR_NOT_INIT without a context; NBODY_ERR_ARG, checked before anything is launched or written, for points == NULL,
+ * tensor == NULL, m < 1 or a skip value outside [-1, N); NBODY_ERR_STATE for the other precision's entry point or while the mailbox is
+ * served. */
+int nbody_tidal(const float *points, int m, const int *skip, float *tensor);
+int nbody_tidal_d(const double *points, int m, const int *skip, double *tensor);
 
 /* ---- nearest neighbour, radius count, closest pair: how close the bodies on the device get (not in the reference) ----
  * A query is a point x with an optional excluded body.  In the context precision T, for every body j on the device:

@@ -42,7 +42,7 @@ SYMBOLS = [
     "nbody_neighbors_rows", "nbody_neighbors_rows_d", "nbody_nearest", "nbody_nearest_d", "nbody_closest_pair", "nbody_closest_pair_d",
     "nbody_knn_rows", "nbody_knn_rows_d", "nbody_knn", "nbody_knn_d", "nbody_fof", "nbody_fof_d",
     "nbody_radial_counts_rows", "nbody_radial_counts_rows_d", "nbody_radial_counts", "nbody_radial_counts_d",
-    "nbody_pair_histogram", "nbody_pair_histogram_d",
+    "nbody_pair_histogram", "nbody_pair_histogram_d", "nbody_tidal", "nbody_tidal_d",
 ]
 
 
@@ -98,6 +98,7 @@ def load():
         "nbody_mailbox_serve": [i, i],
         "nbody_energy": [dp], "nbody_potential_rows": [i, i, fp], "nbody_potential_rows_d": [i, i, dp],
         "nbody_field": [fp, i, C.POINTER(i), fp, fp], "nbody_field_d": [dp, i, C.POINTER(i), dp, dp],
+        "nbody_tidal": [fp, i, C.POINTER(i), fp], "nbody_tidal_d": [dp, i, C.POINTER(i), dp],
         "nbody_neighbors_rows": [i, i, C.POINTER(i), fp, f, C.POINTER(i)], "nbody_neighbors_rows_d": [i, i, C.POINTER(i), dp, d, C.POINTER(i)],
         "nbody_nearest": [fp, i, C.POINTER(i), C.POINTER(i), fp, f, C.POINTER(i)],
         "nbody_nearest_d": [dp, i, C.POINTER(i), C.POINTER(i), dp, d, C.POINTER(i)],

@@ -1,8 +1,8 @@
-// diag_pass.hpp — what the diagnostic passes (energy, field, neighbours, k nearest neighbours, friends-of-friends, radial counts) share, stated once: the two launch constants their hosts and
+// diag_pass.hpp — what the diagnostic passes (energy, field, tidal tensor, neighbours, k nearest neighbours, friends-of-friends, radial counts) share, stated once: the two launch constants their hosts and
 // kernels agree on and the guard of a launch over split sources; for device code, the pair arithmetic of the potential, the plain
 // squared distance of the four distance passes (neighbours, k nearest neighbours, friends-of-friends, radial counts) and the preamble of a
 // one-query-per-lane kernel: the lane, the wave's skip window, the chunk's sources.
-// energy_args.hpp, field_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp and hist_args.hpp include it.  Like them it stays apart from the force path's hashed
+// energy_args.hpp, field_args.hpp, tidal_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp and hist_args.hpp include it.  Like them it stays apart from the force path's hashed
 // source (nbody_args.hpp, nbody_kernels.hpp, kernels.hip, force_loop_gfx950.inc), of which it reads nbody_args.hpp (kSoftBits, NB_CONST) only.
 // The kernels' loops are different computations and stay in their files.
 #pragma once
@@ -10,7 +10,7 @@
 
 namespace nbd {
 
-constexpr int kSrcBlock = 1024;   // sources per block: a level-1 sum of the potential and the field, the unit of a split launch's chunks
+constexpr int kSrcBlock = 1024;   // sources per block: a level-1 sum of the potential, the field and the tidal tensor, the unit of a split launch's chunks
 constexpr int kLanes = 256;       // lanes per workgroup, one row, point or query each
 
 // What a launch over split sources refuses, for any argument block with the geometry members m, first, n_src, n_blocks, chunk_blocks,

@@ -14,21 +14,6 @@ namespace nbi {
 
 namespace {
 
-// The field pass's split: the scratch is per BLOCK, so its size per point does not depend on the number of chunks; the points whose
-// per-block sums fit the scratch bound go together, in whole workgroups, and the chunks are chosen anew for such a batch.  A different
-// rule from query_pass.hpp's chunk_split, and it reads its MB bound as an integer (env_ll) where that one takes fractions (atof).
-SplitPlan field_split(int cnt, int n_blocks, size_t es) {
-  const long long forced = env_ll("NBODY_FIELD_SPLIT", 0);
-  const long long bound = std::max<long long>(0, env_ll("NBODY_FIELD_SCRATCH_MB", 256)) << 20;
-  const long long fit = bound / (long long)field_scratch_bytes(1, (size_t)n_blocks, es) / nbd::kLanes * nbd::kLanes;
-  int batch = cnt;
-  if (choose_chunks(forced, cnt, n_blocks) > 1 && fit < cnt) batch = (int)fit;   // (fit < 256: batch = 0, no split)
-  const int chunks = batch > 0 ? choose_chunks(forced, batch, n_blocks) : 1;
-  if (chunks <= 1) return no_split(cnt, n_blocks);
-  const int chunk_blocks = (n_blocks + chunks - 1) / chunks;
-  return {(n_blocks + chunk_blocks - 1) / chunk_blocks, chunk_blocks, batch};   // no empty chunk
-}
-
 // points [r.first, r.first + r.cnt) of the call on local L (uploaded; outputs left in fd_accel / fd_phi for the copy back)
 int launch_field(Local& L, const void* points, const int* skip, const Range& r, bool want_accel, bool want_phi) {
   HIPC(hipSetDevice(L.device));
@@ -37,7 +22,7 @@ int launch_field(Local& L, const void* points, const int* skip, const Range& r, 
   if (want_accel) NBC(L.fd_accel.ensure((size_t)r.cnt * wb));
   if (want_phi) NBC(L.fd_phi.ensure((size_t)r.cnt * es));
   const int n_blocks = source_blocks();
-  const SplitPlan plan = field_split(r.cnt, n_blocks, es);
+  const SplitPlan plan = block_split("NBODY_FIELD_SPLIT", "NBODY_FIELD_SCRATCH_MB", r.cnt, n_blocks, 4, es);
   if (plan.chunks > 1) NBC(L.q_scratch.ensure(field_scratch_bytes((size_t)plan.batch, (size_t)n_blocks, es)));
   return for_batches(r.cnt, plan, [&](int b0, int m) {
     FieldArgs a;

@@ -4,13 +4,15 @@
 //                 and its HIP graph, state transfer, the strict gate
 //   comm.cpp      RCCL (resolved with dlopen), the transfer plans, the all-gather of a step, probes and self-tests
 //   mailbox.cpp   the reference's mailbox: RAM images, one request (a force pass over a Problem of the request's own N), the service thread
-//   diag_pass.hpp  what the six diagnostic passes below share on the device: the potential's pair arithmetic, the lane and wave
+//   diag_pass.hpp  what the seven diagnostic passes below share on the device: the potential's pair arithmetic, the lane and wave
 //                  preamble of a one-query-per-lane kernel, the block and workgroup sizes (read by their *_args.hpp)
 //   query_pass.hpp what they share on the host: ranges over the locals, upload, the split's batches, launch-then-copy-back, the ranks' words
 //   energy.hip    the energy pass's kernels (energy_args.hpp: its argument block and launch functions)
 //   energy.cpp    nbody_energy, nbody_potential_rows(_d): the energy pass on every local and the sum over the ranks
 //   field.hip     the field pass's kernels (field_args.hpp: its argument block and launch functions)
 //   field.cpp     nbody_field(_d): acceleration and potential at the caller's points, the points divided over the locals
+//   tidal.hip     the tidal pass's kernels (tidal_args.hpp: its argument block and launch functions)
+//   tidal.cpp     nbody_tidal(_d): the tidal tensor at the caller's points, the points divided over the locals
 //   neighbors.hip the neighbour pass's kernels (neighbors_args.hpp: its argument block and launch functions)
 //   neighbors.cpp nbody_neighbors_rows(_d), nbody_nearest(_d), nbody_closest_pair(_d): nearest body, radius count, closest pair
 //   knn.hip       the k-nearest-neighbour pass's kernels (knn_args.hpp: its argument block and launch functions)
@@ -19,7 +21,7 @@
 //   fof.cpp       nbody_fof(_d): the groups of a linking length, rounds of the link pass under a union-find on the host
 //   hist.hip      the radial-count pass's kernels (hist_args.hpp: its argument block and launch functions)
 //   hist.cpp      nbody_radial_counts_rows(_d), nbody_radial_counts(_d), nbody_pair_histogram(_d): bodies per shell of distance, pair counts
-// Only kernels.hip, energy.hip, field.hip, neighbors.hip, knn.hip, fof.hip and hist.hip are device code (a minute of hipcc, as one code object through device.hip);
+// Only kernels.hip, energy.hip, field.hip, tidal.hip, neighbors.hip, knn.hip, fof.hip and hist.hip are device code (a minute of hipcc, as one code object through device.hip);
 // the others are host C++ (seconds).  gfx950 only, no CPU fallback anywhere.
 // Ownership: every stream, event, device and pinned allocation the context uses lives in an owning handle (Stream, Event, DevMem, Pinned,
 // below) that is a member of Global or of one of its Locals; nbody_shutdown() releases them all, and nothing does at process exit (see `g`).
@@ -132,9 +134,10 @@ struct Local {
   DevMem en_part;                      // energy pass (energy.cpp): per-workgroup fp64 partials of {T, U, P, L} ...
   DevMem en_tot;                       // ... the ranks' totals, 8 doubles at word `rank` (all P after an all-gather) ...
   DevMem en_phi;                       // ... and phi of the rows asked for (context precision)
-  DevMem q_points, q_skip;             // field, neighbour, knn and radial-count pass (query_pass.hpp): this local's range of the caller's points and skip indices ...
-  DevMem q_scratch;                    // ... and what a launch whose sources are split leaves for its combine (field_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp, hist_args.hpp)
+  DevMem q_points, q_skip;             // field, tidal, neighbour, knn and radial-count pass (query_pass.hpp): this local's range of the caller's points and skip indices ...
+  DevMem q_scratch;                    // ... and what a launch whose sources are split leaves for its combine (field_args.hpp, tidal_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp, hist_args.hpp)
   DevMem fd_accel, fd_phi;             // field pass (field.cpp): the points' outputs (context precision)
+  DevMem td_tensor;                    // tidal pass (tidal.cpp): the points' six values each (context precision)
   DevMem nb_idx, nb_d2, nb_count;      // neighbour pass (neighbors.cpp): the queries' outputs (d2 in the context precision) ...
   DevMem nb_best;                      // ... and the ranks' closest pairs, one BestPair at word `rank` (all P after an all-gather)
   DevMem kn_idx, kn_d2;                // knn pass (knn.cpp): the queries' outputs, k entries each (d2 in the context precision)

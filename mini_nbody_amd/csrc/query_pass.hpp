@@ -1,8 +1,8 @@
-// query_pass.hpp — the host side that the diagnostic passes share (energy.cpp, field.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp; host C++ only): a call brings
+// query_pass.hpp — the host side that the diagnostic passes share (energy.cpp, field.cpp, tidal.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp; host C++ only): a call brings
 // rows or points, every local takes a contiguous range of them, launches on its compute stream — in batches over a split of the
 // sources when the pass asks for one — and the results are copied back once the stream has drained.  A pass says what differs: which
-// range a local gets, what to launch, which outputs go where, and which of the two split rules (a SplitPlan) it follows: chunk_split
-// here, for the four distance passes whose scratch is per chunk, or field.cpp's field_split, whose scratch is per block.
+// range a local gets, what to launch, which outputs go where, and which of the two split rules (a SplitPlan) it follows: chunk_split,
+// for the four distance passes whose scratch is per chunk, or block_split, for the field and tidal passes, whose scratch is per block.
 // The points, skip indices and split scratch of a call live in one set of buffers per Local (q_points, q_skip, q_scratch), whichever
 // pass runs: every call drains the streams it used before it returns, so no two calls ever use them at once.
 #pragma once
@@ -38,7 +38,7 @@ inline int choose_chunks(long long forced, int queries, int n_blocks, int fill =
 }
 
 // How a local's launch is cut: grid.y = chunks chunks of chunk_blocks whole blocks (no empty chunk), `batch` queries per launch.
-// Two rules make one, chunk_split below and field.cpp's field_split; both fall back to no_split.
+// Two rules make one, chunk_split and block_split below; both fall back to no_split.
 struct SplitPlan { int chunks, chunk_blocks, batch; };
 inline SplitPlan no_split(int cnt, int n_blocks) { return {1, n_blocks, cnt}; }
 
@@ -60,6 +60,22 @@ inline SplitPlan chunk_split(const char* split_env, const char* scratch_mb_env, 
   if (fit < (double)cnt) batch = (int)fit / nbd::kLanes * nbd::kLanes;
   if (batch <= 0) return no_split(cnt, n_blocks);   // not one workgroup's queries fit
   return {chunks, chunk_blocks, batch};
+}
+
+// The split of the field and tidal passes, whose scratch is per BLOCK (values level-1 sums of `es` bytes for every point and block:
+// field_args.hpp, tidal_args.hpp), so its size per point does not depend on the number of chunks: the points whose per-block sums fit
+// the bound of scratch_mb_env go together, in whole workgroups, and the chunks are chosen anew for such a batch — split_env forces their
+// number.  It reads its MB bound as an integer (env_ll; 256 when unset) where chunk_split takes fractions (atof).
+inline SplitPlan block_split(const char* split_env, const char* scratch_mb_env, int cnt, int n_blocks, int values, size_t es) {
+  const long long forced = env_ll(split_env, 0);
+  const long long bound = std::max<long long>(0, env_ll(scratch_mb_env, 256)) << 20;
+  const long long fit = bound / (long long)((size_t)n_blocks * (size_t)values * es) / nbd::kLanes * nbd::kLanes;
+  int batch = cnt;
+  if (choose_chunks(forced, cnt, n_blocks) > 1 && fit < cnt) batch = (int)fit;   // (fit < 256: batch = 0, no split)
+  const int chunks = batch > 0 ? choose_chunks(forced, batch, n_blocks) : 1;
+  if (chunks <= 1) return no_split(cnt, n_blocks);
+  const int chunk_blocks = (n_blocks + chunks - 1) / chunks;
+  return {(n_blocks + chunk_blocks - 1) / chunk_blocks, chunk_blocks, batch};   // no empty chunk
 }
 
 // the sources and the geometry members of a distance pass's argument block (diag_pass.hpp's bad_source_split names them) for a launch

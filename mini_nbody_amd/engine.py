@@ -177,6 +177,35 @@ class NBody:
                    a.ctypes.data_as(C.POINTER(ct)) if accel else None, phi.ctypes.data_as(C.POINTER(ct)) if potential else None))
         return a, phi
 
+    def _queries(self, points, skip):
+        """points ((m, 4) words or (m, 3)) and skip (None or m ints) of a query pass as (words, m, skip array or None): contiguous, in
+        the context dtype, (m, 3) points padded to words"""
+        p = np.asarray(points, self.dtype)
+        if p.ndim != 2 or p.shape[1] not in (3, 4):
+            raise ValueError("expected an (m, 4) or (m, 3) array of %s" % np.dtype(self.dtype).name)
+        if p.shape[1] == 3:
+            p = np.concatenate([p, np.zeros((len(p), 1), self.dtype)], axis=1)
+        p = np.ascontiguousarray(p)
+        sk = None
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, np.int32)
+            if sk.shape != (len(p),):
+                raise ValueError("skip must hold one index per point")
+        return p, len(p), sk
+
+    def tidal(self, points, skip=None):
+        """The tidal tensor T = grad a = -grad grad phi of the bodies on the device at arbitrary points (nbody_tidal):
+        T_ab(x) = sum_j (3 d_a d_b inv^5 - delta_ab inv^3), d = r_j - x, inv = (|d|^2 + eps)^(-1/2), over ALL j.  points and skip as in
+        field().  Returns (m, 6) values {xx, yy, zz, xy, xz, yz} in the context dtype; tidal_matrix() spreads them into (m, 3, 3).
+        Collective in a multi-rank job (every rank brings its own points)."""
+        p, m, sk = self._queries(points, skip)
+        ct = C.c_double if self.fp64 else C.c_float
+        t = np.empty((m, 6), self.dtype)
+        fn = self.lib.nbody_tidal_d if self.fp64 else self.lib.nbody_tidal
+        L.check(fn(p.ctypes.data_as(C.POINTER(ct)), m, sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None,
+                   t.ctypes.data_as(C.POINTER(ct))))
+        return t
+
     def _near_out(self, m, r2):
         ct = C.c_double if self.fp64 else C.c_float
         idx, d2 = np.empty(m, np.int32), np.empty(m, self.dtype)
@@ -412,6 +441,15 @@ class NBody:
 
     def __exit__(self, *exc):
         self.close()
+
+
+def tidal_matrix(t6):
+    """(m, 6) values {xx, yy, zz, xy, xz, yz} of NBody.tidal() (or one point's six) as symmetric (m, 3, 3) matrices (or one (3, 3)),
+    in the same dtype: np.linalg.eigvalsh applies directly."""
+    t6 = np.asarray(t6)
+    if t6.shape[-1:] != (6,):
+        raise ValueError("expected six values {xx, yy, zz, xy, xz, yz} per point")
+    return t6[..., [[0, 3, 4], [3, 1, 5], [4, 5, 2]]]
 
 
 def comm_plan(form, rank, nranks, n):

@@ -8,11 +8,13 @@
  *
  * usage: nbody [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K]
  *              [--sum seq|blocked] [--block K] [--one-launch | --two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16]
- *              [--energy] [--field M] [--closest-pair] [--pair-histogram B]
+ *              [--energy] [--field M] [--tidal M] [--closest-pair] [--pair-histogram B]
  * --energy: E = T + U, T and U of the state on the device (nbody_energy) before the first iteration and after the last, and the
  * relative drift, outside the timed region.
  * --field M: after the last iteration, acceleration and potential of the state on the device (nbody_field) at M points — the position
  * words of an M-body system of the same initial conditions with seed 4242 — as plain ascending fp64 sums, outside the timed region.
+ * --tidal M: after the last iteration, the tidal tensor of the state on the device (nbody_tidal) at the M points of --field M: its trace
+ * and its six values {xx, yy, zz, xy, xz, yz} as plain ascending fp64 sums over the points, outside the timed region.
  * --closest-pair: after the last iteration, the two bodies of the state on the device that are closest and their plain squared distance
  * (nbody_closest_pair), outside the timed region.
  * --pair-histogram B (1 <= B <= 32): after the last iteration, one line "pair histogram: c0 c1 ... c(B-1)", the number of unordered
@@ -86,6 +88,40 @@ static int print_field(int m, int fp64) {
   return 0;
 }
 
+/* the line of --tidal: the trace and the six values of the tidal tensor summed over the m points of --field, ascending, in fp64 */
+static int print_tidal(int m, int fp64) {
+  const size_t words = (size_t)m * 4;
+  double trace_sum = 0.0, t_sum[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+  int rc;
+  if (!fp64) {
+    float *buf = (float *)malloc((2 * words + 6 * (size_t)m) * sizeof(float));
+    if (!buf) return 3;
+    float *pts = buf, *t = buf + 2 * words;   /* buf + words: the velocities the fill also writes */
+    nbody_ic_fill_f32(pts, buf + words, (size_t)m, 0, (size_t)m, FIELD_SEED);
+    rc = nbody_tidal(pts, m, NULL, t);
+    for (int p = 0; p < m && !rc; ++p) {
+      trace_sum += ((double)t[6 * p] + (double)t[6 * p + 1]) + (double)t[6 * p + 2];
+      for (int c = 0; c < 6; ++c) t_sum[c] += (double)t[6 * p + c];
+    }
+    free(buf);
+  } else {
+    double *buf = (double *)malloc((2 * words + 6 * (size_t)m) * sizeof(double));
+    if (!buf) return 3;
+    double *pts = buf, *t = buf + 2 * words;
+    nbody_ic_fill_f64(pts, buf + words, (size_t)m, 0, (size_t)m, FIELD_SEED);
+    rc = nbody_tidal_d(pts, m, NULL, t);
+    for (int p = 0; p < m && !rc; ++p) {
+      trace_sum += (t[6 * p] + t[6 * p + 1]) + t[6 * p + 2];
+      for (int c = 0; c < 6; ++c) t_sum[c] += t[6 * p + c];
+    }
+    free(buf);
+  }
+  if (rc) { fprintf(stderr, "nbody_tidal failed: %s\n", nbody_error_string(rc)); return 1; }
+  printf("tidal of %d points: trace_sum %.17g t_sum %.17g %.17g %.17g %.17g %.17g %.17g\n", m, trace_sum, t_sum[0], t_sum[1], t_sum[2], t_sum[3],
+         t_sum[4], t_sum[5]);
+  return 0;
+}
+
 /* the line of --closest-pair */
 static int print_closest_pair(int fp64) {
   int i = -1, j = -1, rc;
@@ -125,7 +161,7 @@ static int print_pair_histogram(int bins, int fp64) {
 }
 
 int main(int argc, char **argv) {
-  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0, closest = 0, pair_hist = 0;
+  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0, tidal = 0, closest = 0, pair_hist = 0;
   double e0 = 0.0;
   unsigned long long seed = NBODY_IC_DEFAULT_SEED;
   for (int a = 1; a < argc; ++a) {
@@ -139,6 +175,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--rtl")) rtl = 1;
     else if (!strcmp(argv[a], "--energy")) energy = 1;
     else if (!strcmp(argv[a], "--field") && a + 1 < argc) field = atoi(argv[++a]);
+    else if (!strcmp(argv[a], "--tidal") && a + 1 < argc) tidal = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--closest-pair")) closest = 1;
     else if (!strcmp(argv[a], "--pair-histogram") && a + 1 < argc) { pair_hist = atoi(argv[++a]); if (pair_hist < 1 || pair_hist > NBODY_HIST_MAX_BINS) { fprintf(stderr, "--pair-histogram needs 1 <= B <= %d\n", NBODY_HIST_MAX_BINS); return 2; } }
     else if (!strcmp(argv[a], "--two-launch")) two_launch = 1;
@@ -150,9 +187,10 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--block") && a + 1 < argc) block = atoi(argv[++a]);
     else if (argv[a][0] != '-' && npos == 0) { n = atoi(argv[a]); npos++; }
     else if (argv[a][0] != '-' && npos == 1) { iters = atoi(argv[a]); npos++; }
-    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--closest-pair] [--pair-histogram B]\n", argv[0]); return 2; }
+    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--tidal M] [--closest-pair] [--pair-histogram B]\n", argv[0]); return 2; }
   }
   if (field < 0) { fprintf(stderr, "--field needs M >= 1\n"); return 2; }
+  if (tidal < 0) { fprintf(stderr, "--tidal needs M >= 1\n"); return 2; }
   if (n <= 0 || iters < 2) { fprintf(stderr, "need N > 0 and iters >= 2 (iteration 1 is warm-up)\n"); return 2; }
   const float dt = 0.01f;
   const size_t words = (size_t)n * 4;
@@ -201,9 +239,10 @@ int main(int argc, char **argv) {
       total = now_s() - t0;
       CHECK(nbody_download(&p));
     }
-    if ((energy || field || closest || pair_hist) && host_loop) CHECK(nbody_upload(&p));
+    if ((energy || field || tidal || closest || pair_hist) && host_loop) CHECK(nbody_upload(&p));
     if (energy && print_energy(iters, &e0, 0)) return 1;
     if (field && print_field(field, 0)) return 1;
+    if (tidal && print_tidal(tidal, 0)) return 1;
     if (closest && print_closest_pair(0)) return 1;
     if (pair_hist && print_pair_histogram(pair_hist, 0)) return 1;
     double cx = 0, cy = 0, cz = 0;
@@ -234,9 +273,10 @@ int main(int argc, char **argv) {
       total = now_s() - t0;
       CHECK(nbody_download_d(&p));
     }
-    if ((energy || field || closest || pair_hist) && host_loop) CHECK(nbody_upload_d(&p));
+    if ((energy || field || tidal || closest || pair_hist) && host_loop) CHECK(nbody_upload_d(&p));
     if (energy && print_energy(iters, &e0, 0)) return 1;
     if (field && print_field(field, 1)) return 1;
+    if (tidal && print_tidal(tidal, 1)) return 1;
     if (closest && print_closest_pair(1)) return 1;
     if (pair_hist && print_pair_histogram(pair_hist, 1)) return 1;
     double cx = 0, cy = 0, cz = 0;

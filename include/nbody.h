@@ -2,7 +2,7 @@
  *
  * Plain C99: pointers, ints, floats.  No HIP, torch or C++ types cross this
  * boundary.  The library behind it is hand-written HIP for gfx950
- * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, field.hip, tidal.hip, neighbors.hip, knn.hip, fof.hip, hist.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, field.cpp, tidal.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp); there is
+ * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, field.hip, tidal.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, field.cpp, tidal.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp); there is
  * no CPU fallback: every entry
  * point fails with NBODY_ERR_NO_DEVICE when no GPU is usable.
  *
@@ -580,6 +580,52 @@ int nbody_radial_counts(const float *points, int m, const int *skip, const float
 int nbody_radial_counts_d(const double *points, int m, const int *skip, const double *edges2, int n_bins, int *counts);
 int nbody_pair_histogram(const float *edges2, int n_bins, long long *pairs);
 int nbody_pair_histogram_d(const double *edges2, int n_bins, long long *pairs);
+
+/* ---- pair time scales and a shared adaptive time step: how soon two bodies meet (not in the reference) ----
+ * The first pass that reads two bodies' velocities together.  In the context precision T, for a row i and every body j != i:
+ *   dx = xj - xi (dy, dz likewise)         d2 = fma(dx, dx, fma(dy, dy, dz * dz))     the neighbour pass's plain d2, unchanged
+ *   ux = vxj - vxi (uy, uz likewise)       v2 = fma(ux, ux, fma(uy, uy, uz * uz))
+ *   q  = d2 / v2                           the correctly rounded IEEE quotient: the pair crossing time squared
+ * every operation IEEE-exact, contraction off, no softening, and none of it follows NBODY_OPT_ARITH: one definition per precision.
+ *   tau2   the smallest q over j, in T.  A NaN q (0 / 0, a NaN anywhere) is never chosen, nor is q = +inf (v2 = 0 with d2 > 0, a d2
+ *          that overflowed): it is not below +inf.  A v2 that overflows to +inf gives q = +0, a legitimate answer, as is the +0 of a
+ *          coincident body that moves.
+ *   idx    the j that gives it, on equal values the lowest j: what an ascending scan from (+inf, -1) that replaces on strict < arrives
+ *          at.  Without a candidate (N = 1, every q NaN or +inf): idx = -1, tau2 = +inf.
+ *   d2min  the smallest d2 over j, in T: bit for bit the d2 of nbody_neighbors_rows.  The other standard time scale, the pair free-fall
+ *          time, is monotone in the distance and follows from it.
+ * Minima are exact: the values depend on the N positions and velocities and the row alone — not on the number of rows, on the launch
+ * shape (NBODY_TIMESCALE_SPLIT below), on the arithmetic, on the force configuration or on the device or rank count.  No atomics.
+ * nbody_timescale_rows(_d): rows exactly as in nbody_forces_rows (nbody_init: first_row is a global index, the range may span devices;
+ *   nbody_init_rank: a row of the rank's own slice).  The idx returned are always GLOBAL body indices.  tau2, idx or d2min may be NULL
+ *   (at least one is not).
+ * nbody_min_timescale(_d): the smallest tau2 of the whole system, i the lowest row that reaches it and j that row's partner, and the
+ *   smallest d2min of the whole system (nbody_closest_pair's d2); -1, -1 and +inf where there is none.  Any of the four may be NULL
+ *   (not all).  It runs the rows pass over every device's or rank's own rows and keeps each one's best by a fixed-order reduction; the
+ *   winner is picked in rank order with strict <.  Every rank returns the same values.
+ * All of them bring the other slices' positions first and then ALL N velocities to every device: one device reads its own; the devices
+ * of an nbody_init context copy each other's slices device to device; an nbody_init_rank job gathers them with the transport it uses
+ * for positions, so every call is collective there.  A diagnostic call pays for that.  They leave positions, velocities, the arrival
+ * counters, the captured step graph and the force-kernel timer as they were.
+ * nbody_step_adaptive(_d): a shared adaptive time step on top of nbody_step, from t = 0, everything but the step itself in binary64:
+ *     (tau2, d2min) of nbody_min_timescale;  s = d2min + eps (the force's eps);  tff2 = s * sqrt(s) / 2  (the unit-mass pair free-fall
+ *     time squared);  h = eta * sqrt(min(tau2, tff2));  h clamped to [dt_min, dt_max];  h = t_end - t if t + h > t_end;  dt = h rounded
+ *     once to T;  one eager step of dt, exactly nbody_step(dt, 1);  t += (double)dt
+ *   until t >= t_end or max_steps steps are taken (then NBODY_OK with *t_reached < t_end).  *t_reached and *steps_taken (either may be
+ *   NULL) are written after every step.  dt_min > 0 is what keeps coincident bodies (tau2 = 0) from stalling it.  Every rank computes
+ *   the same h from the same values: a multi-rank job needs no further exchange.
+ * Environment, read on every call: NBODY_TIMESCALE_SPLIT = k >= 1 walks the sources in min(k, blocks of 1024) chunks side by side
+ * (unset or 0: chosen from the number of rows and the CU count); NBODY_TIMESCALE_SCRATCH_MB (default 256, fractions allowed) bounds the
+ * 12 (fp64: 20) bytes per row and chunk a split launch stores, larger calls go in consecutive batches of rows.  Same values in every case.
+ * NBODY_ERR_NOT_INIT without a context; NBODY_ERR_ARG, checked before anything is launched or written, for every output NULL, a bad row
+ * range, a non-finite eta, t_end, dt_min or dt_max, eta <= 0, dt_min <= 0, dt_max < dt_min, t_end <= 0 or max_steps < 1;
+ * NBODY_ERR_STATE for the other precision's entry point or while the mailbox is served. */
+int nbody_timescale_rows(int first_row, int n_rows, float *tau2, int *idx, float *d2min);
+int nbody_timescale_rows_d(int first_row, int n_rows, double *tau2, int *idx, double *d2min);
+int nbody_min_timescale(float *tau2, int *i, int *j, float *d2min);
+int nbody_min_timescale_d(double *tau2, int *i, int *j, double *d2min);
+int nbody_step_adaptive(float eta, float t_end, float dt_min, float dt_max, int max_steps, double *t_reached, int *steps_taken);
+int nbody_step_adaptive_d(double eta, double t_end, double dt_min, double dt_max, int max_steps, double *t_reached, int *steps_taken);
 
 #ifdef __cplusplus
 }

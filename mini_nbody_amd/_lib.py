@@ -43,6 +43,8 @@ SYMBOLS = [
     "nbody_knn_rows", "nbody_knn_rows_d", "nbody_knn", "nbody_knn_d", "nbody_fof", "nbody_fof_d",
     "nbody_radial_counts_rows", "nbody_radial_counts_rows_d", "nbody_radial_counts", "nbody_radial_counts_d",
     "nbody_pair_histogram", "nbody_pair_histogram_d", "nbody_tidal", "nbody_tidal_d",
+    "nbody_timescale_rows", "nbody_timescale_rows_d", "nbody_min_timescale", "nbody_min_timescale_d",
+    "nbody_step_adaptive", "nbody_step_adaptive_d",
 ]
 
 
@@ -110,6 +112,9 @@ def load():
         "nbody_radial_counts": [fp, i, C.POINTER(i), fp, i, C.POINTER(i)],
         "nbody_radial_counts_d": [dp, i, C.POINTER(i), dp, i, C.POINTER(i)],
         "nbody_pair_histogram": [fp, i, C.POINTER(C.c_longlong)], "nbody_pair_histogram_d": [dp, i, C.POINTER(C.c_longlong)],
+        "nbody_timescale_rows": [i, i, fp, C.POINTER(i), fp], "nbody_timescale_rows_d": [i, i, dp, C.POINTER(i), dp],
+        "nbody_min_timescale": [fp, C.POINTER(i), C.POINTER(i), fp], "nbody_min_timescale_d": [dp, C.POINTER(i), C.POINTER(i), dp],
+        "nbody_step_adaptive": [f, f, f, f, i, dp, C.POINTER(i)], "nbody_step_adaptive_d": [d, d, d, d, i, dp, C.POINTER(i)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -575,6 +575,8 @@ struct CaptureRestore {
   }
 };
 
+}  // namespace
+
 int step_impl(float dt, double dt64, int nsteps) {
   if (!g.init) return NBODY_ERR_NOT_INIT;
   if (nsteps < 0) return NBODY_ERR_ARG;
@@ -619,6 +621,8 @@ int step_impl(float dt, double dt64, int nsteps) {
   for (; s < nsteps; ++s) NBC(enqueue_step(dt, dt64));
   return NBODY_OK;
 }
+
+namespace {
 
 int body_force_impl(void* pos, void* vel, float dt, double dt64, int n) {
   if (!g.init) return NBODY_ERR_NOT_INIT;

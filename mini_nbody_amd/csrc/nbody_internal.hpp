@@ -4,7 +4,7 @@
 //                 and its HIP graph, state transfer, the strict gate
 //   comm.cpp      RCCL (resolved with dlopen), the transfer plans, the all-gather of a step, probes and self-tests
 //   mailbox.cpp   the reference's mailbox: RAM images, one request (a force pass over a Problem of the request's own N), the service thread
-//   diag_pass.hpp  what the seven diagnostic passes below share on the device: the potential's pair arithmetic, the lane and wave
+//   diag_pass.hpp  what the eight diagnostic passes below share on the device: the potential's pair arithmetic, the lane and wave
 //                  preamble of a one-query-per-lane kernel, the block and workgroup sizes (read by their *_args.hpp)
 //   query_pass.hpp what they share on the host: ranges over the locals, upload, the split's batches, launch-then-copy-back, the ranks' words
 //   energy.hip    the energy pass's kernels (energy_args.hpp: its argument block and launch functions)
@@ -21,7 +21,9 @@
 //   fof.cpp       nbody_fof(_d): the groups of a linking length, rounds of the link pass under a union-find on the host
 //   hist.hip      the radial-count pass's kernels (hist_args.hpp: its argument block and launch functions)
 //   hist.cpp      nbody_radial_counts_rows(_d), nbody_radial_counts(_d), nbody_pair_histogram(_d): bodies per shell of distance, pair counts
-// Only kernels.hip, energy.hip, field.hip, tidal.hip, neighbors.hip, knn.hip, fof.hip and hist.hip are device code (a minute of hipcc, as one code object through device.hip);
+//   timescale.hip the pair time-scale pass's kernels (timescale_args.hpp: its argument block and launch functions)
+//   timescale.cpp nbody_timescale_rows(_d), nbody_min_timescale(_d), nbody_step_adaptive(_d): pair crossing times, the shared adaptive step
+// Only kernels.hip, energy.hip, field.hip, tidal.hip, neighbors.hip, knn.hip, fof.hip, hist.hip and timescale.hip are device code (a minute of hipcc, as one code object through device.hip);
 // the others are host C++ (seconds).  gfx950 only, no CPU fallback anywhere.
 // Ownership: every stream, event, device and pinned allocation the context uses lives in an owning handle (Stream, Event, DevMem, Pinned,
 // below) that is a member of Global or of one of its Locals; nbody_shutdown() releases them all, and nothing does at process exit (see `g`).
@@ -29,7 +31,7 @@
 // Data layout in HBM (per rank; N bodies in total, the rank owns n_local of them starting at first_body):
 //   pos[2]   2 x N words      full position set, double-buffered: a step reads pos[cur] and writes the
 //                             rank's slice of pos[cur^1]; the other slices of pos[cur^1] arrive over xGMI
-//   vel      n_local words    never leaves the rank
+//   vel      n_local words    never leaves the rank in a step; the pair time-scale pass gathers a copy of all N (ts_vel, full_scratch)
 //   partial  nseg x rows'     per-source-segment partial forces (unused when nseg == 1); rows' = the launch's rows rounded up to 64
 //   tickets  1 per 64 rows    arrival counters of the in-launch combine (zero between steps)
 //   force    n_local words    last combined forces (parity entry points)
@@ -135,7 +137,7 @@ struct Local {
   DevMem en_tot;                       // ... the ranks' totals, 8 doubles at word `rank` (all P after an all-gather) ...
   DevMem en_phi;                       // ... and phi of the rows asked for (context precision)
   DevMem q_points, q_skip;             // field, tidal, neighbour, knn and radial-count pass (query_pass.hpp): this local's range of the caller's points and skip indices ...
-  DevMem q_scratch;                    // ... and what a launch whose sources are split leaves for its combine (field_args.hpp, tidal_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp, hist_args.hpp)
+  DevMem q_scratch;                    // ... and what a launch whose sources are split leaves for its combine (field_args.hpp, tidal_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp, hist_args.hpp, timescale_args.hpp)
   DevMem fd_accel, fd_phi;             // field pass (field.cpp): the points' outputs (context precision)
   DevMem td_tensor;                    // tidal pass (tidal.cpp): the points' six values each (context precision)
   DevMem nb_idx, nb_d2, nb_count;      // neighbour pass (neighbors.cpp): the queries' outputs (d2 in the context precision) ...
@@ -143,6 +145,9 @@ struct Local {
   DevMem kn_idx, kn_d2;                // knn pass (knn.cpp): the queries' outputs, k entries each (d2 in the context precision)
   DevMem hi_count;                     // radial-count pass (hist.cpp): the queries' counts, n_bins each ...
   DevMem hi_sums;                      // ... and the ranks' pair-histogram sums, NBODY_HIST_MAX_BINS 64-bit sums at word `rank` (all P after an all-gather)
+  DevMem ts_vel;                       // pair time-scale pass (timescale.cpp): all N velocity words, gathered at the start of a call (several devices in one process) ...
+  DevMem ts_tau2, ts_idx, ts_d2;       // ... the rows' outputs (tau2 and d2min in the context precision) ...
+  DevMem ts_best;                      // ... and the ranks' bests, one BestScale at word `rank` (all P after an all-gather)
   DevMem fo_label, fo_rows, fo_min;    // fof pass (fof.cpp): the N labels of a round, this local's range of the active rows and their m_i
   int cur = 0;
   bool all_present = true;             // pos[cur] holds every slice
@@ -270,6 +275,7 @@ int force_pass(const Problem& p, Local& L, int row0, int row_count, const Finish
 bool takes_rows16(const LaunchConfig& cfg, int row_count);
 int sync_all();
 int complete_positions();
+int step_impl(float dt, double dt64, int nsteps);   // nbody_step(_d): nsteps steps of dt (dt64 in an fp64 context); fewer than 4 are launched eagerly
 int forces_impl(const void* pos_words, void* force_words, int n);
 int device_count(int* ndev);
 int pick_device(int rank, int ndev);

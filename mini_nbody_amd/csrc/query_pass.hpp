@@ -1,8 +1,8 @@
-// query_pass.hpp — the host side that the diagnostic passes share (energy.cpp, field.cpp, tidal.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp; host C++ only): a call brings
+// query_pass.hpp — the host side that the diagnostic passes share (energy.cpp, field.cpp, tidal.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp; host C++ only): a call brings
 // rows or points, every local takes a contiguous range of them, launches on its compute stream — in batches over a split of the
 // sources when the pass asks for one — and the results are copied back once the stream has drained.  A pass says what differs: which
 // range a local gets, what to launch, which outputs go where, and which of the two split rules (a SplitPlan) it follows: chunk_split,
-// for the four distance passes whose scratch is per chunk, or block_split, for the field and tidal passes, whose scratch is per block.
+// for the five distance passes whose scratch is per chunk, or block_split, for the field and tidal passes, whose scratch is per block.
 // The points, skip indices and split scratch of a call live in one set of buffers per Local (q_points, q_skip, q_scratch), whichever
 // pass runs: every call drains the streams it used before it returns, so no two calls ever use them at once.
 #pragma once
@@ -15,7 +15,7 @@ namespace nbi {
 // value, not measured yet for the field, neighbour, knn and fof passes (tools/field_rate.py and tools/neighbors_rate.py time the
 // passes with and without the split).  Measured for the radial-count pass, where 2 is too few: 256 workgroups of 65 536 rows ran up
 // to 2.2 x faster over 16 - 32 chunks than over the 2 this asks for (profiles/r10_hist_rate.txt), so hist.cpp passes its own
-// kHistFill = 16 to chunk_split.  The same launch shape makes the same question worth asking of the siblings.
+// kHistFill = 16 to chunk_split, and timescale.cpp its kTimescaleFill = 16 for the same reason (profiles/r09_timescale.txt).  The same launch shape makes the same question worth asking of the siblings.
 constexpr int kQueryFill = 2;
 
 inline long long env_ll(const char* name, long long dflt) {
@@ -28,7 +28,7 @@ inline int source_blocks() { return (g.n + nbd::kSrcBlock - 1) / nbd::kSrcBlock;
 
 // C, the number of source chunks (grid.y) of a launch of `queries` queries over n_blocks blocks.  forced >= 1 (the pass's *_SPLIT
 // variable): min(forced, n_blocks).  Auto: 1 when the queries alone give kQueryFill workgroups per CU, else the smallest number of
-// chunks that does.  fill: the pass's own number in place of kQueryFill, where it has measured one (hist.cpp).
+// chunks that does.  fill: the pass's own number in place of kQueryFill, where it has measured one (hist.cpp, timescale.cpp).
 inline int choose_chunks(long long forced, int queries, int n_blocks, int fill = kQueryFill) {
   if (forced >= 1) return (int)std::min<long long>(forced, n_blocks);
   const long long groups = ((long long)queries + nbd::kLanes - 1) / nbd::kLanes;
@@ -42,7 +42,7 @@ inline int choose_chunks(long long forced, int queries, int n_blocks, int fill =
 struct SplitPlan { int chunks, chunk_blocks, batch; };
 inline SplitPlan no_split(int cnt, int n_blocks) { return {1, n_blocks, cnt}; }
 
-// The split of the neighbour, k-nearest-neighbour, friends-of-friends and radial-count passes, whose scratch is per CHUNK (bytes_per_query_chunk of
+// The split of the neighbour, k-nearest-neighbour, friends-of-friends, radial-count and pair time-scale passes, whose scratch is per CHUNK (bytes_per_query_chunk of
 // it for every query and chunk): the chunks are chosen from the local's cnt queries — split_env forces their number — and normalised
 // first; the queries whose chunk results fit the bound of scratch_mb_env (MB, fractions allowed; 256 when unset) then go together, in
 // whole workgroups.

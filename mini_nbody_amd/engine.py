@@ -373,6 +373,40 @@ class NBody:
         L.check(fn(ep, nb, pairs.ctypes.data_as(C.POINTER(C.c_longlong))))
         return pairs
 
+    def timescales(self, first_row=0, n_rows=None):
+        """(tau2, idx, d2min) of n_rows bodies from first_row (rows as in forces_rows; default: all of them) from the state on the
+        device (nbody_timescale_rows): tau2 the smallest pair crossing time squared |r_ij|^2 / |v_ij|^2 over the other bodies in the
+        context precision (+inf: none), idx the GLOBAL index of the body that gives it (-1: none; ties to the lowest index), d2min the
+        smallest plain squared distance, bit for bit neighbors()'s d2.  Collective in a multi-rank job."""
+        if n_rows is None:
+            n_rows = self.info(L.INFO_N_LOCAL if self._by_rank else L.INFO_N) - int(first_row)
+        m = int(n_rows)
+        ct = C.c_double if self.fp64 else C.c_float
+        tau2, idx, d2min = np.empty(m, self.dtype), np.empty(m, np.int32), np.empty(m, self.dtype)
+        fn = self.lib.nbody_timescale_rows_d if self.fp64 else self.lib.nbody_timescale_rows
+        L.check(fn(int(first_row), m, tau2.ctypes.data_as(C.POINTER(ct)), idx.ctypes.data_as(C.POINTER(C.c_int)),
+                   d2min.ctypes.data_as(C.POINTER(ct))))
+        return tau2, idx, d2min
+
+    def min_timescale(self):
+        """(tau2, i, j, d2min) of the whole system (nbody_min_timescale): the smallest pair crossing time squared, the lowest row i
+        that reaches it and its partner j, and the smallest plain squared distance (closest_pair()'s d2); (inf, -1, -1, inf) when
+        there is none.  Collective in a multi-rank job; every rank gets the same values."""
+        i, j = C.c_int(), C.c_int()
+        tau2, d2min = (C.c_double(), C.c_double()) if self.fp64 else (C.c_float(), C.c_float())
+        fn = self.lib.nbody_min_timescale_d if self.fp64 else self.lib.nbody_min_timescale
+        L.check(fn(C.byref(tau2), C.byref(i), C.byref(j), C.byref(d2min)))
+        return self.dtype(tau2.value), i.value, j.value, self.dtype(d2min.value)
+
+    def step_adaptive(self, t_end, eta, dt_min, dt_max, max_steps=1000000):
+        """(t_reached, steps): steps of a shared adaptive dt = eta * sqrt(min(tau2, tff2)) clamped to [dt_min, dt_max] from t = 0
+        until t_end or max_steps (nbody_step_adaptive), tau2 and d2min of min_timescale() before every step and tff2 the unit-mass
+        pair free-fall time squared at d2min.  Collective in a multi-rank job."""
+        t, steps = C.c_double(0.0), C.c_int(0)
+        fn = self.lib.nbody_step_adaptive_d if self.fp64 else self.lib.nbody_step_adaptive
+        L.check(fn(eta, t_end, dt_min, dt_max, int(max_steps), C.byref(t), C.byref(steps)))
+        return t.value, steps.value
+
     def comm_selftest(self):
         """Push a patterned array through the RCCL calls of the multi-GPU path (all-gather + one ring step); returns
         the bytes this rank received.  Needs the communicator of NBody(..., rank=, nranks=, uid=)."""

@@ -8,7 +8,7 @@
  *
  * usage: nbody [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K]
  *              [--sum seq|blocked] [--block K] [--one-launch | --two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16]
- *              [--energy] [--field M] [--tidal M] [--closest-pair] [--pair-histogram B]
+ *              [--energy] [--field M] [--tidal M] [--closest-pair] [--pair-histogram B] [--adaptive ETA]
  * --energy: E = T + U, T and U of the state on the device (nbody_energy) before the first iteration and after the last, and the
  * relative drift, outside the timed region.
  * --field M: after the last iteration, acceleration and potential of the state on the device (nbody_field) at M points — the position
@@ -20,6 +20,9 @@
  * --pair-histogram B (1 <= B <= 32): after the last iteration, one line "pair histogram: c0 c1 ... c(B-1)", the number of unordered
  * pairs of the state on the device per bin of squared distance (nbody_pair_histogram), outside the timed region.  The B + 1 edges are
  * edges2[0] = 0 and edges2[b] = 2^(2 (b - B) + 4) for b >= 1: exact powers of two up to 16 in either precision.
+ * --adaptive ETA (ETA > 0): after the last iteration, one line "min timescale: tau2 ... pair i j d2min ... dt ...": the smallest pair
+ * crossing time squared of the state on the device, the pair that gives it and the smallest squared distance (nbody_min_timescale), and
+ * the step dt = ETA * sqrt(min(tau2, tff2)) that nbody_step_adaptive would take unclamped, in fp64, outside the timed region.
  */
 #define _POSIX_C_SOURCE 199309L
 #include <math.h>
@@ -138,6 +141,26 @@ static int print_closest_pair(int fp64) {
   return 0;
 }
 
+/* the line of --adaptive */
+static int print_min_timescale(double eta, int fp64) {
+  int i = -1, j = -1, rc;
+  double tau2 = 0.0, d2min = 0.0;
+  if (!fp64) {
+    float tf = 0.0f, df = 0.0f;
+    rc = nbody_min_timescale(&tf, &i, &j, &df);
+    tau2 = (double)tf; d2min = (double)df;
+  } else {
+    rc = nbody_min_timescale_d(&tau2, &i, &j, &d2min);
+  }
+  if (rc) { fprintf(stderr, "nbody_min_timescale failed: %s\n", nbody_error_string(rc)); return 1; }
+  const unsigned eps_bits = 0x3089705Fu;   /* the force's eps (include/nbody.h) */
+  float eps;
+  memcpy(&eps, &eps_bits, sizeof(eps));
+  const double s = d2min + (double)eps, tff2 = s * sqrt(s) / 2.0;
+  printf("min timescale: tau2 %.17g pair %d %d d2min %.17g dt %.17g\n", tau2, i, j, d2min, eta * sqrt(tau2 < tff2 ? tau2 : tff2));
+  return 0;
+}
+
 /* the line of --pair-histogram */
 static int print_pair_histogram(int bins, int fp64) {
   long long pairs[NBODY_HIST_MAX_BINS];
@@ -162,7 +185,7 @@ static int print_pair_histogram(int bins, int fp64) {
 
 int main(int argc, char **argv) {
   int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0, tidal = 0, closest = 0, pair_hist = 0;
-  double e0 = 0.0;
+  double e0 = 0.0, adaptive = 0.0;
   unsigned long long seed = NBODY_IC_DEFAULT_SEED;
   for (int a = 1; a < argc; ++a) {
     if (!strcmp(argv[a], "--gpus") && a + 1 < argc) gpus = atoi(argv[++a]);
@@ -178,6 +201,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--tidal") && a + 1 < argc) tidal = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--closest-pair")) closest = 1;
     else if (!strcmp(argv[a], "--pair-histogram") && a + 1 < argc) { pair_hist = atoi(argv[++a]); if (pair_hist < 1 || pair_hist > NBODY_HIST_MAX_BINS) { fprintf(stderr, "--pair-histogram needs 1 <= B <= %d\n", NBODY_HIST_MAX_BINS); return 2; } }
+    else if (!strcmp(argv[a], "--adaptive") && a + 1 < argc) { adaptive = atof(argv[++a]); if (!(adaptive > 0.0) || adaptive > 1e300) { fprintf(stderr, "--adaptive needs ETA > 0\n"); return 2; } }
     else if (!strcmp(argv[a], "--two-launch")) two_launch = 1;
     else if (!strcmp(argv[a], "--one-launch")) two_launch = 0;
     else if (!strcmp(argv[a], "--overlap") && a + 1 < argc) overlap = atoi(argv[++a]);
@@ -187,7 +211,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--block") && a + 1 < argc) block = atoi(argv[++a]);
     else if (argv[a][0] != '-' && npos == 0) { n = atoi(argv[a]); npos++; }
     else if (argv[a][0] != '-' && npos == 1) { iters = atoi(argv[a]); npos++; }
-    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--tidal M] [--closest-pair] [--pair-histogram B]\n", argv[0]); return 2; }
+    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--tidal M] [--closest-pair] [--pair-histogram B] [--adaptive ETA]\n", argv[0]); return 2; }
   }
   if (field < 0) { fprintf(stderr, "--field needs M >= 1\n"); return 2; }
   if (tidal < 0) { fprintf(stderr, "--tidal needs M >= 1\n"); return 2; }
@@ -239,12 +263,13 @@ int main(int argc, char **argv) {
       total = now_s() - t0;
       CHECK(nbody_download(&p));
     }
-    if ((energy || field || tidal || closest || pair_hist) && host_loop) CHECK(nbody_upload(&p));
+    if ((energy || field || tidal || closest || pair_hist || adaptive > 0.0) && host_loop) CHECK(nbody_upload(&p));
     if (energy && print_energy(iters, &e0, 0)) return 1;
     if (field && print_field(field, 0)) return 1;
     if (tidal && print_tidal(tidal, 0)) return 1;
     if (closest && print_closest_pair(0)) return 1;
     if (pair_hist && print_pair_histogram(pair_hist, 0)) return 1;
+    if (adaptive > 0.0 && print_min_timescale(adaptive, 0)) return 1;
     double cx = 0, cy = 0, cz = 0;
     for (int i = 0; i < n; ++i) { cx += p.pos[4 * i]; cy += p.pos[4 * i + 1]; cz += p.pos[4 * i + 2]; }
     printf("checksum (sum of positions): %.9g %.9g %.9g\n", cx, cy, cz);
@@ -273,12 +298,13 @@ int main(int argc, char **argv) {
       total = now_s() - t0;
       CHECK(nbody_download_d(&p));
     }
-    if ((energy || field || tidal || closest || pair_hist) && host_loop) CHECK(nbody_upload_d(&p));
+    if ((energy || field || tidal || closest || pair_hist || adaptive > 0.0) && host_loop) CHECK(nbody_upload_d(&p));
     if (energy && print_energy(iters, &e0, 0)) return 1;
     if (field && print_field(field, 1)) return 1;
     if (tidal && print_tidal(tidal, 1)) return 1;
     if (closest && print_closest_pair(1)) return 1;
     if (pair_hist && print_pair_histogram(pair_hist, 1)) return 1;
+    if (adaptive > 0.0 && print_min_timescale(adaptive, 1)) return 1;
     double cx = 0, cy = 0, cz = 0;
     for (int i = 0; i < n; ++i) { cx += p.pos[4 * i]; cy += p.pos[4 * i + 1]; cz += p.pos[4 * i + 2]; }
     printf("checksum (sum of positions): %.17g %.17g %.17g\n", cx, cy, cz);

@@ -12,24 +12,23 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-s
 all: lib host oracle microbench
 
 # The library = ONE device code object (device.hip: the force path's kernels.hip — the nbk kernels + the launch functions that pick an
-# instantiation, ~45 s of hipcc — the energy pass's energy.hip, the field pass's field.hip, the tidal pass's tidal.hip, the neighbour pass's neighbors.hip, the k-nearest-neighbour pass's knn.hip, the friends-of-friends pass's fof.hip, the radial-count pass's hist.hip and the pair time-scale pass's timescale.hip) and eleven
-# host-only C++ files (context, comm, mailbox, energy, field, tidal, neighbors, knn, fof, hist, timescale: seconds each) behind csrc/nbody_internal.hpp.  A host-side edit relinks in seconds.
+# instantiation, ~45 s of hipcc — the energy pass's energy.hip, the field and tidal passes' point_sums.hip, the neighbour pass's neighbors.hip, the k-nearest-neighbour pass's knn.hip, the friends-of-friends pass's fof.hip, the radial-count pass's hist.hip and the pair time-scale pass's timescale.hip) and ten
+# host-only C++ files (context, comm, mailbox, energy, point_sums, neighbors, knn, fof, hist, timescale: seconds each) behind csrc/nbody_internal.hpp.  A host-side edit relinks in seconds.
 # The eight diagnostic passes share csrc/diag_pass.hpp (device code — the distance passes' pair distance and query preamble included — the sizes
 # their hosts read and the guard of a split launch) and csrc/query_pass.hpp (host only: the flow of a call and the two split rules).
 HOSTFLAGS := -O2 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function
 OBJ      := build/obj
 KERNEL_SRC := $(CSRC)/kernels.hip $(CSRC)/nbody_kernels.hpp $(CSRC)/nbody_args.hpp $(CSRC)/force_loop_gfx950.inc
 HOST_HDR := $(CSRC)/nbody_internal.hpp $(CSRC)/nbody_args.hpp $(CSRC)/query_pass.hpp $(CSRC)/diag_pass.hpp include/nbody.h
-HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o $(OBJ)/energy.o $(OBJ)/field.o $(OBJ)/tidal.o $(OBJ)/neighbors.o $(OBJ)/knn.o $(OBJ)/fof.o $(OBJ)/hist.o $(OBJ)/timescale.o
+HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o $(OBJ)/energy.o $(OBJ)/point_sums.o $(OBJ)/neighbors.o $(OBJ)/knn.o $(OBJ)/fof.o $(OBJ)/hist.o $(OBJ)/timescale.o
 # the energy diagnostics' device code (energy.hip, seconds of hipcc on its own) reads nbody_args.hpp and changes nothing of the force path's
 # hashed source (KERNEL_SRC); device.hip compiles it with kernels.hip into the library's one code object.  Its host side is energy.cpp, one
 # of HOST_OBJ.  What it shares with the seven passes below is diag_pass.hpp, which is no part of the hashed source either.
 ENERGY_SRC := $(CSRC)/energy.hip $(CSRC)/energy_args.hpp
-# the field pass (acceleration and potential at arbitrary points) in the same way: field.hip beside energy.hip, field.cpp one of HOST_OBJ
-FIELD_SRC := $(CSRC)/field.hip $(CSRC)/field_args.hpp
-# the tidal pass (the tidal tensor at arbitrary points, the gradient of the field) likewise: tidal.hip beside field.hip, tidal.cpp one of HOST_OBJ
-TIDAL_SRC := $(CSRC)/tidal.hip $(CSRC)/tidal_args.hpp
-# the neighbour pass (nearest body, radius count, closest pair) likewise: neighbors.hip beside field.hip, neighbors.cpp one of HOST_OBJ
+# the field pass (acceleration and potential at arbitrary points) and the tidal pass (the tidal tensor there, the gradient of the field) in
+# the same way, the two as one: point_sums.hip beside energy.hip, point_sums.cpp one of HOST_OBJ
+POINT_SUMS_SRC := $(CSRC)/point_sums.hip $(CSRC)/point_sums_args.hpp
+# the neighbour pass (nearest body, radius count, closest pair) likewise: neighbors.hip beside point_sums.hip, neighbors.cpp one of HOST_OBJ
 NEIGHBORS_SRC := $(CSRC)/neighbors.hip $(CSRC)/neighbors_args.hpp
 # the k-nearest-neighbour pass (the k nearest bodies and their distances) likewise: knn.hip beside neighbors.hip, knn.cpp one of HOST_OBJ
 KNN_SRC := $(CSRC)/knn.hip $(CSRC)/knn_args.hpp
@@ -39,7 +38,7 @@ FOF_SRC := $(CSRC)/fof.hip $(CSRC)/fof_args.hpp
 HIST_SRC := $(CSRC)/hist.hip $(CSRC)/hist_args.hpp
 # the pair time-scale pass (pair crossing times, the closest distance, the shared adaptive step) likewise: timescale.hip beside hist.hip, timescale.cpp one of HOST_OBJ
 TIMESCALE_SRC := $(CSRC)/timescale.hip $(CSRC)/timescale_args.hpp
-DEVICE_SRC := $(CSRC)/device.hip $(KERNEL_SRC) $(CSRC)/diag_pass.hpp $(ENERGY_SRC) $(FIELD_SRC) $(TIDAL_SRC) $(NEIGHBORS_SRC) $(KNN_SRC) $(FOF_SRC) $(HIST_SRC) $(TIMESCALE_SRC)
+DEVICE_SRC := $(CSRC)/device.hip $(KERNEL_SRC) $(CSRC)/diag_pass.hpp $(ENERGY_SRC) $(POINT_SUMS_SRC) $(NEIGHBORS_SRC) $(KNN_SRC) $(FOF_SRC) $(HIST_SRC) $(TIMESCALE_SRC)
 
 lib: $(PKG)/libnbody_hip.so
 $(OBJ)/device.o: $(DEVICE_SRC) $(HOST_HDR)
@@ -49,8 +48,7 @@ $(OBJ)/%.o: $(CSRC)/%.cpp $(HOST_HDR)
 	@mkdir -p $(OBJ)
 	$(HIPCC) $(HOSTFLAGS) -c $< -o $@
 $(OBJ)/energy.o: $(CSRC)/energy_args.hpp
-$(OBJ)/field.o: $(CSRC)/field_args.hpp
-$(OBJ)/tidal.o: $(CSRC)/tidal_args.hpp
+$(OBJ)/point_sums.o: $(CSRC)/point_sums_args.hpp
 $(OBJ)/neighbors.o: $(CSRC)/neighbors_args.hpp
 $(OBJ)/knn.o: $(CSRC)/knn_args.hpp
 $(OBJ)/fof.o: $(CSRC)/fof_args.hpp

@@ -2,7 +2,7 @@
  *
  * Plain C99: pointers, ints, floats.  No HIP, torch or C++ types cross this
  * boundary.  The library behind it is hand-written HIP for gfx950
- * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, field.hip, tidal.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, field.cpp, tidal.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp); there is
+ * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, point_sums.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp); there is
  * no CPU fallback: every entry
  * point fails with NBODY_ERR_NO_DEVICE when no GPU is usable.
  *

@@ -2,9 +2,9 @@
 // kernels agree on and the guard of a launch over split sources; for device code, the pair arithmetic of the potential, the plain
 // squared distance of the five distance passes (neighbours, k nearest neighbours, friends-of-friends, radial counts, pair time scales) and the preamble of a
 // one-query-per-lane kernel: the lane, the wave's skip window, the chunk's sources.
-// energy_args.hpp, field_args.hpp, tidal_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp, hist_args.hpp and timescale_args.hpp include it.  Like them it stays apart from the force path's hashed
+// energy_args.hpp, point_sums_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp, hist_args.hpp and timescale_args.hpp include it.  Like them it stays apart from the force path's hashed
 // source (nbody_args.hpp, nbody_kernels.hpp, kernels.hip, force_loop_gfx950.inc), of which it reads nbody_args.hpp (kSoftBits, NB_CONST) only.
-// The kernels' loops are different computations and stay in their files.
+// The kernels' loops are different computations and stay in their files; the field's and the tidal tensor's are one (point_sums.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

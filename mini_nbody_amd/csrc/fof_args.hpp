@@ -1,5 +1,5 @@
 // fof_args.hpp — what fof.cpp (host) and fof.hip (device) agree on: the argument block of the friends-of-friends link pass and the launch
-// functions of fof.hip.  Like energy_args.hpp, field_args.hpp, neighbors_args.hpp and knn_args.hpp it stays apart from nbody_args.hpp,
+// functions of fof.hip.  Like energy_args.hpp, point_sums_args.hpp, neighbors_args.hpp and knn_args.hpp it stays apart from nbody_args.hpp,
 // the force path's hashed kernel source.
 //
 // One link pass (include/nbody.h, "friends-of-friends groups") gives every row i of the launch the lowest FOREIGN label among its

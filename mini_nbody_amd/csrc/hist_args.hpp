@@ -1,5 +1,5 @@
 // hist_args.hpp — what hist.cpp (host) and hist.hip (device) agree on: the argument block of the radial-count pass and the launch
-// functions of hist.hip.  Like energy_args.hpp, field_args.hpp, neighbors_args.hpp, knn_args.hpp and fof_args.hpp it stays apart from
+// functions of hist.hip.  Like energy_args.hpp, point_sums_args.hpp, neighbors_args.hpp, knn_args.hpp and fof_args.hpp it stays apart from
 // nbody_args.hpp, the force path's hashed kernel source.
 //
 // The result of a query (include/nbody.h, "radial counts, pair histogram") is n_bins integers, differences of the cumulative counts

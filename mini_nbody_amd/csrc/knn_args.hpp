@@ -1,5 +1,5 @@
 // knn_args.hpp — what knn.cpp (host) and knn.hip (device) agree on: the argument block of the k-nearest-neighbour pass and the launch
-// functions of knn.hip.  Like energy_args.hpp, field_args.hpp and neighbors_args.hpp it stays apart from nbody_args.hpp, the force
+// functions of knn.hip.  Like energy_args.hpp, point_sums_args.hpp and neighbors_args.hpp it stays apart from nbody_args.hpp, the force
 // path's hashed kernel source.
 //
 // The result of a query (include/nbody.h, "k nearest neighbours") is the first k candidates in ascending (d2, j) order: a selection, so

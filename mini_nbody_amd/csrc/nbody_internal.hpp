@@ -9,10 +9,10 @@
 //   query_pass.hpp what they share on the host: ranges over the locals, upload, the split's batches, launch-then-copy-back, the ranks' words
 //   energy.hip    the energy pass's kernels (energy_args.hpp: its argument block and launch functions)
 //   energy.cpp    nbody_energy, nbody_potential_rows(_d): the energy pass on every local and the sum over the ranks
-//   field.hip     the field pass's kernels (field_args.hpp: its argument block and launch functions)
-//   field.cpp     nbody_field(_d): acceleration and potential at the caller's points, the points divided over the locals
-//   tidal.hip     the tidal pass's kernels (tidal_args.hpp: its argument block and launch functions)
-//   tidal.cpp     nbody_tidal(_d): the tidal tensor at the caller's points, the points divided over the locals
+//   point_sums.hip the field and tidal passes' kernels: one skeleton of blocked sums, a statement per pass (point_sums_args.hpp: the
+//                  passes, their argument block and launch functions)
+//   point_sums.cpp nbody_field(_d), nbody_tidal(_d): acceleration and potential, and the tidal tensor, at the caller's points, the
+//                  points divided over the locals
 //   neighbors.hip the neighbour pass's kernels (neighbors_args.hpp: its argument block and launch functions)
 //   neighbors.cpp nbody_neighbors_rows(_d), nbody_nearest(_d), nbody_closest_pair(_d): nearest body, radius count, closest pair
 //   knn.hip       the k-nearest-neighbour pass's kernels (knn_args.hpp: its argument block and launch functions)
@@ -23,7 +23,7 @@
 //   hist.cpp      nbody_radial_counts_rows(_d), nbody_radial_counts(_d), nbody_pair_histogram(_d): bodies per shell of distance, pair counts
 //   timescale.hip the pair time-scale pass's kernels (timescale_args.hpp: its argument block and launch functions)
 //   timescale.cpp nbody_timescale_rows(_d), nbody_min_timescale(_d), nbody_step_adaptive(_d): pair crossing times, the shared adaptive step
-// Only kernels.hip, energy.hip, field.hip, tidal.hip, neighbors.hip, knn.hip, fof.hip, hist.hip and timescale.hip are device code (a minute of hipcc, as one code object through device.hip);
+// Only kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip and timescale.hip are device code (a minute of hipcc, as one code object through device.hip);
 // the others are host C++ (seconds).  gfx950 only, no CPU fallback anywhere.
 // Ownership: every stream, event, device and pinned allocation the context uses lives in an owning handle (Stream, Event, DevMem, Pinned,
 // below) that is a member of Global or of one of its Locals; nbody_shutdown() releases them all, and nothing does at process exit (see `g`).
@@ -137,9 +137,8 @@ struct Local {
   DevMem en_tot;                       // ... the ranks' totals, 8 doubles at word `rank` (all P after an all-gather) ...
   DevMem en_phi;                       // ... and phi of the rows asked for (context precision)
   DevMem q_points, q_skip;             // field, tidal, neighbour, knn and radial-count pass (query_pass.hpp): this local's range of the caller's points and skip indices ...
-  DevMem q_scratch;                    // ... and what a launch whose sources are split leaves for its combine (field_args.hpp, tidal_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp, hist_args.hpp, timescale_args.hpp)
-  DevMem fd_accel, fd_phi;             // field pass (field.cpp): the points' outputs (context precision)
-  DevMem td_tensor;                    // tidal pass (tidal.cpp): the points' six values each (context precision)
+  DevMem q_scratch;                    // ... and what a launch whose sources are split leaves for its combine (point_sums_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp, hist_args.hpp, timescale_args.hpp)
+  DevMem q_out[2];                     // field and tidal pass (point_sums.cpp): the points' outputs (context precision), shared as q_points is
   DevMem nb_idx, nb_d2, nb_count;      // neighbour pass (neighbors.cpp): the queries' outputs (d2 in the context precision) ...
   DevMem nb_best;                      // ... and the ranks' closest pairs, one BestPair at word `rank` (all P after an all-gather)
   DevMem kn_idx, kn_d2;                // knn pass (knn.cpp): the queries' outputs, k entries each (d2 in the context precision)

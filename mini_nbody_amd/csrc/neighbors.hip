@@ -1,7 +1,7 @@
 // neighbors.hip — the neighbour pass's device code: per query the nearest of the N bodies on the device, its squared distance and the
 // number of bodies within a radius (neighbors_args.hpp states the rule, include/nbody.h the definitions), the combine of a split launch
 // and the fixed-order reduction of a device's rows to its closest pair.  Compiles on its own; device.hip puts it into the library's
-// one code object after field.hip.  Reads nbody_args.hpp (f4, d4, NB_CONST) and nothing else of the force path.  d2 is
+// one code object after point_sums.hip.  Reads nbody_args.hpp (f4, d4, NB_CONST) and nothing else of the force path.  d2 is
 // diag_pass.hpp's plain_d2, the plain squared distance; the file is compiled with contraction off.  gfx950 only.
 #include <hip/hip_runtime.h>
 
@@ -58,7 +58,7 @@ __device__ __forceinline__ void window64(const NB_CONST V4* src, const V4 me, in
 }
 
 // One query per lane, kLanes queries per workgroup; workgroup (x, y) walks the blocks of chunk y for the queries of x.  Sources
-// arrive with wave-uniform scalar loads (address space 4, as field_kernel).  Lanes beyond m stay in the wave-uniform loops clamped to
+// arrive with wave-uniform scalar loads (address space 4, as block_sums_kernel).  Lanes beyond m stay in the wave-uniform loops clamped to
 // the last query and store nothing.  SKIP: the rows form (a.points == null: query p is source a.first + p and leaves itself out) and
 // the points form with a skip array; only the aligned 64-source windows that overlap [lowest, highest] excluded index of the wave's
 // 64 queries compare j with it (a wave-uniform branch) — in the rows form the one or two windows that hold the wave's own rows.

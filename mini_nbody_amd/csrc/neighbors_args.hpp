@@ -1,5 +1,5 @@
 // neighbors_args.hpp — what neighbors.cpp (host) and neighbors.hip (device) agree on: the argument block of the neighbour pass and the
-// launch functions of neighbors.hip.  Like energy_args.hpp and field_args.hpp it stays apart from nbody_args.hpp, the force path's
+// launch functions of neighbors.hip.  Like energy_args.hpp and point_sums_args.hpp it stays apart from nbody_args.hpp, the force path's
 // hashed kernel source.
 //
 // The result of a query (include/nbody.h, "nearest neighbour, radius count, closest pair") is a minimum and an integer count, both exact,

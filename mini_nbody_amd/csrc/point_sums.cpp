@@ -1,0 +1,84 @@
+// point_sums.cpp — nbody_field(_d) and nbody_tidal(_d): the field (acceleration and potential) and the tidal tensor of the bodies on the
+// device at m points the caller brings (point_sums.hip).  Host C++ only; one flow, the pass (point_sums_args.hpp) says what differs.
+// Flow (query_pass.hpp): reconfigure(), complete_positions() (the other slices, as nbody_forces_rows brings them), then per local its
+// contiguous range of the points: upload, the launch (and the combine launch when the sources are split) on the local's compute stream,
+// stream sync, copy back.  nbody_init_rank contexts: every rank evaluates the points IT was given on its own device; the call is
+// collective only through complete_positions().
+// A call reads pos[cur] and writes only the Local's q_* buffers: positions, velocities, arrival counters, partial forces, the captured
+// step graph and the force-kernel timer stay as they were.  Nothing outside this file refers to it.
+#include "query_pass.hpp"
+#include "point_sums_args.hpp"
+
+using namespace nbp;
+
+namespace nbi {
+
+namespace {
+
+// points [r.first, r.first + r.cnt) of the call on local L (uploaded; the outputs asked for left in q_out for the copy back)
+int launch_point_sums(Local& L, const PointPass& pass, const void* points, const int* skip, const Range& r, void* const (&out)[2]) {
+  HIPC(hipSetDevice(L.device));
+  const size_t wb = word_bytes(), es = elem_bytes();
+  const size_t ob[2] = {pass.out_values[0] * es, pass.out_values[1] * es};   // bytes per point of each output
+  NBC(upload_queries(L, points, skip, r.first, r.cnt));
+  for (int i = 0; i < 2; ++i)
+    if (out[i]) NBC(L.q_out[i].ensure((size_t)r.cnt * ob[i]));
+  const int n_blocks = source_blocks();
+  const SplitPlan plan = block_split(pass.split_env, pass.scratch_mb_env, r.cnt, n_blocks, pass.sums, es);
+  if (plan.chunks > 1) NBC(L.q_scratch.ensure(point_sums_scratch_bytes((size_t)plan.batch, (size_t)n_blocks, (size_t)pass.sums, es)));
+  return for_batches(r.cnt, plan, [&](int b0, int m) {
+    PointSumsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.src = L.pos[L.cur];
+    a.points = L.q_points.as<char>() + (size_t)b0 * wb;
+    a.skip = skip ? L.q_skip.as<int>() + b0 : nullptr;
+    for (int i = 0; i < 2; ++i) a.out[i] = out[i] ? L.q_out[i].as<char>() + (size_t)b0 * ob[i] : nullptr;
+    a.scratch = plan.chunks > 1 ? L.q_scratch.as<void>() : nullptr;
+    a.n_src = g.n;
+    a.m = m;
+    a.n_blocks = n_blocks;
+    a.chunk_blocks = plan.chunk_blocks;
+    HIPC((hipError_t)nbl::launch_point_sums_kernel(pass, g.fp64, g.opt.arith, L.compute, plan.chunks, a));
+    if (plan.chunks > 1) HIPC((hipError_t)nbl::launch_point_sums_combine_kernel(pass, g.fp64, L.compute, a));
+    return NBODY_OK;
+  });
+}
+
+// out: the caller's arrays, null where the pass has no such output or the caller does not ask for it; at least one
+int point_sums_impl(const PointPass& pass, const void* points, int m, const int* skip, void* out0, void* out1) {
+  void* const out[2] = {out0, out1};
+  if (!g.init) return NBODY_ERR_NOT_INIT;
+  if (!points || m < 1 || (!out[0] && !out[1])) return NBODY_ERR_ARG;
+  NBC(check_skip(skip, m));
+  NBC(reconfigure());
+  NBC(complete_positions());
+  return run_on_locals([&](int l) { return points_of(m, l); },
+                       [&](Local& L, const Range& r) { return launch_point_sums(L, pass, points, skip, r, out); },
+                       [&](Local& L, const Range& r) {
+                         NBC(copy_out(out[0], r.out, L.q_out[0], r.cnt, pass.out_values[0] * elem_bytes()));
+                         return copy_out(out[1], r.out, L.q_out[1], r.cnt, pass.out_values[1] * elem_bytes());
+                       });
+}
+
+}  // namespace
+
+}  // namespace nbi
+
+using namespace nbi;
+
+extern "C" {
+
+int nbody_field(const float* points, int m, const int* skip, float* accel, float* phi) { NB_ENTER(0);
+  return point_sums_impl(kFieldPass, points, m, skip, accel, phi);
+}
+int nbody_field_d(const double* points, int m, const int* skip, double* accel, double* phi) { NB_ENTER(1);
+  return point_sums_impl(kFieldPass, points, m, skip, accel, phi);
+}
+int nbody_tidal(const float* points, int m, const int* skip, float* tensor) { NB_ENTER(0);
+  return point_sums_impl(kTidalPass, points, m, skip, tensor, nullptr);
+}
+int nbody_tidal_d(const double* points, int m, const int* skip, double* tensor) { NB_ENTER(1);
+  return point_sums_impl(kTidalPass, points, m, skip, tensor, nullptr);
+}
+
+}  // extern "C"

@@ -1,0 +1,181 @@
+// point_sums.hip — the device code of the two point-sum passes: the field (acceleration and potential) and the tidal tensor T = grad a =
+// -grad grad phi of the N bodies on the device at m arbitrary points (point_sums_args.hpp states the order, include/nbody.h the
+// definitions).  One skeleton — a kernel of blocked level-1 sums, its combine, one launcher pair — and a statement per pass of what
+// differs: the number of sums, the pair, the store.  Compiles on its own; device.hip puts it into the library's one code object after
+// kernels.hip and energy.hip.  Reads nbody_args.hpp (f4, d4, NB_CONST) and nothing else of the force path: d2 and 1/sqrt are
+// diag_pass.hpp's inv_dist, the potential's; the field's cube and three fma follow the force's pair_f32 / pair_f64.  gfx950 only.
+#include <hip/hip_runtime.h>
+
+#include "../../include/nbody.h"
+#include "point_sums_args.hpp"
+#include "nbody_args.hpp"
+
+using namespace nbk;
+using namespace nbp;
+using namespace nbd;
+
+#define NBP_HIDDEN __attribute__((visibility("hidden")))
+
+namespace {
+
+// ---- the pass statements.  pair: one source into the level-1 sums c of a point; every intermediate comes before the CMP return, which
+// ---- keeps the CMP = false body free of branches; CMP: source j == sk leaves c as it is.  store: a point's result from its level-2 sums.
+
+struct FieldSums {
+  static constexpr int kSums = kFieldPass.sums;   // {ax, ay, az, s}
+  // 3 sub, d2, 1/sqrt, 2 mul (the force's cube), 3 fma, 1 add
+  template <int ARITH, bool CMP, typename T, typename V4>
+  static __device__ __forceinline__ void pair(const V4 p, const V4 me, T eps, int j, int sk, T (&c)[kSums]) {
+    const T dx = p.x - me.x, dy = p.y - me.y, dz = p.z - me.z;
+    const T inv = inv_dist<ARITH>(dx, dy, dz, eps);
+    const T inv2 = inv * inv;
+    const T inv3 = inv * inv2;
+    const T ax = fma_of(dx, inv3, c[0]), ay = fma_of(dy, inv3, c[1]), az = fma_of(dz, inv3, c[2]), s = c[3] + inv;
+    if (CMP && j == sk) return;
+    c[0] = ax; c[1] = ay; c[2] = az; c[3] = s;
+  }
+  template <typename T, typename V4>
+  static __device__ __forceinline__ void store(const PointSumsArgs& a, int p, const double (&l2)[kSums]) {
+    if (a.out[0]) ((V4*)a.out[0])[p] = V4{(T)l2[0], (T)l2[1], (T)l2[2], (T)0};
+    if (a.out[1]) ((T*)a.out[1])[p] = (T)(0.0 - l2[3]);
+  }
+};
+
+struct TidalSums {
+  static constexpr int kSums = kTidalPass.sums;   // {qxx, qyy, qzz, qxy, qxz, qyz, s3}
+  // 3 sub, d2, 1/sqrt, 3 mul (inv2, inv3, inv5), 1 mul (w = 3 inv5), 3 mul (w d), 6 fma, 1 add: 21 VALU + 1 transcendental in the fp32
+  // timed form
+  template <int ARITH, bool CMP, typename T, typename V4>
+  static __device__ __forceinline__ void pair(const V4 p, const V4 me, T eps, int j, int sk, T (&c)[kSums]) {
+    const T dx = p.x - me.x, dy = p.y - me.y, dz = p.z - me.z;
+    const T inv = inv_dist<ARITH>(dx, dy, dz, eps);
+    const T inv2 = inv * inv;
+    const T inv3 = inv * inv2;
+    const T inv5 = inv3 * inv2;
+    const T w = (T)3 * inv5;
+    const T wx = w * dx, wy = w * dy, wz = w * dz;
+    const T xx = fma_of(wx, dx, c[0]), yy = fma_of(wy, dy, c[1]), zz = fma_of(wz, dz, c[2]);
+    const T xy = fma_of(wx, dy, c[3]), xz = fma_of(wx, dz, c[4]), yz = fma_of(wy, dz, c[5]);
+    const T s3 = c[6] + inv3;
+    if (CMP && j == sk) return;
+    c[0] = xx; c[1] = yy; c[2] = zz; c[3] = xy; c[4] = xz; c[5] = yz; c[6] = s3;
+  }
+  // the six values {xx, yy, zz, xy, xz, yz}: the diagonal's subtraction in fp64, rounded once
+  template <typename T, typename V4>
+  static __device__ __forceinline__ void store(const PointSumsArgs& a, int p, const double (&l2)[kSums]) {
+    T* out = (T*)a.out[0] + (size_t)p * kTidalPass.out_values[0];
+    out[0] = (T)(l2[0] - l2[6]); out[1] = (T)(l2[1] - l2[6]); out[2] = (T)(l2[2] - l2[6]);
+    out[3] = (T)l2[3]; out[4] = (T)l2[4]; out[5] = (T)l2[5];
+  }
+};
+
+// ---- the skeleton ----
+
+// One point per lane, kLanes points per workgroup; workgroup (x, y) walks the blocks of chunk y for the points of x.  Sources
+// arrive with wave-uniform scalar loads (address space 4, as energy_kernel).  Lanes beyond m stay in the wave-uniform loops clamped to
+// the last point and store nothing.  SKIP: only the aligned 64-source windows that overlap [lowest, highest] skip index of the wave's
+// 64 points compare j with skip (a wave-uniform branch); every other window, and every window of the SKIP = false form, is the pass's
+// branch-free pair (field: 3 sub, 3 fma, 1 rsq, 2 mul, 3 fma and 1 add).
+template <class P, typename T, typename V4, int ARITH, bool SKIP>
+__global__ void __launch_bounds__(kLanes) block_sums_kernel(PointSumsArgs a) {
+  constexpr int S = P::kSums;
+  const auto [p, live, pc] = lane_of(a.m);
+  const V4 me = ((const V4*)a.points)[pc];
+  const auto [sk, wlo, whi] = wave_skip_window<SKIP>(SKIP ? a.skip[pc] : -1);
+  const T eps = soft<T>();
+  const NB_CONST V4* src = scalar_src<V4>(a.src);
+  T* sc = (T*)a.scratch;
+  const auto [blk0, blk1] = chunk_of(a.chunk_blocks, a.n_blocks);
+  double l2[S] = {};
+  for (int blk = blk0; blk < blk1; ++blk) {
+    const int b0 = blk * kSrcBlock;
+    const int b1 = min(b0 + kSrcBlock, a.n_src);
+    T c[S] = {};
+    int j = b0;
+    for (; j + 64 <= b1; j += 64) {
+      if (!SKIP || j + 63 < wlo || j > whi) {
+#pragma unroll 8
+        for (int k = 0; k < 64; ++k) P::template pair<ARITH, false, T, V4>(src[j + k], me, eps, j + k, sk, c);
+      } else {
+#pragma unroll 8
+        for (int k = 0; k < 64; ++k) P::template pair<ARITH, true, T, V4>(src[j + k], me, eps, j + k, sk, c);
+      }
+    }
+    for (; j < b1; ++j) P::template pair<ARITH, SKIP, T, V4>(src[j], me, eps, j, sk, c);   // the last block's tail (N not a multiple of 64)
+    if (sc) {
+      if (live) {
+        const size_t w = (size_t)blk * S * (size_t)a.m + (size_t)p;
+#pragma unroll
+        for (int q = 0; q < S; ++q) sc[w + (size_t)q * (size_t)a.m] = c[q];
+      }
+    } else {
+#pragma unroll
+      for (int q = 0; q < S; ++q) l2[q] += (double)c[q];
+    }
+  }
+  if (!sc && live) P::template store<T, V4>(a, p, l2);
+}
+
+// level 2 from the stored per-block sums: blocks ascending, fp64, one point per lane (a wave reads 64 consecutive values per word)
+template <class P, typename T, typename V4>
+__global__ void __launch_bounds__(kLanes) block_sums_combine(PointSumsArgs a) {
+  constexpr int S = P::kSums;
+  const int p = (int)blockIdx.x * kLanes + (int)threadIdx.x;
+  if (p >= a.m) return;
+  const T* sc = (const T*)a.scratch;
+  const size_t m = (size_t)a.m;
+  double l2[S] = {};
+  for (int blk = 0; blk < a.n_blocks; ++blk) {
+    const size_t w = (size_t)blk * S * m + (size_t)p;
+#pragma unroll
+    for (int q = 0; q < S; ++q) l2[q] += (double)sc[w + (size_t)q * m];
+  }
+  P::template store<T, V4>(a, p, l2);
+}
+
+template <class P, typename T, typename V4, int ARITH>
+void launch_sums_one(hipStream_t st, int chunks, const PointSumsArgs& a) {
+  const dim3 grid((a.m + kLanes - 1) / kLanes, chunks);
+  if (a.skip) hipLaunchKernelGGL((block_sums_kernel<P, T, V4, ARITH, true>), grid, dim3(kLanes), 0, st, a);
+  else hipLaunchKernelGGL((block_sums_kernel<P, T, V4, ARITH, false>), grid, dim3(kLanes), 0, st, a);
+}
+
+template <class P>
+int launch_sums(int fp64, int arith, hipStream_t st, int chunks, const PointSumsArgs& a) {
+  if (a.m <= 0 || chunks < 1 || (chunks > 1 && !a.scratch) || (!a.out[0] && !a.out[1])) return (int)hipErrorInvalidValue;
+  if (fp64) {   // fp64 contexts have one d2 form: REFERENCE = FMA3, REFERENCE_STRICT = STRICT
+    if (arith & kStrict) launch_sums_one<P, double, d4, kStrict>(st, chunks, a);
+    else launch_sums_one<P, double, d4, 0>(st, chunks, a);
+  } else {
+    switch (arith) {
+      case NBODY_ARITH_REFERENCE: launch_sums_one<P, float, f4, kRef>(st, chunks, a); break;
+      case NBODY_ARITH_STRICT: launch_sums_one<P, float, f4, kStrict>(st, chunks, a); break;
+      case NBODY_ARITH_REFERENCE_STRICT: launch_sums_one<P, float, f4, kRef | kStrict>(st, chunks, a); break;
+      default: launch_sums_one<P, float, f4, 0>(st, chunks, a); break;
+    }
+  }
+  return (int)hipGetLastError();
+}
+
+template <class P>
+int launch_combine(int fp64, hipStream_t st, const PointSumsArgs& a) {
+  if (a.m <= 0 || !a.scratch || (!a.out[0] && !a.out[1])) return (int)hipErrorInvalidValue;
+  const dim3 grid((a.m + kLanes - 1) / kLanes);
+  if (fp64) hipLaunchKernelGGL((block_sums_combine<P, double, d4>), grid, dim3(kLanes), 0, st, a);
+  else hipLaunchKernelGGL((block_sums_combine<P, float, f4>), grid, dim3(kLanes), 0, st, a);
+  return (int)hipGetLastError();
+}
+
+}  // namespace
+
+namespace nbl {
+
+NBP_HIDDEN int launch_point_sums_kernel(const PointPass& pass, int fp64, int arith, hipStream_t st, int chunks, const PointSumsArgs& a) {
+  return pass.id == kTidalPass.id ? launch_sums<TidalSums>(fp64, arith, st, chunks, a) : launch_sums<FieldSums>(fp64, arith, st, chunks, a);
+}
+
+NBP_HIDDEN int launch_point_sums_combine_kernel(const PointPass& pass, int fp64, hipStream_t st, const PointSumsArgs& a) {
+  return pass.id == kTidalPass.id ? launch_combine<TidalSums>(fp64, st, a) : launch_combine<FieldSums>(fp64, st, a);
+}
+
+}  // namespace nbl

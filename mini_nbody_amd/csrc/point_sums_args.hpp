@@ -1,0 +1,61 @@
+// point_sums_args.hpp — what point_sums.cpp (host) and point_sums.hip (device) agree on: the two point-sum passes (the field and the
+// tidal tensor of the N bodies at m arbitrary points), their one argument block and the launch functions of point_sums.hip.  Like
+// energy_args.hpp it stays apart from nbody_args.hpp, the force path's hashed kernel source.
+//
+// The order of every sum (include/nbody.h, "field at arbitrary points" and "tidal tensor at arbitrary points") is fixed by N alone and
+// is the potential's.  A pass has `sums` accumulators per point:
+//   level 1  sources in blocks of nbd::kSrcBlock consecutive bodies; per block the accumulators from +0 in ascending j in the context
+//            precision; j == skip[p] leaves all of them as they are.
+//              field (4)  ax = fma(dx, inv3, ax), ay, az likewise, s = s + inv;
+//              tidal (7)  w = 3 inv5, q_ab = fma(w d_a, d_b, q_ab) for ab = xx, yy, zz, xy, xz, yz, s3 = s3 + inv3;
+//   level 2  the blocks' sums converted to fp64 and added in ascending block order from zero, then rounded once.
+//              field      accel = (T){A}, phi = (T)(0 - S);
+//              tidal      T_aa = (T)(Q_aa - S3), T_ab = (T)Q_ab.
+// Level 2 happens in registers when one workgroup walks every block of its points (grid.y = 1, scratch == null).  When the sources are
+// split over grid.y chunks of whole blocks, every workgroup stores its blocks' level-1 sums — per BLOCK, never per chunk, which is
+// what keeps the bits independent of the number of chunks — and the combine kernel adds them.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "diag_pass.hpp"
+
+namespace nbp {
+
+// A pass, as the host and the launch functions see it; point_sums.hip states its pair arithmetic and its store.
+struct PointPass {
+  int id;                       // which of the two
+  int sums;                     // kSums: level-1 sums of a point and block
+  int out_values[2];            // kOut: values of the context precision per point in each output (0: the pass has no such output)
+  const char* split_env;        // the host's variables: the forced number of chunks ...
+  const char* scratch_mb_env;   // ... and the bound of the scratch (query_pass.hpp, block_split)
+};
+// field: sums {ax, ay, az, s}; out[0] = accel, words {ax, ay, az, 0}, out[1] = phi; either may be null
+inline constexpr PointPass kFieldPass = {0, 4, {4, 1}, "NBODY_FIELD_SPLIT", "NBODY_FIELD_SCRATCH_MB"};
+// tidal: sums {qxx, qyy, qzz, qxy, qxz, qyz, s3}; out[0] = the tensor, values {xx, yy, zz, xy, xz, yz}, out[1] stays null
+inline constexpr PointPass kTidalPass = {1, 7, {6, 0}, "NBODY_TIDAL_SPLIT", "NBODY_TIDAL_SCRATCH_MB"};
+
+struct PointSumsArgs {
+  const void* src;      // all N source words (16-B or 32-B {x, y, z, w}), ascending
+  const void* points;   // [m] words {x, y, z, ignored} of this launch's points
+  const int* skip;      // [m] global body index to leave out, or -1; null: nothing is left out (the kernel's SKIP = false form)
+  void* out[2];         // [m][out_values[i]] values in the context precision, as the pass lays them out
+  void* scratch;        // null (grid.y = 1), else [n_blocks][sums][m] level-1 sums in the context precision: word (b, q, p) at
+                        // (b * sums + q) * m + p, so that a wave's 64 stores of one (b, q) are contiguous
+  int n_src;            // N
+  int m;                // points of this launch
+  int n_blocks;         // ceil(N / nbd::kSrcBlock)
+  int chunk_blocks;     // blocks per chunk: workgroup (x, y) walks blocks [y * chunk_blocks, min((y + 1) * chunk_blocks, n_blocks))
+};
+
+// scratch bytes of a launch of m points (per-block sums: independent of the number of chunks)
+inline size_t point_sums_scratch_bytes(size_t m, size_t n_blocks, size_t sums, size_t elem) { return m * n_blocks * sums * elem; }
+
+}  // namespace nbp
+
+namespace nbl {
+// both return a hipError_t as int (0 = launched) and refuse a launch with no output at all.  arith: NBODY_ARITH_* (fp64 contexts:
+// strict or not).  grid = (ceil(m / nbd::kLanes), chunks); chunks > 1 needs a.scratch and is followed by launch_point_sums_combine_kernel
+int launch_point_sums_kernel(const nbp::PointPass& pass, int fp64, int arith, hipStream_t stream, int chunks, const nbp::PointSumsArgs& a);
+// level 2 of every point of the launch from a.scratch: blocks ascending in fp64, then the pass's store
+int launch_point_sums_combine_kernel(const nbp::PointPass& pass, int fp64, hipStream_t stream, const nbp::PointSumsArgs& a);
+}  // namespace nbl

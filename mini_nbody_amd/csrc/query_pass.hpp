@@ -1,10 +1,10 @@
-// query_pass.hpp — the host side that the diagnostic passes share (energy.cpp, field.cpp, tidal.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp; host C++ only): a call brings
+// query_pass.hpp — the host side that the diagnostic passes share (energy.cpp, point_sums.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp; host C++ only): a call brings
 // rows or points, every local takes a contiguous range of them, launches on its compute stream — in batches over a split of the
 // sources when the pass asks for one — and the results are copied back once the stream has drained.  A pass says what differs: which
 // range a local gets, what to launch, which outputs go where, and which of the two split rules (a SplitPlan) it follows: chunk_split,
 // for the five distance passes whose scratch is per chunk, or block_split, for the field and tidal passes, whose scratch is per block.
-// The points, skip indices and split scratch of a call live in one set of buffers per Local (q_points, q_skip, q_scratch), whichever
-// pass runs: every call drains the streams it used before it returns, so no two calls ever use them at once.
+// The points, skip indices and split scratch of a call live in one set of buffers per Local (q_points, q_skip, q_scratch; q_out, the
+// outputs of the field and tidal passes, likewise), whichever pass runs: every call drains the streams it used before it returns, so no two calls ever use them at once.
 #pragma once
 #include "nbody_internal.hpp"
 #include "diag_pass.hpp"
@@ -63,7 +63,7 @@ inline SplitPlan chunk_split(const char* split_env, const char* scratch_mb_env, 
 }
 
 // The split of the field and tidal passes, whose scratch is per BLOCK (values level-1 sums of `es` bytes for every point and block:
-// field_args.hpp, tidal_args.hpp), so its size per point does not depend on the number of chunks: the points whose per-block sums fit
+// point_sums_args.hpp), so its size per point does not depend on the number of chunks: the points whose per-block sums fit
 // the bound of scratch_mb_env go together, in whole workgroups, and the chunks are chosen anew for such a batch — split_env forces their
 // number.  It reads its MB bound as an integer (env_ll; 256 when unset) where chunk_split takes fractions (atof).
 inline SplitPlan block_split(const char* split_env, const char* scratch_mb_env, int cnt, int n_blocks, int values, size_t es) {

@@ -155,19 +155,8 @@ class NBody:
         phi(x) = -sum_j (|r_j - x|^2 + eps)^(-1/2) over ALL j.  points: (m, 4) words or (m, 3) in the context dtype; skip: None or m
         ints, each -1 or the global index of a body to leave out of that point's sums.  accel: (m, 4) {ax, ay, az, 0} or None when not
         asked for; phi: (m,) or None.  Collective in a multi-rank job (every rank brings its own points)."""
-        p = np.asarray(points, self.dtype)
-        if p.ndim != 2 or p.shape[1] not in (3, 4):
-            raise ValueError("expected an (m, 4) or (m, 3) array of %s" % np.dtype(self.dtype).name)
-        if p.shape[1] == 3:
-            p = np.concatenate([p, np.zeros((len(p), 1), self.dtype)], axis=1)
-        p = np.ascontiguousarray(p)
-        m = len(p)
+        p, m, sk = self._queries(points, skip)
         ct = C.c_double if self.fp64 else C.c_float
-        sk = None
-        if skip is not None:
-            sk = np.ascontiguousarray(skip, np.int32)
-            if sk.shape != (m,):
-                raise ValueError("skip must hold one index per point")
         if not (accel or potential):
             raise ValueError("ask for accel, potential or both")
         a = np.empty((m, 4), self.dtype) if accel else None

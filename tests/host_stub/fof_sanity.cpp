@@ -1,5 +1,5 @@
 // fof_sanity.cpp — TEST INFRASTRUCTURE (tests/test_host_sanitizers.py): drives nbody_fof and nbody_fof_d of the library's host
-// code (fof.cpp beside context.cpp, comm.cpp, mailbox.cpp, energy.cpp, field.cpp, neighbors.cpp, knn.cpp) against
+// code (fof.cpp beside context.cpp, comm.cpp, mailbox.cpp, energy.cpp, point_sums.cpp, neighbors.cpp, knn.cpp) against
 // tests/host_stub/hip_stub.cpp and fof_stub.cpp under AddressSanitizer + UBSan.  What it checks is the host's logic: the union-find and
 // its rounds, the division of the active rows over the devices, the upload of the labels and of the active-row list, the copy-back
 // offsets, the choice of the source split, the scratch size and the batches, the argument checks, lifetimes at shutdown and the

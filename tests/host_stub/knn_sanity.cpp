@@ -1,9 +1,9 @@
 // knn_sanity.cpp — TEST INFRASTRUCTURE (tests/test_host_sanitizers.py): drives nbody_knn_rows and nbody_knn (and their _d forms) of
-// the library's host code (knn.cpp beside context.cpp, comm.cpp, mailbox.cpp, energy.cpp, field.cpp, neighbors.cpp) against
+// the library's host code (knn.cpp beside context.cpp, comm.cpp, mailbox.cpp, energy.cpp, point_sums.cpp, neighbors.cpp) against
 // tests/host_stub/hip_stub.cpp and knn_stub.cpp under AddressSanitizer + UBSan.  What it checks is the host's logic: the rows of a
 // window and the division of the points over the devices, the upload and copy-back offsets of [m][k] outputs, the choice of the source
 // split, the k-dependent scratch size and the batches, the argument checks, lifetimes at shutdown and the failure paths.  knn_stub.cpp
-// states the values expected here.  neighbors_stub.cpp and field_stub.cpp are linked for neighbors.cpp and field.cpp; nbody_nearest
+// states the values expected here.  neighbors_stub.cpp and point_sums_stub.cpp are linked for neighbors.cpp and point_sums.cpp; nbody_nearest
 // runs between knn calls on one context (the passes share their query buffers).
 #include <math.h>
 #include <string.h>

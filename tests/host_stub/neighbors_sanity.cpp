@@ -3,7 +3,7 @@
 // energy.cpp) against tests/host_stub/hip_stub.cpp and neighbors_stub.cpp under AddressSanitizer + UBSan.  What it checks is the host's
 // logic: the rows of a window and the division of the points over the devices, the upload and copy-back offsets, the choice of the
 // source split, the scratch size and the batches, the argument checks, the closest pair over the devices, lifetimes at shutdown and
-// the failure paths.  neighbors_stub.cpp states the values expected here.  field.cpp and field_stub.cpp are linked too, for the
+// the failure paths.  neighbors_stub.cpp states the values expected here.  point_sums.cpp and point_sums_stub.cpp are linked too, for the
 // nbody_field calls between neighbour calls on one context (the two passes share their query buffers).
 #include <math.h>
 #include <string.h>
@@ -93,7 +93,7 @@ struct Case {
     OK(pair(nullptr, &j2, (T*)nullptr));
     CHECK(j2 == bj);
   }
-  // nbody_field at the first `count` points, with skip, against what field_stub.cpp makes of them
+  // nbody_field at the first `count` points, with skip, against what point_sums_stub.cpp makes of them
   void run_field(int count) {
     std::vector<T> acc((size_t)count * 4 + 4, (T)-77), phi((size_t)count + 1, (T)-77);
     OK(field(pts.data(), count, skip.data(), acc.data(), phi.data()));

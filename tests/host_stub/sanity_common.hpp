@@ -1,4 +1,4 @@
-// sanity_common.hpp — TEST INFRASTRUCTURE: what the sanitizer drivers (host_sanity.cpp, field_sanity.cpp, neighbors_sanity.cpp) share.
+// sanity_common.hpp — TEST INFRASTRUCTURE: what the sanitizer drivers (host_sanity.cpp, point_sums_sanity.cpp, neighbors_sanity.cpp and their siblings) share.
 // A driver defines SANITY_NAME, the name its messages carry, before it includes this.
 #pragma once
 #include <stdio.h>

@@ -5,14 +5,16 @@ tests/host_stub/hip_stub.cpp stands in for the HIP runtime ("device" memory is m
 streams run synchronously, a capture records closures) and for kernels.hip (a simple stand-in force pushed through the REAL data flow
 of a launch: ForceArgs, segment bounds, partial sums, arrival counters, ascending combine, apply, the mailbox's ingest and
 device-written completion) and energy.hip (predictable values written through the real EnergyArgs); <pass>_stub.cpp stands in for
-<pass>.hip the same way (predictable values pushed through the real FieldArgs / NeighborsArgs / KnnArgs / FofArgs: chunk bounds, the
-chunks' scratch layout, the combine).  The drivers, one per row of CASES:
+<pass>.hip the same way (predictable values pushed through the real PointSumsArgs / NeighborsArgs / KnnArgs / FofArgs: chunk bounds, the
+blocks' or chunks' scratch layout, the combine).  The drivers, one per row of CASES (point_sums_sanity.cpp serves two, by its argument):
   host_sanity.cpp       contexts of several sizes, 70-step loops (graph capture and replay), every segmentation / combine form / wave
                         split, row windows, the energy entry points, fp64, one process over three stub devices with ragged slices, the
                         mailbox in every form with the RTL's address map checked against a sentinel, a request whose completion wait
                         fails, and the SERVED mailbox with a second thread hammering nbody_get_info and the refused entry points (VERDICT
                         r05 item 4: "a TSan build of a host-only stub of the serve loop");
-  field_sanity.cpp      nbody_field(_d): m = 1, 255, 256, 257, 5000, skip present and absent, either output NULL;
+  point_sums_sanity.cpp field: nbody_field(_d): m = 1, 255, 256, 257, 5000, skip present and absent, either output NULL;
+                        tidal: nbody_tidal(_d) likewise, the six values per point, nbody_field calls between tidal calls on one
+                        context, whose query and output buffers the two passes share;
   neighbors_sanity.cpp  nbody_neighbors_rows, nbody_nearest, nbody_closest_pair: row windows that straddle devices, each output NULL in
                         turn, the closest pair over three devices, nbody_field calls between nbody_nearest calls on one context, whose
                         query buffers the two passes share;
@@ -43,15 +45,17 @@ NEIGHBORS_ENV = ("NBODY_NEIGHBORS_SPLIT", "NBODY_NEIGHBORS_SCRATCH_MB", "NBODY_N
 #        variables it must not inherit, the line it prints when everything held)
 CASES = {
     "host": (HOST, ("hip_stub.cpp", "host_sanity.cpp"), ["2000"], (), "host_sanity ok"),
-    "field": (HOST + ("field.cpp",), ("hip_stub.cpp", "field_stub.cpp", "field_sanity.cpp"), [],
-              ("NBODY_FIELD_SPLIT", "NBODY_FIELD_SCRATCH_MB"), "field_sanity ok"),
-    "neighbors": (HOST + ("neighbors.cpp", "field.cpp"), ("hip_stub.cpp", "neighbors_stub.cpp", "field_stub.cpp", "neighbors_sanity.cpp"), [],
+    "field": (HOST + ("point_sums.cpp",), ("hip_stub.cpp", "point_sums_stub.cpp", "point_sums_sanity.cpp"), ["field"],
+              ("NBODY_FIELD_SPLIT", "NBODY_FIELD_SCRATCH_MB"), "point_sums_sanity field ok"),
+    "tidal": (HOST + ("point_sums.cpp",), ("hip_stub.cpp", "point_sums_stub.cpp", "point_sums_sanity.cpp"), ["tidal"],
+              ("NBODY_TIDAL_SPLIT", "NBODY_TIDAL_SCRATCH_MB", "NBODY_FIELD_SPLIT", "NBODY_FIELD_SCRATCH_MB"), "point_sums_sanity tidal ok"),
+    "neighbors": (HOST + ("neighbors.cpp", "point_sums.cpp"), ("hip_stub.cpp", "neighbors_stub.cpp", "point_sums_stub.cpp", "neighbors_sanity.cpp"), [],
                   NEIGHBORS_ENV, "neighbors_sanity ok"),
-    "knn": (HOST + ("neighbors.cpp", "field.cpp", "knn.cpp"),
-            ("hip_stub.cpp", "neighbors_stub.cpp", "field_stub.cpp", "knn_stub.cpp", "knn_sanity.cpp"), [],
+    "knn": (HOST + ("neighbors.cpp", "point_sums.cpp", "knn.cpp"),
+            ("hip_stub.cpp", "neighbors_stub.cpp", "point_sums_stub.cpp", "knn_stub.cpp", "knn_sanity.cpp"), [],
             ("NBODY_KNN_SPLIT", "NBODY_KNN_SCRATCH_MB") + NEIGHBORS_ENV, "knn_sanity ok"),
-    "fof": (HOST + ("neighbors.cpp", "field.cpp", "knn.cpp", "fof.cpp"),
-            ("hip_stub.cpp", "neighbors_stub.cpp", "field_stub.cpp", "knn_stub.cpp", "fof_stub.cpp", "fof_sanity.cpp"), [],
+    "fof": (HOST + ("neighbors.cpp", "point_sums.cpp", "knn.cpp", "fof.cpp"),
+            ("hip_stub.cpp", "neighbors_stub.cpp", "point_sums_stub.cpp", "knn_stub.cpp", "fof_stub.cpp", "fof_sanity.cpp"), [],
             ("NBODY_FOF_SPLIT", "NBODY_FOF_SCRATCH_MB", "NBODY_FOF_ALL_ROWS"), "fof_sanity ok"),
 }
 _objects = {}      # (source, sanitizer flags) -> object file: every source is compiled once per flag set and session

@@ -1,5 +1,5 @@
 """timescale.cpp — the host side of the pair time-scale pass and of the shared adaptive step — under AddressSanitizer + UBSan on the
-CPU, as tests/test_tidal_host_sanitizers.py runs its sibling: a stand-alone program with its own main
+CPU, as tests/test_hist_host_sanitizers.py runs its sibling: a stand-alone program with its own main
 (tests/host_stub/timescale_sanity.cpp), linked from the host files under test, hip_stub.cpp and timescale_stub.cpp (predictable values
 pushed through the real TimescaleArgs: chunk bounds, the chunks' scratch layout of two minima and an index, the combine, both source
 streams); nothing is loaded into Python under a sanitizer.  The driver covers one and three stub devices with ragged slices, windows of

@@ -23,6 +23,14 @@ inline bool bad_source_split(const A& a, bool indexed_by_first) {
   if ((long long)a.chunks * a.chunk_blocks < a.n_blocks || (long long)(a.chunks - 1) * a.chunk_blocks >= a.n_blocks) return true;
   return indexed_by_first && (a.first < 0 || a.first > a.n_src - a.m);
 }
+// What the combine of a split launch refuses, for any argument block with m, scratch and chunks: no query, no scratch to read, no chunk.
+template <class A>
+inline bool bad_combine(const A& a) { return a.m <= 0 || !a.scratch || a.chunks < 1; }
+// What a reduction over `rows` rows' arrays (a *_best or *_reduce launch) refuses: a negative count, no output, and rows without every
+// input array (have_inputs); no rows at all need none.
+inline bool bad_row_reduce(int rows, const void* out, bool have_inputs) { return rows < 0 || !out || (rows > 0 && !have_inputs); }
+// A pass states its further terms beside its argument block (bad_*_launch, bad_*_combine in its *_args.hpp); the launch functions and
+// the host sanitizer harness's stand-ins for them (tests/host_stub) call the same predicates.
 
 }  // namespace nbd
 

@@ -76,7 +76,7 @@ __global__ void __launch_bounds__(kLanes) fof_combine(FofArgs a) {
 namespace nbl {
 
 NBG_HIDDEN int launch_fof_kernel(int fp64, hipStream_t st, const FofArgs& a) {
-  if (bad_source_split(a, !a.rows) || !a.src || !a.label || !a.out) return (int)hipErrorInvalidValue;
+  if (bad_fof_launch(a)) return (int)hipErrorInvalidValue;
   const dim3 grid((a.m + kLanes - 1) / kLanes, a.chunks), block(kLanes);
   if (fp64) hipLaunchKernelGGL((fof_kernel<double, d4>), grid, block, 0, st, a);
   else hipLaunchKernelGGL((fof_kernel<float, f4>), grid, block, 0, st, a);
@@ -84,7 +84,7 @@ NBG_HIDDEN int launch_fof_kernel(int fp64, hipStream_t st, const FofArgs& a) {
 }
 
 NBG_HIDDEN int launch_fof_combine_kernel(hipStream_t st, const FofArgs& a) {
-  if (a.m <= 0 || !a.scratch || !a.out || a.chunks < 1) return (int)hipErrorInvalidValue;
+  if (bad_fof_combine(a)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(fof_combine, dim3((a.m + kLanes - 1) / kLanes), dim3(kLanes), 0, st, a);
   return (int)hipGetLastError();
 }

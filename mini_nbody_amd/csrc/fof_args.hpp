@@ -35,6 +35,10 @@ struct FofArgs {
 // scratch of a launch of m rows over `chunks` chunks: 4 bytes per (row, chunk)
 inline size_t fof_scratch_bytes(size_t m, size_t chunks) { return m * chunks * sizeof(int); }
 
+// what launch_fof_kernel and launch_fof_combine_kernel refuse
+inline bool bad_fof_launch(const FofArgs& a) { return nbd::bad_source_split(a, !a.rows) || !a.src || !a.label || !a.out; }
+inline bool bad_fof_combine(const FofArgs& a) { return nbd::bad_combine(a) || !a.out; }
+
 }  // namespace nbg
 
 namespace nbl {

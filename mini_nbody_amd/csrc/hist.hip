@@ -164,14 +164,12 @@ void launch_hist_of(hipStream_t st, const HistArgs& a) {
   }
 }
 
-bool bad_bins(int n_bins) { return n_bins < 1 || n_bins > kHistMaxBins; }
-
 }  // namespace
 
 namespace nbl {
 
 NBH_HIDDEN int launch_hist_kernel(int fp64, int loop, hipStream_t st, const HistArgs& a) {
-  if (bad_source_split(a, !a.points) || bad_bins(a.n_bins) || (!a.scratch && !a.counts)) return (int)hipErrorInvalidValue;
+  if (bad_hist_launch(a)) return (int)hipErrorInvalidValue;
   if (fp64) {
     if (loop == kHistLoopGated) launch_hist_of<double, d4, kHistLoopGated>(st, a);
     else launch_hist_of<double, d4, kHistLoopScan>(st, a);
@@ -183,13 +181,13 @@ NBH_HIDDEN int launch_hist_kernel(int fp64, int loop, hipStream_t st, const Hist
 }
 
 NBH_HIDDEN int launch_hist_combine_kernel(hipStream_t st, const HistArgs& a) {
-  if (a.m <= 0 || bad_bins(a.n_bins) || !a.scratch || !a.counts || a.chunks < 1) return (int)hipErrorInvalidValue;
+  if (bad_hist_combine(a)) return (int)hipErrorInvalidValue;
   hipLaunchKernelGGL(hist_combine, dim3((a.m + kLanes - 1) / kLanes, a.n_bins), dim3(kLanes), 0, st, a);
   return (int)hipGetLastError();
 }
 
 NBH_HIDDEN int launch_hist_reduce_kernel(hipStream_t st, const int* counts, int rows, int n_bins, unsigned long long* sums) {
-  if (rows < 0 || bad_bins(n_bins) || !sums || (rows > 0 && !counts)) return (int)hipErrorInvalidValue;
+  if (bad_hist_reduce(counts, rows, n_bins, sums)) return (int)hipErrorInvalidValue;
   if (rows == 0) return (int)hipSuccess;
   const int groups = std::min((rows + kReduceRows - 1) / kReduceRows, 1024);
   hipLaunchKernelGGL(hist_reduce, dim3(groups), dim3(kLanes), 0, st, counts, rows, n_bins, sums);

@@ -59,6 +59,14 @@ inline void hist_set_edges(HistArgs& a, const T* edges2, int n_bins) {
   for (int s = 0; s < kHistSlots; ++s) slot[s] = s < lead ? -(T)__builtin_huge_valf() : edges2[s - lead];
 }
 
+// what the three launch functions refuse: an n_bins outside 1 .. kHistMaxBins, nowhere to leave the counts
+inline bool bad_bins(int n_bins) { return n_bins < 1 || n_bins > kHistMaxBins; }
+inline bool bad_hist_launch(const HistArgs& a) { return nbd::bad_source_split(a, !a.points) || bad_bins(a.n_bins) || (!a.scratch && !a.counts); }
+inline bool bad_hist_combine(const HistArgs& a) { return nbd::bad_combine(a) || bad_bins(a.n_bins) || !a.counts; }
+inline bool bad_hist_reduce(const int* counts, int rows, int n_bins, const unsigned long long* sums) {
+  return bad_bins(n_bins) || nbd::bad_row_reduce(rows, sums, counts != nullptr);
+}
+
 }  // namespace nbh
 
 namespace nbl {

@@ -182,14 +182,14 @@ void launch_knn_combine_of(hipStream_t st, const KnnArgs& a) {
 namespace nbl {
 
 NBQ_HIDDEN int launch_knn_kernel(int fp64, hipStream_t st, const KnnArgs& a) {
-  if (bad_source_split(a, !a.points) || a.k < 1 || a.k > kKnMax || (!a.scratch && !a.idx && !a.d2)) return (int)hipErrorInvalidValue;
+  if (bad_knn_launch(a)) return (int)hipErrorInvalidValue;
   if (fp64) launch_knn_of<double, d4>(st, a);
   else launch_knn_of<float, f4>(st, a);
   return (int)hipGetLastError();
 }
 
 NBQ_HIDDEN int launch_knn_combine_kernel(int fp64, hipStream_t st, const KnnArgs& a) {
-  if (a.m <= 0 || a.k < 1 || a.k > kKnMax || !a.scratch || a.chunks < 1 || (!a.idx && !a.d2)) return (int)hipErrorInvalidValue;
+  if (bad_knn_combine(a)) return (int)hipErrorInvalidValue;
   if (fp64) launch_knn_combine_of<double>(st, a);
   else launch_knn_combine_of<float>(st, a);
   return (int)hipGetLastError();

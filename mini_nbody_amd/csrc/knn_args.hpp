@@ -48,6 +48,11 @@ __host__ __device__ inline size_t knn_scratch_at(const KnnArgs& a, int c, int r,
   return ((size_t)c * (size_t)a.k + (size_t)r) * (size_t)a.m + (size_t)p;
 }
 
+// what launch_knn_kernel and launch_knn_combine_kernel refuse: a k outside 1 .. kKnMax, nowhere to leave the lists
+inline bool bad_k(int k) { return k < 1 || k > kKnMax; }
+inline bool bad_knn_launch(const KnnArgs& a) { return nbd::bad_source_split(a, !a.points) || bad_k(a.k) || (!a.scratch && !a.idx && !a.d2); }
+inline bool bad_knn_combine(const KnnArgs& a) { return nbd::bad_combine(a) || bad_k(a.k) || (!a.idx && !a.d2); }
+
 }  // namespace nbq
 
 namespace nbl {

@@ -174,7 +174,7 @@ NBN_HIDDEN int launch_neighbors_kernel(int fp64, int loop, hipStream_t st, const
 }
 
 NBN_HIDDEN int launch_neighbors_combine_kernel(int fp64, hipStream_t st, const NeighborsArgs& a) {
-  if (a.m <= 0 || !a.scratch || a.chunks < 1) return (int)hipErrorInvalidValue;
+  if (bad_combine(a)) return (int)hipErrorInvalidValue;
   const dim3 grid((a.m + kLanes - 1) / kLanes);
   if (fp64) hipLaunchKernelGGL((neighbors_combine<double>), grid, dim3(kLanes), 0, st, a);
   else hipLaunchKernelGGL((neighbors_combine<float>), grid, dim3(kLanes), 0, st, a);
@@ -182,7 +182,7 @@ NBN_HIDDEN int launch_neighbors_combine_kernel(int fp64, hipStream_t st, const N
 }
 
 NBN_HIDDEN int launch_neighbors_best_kernel(int fp64, hipStream_t st, const void* d2, const int* idx, int rows, int first, BestPair* out) {
-  if (rows < 0 || !out || (rows > 0 && (!d2 || !idx))) return (int)hipErrorInvalidValue;
+  if (bad_row_reduce(rows, out, d2 && idx)) return (int)hipErrorInvalidValue;
   if (fp64) hipLaunchKernelGGL((neighbors_best<double>), dim3(1), dim3(kLanes), 0, st, (const double*)d2, idx, rows, first, out);
   else hipLaunchKernelGGL((neighbors_best<float>), dim3(1), dim3(kLanes), 0, st, (const float*)d2, idx, rows, first, out);
   return (int)hipGetLastError();

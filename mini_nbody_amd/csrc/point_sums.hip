@@ -142,7 +142,7 @@ void launch_sums_one(hipStream_t st, int chunks, const PointSumsArgs& a) {
 
 template <class P>
 int launch_sums(int fp64, int arith, hipStream_t st, int chunks, const PointSumsArgs& a) {
-  if (a.m <= 0 || chunks < 1 || (chunks > 1 && !a.scratch) || (!a.out[0] && !a.out[1])) return (int)hipErrorInvalidValue;
+  if (bad_point_sums_launch(a, chunks)) return (int)hipErrorInvalidValue;
   if (fp64) {   // fp64 contexts have one d2 form: REFERENCE = FMA3, REFERENCE_STRICT = STRICT
     if (arith & kStrict) launch_sums_one<P, double, d4, kStrict>(st, chunks, a);
     else launch_sums_one<P, double, d4, 0>(st, chunks, a);
@@ -159,7 +159,7 @@ int launch_sums(int fp64, int arith, hipStream_t st, int chunks, const PointSums
 
 template <class P>
 int launch_combine(int fp64, hipStream_t st, const PointSumsArgs& a) {
-  if (a.m <= 0 || !a.scratch || (!a.out[0] && !a.out[1])) return (int)hipErrorInvalidValue;
+  if (bad_point_sums_combine(a)) return (int)hipErrorInvalidValue;
   const dim3 grid((a.m + kLanes - 1) / kLanes);
   if (fp64) hipLaunchKernelGGL((block_sums_combine<P, double, d4>), grid, dim3(kLanes), 0, st, a);
   else hipLaunchKernelGGL((block_sums_combine<P, float, f4>), grid, dim3(kLanes), 0, st, a);

@@ -50,6 +50,13 @@ struct PointSumsArgs {
 // scratch bytes of a launch of m points (per-block sums: independent of the number of chunks)
 inline size_t point_sums_scratch_bytes(size_t m, size_t n_blocks, size_t sums, size_t elem) { return m * n_blocks * sums * elem; }
 
+// what launch_point_sums_kernel and launch_point_sums_combine_kernel refuse: no point, chunks that need scratch and have none, no
+// output at all (the block has no `chunks`: the kernel launch takes it beside the block, the combine walks all n_blocks)
+inline bool bad_point_sums_launch(const PointSumsArgs& a, int chunks) {
+  return a.m <= 0 || chunks < 1 || (chunks > 1 && !a.scratch) || (!a.out[0] && !a.out[1]);
+}
+inline bool bad_point_sums_combine(const PointSumsArgs& a) { return a.m <= 0 || !a.scratch || (!a.out[0] && !a.out[1]); }
+
 }  // namespace nbp
 
 namespace nbl {

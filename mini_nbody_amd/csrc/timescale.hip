@@ -127,7 +127,7 @@ __global__ void __launch_bounds__(kLanes) timescale_best(const T* tau2, const in
 namespace nbl {
 
 NBTS_HIDDEN int launch_timescale_kernel(int fp64, hipStream_t st, const TimescaleArgs& a) {
-  if (bad_source_split(a, true) || !a.src || !a.vsrc) return (int)hipErrorInvalidValue;
+  if (bad_timescale_launch(a)) return (int)hipErrorInvalidValue;
   const dim3 grid((a.m + kLanes - 1) / kLanes, a.chunks), block(kLanes);
   if (fp64) hipLaunchKernelGGL((timescale_kernel<double, d4>), grid, block, 0, st, a);
   else hipLaunchKernelGGL((timescale_kernel<float, f4>), grid, block, 0, st, a);
@@ -135,7 +135,7 @@ NBTS_HIDDEN int launch_timescale_kernel(int fp64, hipStream_t st, const Timescal
 }
 
 NBTS_HIDDEN int launch_timescale_combine_kernel(int fp64, hipStream_t st, const TimescaleArgs& a) {
-  if (a.m <= 0 || !a.scratch || a.chunks < 1) return (int)hipErrorInvalidValue;
+  if (bad_combine(a)) return (int)hipErrorInvalidValue;
   const dim3 grid((a.m + kLanes - 1) / kLanes);
   if (fp64) hipLaunchKernelGGL((timescale_combine<double>), grid, dim3(kLanes), 0, st, a);
   else hipLaunchKernelGGL((timescale_combine<float>), grid, dim3(kLanes), 0, st, a);
@@ -144,7 +144,7 @@ NBTS_HIDDEN int launch_timescale_combine_kernel(int fp64, hipStream_t st, const 
 
 NBTS_HIDDEN int launch_timescale_best_kernel(int fp64, hipStream_t st, const void* tau2, const int* idx, const void* d2min, int rows, int first,
                                              BestScale* out) {
-  if (rows < 0 || !out || (rows > 0 && (!tau2 || !idx || !d2min))) return (int)hipErrorInvalidValue;
+  if (bad_row_reduce(rows, out, tau2 && idx && d2min)) return (int)hipErrorInvalidValue;
   if (fp64) hipLaunchKernelGGL((timescale_best<double>), dim3(1), dim3(kLanes), 0, st, (const double*)tau2, idx, (const double*)d2min, rows, first, out);
   else hipLaunchKernelGGL((timescale_best<float>), dim3(1), dim3(kLanes), 0, st, (const float*)tau2, idx, (const float*)d2min, rows, first, out);
   return (int)hipGetLastError();

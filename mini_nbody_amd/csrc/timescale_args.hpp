@@ -41,6 +41,9 @@ __host__ __device__ inline int* scratch_idx(const TimescaleArgs& a, size_t elem)
   return (int*)((char*)a.scratch + 2 * (size_t)a.chunks * (size_t)a.m * elem);
 }
 
+// what launch_timescale_kernel refuses
+inline bool bad_timescale_launch(const TimescaleArgs& a) { return nbd::bad_source_split(a, true) || !a.src || !a.vsrc; }
+
 // what timescale_best leaves per device or rank: its rows' smallest tau2 with the row i that reaches it first and that row's partner j
 // (i < 0: none, tau2 = +inf), and its rows' smallest d2min (+inf: none); both converted exactly to fp64
 struct BestScale { double tau2, d2min; int i, j; };

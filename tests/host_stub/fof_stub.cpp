@@ -8,23 +8,16 @@
 // about the kernels' arithmetic (the GPU tests do).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <atomic>
-
 #include "../../mini_nbody_amd/csrc/fof_args.hpp"
+#include "stub_common.hpp"
 
 namespace {
 
 using namespace nbg;
 
 template <typename T>
-struct W4 { T x, y, z, w; };
-
-std::atomic<long> g_combines{0}, g_rows{0}, g_listed{0};
-
-template <typename T>
 void link(const FofArgs& a) {
-  typedef W4<T> V;
+  typedef stub::W4<T> V;
   const V* src = (const V*)a.src;
   const T b2 = (T)a.b2;
   for (int p = 0; p < a.m; ++p) {
@@ -48,25 +41,26 @@ void link(const FofArgs& a) {
 }  // namespace
 
 // combine launches so far (one per batch of a split launch), rows walked so far, and how many of them came from an active-row list
-extern "C" long fof_stub_combines(void) { return g_combines.load(); }
-extern "C" long fof_stub_rows(void) { return g_rows.load(); }
-extern "C" long fof_stub_listed(void) { return g_listed.load(); }
+STUB_COUNTER(fof_stub_combines)
+STUB_COUNTER(fof_stub_rows)
+STUB_COUNTER(fof_stub_listed)
 
 namespace nbl {
 int launch_fof_kernel(int fp64, hipStream_t, const nbg::FofArgs& a) {
-  if (nbd::bad_source_split(a, !a.rows) || !a.src || !a.label || !a.out) return (int)hipErrorInvalidValue;
+  if (nbg::bad_fof_launch(a)) return (int)hipErrorInvalidValue;
+  // the stub's own: what the host promises beyond the guard (the block count, a linking length that is no NaN, ascending rows in range)
   if (a.n_blocks != (a.n_src + nbd::kSrcBlock - 1) / nbd::kSrcBlock || !(a.b2 >= 0.0)) return (int)hipErrorInvalidValue;
   if (a.rows)
     for (int p = 0; p < a.m; ++p)
       if (a.rows[p] < 0 || a.rows[p] >= a.n_src || (p > 0 && a.rows[p] <= a.rows[p - 1])) return (int)hipErrorInvalidValue;
-  g_rows.fetch_add(a.m);
-  if (a.rows) g_listed.fetch_add(a.m);
+  g_fof_stub_rows.fetch_add(a.m);
+  if (a.rows) g_fof_stub_listed.fetch_add(a.m);
   if (fp64) link<double>(a); else link<float>(a);
   return 0;
 }
 int launch_fof_combine_kernel(hipStream_t, const nbg::FofArgs& a) {
-  if (a.m <= 0 || !a.scratch || !a.out || a.chunks < 1) return (int)hipErrorInvalidValue;
-  g_combines.fetch_add(1);
+  if (nbg::bad_fof_combine(a)) return (int)hipErrorInvalidValue;
+  g_fof_stub_combines.fetch_add(1);
   for (int p = 0; p < a.m; ++p) {
     int m = nbg::kFoNone;
     for (int y = 0; y < a.chunks; ++y) m = std::min(m, a.scratch[(size_t)y * (size_t)a.m + (size_t)p]);

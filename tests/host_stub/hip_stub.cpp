@@ -20,8 +20,10 @@
 
 #include "../../mini_nbody_amd/csrc/nbody_internal.hpp"
 #include "../../mini_nbody_amd/csrc/energy_args.hpp"
+#include "stub_common.hpp"
 
 using nbk::ForceArgs;
+using stub::W4;
 
 namespace {
 struct FakeEvent { double ms; };
@@ -37,9 +39,6 @@ int enqueue(std::function<void()> f) {
   else f();
   return 0;
 }
-
-template <typename T>
-struct W4 { T x, y, z, w; };
 
 template <typename T>
 void apply(const ForceArgs& a, int i, T fx, T fy, T fz) {

@@ -62,7 +62,7 @@ static std::vector<float> stepped(int n, int steps, bool step_now = true) {
 
 // the failure paths of everything that creates a resource: sweep() (sanity_common.hpp) walks every creating call of an entry point,
 // the timer rings' 2 x 2 x 256 events per local included
-static void failure_sweeps(bool three_devices) {
+static void failure_sweeps() {
   const int n = 200, n3 = 100;   // n3: ragged over three devices (34, 33, 33)
   std::vector<float> pos, vel;
   bodies(pos, n, 1); bodies(vel, n, 2);
@@ -81,7 +81,7 @@ static void failure_sweeps(bool three_devices) {
 
   int made = sweep("nbody_init", [] {}, [&] { return nbody_init(n, 1, 0, 0); }, [&] { CHECK(info(NBODY_INFO_N) == n && stepped(n, 4) == want4); });
   CHECK(made >= 2 + 5 + 3 + 4 * 256);   // streams, buffers, events and both timer rings were all walked
-  if (three_devices) {
+  if (three_devices()) {
     OK(nbody_init(n3, 3, 0, 0));
     const std::vector<float> want3 = stepped(n3, 4);
     SHUTDOWN();
@@ -121,7 +121,6 @@ static void failure_sweeps(bool three_devices) {
 int main(int argc, char** argv) {
   const int serve_requests = argc > 1 ? atoi(argv[1]) : 10000;
   const bool mailbox_only = argc > 2;
-  const bool three_devices = getenv("STUB_DEVICES") && atoi(getenv("STUB_DEVICES")) >= 3;
   std::vector<float> pos, vel, p2, v2, f, f2;
   // ---- a context, the step loop with its graphs, forces, row windows, options that re-segment ----
   for (int n : {1, 63, 1000, 2085}) {
@@ -161,7 +160,7 @@ int main(int argc, char** argv) {
     check_energy(n, dp, dv, nbody_potential_rows_d);
     CHECK(nbody_step(0.01f, 1) == NBODY_ERR_STATE);
     SHUTDOWN();
-    if (three_devices) {
+    if (three_devices()) {
       bodies(pos, n, 5); bodies(vel, n, 6);
       OK(nbody_init(n, 3, 0, 0));
       BodySystem bb = {pos.data(), vel.data()};
@@ -172,7 +171,7 @@ int main(int argc, char** argv) {
       SHUTDOWN();
     }
   }
-  if (!mailbox_only) failure_sweeps(three_devices);
+  if (!mailbox_only) failure_sweeps();
   // ---- the mailbox: the address map, every form, the guard ----
   const int cap = 700;
   OK(nbody_mailbox_open(cap, 0));

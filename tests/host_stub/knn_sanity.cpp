@@ -8,17 +8,12 @@
 #include <math.h>
 #include <string.h>
 
-#include <algorithm>
-
 #define SANITY_NAME "knn_sanity"
 #include "sanity_common.hpp"
 
 extern "C" long knn_stub_combines(void);   // knn_stub.cpp: combine launches so far, one per batch of a split launch
 
-static void set_env(const char* split, const char* scratch_mb) {
-  if (split) setenv("NBODY_KNN_SPLIT", split, 1); else unsetenv("NBODY_KNN_SPLIT");
-  if (scratch_mb) setenv("NBODY_KNN_SCRATCH_MB", scratch_mb, 1); else unsetenv("NBODY_KNN_SCRATCH_MB");
-}
+static const SplitEnv env = {"NBODY_KNN_SPLIT", "NBODY_KNN_SCRATCH_MB"};
 
 static int rows(int f, int n, int k, int* i, float* d) { return nbody_knn_rows(f, n, k, i, d); }
 static int rows(int f, int n, int k, int* i, double* d) { return nbody_knn_rows_d(f, n, k, i, d); }
@@ -27,69 +22,60 @@ static int at(const double* p, int m, const int* sk, int k, int* i, double* d) {
 static int nearest(const float* p, int m, const int* sk, int* i, float* d) { return nbody_nearest(p, m, sk, i, d, 0.f, nullptr); }
 static int nearest(const double* p, int m, const int* sk, int* i, double* d) { return nbody_nearest_d(p, m, sk, i, d, 0.0, nullptr); }
 
-// small integers everywhere: every value of knn_stub.cpp is exact in either precision
 template <typename T>
-struct Case {
-  int n, m;
-  std::vector<T> pos, vel, pts, d2;
-  std::vector<int> skip, idx;
-  Case(int n_, int m_) : n(n_), m(m_), pos((size_t)n_ * 4), vel((size_t)n_ * 4, (T)0), pts((size_t)m_ * 4), d2((size_t)std::max(n_, m_) * NBODY_KNN_MAX + 1),
-                         skip((size_t)m_), idx((size_t)std::max(n_, m_) * NBODY_KNN_MAX + 1) {
-    for (int j = 0; j < n; ++j) { pos[4 * (size_t)j] = (T)((j * 37) % 101); pos[4 * (size_t)j + 1] = (T)(j % 7); pos[4 * (size_t)j + 2] = (T)1; pos[4 * (size_t)j + 3] = (T)(j % 977); }
-    for (int p = 0; p < m; ++p) {
-      pts[4 * (size_t)p] = (T)(p % 17); pts[4 * (size_t)p + 1] = (T)(p % 5); pts[4 * (size_t)p + 2] = (T)3; pts[4 * (size_t)p + 3] = (T)p;
-      skip[(size_t)p] = p % 3 == 0 ? -1 : (int)(((long long)p * 7919) % n);
-    }
-  }
-  void open(int ngpus) { OK(nbody_init(n, ngpus, sizeof(T) == 8, 0)); OK(upload<T>(pos, vel)); }
-  // what knn_stub.cpp makes of a query {x, w} with the excluded body sk: k entries
-  void expect(T x, T w, int sk, int k, int* e_idx, T* e_d2) const {
+struct Case : Fixture<T> {
+  using F = Fixture<T>;
+  using Q = typename F::Q;
+  using F::n; using F::m; using F::pos; using F::pts; using F::skip;
+  std::vector<T> d2;
+  std::vector<int> idx;
+  Case(int n_, int m_) : F(n_, m_), d2((size_t)std::max(n_, m_) * NBODY_KNN_MAX + 1), idx((size_t)std::max(n_, m_) * NBODY_KNN_MAX + 1) {}
+  // what knn_stub.cpp makes of a query: k entries
+  void expect(const Q& q, int k, int* e_idx, T* e_d2) const {
     for (int r = 0; r < k; ++r) { e_idx[r] = -1; e_d2[r] = (T)INFINITY; }
-    for (int b = 0; b * 1024 < n; ++b) {
-      const int b0 = b * 1024, len = std::min(1024, n - b0), j = b0 + ((int)w + b) % len;
-      const T d = pos[4 * (size_t)j] - x, v = d < 0 ? -d : d;
-      if (j == sk || !(v < e_d2[k - 1])) continue;
+    for (int b = 0; b < stub::blocks_of(n); ++b) {
+      const int j = stub::candidate(n, q.w, b).j;
+      const T v = stub::absdiff(pos[4 * (size_t)j], q.x);
+      if (j == q.sk || !(v < e_d2[k - 1])) continue;
       int r = k - 1;
       for (; r > 0 && v < e_d2[r - 1]; --r) { e_d2[r] = e_d2[r - 1]; e_idx[r] = e_idx[r - 1]; }
       e_d2[r] = v; e_idx[r] = j;
     }
   }
-  void verify(int cnt_q, int k, const std::function<void(int, T*, T*, int*)>& query, bool w_idx, bool w_d2) {
+  void verify(int cnt_q, int k, const std::function<Q(int)>& query, bool w_idx, bool w_d2) {
     for (int q = 0; q < cnt_q; ++q) {
-      T x, w, e_d2[NBODY_KNN_MAX]; int sk, e_idx[NBODY_KNN_MAX];
-      query(q, &x, &w, &sk);
-      expect(x, w, sk, k, e_idx, e_d2);
+      T e_d2[NBODY_KNN_MAX]; int e_idx[NBODY_KNN_MAX];
+      expect(query(q), k, e_idx, e_d2);
       for (int r = 0; r < k; ++r) {
-        CHECK(idx[(size_t)q * k + r] == (w_idx ? e_idx[r] : -77));
-        CHECK(d2[(size_t)q * k + r] == (w_d2 ? e_d2[r] : (T)-77));
+        CHECK(idx[(size_t)q * k + r] == (w_idx ? e_idx[r] : kMark));
+        CHECK(d2[(size_t)q * k + r] == (w_d2 ? e_d2[r] : (T)kMark));
       }
     }
-    for (size_t e = (size_t)cnt_q * k; e < idx.size(); ++e) CHECK(idx[e] == -77 && d2[e] == (T)-77);   // nothing beyond
+    CHECK(nothing_beyond(idx, (size_t)cnt_q * k) && nothing_beyond(d2, (size_t)cnt_q * k));
   }
-  void mark() { std::fill(idx.begin(), idx.end(), -77); std::fill(d2.begin(), d2.end(), (T)-77); }
+  void mark_all() { mark(idx); mark(d2); }
   void run_rows(int first, int count, int k, bool w_idx, bool w_d2) {
-    mark();
+    mark_all();
     OK(rows(first, count, k, w_idx ? idx.data() : nullptr, w_d2 ? d2.data() : nullptr));
-    verify(count, k, [&](int q, T* x, T* w, int* sk) { *x = pos[4 * (size_t)(first + q)]; *w = pos[4 * (size_t)(first + q) + 3]; *sk = first + q; }, w_idx, w_d2);
+    verify(count, k, [&](int q) { return this->row(first + q); }, w_idx, w_d2);
   }
   void run_points(bool with_skip, int k, bool w_idx, bool w_d2, int p0 = 0, int count = -1) {
     if (count < 0) count = m - p0;
-    mark();
+    mark_all();
     OK(at(pts.data() + 4 * (size_t)p0, count, with_skip ? skip.data() + p0 : nullptr, k, w_idx ? idx.data() : nullptr, w_d2 ? d2.data() : nullptr));
-    verify(count, k, [&](int q, T* x, T* w, int* sk) { *x = pts[4 * (size_t)(p0 + q)]; *w = pts[4 * (size_t)(p0 + q) + 3]; *sk = with_skip ? skip[(size_t)(p0 + q)] : -1; },
-           w_idx, w_d2);
+    verify(count, k, [&](int q) { return this->point(p0 + q, with_skip); }, w_idx, w_d2);
   }
   // nbody_nearest at the first `count` points equals entry 0 of the knn stub's list (both stubs offer the same candidates)
   void run_nearest(int count) {
-    std::vector<int> ni((size_t)count + 1, -77);
-    std::vector<T> nd((size_t)count + 1, (T)-77);
+    std::vector<int> ni((size_t)count + 1, kMark);
+    std::vector<T> nd((size_t)count + 1, (T)kMark);
     OK(nearest(pts.data(), count, skip.data(), ni.data(), nd.data()));
     for (int q = 0; q < count; ++q) {
       int e_idx; T e_d2;
-      expect(pts[4 * (size_t)q], pts[4 * (size_t)q + 3], skip[(size_t)q], 1, &e_idx, &e_d2);
+      expect(this->point(q, true), 1, &e_idx, &e_d2);
       CHECK(ni[(size_t)q] == e_idx && nd[(size_t)q] == e_d2);
     }
-    CHECK(ni[(size_t)count] == -77 && nd[(size_t)count] == (T)-77);
+    CHECK(nothing_beyond(ni, (size_t)count) && nothing_beyond(nd, (size_t)count));
   }
   void run_all() {
     for (int k : {1, 5, 32}) {
@@ -109,14 +95,10 @@ struct Case {
 
 template <typename T>
 static void shapes(int n, int ngpus) {
-  for (int m : {1, 255, 256, 257, 5000}) {
+  for (int m : kShapeM) {
     Case<T> c(n, m);
     c.open(ngpus);
-    for (const char* split : {(const char*)nullptr, "0", "1", "3", "1000"}) {
-      set_env(split, nullptr);
-      c.run_all();
-    }
-    set_env(nullptr, nullptr);
+    for_splits(env, {nullptr, "0", "1", "3", "1000"}, [&] { c.run_all(); });
     SHUTDOWN();
   }
 }
@@ -133,11 +115,11 @@ static void interleaved(int ngpus) {
   c.open(ngpus);
   const long batches = ngpus > 1 ? ngpus : sizeof(T) == 4 ? 2 : 3;
   for (int round = 0; round < 2; ++round) {
-    set_env("3", "0.06");
+    env.set("3", "0.06");
     const long before = knn_stub_combines();
     c.run_points(true, 5, true, true, 0, 700);
     CHECK(knn_stub_combines() - before == batches);
-    set_env(nullptr, nullptr);
+    env.set(nullptr, nullptr);
     c.run_nearest(257);
     c.run_points(true, 32, true, true);
     c.run_nearest(5000);
@@ -147,7 +129,6 @@ static void interleaved(int ngpus) {
 }
 
 int main() {
-  const bool three_devices = getenv("STUB_DEVICES") && atoi(getenv("STUB_DEVICES")) >= 3;
   {
     float one[4] = {0, 0, 0, 0}, d[2] = {5, 5};
     double oned[4] = {0, 0, 0, 0}, dd[2] = {5, 5};
@@ -158,80 +139,65 @@ int main() {
   }
 
   // ---- one block, six blocks with a short last one; one device and three with ragged slices (5200 = 1733 + 1733 + 1734, 1000 = 333 + 333 + 334) ----
-  for (int n : {1, 1000, 5200}) {
-    shapes<float>(n, 1);
-    if (three_devices && n >= 3) shapes<float>(n, 3);
-  }
-  shapes<double>(5200, 1);
-  if (three_devices) shapes<double>(1000, 3);
+  for_sizes({1, 1000, 5200}, shapes<float>, shapes<double>);
 
   // ---- the batched path: 5000 queries x 6 chunks x k x 8 B (k = 32: 7.7 MB) against 0.05 MB: k = 1 (48 B a query) in batches of 1024,
   //      k = 5 (240 B: 218 fit) and k = 32 (1536 B: 34 fit) not one workgroup, hence unsplit; against 1 MB: k = 5 in batches of 4352,
   //      k = 32 in batches of 512 ----
-  for (int ngpus : {1, 3}) {
-    if (ngpus > 1 && !three_devices) continue;
+  for_device_counts([](int ngpus) {
     Case<float> c(5200, 5000);
     c.open(ngpus);
     for (const char* mb : {"0.05", "1"})
       for (const char* split : {(const char*)nullptr, "4", "6"}) {
-        set_env(split, mb);
+        env.set(split, mb);
         const long before = knn_stub_combines();
         c.run_all();
         CHECK(knn_stub_combines() > before);
       }
-    set_env(nullptr, "0");    // not one workgroup's queries fit: no split
+    env.set(nullptr, "0");    // not one workgroup's queries fit: no split
     long before = knn_stub_combines();
     c.run_all();
-    set_env("5", "0");
+    env.set("5", "0");
     c.run_all();
     CHECK(knn_stub_combines() == before);
     SHUTDOWN();
-  }
+  });
   {
     Case<double> c(5200, 1000);
     c.open(1);
-    set_env(nullptr, "0.3");
+    env.set(nullptr, "0.3");
     c.run_all();
     SHUTDOWN();
   }
-  set_env(nullptr, nullptr);
+  env.set(nullptr, nullptr);
 
   // ---- the argument checks: nothing is written, the context stays usable ----
   {
     Case<float> c(5200, 300);
-    c.open(three_devices ? 3 : 1);
+    c.open(three_devices() ? 3 : 1);
     float* pts = c.pts.data();
-    c.mark();
+    c.mark_all();
     int* I = c.idx.data(); float* D = c.d2.data();
     CHECK(nbody_knn_rows(0, 300, 5, nullptr, nullptr) == NBODY_ERR_ARG);
     for (int k : {0, -1, NBODY_KNN_MAX + 1, 1 << 30}) {
       CHECK(nbody_knn_rows(0, 300, k, I, D) == NBODY_ERR_ARG);
       CHECK(nbody_knn(pts, 300, nullptr, k, I, D) == NBODY_ERR_ARG);
     }
-    CHECK(nbody_knn_rows(-1, 300, 5, I, D) == NBODY_ERR_ARG);
-    CHECK(nbody_knn_rows(0, 0, 5, I, D) == NBODY_ERR_ARG);
-    CHECK(nbody_knn_rows(0, -4, 5, I, D) == NBODY_ERR_ARG);
-    CHECK(nbody_knn_rows(5200, 1, 5, I, D) == NBODY_ERR_ARG);
-    CHECK(nbody_knn_rows(5000, 201, 5, I, D) == NBODY_ERR_ARG);
-    CHECK(nbody_knn_rows(1 << 30, 1 << 30, 5, I, D) == NBODY_ERR_ARG);
+    for (const Window& w : refused_windows(5200, 300)) CHECK(nbody_knn_rows(w.first, w.count, 5, I, D) == NBODY_ERR_ARG);
     CHECK(nbody_knn(nullptr, 300, nullptr, 5, I, D) == NBODY_ERR_ARG);
     CHECK(nbody_knn(pts, 0, nullptr, 5, I, D) == NBODY_ERR_ARG);
     CHECK(nbody_knn(pts, -1, nullptr, 5, I, D) == NBODY_ERR_ARG);
     CHECK(nbody_knn(pts, 300, nullptr, 5, nullptr, nullptr) == NBODY_ERR_ARG);
-    for (int bad : {5200, -2, 1 << 30}) {
-      std::vector<int> sk = c.skip;
-      sk[299] = bad;
-      CHECK(nbody_knn(pts, 300, sk.data(), 5, I, D) == NBODY_ERR_ARG);
-    }
+    for (int bad : refused_skips(5200)) CHECK(nbody_knn(pts, 300, c.skip_with(299, bad).data(), 5, I, D) == NBODY_ERR_ARG);
     std::vector<double> pd(1200, 0.0), dd(1500, 5.0);
     CHECK(nbody_knn_d(pd.data(), 300, nullptr, 5, I, dd.data()) == NBODY_ERR_STATE);
     CHECK(nbody_knn_rows_d(0, 300, 5, I, dd.data()) == NBODY_ERR_STATE);
     CHECK(dd[0] == 5.0 && dd[1499] == 5.0);
-    for (size_t e = 0; e < c.idx.size(); ++e) CHECK(c.idx[e] == -77 && c.d2[e] == -77.f);
+    CHECK(nothing_beyond(c.idx, 0) && nothing_beyond(c.d2, 0));
     std::vector<int> edge = c.skip;
     edge[0] = 5199; edge[299] = 0;
     OK(nbody_knn(pts, 300, edge.data(), 5, I, nullptr));
-    CHECK(c.d2[0] == -77.f && c.idx[0] != -77);
+    CHECK(c.d2[0] == (float)kMark && c.idx[0] != kMark);
     c.run_all();
     SHUTDOWN();
     Case<double> d(1000, 10);
@@ -242,29 +208,27 @@ int main() {
   }
 
   // ---- the buffers shared with the neighbour pass ----
-  for (int ngpus : {1, 3}) {
-    if (ngpus > 1 && !three_devices) continue;
+  for_device_counts([](int ngpus) {
     interleaved<float>(ngpus);
     interleaved<double>(ngpus);
-  }
+  });
 
   // ---- the failure paths: every allocating call of a call, one device and three, split (scratch) and not ----
-  for (int ngpus : {1, 3}) {
-    if (ngpus > 1 && !three_devices) continue;
+  for_device_counts([](int ngpus) {
     Case<float> c(5200, 700);
-    set_env("3", nullptr);
+    env.set("3", nullptr);
     int made = sweep("nbody_knn split", [&] { c.open(ngpus); }, [&] { return nbody_knn(c.pts.data(), c.m, c.skip.data(), 5, c.idx.data(), c.d2.data()); },
                      [&] { c.run_points(true, 5, true, true); });
     CHECK(made == 5 * ngpus);   // points, skip, idx, d2, scratch per device
     made = sweep("nbody_knn_rows split", [&] { c.open(ngpus); }, [&] { return nbody_knn_rows(0, 5200, 32, c.idx.data(), c.d2.data()); },
                  [&] { c.run_rows(0, 5200, 32, true, true); });
     CHECK(made == 3 * ngpus);   // idx, d2, scratch
-    set_env("1", nullptr);
+    env.set("1", nullptr);
     made = sweep("nbody_knn", [&] { c.open(ngpus); }, [&] { return nbody_knn(c.pts.data(), c.m, nullptr, 1, nullptr, c.d2.data()); },
                  [&] { c.run_points(false, 1, false, true); });
     CHECK(made == 2 * ngpus);   // points, d2
-  }
-  set_env(nullptr, nullptr);
+  });
+  env.set(nullptr, nullptr);
   printf("knn_sanity ok\n");
   return 0;
 }

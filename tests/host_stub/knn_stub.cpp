@@ -3,26 +3,20 @@
 // are synchronous and the pass is never captured, so both functions execute at launch.
 // The stand-in pushes values a test can predict through the REAL KnnArgs — chunk bounds, the chunks' scratch layout [chunk][r][m], the
 // combine's stable insertion, pointers the host offset per local and per batch, the [m][k] outputs, the rows form's first — so ASan sees
-// every offset the host computed.  Per query p (q = points[p], or in the rows form source first + p; sk = skip[p], -1, or in the rows
-// form first + p) every block b of 1024 sources (len_b of them) offers ONE candidate, as neighbors_stub.cpp's:
-//   j_b = 1024 b + ((int)q.w + b) mod len_b      d2_b = |src[j_b].x - q.x|      (none if j_b == sk)
-// taken in ascending b into a list of k entries from (+inf, -1), each behind every entry with d2 <= its own, the last entry dropped;
-// q.w, which the real kernel ignores, lets a driver steer the candidates.  It says nothing about the kernels' arithmetic (the GPU
-// tests do).
+// every offset the host computed.  Per query p (stub_common.hpp: the word q and the excluded body sk) every block b offers the ONE
+// candidate of stub_rule.hpp (j_b, d2_b; none if j_b == sk), as neighbors_stub.cpp's,
+// taken in ascending b into a list of k entries from (+inf, -1), each behind every entry with d2 <= its own, the last entry dropped.
+// It says nothing about the kernels' arithmetic (the GPU tests do).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <atomic>
 #include <limits>
 
 #include "../../mini_nbody_amd/csrc/knn_args.hpp"
+#include "stub_common.hpp"
 
 namespace {
 
 using namespace nbq;
-
-template <typename T>
-struct W4 { T x, y, z, w; };
 
 template <typename T>
 struct List {
@@ -40,14 +34,9 @@ struct List {
 
 template <typename T>
 void block(const KnnArgs& a, int p, int b, List<T>& c) {
-  typedef W4<T> V;
-  const V* src = (const V*)a.src;
-  const V q = a.points ? ((const V*)a.points)[p] : src[a.first + p];
-  const int sk = a.points ? (a.skip ? a.skip[p] : -1) : a.first + p;
-  const int b0 = b * nbd::kSrcBlock, len = std::min(nbd::kSrcBlock, a.n_src - b0);
-  const int j = b0 + ((int)q.w + b) % len;
-  const T d = src[j].x - q.x, d2 = d < 0 ? -d : d;
-  if (j != sk) c.push(d2, j);
+  const auto [q, sk] = stub::query_of<T>(a, p);
+  const int j = stub::candidate(a.n_src, q.w, b).j;
+  if (j != sk) c.push(stub::absdiff(((const stub::W4<T>*)a.src)[j].x, q.x), j);
 }
 
 template <typename T>
@@ -60,21 +49,19 @@ void store(const KnnArgs& a, int p, const List<T>& c) {
 
 template <typename T>
 void knn(const KnnArgs& a) {
-  for (int p = 0; p < a.m; ++p)
-    for (int y = 0; y < a.chunks; ++y) {
-      List<T> c(a.k);
-      const int blk1 = std::min((y + 1) * a.chunk_blocks, a.n_blocks);
-      for (int b = y * a.chunk_blocks; b < blk1; ++b) block<T>(a, p, b, c);
-      if (a.scratch) {
-        for (int r = 0; r < a.k; ++r) {
-          const size_t w = knn_scratch_at(a, y, r, p);
-          ((T*)knn_scratch_d2(a))[w] = c.d[r];
-          knn_scratch_idx(a, sizeof(T))[w] = c.i[r];
-        }
-      } else {
-        store<T>(a, p, c);
+  stub::for_each_chunk(a, [&](int p, int y, int b0, int b1) {
+    List<T> c(a.k);
+    for (int b = b0; b < b1; ++b) block<T>(a, p, b, c);
+    if (a.scratch) {
+      for (int r = 0; r < a.k; ++r) {
+        const size_t w = knn_scratch_at(a, y, r, p);
+        ((T*)knn_scratch_d2(a))[w] = c.d[r];
+        knn_scratch_idx(a, sizeof(T))[w] = c.i[r];
       }
+    } else {
+      store<T>(a, p, c);
     }
+  });
 }
 
 template <typename T>
@@ -90,23 +77,20 @@ void combine(const KnnArgs& a) {
   }
 }
 
-std::atomic<long> g_combines{0};
-
 }  // namespace
 
 // combine launches so far: one per batch of a split launch, none when the sources are not split
-extern "C" long knn_stub_combines(void) { return g_combines.load(); }
+STUB_COUNTER(knn_stub_combines)
 
 namespace nbl {
 int launch_knn_kernel(int fp64, hipStream_t, const nbq::KnnArgs& a) {
-  if (nbd::bad_source_split(a, !a.points) || a.k < 1 || a.k > nbq::kKnMax) return (int)hipErrorInvalidValue;
-  if (!a.scratch && !a.idx && !a.d2) return (int)hipErrorInvalidValue;
+  if (nbq::bad_knn_launch(a)) return (int)hipErrorInvalidValue;
   if (fp64) knn<double>(a); else knn<float>(a);
   return 0;
 }
 int launch_knn_combine_kernel(int fp64, hipStream_t, const nbq::KnnArgs& a) {
-  if (a.m <= 0 || a.k < 1 || a.k > nbq::kKnMax || !a.scratch || a.chunks < 1 || (!a.idx && !a.d2)) return (int)hipErrorInvalidValue;
-  g_combines.fetch_add(1);
+  if (nbq::bad_knn_combine(a)) return (int)hipErrorInvalidValue;
+  g_knn_stub_combines.fetch_add(1);
   if (fp64) combine<double>(a); else combine<float>(a);
   return 0;
 }

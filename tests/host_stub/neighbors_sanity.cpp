@@ -8,17 +8,12 @@
 #include <math.h>
 #include <string.h>
 
-#include <algorithm>
-
 #define SANITY_NAME "neighbors_sanity"
 #include "sanity_common.hpp"
 
 extern "C" long neighbors_stub_combines(void);   // neighbors_stub.cpp: combine launches so far, one per batch of a split launch
 
-static void set_env(const char* split, const char* scratch_mb) {
-  if (split) setenv("NBODY_NEIGHBORS_SPLIT", split, 1); else unsetenv("NBODY_NEIGHBORS_SPLIT");
-  if (scratch_mb) setenv("NBODY_NEIGHBORS_SCRATCH_MB", scratch_mb, 1); else unsetenv("NBODY_NEIGHBORS_SCRATCH_MB");
-}
+static const SplitEnv env = {"NBODY_NEIGHBORS_SPLIT", "NBODY_NEIGHBORS_SCRATCH_MB"};
 
 static int rows(int f, int n, int* i, float* d, float r2, int* c) { return nbody_neighbors_rows(f, n, i, d, r2, c); }
 static int rows(int f, int n, int* i, double* d, double r2, int* c) { return nbody_neighbors_rows_d(f, n, i, d, r2, c); }
@@ -29,61 +24,52 @@ static int pair(int* i, int* j, double* d) { return nbody_closest_pair_d(i, j, d
 static int field(const float* p, int m, const int* sk, float* a, float* phi) { return nbody_field(p, m, sk, a, phi); }
 static int field(const double* p, int m, const int* sk, double* a, double* phi) { return nbody_field_d(p, m, sk, a, phi); }
 
-// small integers everywhere: every value of neighbors_stub.cpp is exact in either precision
 template <typename T>
-struct Case {
-  int n, m;
-  std::vector<T> pos, vel, pts, d2;
-  std::vector<int> skip, idx, cnt;
-  Case(int n_, int m_) : n(n_), m(m_), pos((size_t)n_ * 4), vel((size_t)n_ * 4, (T)0), pts((size_t)m_ * 4), d2((size_t)std::max(n_, m_)),
-                         skip((size_t)m_), idx((size_t)std::max(n_, m_)), cnt((size_t)std::max(n_, m_)) {
-    for (int j = 0; j < n; ++j) { pos[4 * (size_t)j] = (T)((j * 37) % 101); pos[4 * (size_t)j + 1] = (T)(j % 7); pos[4 * (size_t)j + 2] = (T)1; pos[4 * (size_t)j + 3] = (T)(j % 977); }
-    for (int p = 0; p < m; ++p) {
-      pts[4 * (size_t)p] = (T)(p % 17); pts[4 * (size_t)p + 1] = (T)(p % 5); pts[4 * (size_t)p + 2] = (T)3; pts[4 * (size_t)p + 3] = (T)p;
-      skip[(size_t)p] = p % 3 == 0 ? -1 : (int)(((long long)p * 7919) % n);
-    }
-  }
-  void open(int ngpus) { OK(nbody_init(n, ngpus, sizeof(T) == 8, 0)); OK(upload<T>(pos, vel)); }
-  // what neighbors_stub.cpp makes of a query {x, w} with the excluded body sk
-  void expect(T x, T w, int sk, T r2, int* e_idx, T* e_d2, int* e_cnt) const {
+struct Case : Fixture<T> {
+  using F = Fixture<T>;
+  using Q = typename F::Q;
+  using F::n; using F::m; using F::pos; using F::pts; using F::skip;
+  std::vector<T> d2;
+  std::vector<int> idx, cnt;
+  Case(int n_, int m_) : F(n_, m_), d2((size_t)std::max(n_, m_)), idx((size_t)std::max(n_, m_)), cnt((size_t)std::max(n_, m_)) {}
+  // what neighbors_stub.cpp makes of a query
+  void expect(const Q& q, T r2, int* e_idx, T* e_d2, int* e_cnt) const {
     *e_idx = -1; *e_d2 = (T)INFINITY; *e_cnt = 0;
-    for (int b = 0; b * 1024 < n; ++b) {
-      const int b0 = b * 1024, len = std::min(1024, n - b0), j = b0 + ((int)w + b) % len;
-      const T d = pos[4 * (size_t)j] - x, v = d < 0 ? -d : d;
-      if (j != sk && v < *e_d2) { *e_d2 = v; *e_idx = j; }
-      if ((T)b <= r2) *e_cnt += len - (sk >= b0 && sk < b0 + len ? 1 : 0);
+    for (int b = 0; b < stub::blocks_of(n); ++b) {
+      const auto [j, b0, len] = stub::candidate(n, q.w, b);
+      const T v = stub::absdiff(pos[4 * (size_t)j], q.x);
+      if (j != q.sk && v < *e_d2) { *e_d2 = v; *e_idx = j; }
+      if ((T)b <= r2) *e_cnt += len - (q.sk >= b0 && q.sk < b0 + len ? 1 : 0);
     }
   }
-  void verify(int cnt_q, const std::function<void(int, T*, T*, int*)>& query, T r2, bool w_idx, bool w_d2, bool w_cnt) {
+  void verify(int cnt_q, const std::function<Q(int)>& query, T r2, bool w_idx, bool w_d2, bool w_cnt) {
     for (int k = 0; k < cnt_q; ++k) {
-      T x, w, e_d2; int sk, e_idx, e_cnt;
-      query(k, &x, &w, &sk);
-      expect(x, w, sk, r2, &e_idx, &e_d2, &e_cnt);
-      CHECK(idx[(size_t)k] == (w_idx ? e_idx : -77));
-      CHECK(d2[(size_t)k] == (w_d2 ? e_d2 : (T)-77));
-      CHECK(cnt[(size_t)k] == (w_cnt ? e_cnt : -77));
+      T e_d2; int e_idx, e_cnt;
+      expect(query(k), r2, &e_idx, &e_d2, &e_cnt);
+      CHECK(idx[(size_t)k] == (w_idx ? e_idx : kMark));
+      CHECK(d2[(size_t)k] == (w_d2 ? e_d2 : (T)kMark));
+      CHECK(cnt[(size_t)k] == (w_cnt ? e_cnt : kMark));
     }
-    for (size_t k = (size_t)cnt_q; k < idx.size(); ++k) CHECK(idx[k] == -77 && d2[k] == (T)-77 && cnt[k] == -77);   // nothing beyond
+    CHECK(nothing_beyond(idx, (size_t)cnt_q) && nothing_beyond(d2, (size_t)cnt_q) && nothing_beyond(cnt, (size_t)cnt_q));
   }
-  void mark() { std::fill(idx.begin(), idx.end(), -77); std::fill(d2.begin(), d2.end(), (T)-77); std::fill(cnt.begin(), cnt.end(), -77); }
+  void mark_all() { mark(idx); mark(d2); mark(cnt); }
   void run_rows(int first, int count, bool w_idx, bool w_d2, bool w_cnt, T r2) {
-    mark();
+    mark_all();
     OK(rows(first, count, w_idx ? idx.data() : nullptr, w_d2 ? d2.data() : nullptr, r2, w_cnt ? cnt.data() : nullptr));
-    verify(count, [&](int k, T* x, T* w, int* sk) { *x = pos[4 * (size_t)(first + k)]; *w = pos[4 * (size_t)(first + k) + 3]; *sk = first + k; }, r2, w_idx, w_d2, w_cnt);
+    verify(count, [&](int k) { return this->row(first + k); }, r2, w_idx, w_d2, w_cnt);
   }
   void run_points(bool with_skip, bool w_idx, bool w_d2, bool w_cnt, T r2, int p0 = 0, int count = -1) {
     if (count < 0) count = m - p0;
-    mark();
+    mark_all();
     OK(nearest(pts.data() + 4 * (size_t)p0, count, with_skip ? skip.data() + p0 : nullptr, w_idx ? idx.data() : nullptr, w_d2 ? d2.data() : nullptr, r2,
                w_cnt ? cnt.data() : nullptr));
-    verify(count, [&](int k, T* x, T* w, int* sk) { *x = pts[4 * (size_t)(p0 + k)]; *w = pts[4 * (size_t)(p0 + k) + 3]; *sk = with_skip ? skip[(size_t)(p0 + k)] : -1; },
-           r2, w_idx, w_d2, w_cnt);
+    verify(count, [&](int k) { return this->point(p0 + k, with_skip); }, r2, w_idx, w_d2, w_cnt);
   }
   void run_pair() {
     int bi = -1, bj = -1; T bd = (T)INFINITY;
     for (int r = 0; r < n; ++r) {
       int e_idx, e_cnt; T e_d2;
-      expect(pos[4 * (size_t)r], pos[4 * (size_t)r + 3], r, (T)0, &e_idx, &e_d2, &e_cnt);
+      expect(this->row(r), (T)0, &e_idx, &e_d2, &e_cnt);
       if (e_d2 < bd) { bd = e_d2; bi = r; bj = e_idx; }
     }
     int i = -5, j = -5; T d = (T)-5;
@@ -95,20 +81,20 @@ struct Case {
   }
   // nbody_field at the first `count` points, with skip, against what point_sums_stub.cpp makes of them
   void run_field(int count) {
-    std::vector<T> acc((size_t)count * 4 + 4, (T)-77), phi((size_t)count + 1, (T)-77);
+    std::vector<T> acc((size_t)count * 4 + 4, (T)kMark), phi((size_t)count + 1, (T)kMark);
     OK(field(pts.data(), count, skip.data(), acc.data(), phi.data()));
-    const int nb = (n + 1023) / 1024;
+    const int nb = stub::blocks_of(n);
     for (int p = 0; p < count; ++p) {
       double ax = 0.0, ay = 0.0, az = 0.0;
       for (int b = 0; b < nb; ++b) {
-        ax += (double)(T)(pos[4 * (size_t)b * 1024] - pts[4 * (size_t)p]);
+        ax += (double)(T)(pos[4 * (size_t)b * stub::kBlock] - pts[4 * (size_t)p]);
         ay += (double)(T)(pts[4 * (size_t)p + 1] + (T)b);
         az += (double)(T)((T)skip[(size_t)p] + (b == nb - 1 ? pos[4 * (size_t)(n - 1)] : (T)0));
       }
       CHECK(acc[4 * (size_t)p] == (T)ax && acc[4 * (size_t)p + 1] == (T)ay && acc[4 * (size_t)p + 2] == (T)az && acc[4 * (size_t)p + 3] == (T)0);
       CHECK(phi[(size_t)p] == (T)(0.0 - (double)nb * (double)p));
     }
-    CHECK(acc[4 * (size_t)count] == (T)-77 && phi[(size_t)count] == (T)-77);   // nothing beyond
+    CHECK(nothing_beyond(acc, 4 * (size_t)count) && nothing_beyond(phi, (size_t)count));
   }
   void run_all() {
     run_points(false, true, true, true, (T)1);
@@ -128,14 +114,10 @@ struct Case {
 
 template <typename T>
 static void shapes(int n, int ngpus) {
-  for (int m : {1, 255, 256, 257, 5000}) {
+  for (int m : kShapeM) {
     Case<T> c(n, m);
     c.open(ngpus);
-    for (const char* split : {(const char*)nullptr, "0", "1", "2", "3", "1000"}) {
-      set_env(split, nullptr);
-      c.run_all();
-    }
-    set_env(nullptr, nullptr);
+    for_splits(env, {nullptr, "0", "1", "2", "3", "1000"}, [&] { c.run_all(); });
     c.run_pair();
     SHUTDOWN();
   }
@@ -155,11 +137,11 @@ static void interleaved(int ngpus) {
   c.open(ngpus);
   const long batches = ngpus > 1 ? ngpus : sizeof(T) == 4 ? 2 : 3;
   for (int round = 0; round < 2; ++round) {
-    set_env("3", "0.02");
+    env.set("3", "0.02");
     const long before = neighbors_stub_combines();
     c.run_points(true, true, true, true, (T)1, 0, 700);
     CHECK(neighbors_stub_combines() - before == batches);
-    set_env(nullptr, nullptr);
+    env.set(nullptr, nullptr);
     c.run_field(257);
     c.run_points(true, true, true, true, (T)1);
   }
@@ -167,7 +149,6 @@ static void interleaved(int ngpus) {
 }
 
 int main() {
-  const bool three_devices = getenv("STUB_DEVICES") && atoi(getenv("STUB_DEVICES")) >= 3;
   {
     float one[4] = {0, 0, 0, 0}, d[1] = {5};
     double oned[4] = {0, 0, 0, 0}, dd[1] = {5};
@@ -179,72 +160,57 @@ int main() {
   }
 
   // ---- one block, six blocks with a short last one; one device and three with ragged slices (5200 = 1733 + 1733 + 1734, 1000 = 333 + 333 + 334) ----
-  for (int n : {1, 1000, 5200}) {
-    shapes<float>(n, 1);
-    if (three_devices && n >= 3) shapes<float>(n, 3);
-  }
-  shapes<double>(5200, 1);
-  if (three_devices) shapes<double>(1000, 3);
+  for_sizes({1, 1000, 5200}, shapes<float>, shapes<double>);
 
   // ---- the batched path: 5000 queries x 6 chunks x 12 B = 360 kB against 0.05 MB: batches of 512 (fp32), of 512 at 16 B too (fp64) ----
-  for (int ngpus : {1, 3}) {
-    if (ngpus > 1 && !three_devices) continue;
+  for_device_counts([](int ngpus) {
     Case<float> c(5200, 5000);
     c.open(ngpus);
     for (const char* split : {(const char*)nullptr, "4", "6"}) {
-      set_env(split, "0.05");
+      env.set(split, "0.05");
       c.run_all();
     }
-    set_env(nullptr, "0");    // not one workgroup's queries fit: no split
+    env.set(nullptr, "0");    // not one workgroup's queries fit: no split
     c.run_all();
-    set_env("5", "0");
+    env.set("5", "0");
     c.run_all();
-    set_env(nullptr, "0.05");
+    env.set(nullptr, "0.05");
     c.run_pair();
     SHUTDOWN();
-  }
+  });
   {
     Case<double> c(5200, 1000);
     c.open(1);
-    set_env(nullptr, "0.05");
+    env.set(nullptr, "0.05");
     c.run_all();
     SHUTDOWN();
   }
-  set_env(nullptr, nullptr);
+  env.set(nullptr, nullptr);
 
   // ---- the argument checks: nothing is written, the context stays usable ----
   {
     Case<float> c(5200, 300);
-    c.open(three_devices ? 3 : 1);
+    c.open(three_devices() ? 3 : 1);
     float* pts = c.pts.data();
-    c.mark();
+    c.mark_all();
     int* I = c.idx.data(); float* D = c.d2.data(); int* N = c.cnt.data();
     CHECK(nbody_neighbors_rows(0, 300, nullptr, nullptr, 1.f, nullptr) == NBODY_ERR_ARG);
-    CHECK(nbody_neighbors_rows(-1, 300, I, D, 1.f, N) == NBODY_ERR_ARG);
-    CHECK(nbody_neighbors_rows(0, 0, I, D, 1.f, N) == NBODY_ERR_ARG);
-    CHECK(nbody_neighbors_rows(0, -4, I, D, 1.f, N) == NBODY_ERR_ARG);
-    CHECK(nbody_neighbors_rows(5200, 1, I, D, 1.f, N) == NBODY_ERR_ARG);
-    CHECK(nbody_neighbors_rows(5000, 201, I, D, 1.f, N) == NBODY_ERR_ARG);
-    CHECK(nbody_neighbors_rows(1 << 30, 1 << 30, I, D, 1.f, N) == NBODY_ERR_ARG);
+    for (const Window& w : refused_windows(5200, 300)) CHECK(nbody_neighbors_rows(w.first, w.count, I, D, 1.f, N) == NBODY_ERR_ARG);
     CHECK(nbody_nearest(nullptr, 300, nullptr, I, D, 1.f, N) == NBODY_ERR_ARG);
     CHECK(nbody_nearest(pts, 0, nullptr, I, D, 1.f, N) == NBODY_ERR_ARG);
     CHECK(nbody_nearest(pts, -1, nullptr, I, D, 1.f, N) == NBODY_ERR_ARG);
     CHECK(nbody_nearest(pts, 300, nullptr, nullptr, nullptr, 1.f, nullptr) == NBODY_ERR_ARG);
-    for (int bad : {5200, -2, 1 << 30}) {
-      std::vector<int> sk = c.skip;
-      sk[299] = bad;
-      CHECK(nbody_nearest(pts, 300, sk.data(), I, D, 1.f, N) == NBODY_ERR_ARG);
-    }
+    for (int bad : refused_skips(5200)) CHECK(nbody_nearest(pts, 300, c.skip_with(299, bad).data(), I, D, 1.f, N) == NBODY_ERR_ARG);
     CHECK(nbody_closest_pair(nullptr, nullptr, nullptr) == NBODY_ERR_ARG);
     std::vector<double> pd(1200, 0.0), dd(300, 5.0);
     CHECK(nbody_nearest_d(pd.data(), 300, nullptr, I, dd.data(), 1.0, N) == NBODY_ERR_STATE);
     CHECK(nbody_neighbors_rows_d(0, 300, I, dd.data(), 1.0, N) == NBODY_ERR_STATE && nbody_closest_pair_d(I, I + 1, dd.data()) == NBODY_ERR_STATE);
     CHECK(dd[0] == 5.0 && dd[299] == 5.0);
-    for (size_t k = 0; k < c.idx.size(); ++k) CHECK(c.idx[k] == -77 && c.d2[k] == -77.f && c.cnt[k] == -77);
+    CHECK(nothing_beyond(c.idx, 0) && nothing_beyond(c.d2, 0) && nothing_beyond(c.cnt, 0));
     std::vector<int> edge = c.skip;
     edge[0] = 5199; edge[299] = 0;
     OK(nbody_nearest(pts, 300, edge.data(), I, nullptr, 1.f, nullptr));
-    CHECK(c.d2[0] == -77.f && c.cnt[0] == -77 && c.idx[0] != -77);
+    CHECK(c.d2[0] == (float)kMark && c.cnt[0] == kMark && c.idx[0] != kMark);
     c.run_all();
     SHUTDOWN();
     Case<double> d(1000, 10);
@@ -257,32 +223,30 @@ int main() {
   }
 
   // ---- the buffers shared with the field pass ----
-  for (int ngpus : {1, 3}) {
-    if (ngpus > 1 && !three_devices) continue;
+  for_device_counts([](int ngpus) {
     interleaved<float>(ngpus);
     interleaved<double>(ngpus);
-  }
+  });
 
   // ---- the failure paths: every allocating call of a call, one device and three, split (scratch) and not ----
-  for (int ngpus : {1, 3}) {
-    if (ngpus > 1 && !three_devices) continue;
+  for_device_counts([](int ngpus) {
     Case<float> c(5200, 700);
-    set_env("3", nullptr);
+    env.set("3", nullptr);
     int made = sweep("nbody_nearest split", [&] { c.open(ngpus); }, [&] { return nbody_nearest(c.pts.data(), c.m, c.skip.data(), c.idx.data(), c.d2.data(), 1.f, c.cnt.data()); },
                      [&] { c.run_points(true, true, true, true, 1.f); });
     CHECK(made == 6 * ngpus);   // points, skip, idx, d2, count, scratch per device
     made = sweep("nbody_neighbors_rows split", [&] { c.open(ngpus); }, [&] { return nbody_neighbors_rows(0, 5200, c.idx.data(), c.d2.data(), 1.f, nullptr); },
                  [&] { c.run_rows(0, 5200, true, true, false, 1.f); });
     CHECK(made == 3 * ngpus);   // idx, d2, scratch
-    set_env("1", nullptr);
+    env.set("1", nullptr);
     made = sweep("nbody_nearest", [&] { c.open(ngpus); }, [&] { return nbody_nearest(c.pts.data(), c.m, nullptr, nullptr, c.d2.data(), 1.f, nullptr); },
                  [&] { c.run_points(false, false, true, false, 1.f); });
     CHECK(made == 2 * ngpus);   // points, d2
     int i, j; float d;
     made = sweep("nbody_closest_pair", [&] { c.open(ngpus); }, [&] { return nbody_closest_pair(&i, &j, &d); }, [&] { c.run_pair(); });
     CHECK(made == 3 * ngpus);   // idx, d2, the best pairs
-  }
-  set_env(nullptr, nullptr);
+  });
+  env.set(nullptr, nullptr);
   printf("neighbors_sanity ok\n");
   return 0;
 }

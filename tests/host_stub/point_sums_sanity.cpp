@@ -6,41 +6,29 @@
 // and the failure paths.  point_sums_stub.cpp states the values expected here.
 #include <string.h>
 
-#include <string>
-
 #define SANITY_NAME "point_sums_sanity"
 #include "sanity_common.hpp"
 
-static std::string g_split_env, g_scratch_env;   // the two variables of the pass under test
-static void set_env(const char* split, const char* scratch_mb) {
-  if (split) setenv(g_split_env.c_str(), split, 1); else unsetenv(g_split_env.c_str());
-  if (scratch_mb) setenv(g_scratch_env.c_str(), scratch_mb, 1); else unsetenv(g_scratch_env.c_str());
-}
+static SplitEnv env;   // the two variables of the pass under test: main sets them
 
 static int field(const float* p, int m, const int* sk, float* a, float* phi) { return nbody_field(p, m, sk, a, phi); }
 static int field(const double* p, int m, const int* sk, double* a, double* phi) { return nbody_field_d(p, m, sk, a, phi); }
 static int tidal(const float* p, int m, const int* sk, float* t) { return nbody_tidal(p, m, sk, t); }
 static int tidal(const double* p, int m, const int* sk, double* t) { return nbody_tidal_d(p, m, sk, t); }
 
-// what both passes' cases are made of: the bodies, the points, the skip indices and the stub's sums at a point.  Small integers
-// everywhere: every sum of point_sums_stub.cpp is exact in either precision
+// what both passes' cases are made of: the shared fixture's points and skip indices, this driver's own bodies (x = j mod 13, in which
+// the stub's sums have a closed form) and the stub's sums at a point
 template <typename T>
-struct Points {
-  int n, m, nb;
-  std::vector<T> pos, vel, pts;
-  std::vector<int> skip;
-  Points(int n_, int m_) : n(n_), m(m_), nb((n_ + 1023) / 1024), pos((size_t)n_ * 4), vel((size_t)n_ * 4, (T)0), pts((size_t)m_ * 4), skip((size_t)m_) {
-    for (int j = 0; j < n; ++j) { pos[4 * (size_t)j] = (T)(j % 13); pos[4 * (size_t)j + 1] = (T)(j % 7); pos[4 * (size_t)j + 2] = (T)1; pos[4 * (size_t)j + 3] = (T)1; }
-    for (int p = 0; p < m; ++p) {
-      pts[4 * (size_t)p] = (T)(p % 17); pts[4 * (size_t)p + 1] = (T)(p % 5); pts[4 * (size_t)p + 2] = (T)3; pts[4 * (size_t)p + 3] = (T)p;
-      skip[(size_t)p] = p % 3 == 0 ? -1 : (int)(((long long)p * 7919) % n);
-    }
+struct Points : Fixture<T> {
+  using Fixture<T>::n; using Fixture<T>::skip;
+  int nb;
+  Points(int n_, int m_) : Fixture<T>(n_, m_), nb(stub::blocks_of(n_)) {
+    for (int j = 0; j < n; ++j) this->set(this->pos, j, (T)(j % 13), (T)(j % 7), (T)1, (T)1);
   }
-  void open(int ngpus) { OK(nbody_init(n, ngpus, sizeof(T) == 8, 0)); OK(upload<T>(pos, vel)); }
   // the level-2 sums Q0, Q1, Q2 of point p (Q3 = nb p, Q4 = nb (nb - 1) / 2, Q5 = nb, Q6 = 3 nb)
   void sums(int p, bool with_skip, double q[3]) const {
     q[0] = q[1] = 0.0;
-    for (int b = 0; b < nb; ++b) { q[0] += (double)(T)((T)((b * 1024) % 13) - (T)(p % 17)); q[1] += (double)(T)((T)(p % 5) + (T)b); }
+    for (int b = 0; b < nb; ++b) { q[0] += (double)(T)((T)((b * stub::kBlock) % 13) - (T)(p % 17)); q[1] += (double)(T)((T)(p % 5) + (T)b); }
     q[2] = (double)nb * (double)(with_skip ? skip[(size_t)p] : -1) + (double)((n - 1) % 13);
   }
 };
@@ -53,20 +41,19 @@ struct FieldCase : Points<T> {
   void run(bool with_skip, bool want_acc, bool want_phi, int p0 = 0, int cnt = -1) {
     const int m = this->m;
     if (cnt < 0) cnt = m - p0;
-    const T mark = (T)-77;
-    std::fill(acc.begin(), acc.end(), mark);
-    std::fill(phi.begin(), phi.end(), mark);
+    const T unwritten = (T)kMark;
+    mark(acc); mark(phi);
     OK(field(this->pts.data() + 4 * (size_t)p0, cnt, with_skip ? this->skip.data() + p0 : nullptr, want_acc ? acc.data() : nullptr, want_phi ? phi.data() : nullptr));
     for (int k = 0; k < cnt; ++k) {
       const int p = p0 + k;
       double q[3];
       this->sums(p, with_skip, q);
       if (want_acc) CHECK(acc[4 * (size_t)k] == (T)q[0] && acc[4 * (size_t)k + 1] == (T)q[1] && acc[4 * (size_t)k + 2] == (T)q[2] && acc[4 * (size_t)k + 3] == (T)0);
-      else CHECK(acc[4 * (size_t)k] == mark);
+      else CHECK(acc[4 * (size_t)k] == unwritten);
       if (want_phi) CHECK(phi[(size_t)k] == (T)(0.0 - (double)this->nb * (double)p));
-      else CHECK(phi[(size_t)k] == mark);
+      else CHECK(phi[(size_t)k] == unwritten);
     }
-    for (size_t k = (size_t)cnt; k < (size_t)m; ++k) CHECK(acc[4 * k] == mark && phi[k] == mark);   // nothing beyond the points asked for
+    CHECK(nothing_beyond(acc, 4 * (size_t)cnt) && nothing_beyond(phi, (size_t)cnt));   // nothing beyond the points asked for
   }
   void run_all() {
     run(false, true, true);
@@ -84,8 +71,7 @@ struct TidalCase : Points<T> {
   // points [p0, p0 + cnt) of the case, with or without skip
   void run(bool with_skip, int p0 = 0, int cnt = -1) {
     if (cnt < 0) cnt = this->m - p0;
-    const T mark = (T)-77;
-    std::fill(out.begin(), out.end(), mark);
+    mark(out);
     OK(tidal(this->pts.data() + 4 * (size_t)p0, cnt, with_skip ? this->skip.data() + p0 : nullptr, out.data()));
     const int nb = this->nb;
     const double s3 = 3.0 * (double)nb;
@@ -97,7 +83,7 @@ struct TidalCase : Points<T> {
       CHECK(t[0] == (T)(q[0] - s3) && t[1] == (T)(q[1] - s3) && t[2] == (T)(q[2] - s3));
       CHECK(t[3] == (T)((double)nb * (double)p) && t[4] == (T)((double)nb * (double)(nb - 1) / 2.0) && t[5] == (T)nb);
     }
-    for (size_t k = 6 * (size_t)cnt; k < out.size(); ++k) CHECK(out[k] == mark);   // nothing beyond the points asked for
+    CHECK(nothing_beyond(out, 6 * (size_t)cnt));   // nothing beyond the points asked for
   }
   // a field call on the same context: phi alone
   void run_field() {
@@ -114,82 +100,67 @@ struct TidalCase : Points<T> {
 
 template <class C>
 static void shapes(int n, int ngpus) {
-  for (int m : {1, 255, 256, 257, 5000}) {
+  for (int m : kShapeM) {
     C c(n, m);
     c.open(ngpus);
-    for (const char* split : {(const char*)nullptr, "0", "1", "2", "3", "1000"}) {
-      set_env(split, nullptr);
-      c.run_all();
-    }
+    for_splits(env, {nullptr, "0", "1", "2", "3", "1000"}, [&] { c.run_all(); });
     SHUTDOWN();
   }
-  set_env(nullptr, nullptr);
 }
 
 // what the two passes are driven through alike (C: FieldCase or TidalCase)
 template <template <typename> class C>
-static void shapes_and_batches(bool three_devices) {
+static void shapes_and_batches() {
   // ---- one block, three blocks with a short last one; one device and three with ragged slices (2085 = 695 + 695 + 695, 1000 = 333 + 333 + 334) ----
-  for (int n : {1, 1000, 2085}) {
-    shapes<C<float>>(n, 1);
-    if (three_devices && n >= 3) shapes<C<float>>(n, 3);
-  }
-  shapes<C<double>>(2085, 1);
-  if (three_devices) shapes<C<double>>(1000, 3);
+  for_sizes({1, 1000, 2085}, shapes<C<float>>, shapes<C<double>>);
 
   // ---- the batched path: 69 blocks of per-block sums per point against 1 MB, fp32: field 69 x 16 B = 1104 B, batches of 768 points;
   // ---- tidal 69 x 28 B = 1932 B, batches of 512 ----
-  for (int ngpus : {1, 3}) {
-    if (ngpus > 1 && !three_devices) continue;
+  for_device_counts([](int ngpus) {
     C<float> c(70000, 5000);
     c.open(ngpus);
     for (const char* split : {(const char*)nullptr, "7", "69"}) {
-      set_env(split, "1");
+      env.set(split, "1");
       c.run_all();
     }
-    set_env(nullptr, "0");    // not one workgroup's points fit: no split
+    env.set(nullptr, "0");    // not one workgroup's points fit: no split
     c.run_all();
-    set_env("5", "0");
+    env.set("5", "0");
     c.run_all();
     SHUTDOWN();
-  }
+  });
   {
     C<double> c(70000, 1000);   // field 2208 B per point, tidal 3864 B: batches of 256
     c.open(1);
-    set_env(nullptr, "1");
+    env.set(nullptr, "1");
     c.run_all();
     SHUTDOWN();
   }
-  set_env(nullptr, nullptr);
+  env.set(nullptr, nullptr);
 }
 
-static void field_main(bool three_devices) {
+static void field_main() {
   float one[4] = {0, 0, 0, 0}, out[4] = {5, 5, 5, 5}, ph[1] = {5};
   double oned[4] = {0, 0, 0, 0}, outd[4] = {5, 5, 5, 5}, phd[1] = {5};
   CHECK(nbody_field(one, 1, nullptr, out, ph) == NBODY_ERR_NOT_INIT && nbody_field_d(oned, 1, nullptr, outd, phd) == NBODY_ERR_NOT_INIT);
 
-  shapes_and_batches<FieldCase>(three_devices);
+  shapes_and_batches<FieldCase>();
 
   // ---- the argument checks: nothing is written, the context stays usable ----
   {
     FieldCase<float> c(2085, 300);
-    c.open(three_devices ? 3 : 1);
+    c.open(three_devices() ? 3 : 1);
     float* pts = c.pts.data();
-    std::fill(c.acc.begin(), c.acc.end(), -77.f);
-    std::fill(c.phi.begin(), c.phi.end(), -77.f);
+    mark(c.acc); mark(c.phi);
     CHECK(nbody_field(nullptr, 300, nullptr, c.acc.data(), c.phi.data()) == NBODY_ERR_ARG);
     CHECK(nbody_field(pts, 0, nullptr, c.acc.data(), c.phi.data()) == NBODY_ERR_ARG);
     CHECK(nbody_field(pts, -1, nullptr, c.acc.data(), c.phi.data()) == NBODY_ERR_ARG);
     CHECK(nbody_field(pts, 300, nullptr, nullptr, nullptr) == NBODY_ERR_ARG);
-    for (int bad : {2085, -2, 1 << 30}) {
-      std::vector<int> sk = c.skip;
-      sk[299] = bad;
-      CHECK(nbody_field(pts, 300, sk.data(), c.acc.data(), c.phi.data()) == NBODY_ERR_ARG);
-    }
+    for (int bad : refused_skips(2085)) CHECK(nbody_field(pts, 300, c.skip_with(299, bad).data(), c.acc.data(), c.phi.data()) == NBODY_ERR_ARG);
     std::vector<int> edge = c.skip;
     edge[0] = 2084; edge[299] = 0;
     OK(nbody_field(pts, 300, edge.data(), nullptr, c.phi.data()));
-    for (float v : c.acc) CHECK(v == -77.f);
+    CHECK(nothing_beyond(c.acc, 0));
     std::vector<double> pd(1200, 0.0), ad(1200, 5.0), fd(300, 5.0);
     CHECK(nbody_field_d(pd.data(), 300, nullptr, ad.data(), fd.data()) == NBODY_ERR_STATE && ad[0] == 5.0 && fd[299] == 5.0);
     c.run_all();
@@ -202,45 +173,40 @@ static void field_main(bool three_devices) {
   }
 
   // ---- the failure paths: every allocating call of a field call, one device and three, split (scratch) and not ----
-  for (int ngpus : {1, 3}) {
-    if (ngpus > 1 && !three_devices) continue;
+  for_device_counts([](int ngpus) {
     FieldCase<float> c(2085, 700);
-    set_env("3", nullptr);
+    env.set("3", nullptr);
     int made = sweep("nbody_field split", [&] { c.open(ngpus); }, [&] { return nbody_field(c.pts.data(), c.m, c.skip.data(), c.acc.data(), c.phi.data()); },
                      [&] { c.run(true, true, true); });
     CHECK(made == 5 * ngpus);   // points, skip, accel, phi, scratch per device
-    set_env("1", nullptr);
+    env.set("1", nullptr);
     made = sweep("nbody_field", [&] { c.open(ngpus); }, [&] { return nbody_field(c.pts.data(), c.m, nullptr, nullptr, c.phi.data()); },
                  [&] { c.run(false, false, true); });
     CHECK(made == 2 * ngpus);   // points, phi
-  }
-  set_env(nullptr, nullptr);
+  });
+  env.set(nullptr, nullptr);
 }
 
-static void tidal_main(bool three_devices) {
+static void tidal_main() {
   float one[4] = {0, 0, 0, 0}, out[6] = {5, 5, 5, 5, 5, 5};
   double oned[4] = {0, 0, 0, 0}, outd[6] = {5, 5, 5, 5, 5, 5};
   CHECK(nbody_tidal(one, 1, nullptr, out) == NBODY_ERR_NOT_INIT && nbody_tidal_d(oned, 1, nullptr, outd) == NBODY_ERR_NOT_INIT);
   CHECK(out[0] == 5 && outd[5] == 5);
 
-  shapes_and_batches<TidalCase>(three_devices);
+  shapes_and_batches<TidalCase>();
 
   // ---- the argument checks: nothing is written, the context stays usable ----
   {
     TidalCase<float> c(2085, 300);
-    c.open(three_devices ? 3 : 1);
+    c.open(three_devices() ? 3 : 1);
     float* pts = c.pts.data();
-    std::fill(c.out.begin(), c.out.end(), -77.f);
+    mark(c.out);
     CHECK(nbody_tidal(nullptr, 300, nullptr, c.out.data()) == NBODY_ERR_ARG);
     CHECK(nbody_tidal(pts, 300, nullptr, nullptr) == NBODY_ERR_ARG);
     CHECK(nbody_tidal(pts, 0, nullptr, c.out.data()) == NBODY_ERR_ARG);
     CHECK(nbody_tidal(pts, -1, nullptr, c.out.data()) == NBODY_ERR_ARG);
-    for (int bad : {2085, -2, 1 << 30}) {
-      std::vector<int> sk = c.skip;
-      sk[299] = bad;
-      CHECK(nbody_tidal(pts, 300, sk.data(), c.out.data()) == NBODY_ERR_ARG);
-    }
-    for (float v : c.out) CHECK(v == -77.f);
+    for (int bad : refused_skips(2085)) CHECK(nbody_tidal(pts, 300, c.skip_with(299, bad).data(), c.out.data()) == NBODY_ERR_ARG);
+    CHECK(nothing_beyond(c.out, 0));
     std::vector<int> edge = c.skip;
     edge[0] = 2084; edge[299] = 0;
     OK(nbody_tidal(pts, 300, edge.data(), c.out.data()));
@@ -256,28 +222,25 @@ static void tidal_main(bool three_devices) {
   }
 
   // ---- the failure paths: every allocating call of a tidal call, one device and three, split (scratch) and not ----
-  for (int ngpus : {1, 3}) {
-    if (ngpus > 1 && !three_devices) continue;
+  for_device_counts([](int ngpus) {
     TidalCase<float> c(2085, 700);
-    set_env("3", nullptr);
+    env.set("3", nullptr);
     int made = sweep("nbody_tidal split", [&] { c.open(ngpus); }, [&] { return nbody_tidal(c.pts.data(), c.m, c.skip.data(), c.out.data()); },
                      [&] { c.run(true); });
     CHECK(made == 4 * ngpus);   // points, skip, tensor, scratch per device
-    set_env("1", nullptr);
+    env.set("1", nullptr);
     made = sweep("nbody_tidal", [&] { c.open(ngpus); }, [&] { return nbody_tidal(c.pts.data(), c.m, nullptr, c.out.data()); },
                  [&] { c.run(false); });
     CHECK(made == 2 * ngpus);   // points, tensor
-  }
-  set_env(nullptr, nullptr);
+  });
+  env.set(nullptr, nullptr);
 }
 
 int main(int argc, char** argv) {
-  const bool three_devices = getenv("STUB_DEVICES") && atoi(getenv("STUB_DEVICES")) >= 3;
   const std::string pass = argc > 1 ? argv[1] : "";
   CHECK(pass == "field" || pass == "tidal");
-  g_split_env = pass == "field" ? "NBODY_FIELD_SPLIT" : "NBODY_TIDAL_SPLIT";
-  g_scratch_env = pass == "field" ? "NBODY_FIELD_SCRATCH_MB" : "NBODY_TIDAL_SCRATCH_MB";
-  if (pass == "field") field_main(three_devices); else tidal_main(three_devices);
+  env = pass == "field" ? SplitEnv{"NBODY_FIELD_SPLIT", "NBODY_FIELD_SCRATCH_MB"} : SplitEnv{"NBODY_TIDAL_SPLIT", "NBODY_TIDAL_SCRATCH_MB"};
+  if (pass == "field") field_main(); else tidal_main();
   printf("point_sums_sanity %s ok\n", pass.c_str());
   return 0;
 }

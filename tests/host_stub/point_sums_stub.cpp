@@ -12,19 +12,16 @@
 // (T)(Q2 - Q6), (T)Q3, (T)Q4, (T)Q5.  It says nothing about the kernels' arithmetic (the GPU tests do).
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "../../mini_nbody_amd/csrc/point_sums_args.hpp"
+#include "stub_common.hpp"
 
 namespace {
 
 using nbp::PointPass;
 using nbp::PointSumsArgs;
+using stub::W4;
 
 constexpr int kMaxSums = 7;
-
-template <typename T>
-struct W4 { T x, y, z, w; };
 
 template <typename T>
 void block_sums(const PointSumsArgs& a, int p, int b, T out[kMaxSums]) {
@@ -89,12 +86,12 @@ void combine(const PointPass& pass, const PointSumsArgs& a) {
 
 namespace nbl {
 int launch_point_sums_kernel(const PointPass& pass, int fp64, int, hipStream_t, int chunks, const PointSumsArgs& a) {
-  if (a.m <= 0 || chunks < 1 || (chunks > 1 && !a.scratch) || (!a.out[0] && !a.out[1])) return (int)hipErrorInvalidValue;
+  if (nbp::bad_point_sums_launch(a, chunks)) return (int)hipErrorInvalidValue;
   if (fp64) sums<double>(pass, a, chunks); else sums<float>(pass, a, chunks);
   return 0;
 }
 int launch_point_sums_combine_kernel(const PointPass& pass, int fp64, hipStream_t, const PointSumsArgs& a) {
-  if (a.m <= 0 || !a.scratch || (!a.out[0] && !a.out[1])) return (int)hipErrorInvalidValue;
+  if (nbp::bad_point_sums_combine(a)) return (int)hipErrorInvalidValue;
   if (fp64) combine<double>(pass, a); else combine<float>(pass, a);
   return 0;
 }

@@ -1,9 +1,12 @@
-// timescale_sanity.cpp — TEST INFRASTRUCTURE (tests/test_timescale_host_sanitizers.py): drives nbody_timescale_rows(_d),
+// timescale_sanity.cpp — TEST INFRASTRUCTURE (tests/test_host_sanitizers.py, case `timescale`): drives nbody_timescale_rows(_d),
 // nbody_min_timescale(_d) and nbody_step_adaptive(_d) of the library's host code (timescale.cpp beside context.cpp, comm.cpp,
 // mailbox.cpp and energy.cpp) against tests/host_stub/hip_stub.cpp and timescale_stub.cpp under AddressSanitizer + UBSan.  What it
 // checks is the host's logic: the rows of a window over the devices, the copy-back offsets of the three outputs, the gather of all N
 // velocities to every device, the choice of the source split, the scratch size and the batches, the ranks' words of the system form,
 // the driver loop, the argument checks, lifetimes at shutdown and the failure paths.  timescale_stub.cpp states the values expected here.
+// It covers one and three stub devices with ragged slices, windows of rows across the devices, the source split forced and automatic,
+// the batched path under a small scratch bound, the gather of all N velocities on three devices after steps have changed them, every
+// NBODY_ERR_ARG case, the driver loop against nbody_step and the failure sweep of sanity_common.hpp.
 #include <math.h>
 #include <string.h>
 
@@ -12,10 +15,7 @@
 #define SANITY_NAME "timescale_sanity"
 #include "sanity_common.hpp"
 
-static void set_env(const char* split, const char* scratch_mb) {
-  if (split) setenv("NBODY_TIMESCALE_SPLIT", split, 1); else unsetenv("NBODY_TIMESCALE_SPLIT");
-  if (scratch_mb) setenv("NBODY_TIMESCALE_SCRATCH_MB", scratch_mb, 1); else unsetenv("NBODY_TIMESCALE_SCRATCH_MB");
-}
+static const SplitEnv env = {"NBODY_TIMESCALE_SPLIT", "NBODY_TIMESCALE_SCRATCH_MB"};
 
 static int rows(int f, int m, float* t, int* i, float* d) { return nbody_timescale_rows(f, m, t, i, d); }
 static int rows(int f, int m, double* t, int* i, double* d) { return nbody_timescale_rows_d(f, m, t, i, d); }
@@ -35,27 +35,24 @@ template <> int download<double>(std::vector<double>& pos, std::vector<double>& 
 
 // small integers everywhere: every value of timescale_stub.cpp is exact in either precision
 template <typename T>
-struct Case {
-  int n;
-  std::vector<T> pos, vel, tau2, d2;
+struct Case : System<T> {
+  using System<T>::n; using System<T>::pos; using System<T>::vel;
+  std::vector<T> tau2, d2;
   std::vector<int> idx;
-  explicit Case(int n_) : n(n_), pos((size_t)n_ * 4), vel((size_t)n_ * 4, (T)0), tau2((size_t)n_), d2((size_t)n_), idx((size_t)n_) {
+  explicit Case(int n_) : System<T>(n_), tau2((size_t)n_), d2((size_t)n_), idx((size_t)n_) {
     for (int j = 0; j < n; ++j) {
-      pos[4 * (size_t)j] = (T)(j % 13); pos[4 * (size_t)j + 1] = (T)(j % 7); pos[4 * (size_t)j + 2] = (T)1; pos[4 * (size_t)j + 3] = (T)(j % 50);
+      this->set(pos, j, (T)(j % 13), (T)(j % 7), (T)1, (T)(j % 50));
       vel[4 * (size_t)j] = (T)((j * 7) % 11);
     }
   }
-  void open(int ngpus) { OK(nbody_init(n, ngpus, sizeof(T) == 8, 0)); OK(upload<T>(pos, vel)); }
   // what the stub makes of row i of the state in pos / vel
   void expect(int i, T* t, int* ix, T* d) const {
     const T inf = std::numeric_limits<T>::infinity();
     *t = inf; *ix = -1; *d = inf;
-    const int nb = (n + 1023) / 1024;
-    for (int b = 0; b < nb; ++b) {
-      const int b0 = b * 1024, len = std::min(1024, n - b0);
-      const int j = b0 + ((int)pos[4 * (size_t)i + 3] + b) % len;
+    for (int b = 0; b < stub::blocks_of(n); ++b) {
+      const int j = stub::candidate(n, pos[4 * (size_t)i + 3], b).j;
       if (j == i) continue;
-      const T q = (T)fabs((double)(pos[4 * (size_t)j] - pos[4 * (size_t)i])), v = (T)fabs((double)(vel[4 * (size_t)j] - vel[4 * (size_t)i]));
+      const T q = stub::absdiff(pos[4 * (size_t)j], pos[4 * (size_t)i]), v = stub::absdiff(vel[4 * (size_t)j], vel[4 * (size_t)i]);
       if (q < *t) { *t = q; *ix = j; }
       if (v < *d) *d = v;
     }
@@ -63,20 +60,17 @@ struct Case {
   // rows [first, first + cnt) with the outputs in `which` (bit 0 tau2, 1 idx, 2 d2min)
   void run(int first = 0, int cnt = -1, int which = 7) {
     if (cnt < 0) cnt = n - first;
-    const T mark = (T)-77;
-    std::fill(tau2.begin(), tau2.end(), mark);
-    std::fill(d2.begin(), d2.end(), mark);
-    std::fill(idx.begin(), idx.end(), -77);
+    mark(tau2); mark(d2); mark(idx);
     OK(rows(first, cnt, which & 1 ? tau2.data() : nullptr, which & 2 ? idx.data() : nullptr, which & 4 ? d2.data() : nullptr));
     for (int k = 0; k < cnt; ++k) {
       T t, d;
       int ix;
       expect(first + k, &t, &ix, &d);
-      CHECK(which & 1 ? tau2[(size_t)k] == t : tau2[(size_t)k] == mark);
-      CHECK(which & 2 ? idx[(size_t)k] == ix : idx[(size_t)k] == -77);
-      CHECK(which & 4 ? d2[(size_t)k] == d : d2[(size_t)k] == mark);
+      CHECK(tau2[(size_t)k] == (which & 1 ? t : (T)kMark));
+      CHECK(idx[(size_t)k] == (which & 2 ? ix : kMark));
+      CHECK(d2[(size_t)k] == (which & 4 ? d : (T)kMark));
     }
-    for (size_t k = (size_t)cnt; k < (size_t)n; ++k) CHECK(tau2[k] == mark && idx[k] == -77 && d2[k] == mark);   // nothing beyond the rows asked for
+    CHECK(nothing_beyond(tau2, (size_t)cnt) && nothing_beyond(idx, (size_t)cnt) && nothing_beyond(d2, (size_t)cnt));   // nothing beyond the rows asked for
   }
   void run_system() {
     const T inf = std::numeric_limits<T>::infinity();
@@ -89,11 +83,11 @@ struct Case {
       if (t < bt) { bt = t; bi = i; bj = ix; }
       if (d < bd) bd = d;
     }
-    T t = (T)-77, d = (T)-77;
-    int i = -77, j = -77;
+    T t = (T)kMark, d = (T)kMark;
+    int i = kMark, j = kMark;
     OK(system_min(&t, &i, &j, &d));
     CHECK(t == bt && i == bi && j == bj && d == bd);
-    i = -77;
+    i = kMark;
     OK(system_min((T*)nullptr, &i, nullptr, (T*)nullptr));
     CHECK(i == bi);
   }
@@ -110,18 +104,15 @@ template <typename T>
 static void shapes(int n, int ngpus) {
   Case<T> c(n);
   c.open(ngpus);
-  for (const char* split : {(const char*)nullptr, "0", "1", "2", "3", "1000"}) {
-    set_env(split, nullptr);
-    c.run_all();
-  }
+  for_splits(env, {nullptr, "0", "1", "2", "3", "1000"}, [&] { c.run_all(); });
   // after two steps every device's velocities differ from the upload: all N of them must be gathered anew
   if (n >= 3) {
     OK(step(T(), 0.0078125));
     OK(step(T(), 0.0078125));
     c.refresh();
-    set_env("2", nullptr);
+    env.set("2", nullptr);
     c.run_all();
-    set_env(nullptr, nullptr);
+    env.set(nullptr, nullptr);
     c.run_all();
   }
   SHUTDOWN();
@@ -170,7 +161,6 @@ static void driver(int ngpus) {
 }
 
 int main() {
-  const bool three_devices = getenv("STUB_DEVICES") && atoi(getenv("STUB_DEVICES")) >= 3;
   {
     float t[4] = {5, 5, 5, 5};
     double td[4] = {5, 5, 5, 5}, tr = 5.0;
@@ -183,55 +173,48 @@ int main() {
   }
 
   // ---- one block, three blocks with a short last one; one device and three with ragged slices (2085 = 695 x 3, 1000 = 333 + 333 + 334) ----
-  for (int n : {1, 2, 1000, 2085}) {
-    shapes<float>(n, 1);
-    if (three_devices && n >= 3) shapes<float>(n, 3);
-  }
-  shapes<double>(2085, 1);
-  if (three_devices) shapes<double>(1000, 3);
+  for_sizes({1, 2, 1000, 2085}, shapes<float>, shapes<double>);
 
   // ---- the batched path: 7 chunks x 12 B = 84 B per row against 0.05 MB = 52428 B: batches of 512 rows (fp32); a window across the
   //      devices' boundary 23333 | 23334 ----
-  for (int ngpus : {1, 3}) {
-    if (ngpus > 1 && !three_devices) continue;
+  for_device_counts([](int ngpus) {
     Case<float> c(70000);
     c.open(ngpus);
     for (const char* split : {"7", "69"}) {
-      set_env(split, "0.05");
+      env.set(split, "0.05");
       c.run(20000, 5000);
       c.run(23000, 700, 5);
     }
-    set_env(nullptr, "0.05");
+    env.set(nullptr, "0.05");
     c.run(20000, 5000);
-    set_env("5", "0");    // not one workgroup's rows fit: no split
+    env.set("5", "0");    // not one workgroup's rows fit: no split
     c.run(23000, 700);
-    set_env("3", "0.05");
+    env.set("3", "0.05");
     c.run_system();
     SHUTDOWN();
-  }
+  });
   {
     Case<double> c(70000);   // 7 chunks x 20 B = 140 B per row: batches of 256
     c.open(1);
-    set_env("7", "0.05");
+    env.set("7", "0.05");
     c.run(100, 1000);
     SHUTDOWN();
   }
-  set_env(nullptr, nullptr);
+  env.set(nullptr, nullptr);
 
   // ---- the driver loop ----
-  driver<float>(1);
-  driver<double>(1);
-  if (three_devices) { driver<float>(3); driver<double>(3); }
+  for_device_counts([](int ngpus) { driver<float>(ngpus); driver<double>(ngpus); });
 
   // ---- the argument checks: nothing is written, the context stays usable ----
   {
     Case<float> c(2085);
-    c.open(three_devices ? 3 : 1);
-    std::vector<float> t(2085, -77.f);
-    std::vector<int> ix(2085, -77);
-    double tr = -77.0;
-    int st = -77;
+    c.open(three_devices() ? 3 : 1);
+    std::vector<float> t(2085, (float)kMark);
+    std::vector<int> ix(2085, kMark);
+    double tr = kMark;
+    int st = kMark;
     CHECK(nbody_timescale_rows(0, 2085, nullptr, nullptr, nullptr) == NBODY_ERR_ARG);
+    // this pass's own windows (a rows form only, no count of 300): not sanity_common.hpp's list
     const int bad_rows[][2] = {{-1, 4}, {0, 0}, {0, -2}, {2082, 4}, {2085, 1}, {0, 2086}, {1 << 30, 1 << 30}};
     for (const auto& r : bad_rows) CHECK(nbody_timescale_rows(r[0], r[1], t.data(), ix.data(), t.data()) == NBODY_ERR_ARG);
     CHECK(nbody_min_timescale(nullptr, nullptr, nullptr, nullptr) == NBODY_ERR_ARG);
@@ -241,13 +224,12 @@ int main() {
                             {0.5f, 1.f, 0.1f, inf}, {nan, 1.f, 0.1f, 0.2f}, {0.5f, nan, 0.1f, 0.2f}, {0.5f, 1.f, nan, 0.2f}, {0.5f, 1.f, 0.1f, nan}};
     for (const auto& b : bad) CHECK(nbody_step_adaptive(b[0], b[1], b[2], b[3], 10, &tr, &st) == NBODY_ERR_ARG);
     CHECK(nbody_step_adaptive(0.5f, 1.f, 0.1f, 0.2f, 0, &tr, &st) == NBODY_ERR_ARG && nbody_step_adaptive(0.5f, 1.f, 0.1f, 0.2f, -3, &tr, &st) == NBODY_ERR_ARG);
-    for (float v : t) CHECK(v == -77.f);
-    for (int v : ix) CHECK(v == -77);
-    CHECK(tr == -77.0 && st == -77);
+    CHECK(nothing_beyond(t, 0) && nothing_beyond(ix, 0));
+    CHECK(tr == kMark && st == kMark);
     std::vector<double> td(2085, 5.0);
     CHECK(nbody_timescale_rows_d(0, 2085, td.data(), ix.data(), td.data()) == NBODY_ERR_STATE && td[0] == 5.0 && td[2084] == 5.0);
-    CHECK(nbody_min_timescale_d(td.data(), ix.data(), ix.data() + 1, td.data() + 1) == NBODY_ERR_STATE && td[0] == 5.0 && ix[0] == -77);
-    CHECK(nbody_step_adaptive_d(0.5, 1., 0.1, 0.2, 3, &tr, &st) == NBODY_ERR_STATE && tr == -77.0 && st == -77);
+    CHECK(nbody_min_timescale_d(td.data(), ix.data(), ix.data() + 1, td.data() + 1) == NBODY_ERR_STATE && td[0] == 5.0 && ix[0] == kMark);
+    CHECK(nbody_step_adaptive_d(0.5, 1., 0.1, 0.2, 3, &tr, &st) == NBODY_ERR_STATE && tr == kMark && st == kMark);
     c.run_all();
     SHUTDOWN();
     Case<double> d(1000);
@@ -260,15 +242,14 @@ int main() {
   }
 
   // ---- the failure paths: every allocating call of a call, one device and three, split (scratch) and not ----
-  for (int ngpus : {1, 3}) {
-    if (ngpus > 1 && !three_devices) continue;
+  for_device_counts([](int ngpus) {
     Case<float> c(2085);
     const int gather = ngpus > 1 ? 1 : 0;   // ts_vel, where the velocities have to travel
-    set_env("3", nullptr);
+    env.set("3", nullptr);
     int made = sweep("nbody_timescale_rows split", [&] { c.open(ngpus); },
                      [&] { return nbody_timescale_rows(0, c.n, c.tau2.data(), c.idx.data(), c.d2.data()); }, [&] { c.run(); });
     CHECK(made == (4 + gather) * ngpus);   // tau2, idx, d2min, scratch per device
-    set_env("1", nullptr);
+    env.set("1", nullptr);
     made = sweep("nbody_timescale_rows", [&] { c.open(ngpus); }, [&] { return nbody_timescale_rows(0, c.n, c.tau2.data(), nullptr, nullptr); },
                  [&] { c.run(0, -1, 1); });
     CHECK(made == (1 + gather) * ngpus);   // tau2
@@ -280,8 +261,8 @@ int main() {
     int st;
     sweep("nbody_step_adaptive", [&] { c.open(ngpus); }, [&] { return nbody_step_adaptive(0.5f, 0.5f, 0.25f, 0.25f, 5, &tr, &st); },
           [&] { CHECK(st == 2 && tr == 0.5); });
-  }
-  set_env(nullptr, nullptr);
+  });
+  env.set(nullptr, nullptr);
   printf("timescale_sanity ok\n");
   return 0;
 }

@@ -5,8 +5,11 @@ tests/host_stub/hip_stub.cpp stands in for the HIP runtime ("device" memory is m
 streams run synchronously, a capture records closures) and for kernels.hip (a simple stand-in force pushed through the REAL data flow
 of a launch: ForceArgs, segment bounds, partial sums, arrival counters, ascending combine, apply, the mailbox's ingest and
 device-written completion) and energy.hip (predictable values written through the real EnergyArgs); <pass>_stub.cpp stands in for
-<pass>.hip the same way (predictable values pushed through the real PointSumsArgs / NeighborsArgs / KnnArgs / FofArgs: chunk bounds, the
-blocks' or chunks' scratch layout, the combine).  The drivers, one per row of CASES (point_sums_sanity.cpp serves two, by its argument):
+<pass>.hip the same way (predictable values pushed through the real PointSumsArgs / NeighborsArgs / KnnArgs / FofArgs / HistArgs /
+TimescaleArgs: chunk bounds, the blocks' or chunks' scratch layout, the combine) and refuses what the real launch functions refuse, by
+the same predicates (diag_pass.hpp and the passes' *_args.hpp).  stub_rule.hpp is the contract between the distance passes' stubs and
+their drivers — the one candidate a block of sources offers a query — stub_common.hpp the stubs' skeleton, sanity_common.hpp the
+drivers' kit.  The drivers, one per row of CASES (point_sums_sanity.cpp serves two, by its argument):
   host_sanity.cpp       contexts of several sizes, 70-step loops (graph capture and replay), every segmentation / combine form / wave
                         split, row windows, the energy entry points, fp64, one process over three stub devices with ragged slices, the
                         mailbox in every form with the RTL's address map checked against a sentinel, a request whose completion wait
@@ -20,7 +23,13 @@ blocks' or chunks' scratch layout, the combine).  The drivers, one per row of CA
                         query buffers the two passes share;
   knn_sanity.cpp        nbody_knn_rows, nbody_knn: k = 1, 5 and 32, the [m][k] outputs, nbody_nearest calls between nbody_knn calls;
   fof_sanity.cpp        nbody_fof(_d) on a one-dimensional system whose groups it finds by sorting: N = 1, 255, 256, 257 and 5000, the
-                        active-row list against NBODY_FOF_ALL_ROWS=1.
+                        active-row list against NBODY_FOF_ALL_ROWS=1;
+  hist_sanity.cpp       nbody_radial_counts_rows, nbody_radial_counts, nbody_pair_histogram: n_bins = 1, 5 and 32, the right-aligned
+                        edge slots, the [m][n_bins] outputs, the batches of the pair histogram's rows and its 64-bit sums over the
+                        devices, nbody_nearest calls between histogram calls;
+  timescale_sanity.cpp  nbody_timescale_rows, nbody_min_timescale, nbody_step_adaptive: windows of rows across the devices, the two
+                        minima and an index per row, both source streams — the gather of all N velocities on three devices after
+                        steps have changed them — and the driver loop against nbody_step.
 Every pass driver runs over one and three stub devices with ragged slices, the source split forced and automatic, the batched path
 and every NBODY_ERR_ARG case; and every driver runs the failure sweep (the stub fails the k-th creating call of every entry point that
 allocates, k = 1, 2, ...: the call reports it, nothing is live after nbody_shutdown, the same call then works).
@@ -57,6 +66,10 @@ CASES = {
     "fof": (HOST + ("neighbors.cpp", "point_sums.cpp", "knn.cpp", "fof.cpp"),
             ("hip_stub.cpp", "neighbors_stub.cpp", "point_sums_stub.cpp", "knn_stub.cpp", "fof_stub.cpp", "fof_sanity.cpp"), [],
             ("NBODY_FOF_SPLIT", "NBODY_FOF_SCRATCH_MB", "NBODY_FOF_ALL_ROWS"), "fof_sanity ok"),
+    "hist": (HOST + ("neighbors.cpp", "hist.cpp"), ("hip_stub.cpp", "neighbors_stub.cpp", "hist_stub.cpp", "hist_sanity.cpp"), [],
+             ("NBODY_HIST_SPLIT", "NBODY_HIST_SCRATCH_MB", "NBODY_HIST_LOOP") + NEIGHBORS_ENV, "hist_sanity ok"),
+    "timescale": (HOST + ("timescale.cpp",), ("hip_stub.cpp", "timescale_stub.cpp", "timescale_sanity.cpp"), [],
+                  ("NBODY_TIMESCALE_SPLIT", "NBODY_TIMESCALE_SCRATCH_MB"), "timescale_sanity ok"),
 }
 _objects = {}      # (source, sanitizer flags) -> object file: every source is compiled once per flag set and session
 _dir = []

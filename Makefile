@@ -12,7 +12,7 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-s
 all: lib host oracle microbench
 
 # The library = ONE device code object (device.hip: the force path's kernels.hip — the nbk kernels + the launch functions that pick an
-# instantiation, ~45 s of hipcc — the energy pass's energy.hip, the field and tidal passes' point_sums.hip, the neighbour pass's neighbors.hip, the k-nearest-neighbour pass's knn.hip, the friends-of-friends pass's fof.hip, the radial-count pass's hist.hip and the pair time-scale pass's timescale.hip) and ten
+# instantiation, ~45 s of hipcc — the energy pass's energy.hip, the field, tidal and jerk passes' point_sums.hip, the neighbour pass's neighbors.hip, the k-nearest-neighbour pass's knn.hip, the friends-of-friends pass's fof.hip, the radial-count pass's hist.hip and the pair time-scale pass's timescale.hip) and ten
 # host-only C++ files (context, comm, mailbox, energy, point_sums, neighbors, knn, fof, hist, timescale: seconds each) behind csrc/nbody_internal.hpp.  A host-side edit relinks in seconds.
 # The eight diagnostic passes share csrc/diag_pass.hpp (device code — the distance passes' pair distance and query preamble included — the sizes
 # their hosts read and the guard of a split launch) and csrc/query_pass.hpp (host only: the flow of a call and the two split rules).
@@ -25,8 +25,9 @@ HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o $(OBJ)/energy.o $(OB
 # hashed source (KERNEL_SRC); device.hip compiles it with kernels.hip into the library's one code object.  Its host side is energy.cpp, one
 # of HOST_OBJ.  What it shares with the seven passes below is diag_pass.hpp, which is no part of the hashed source either.
 ENERGY_SRC := $(CSRC)/energy.hip $(CSRC)/energy_args.hpp
-# the field pass (acceleration and potential at arbitrary points) and the tidal pass (the tidal tensor there, the gradient of the field) in
-# the same way, the two as one: point_sums.hip beside energy.hip, point_sums.cpp one of HOST_OBJ
+# the field pass (acceleration and potential at arbitrary points), the tidal pass (the tidal tensor there, the gradient of the field) and
+# the jerk pass (the field's time derivative at rows and phase-space points) in the same way, the three as one: point_sums.hip beside
+# energy.hip, point_sums.cpp one of HOST_OBJ
 POINT_SUMS_SRC := $(CSRC)/point_sums.hip $(CSRC)/point_sums_args.hpp
 # the neighbour pass (nearest body, radius count, closest pair) likewise: neighbors.hip beside point_sums.hip, neighbors.cpp one of HOST_OBJ
 NEIGHBORS_SRC := $(CSRC)/neighbors.hip $(CSRC)/neighbors_args.hpp

@@ -423,6 +423,58 @@ int nbody_field_d(const double *points, int m, const int *skip, double *accel, d
 int nbody_tidal(const float *points, int m, const int *skip, float *tensor);
 int nbody_tidal_d(const double *points, int m, const int *skip, double *tensor);
 
+/* ---- jerk: the time derivative of the acceleration, at rows and at phase-space points (not in the reference) ----
+ * For a point x that moves with velocity u and the N bodies on the device (positions r_j, velocities v_j), unit masses, G = 1, eps the
+ * force's softening (bits 0x3089705F), d = r_j - x, w = v_j - u, inv = (|d|^2 + eps)^(-1/2):
+ *   a(x)    = sum_j d inv^3                                  the acceleration of nbody_field, bit for bit
+ *   j(x, u) = da/dt = sum_j ( w inv^3 - 3 (d . w) d inv^5 )
+ * over ALL j; skip[p] = a global body index leaves that body out of point p's sums (-1: nothing), exactly as in nbody_field.  What it is
+ * for: the Aarseth time step eta |a| / |j|, the predictor of a Hermite scheme, the error estimate of a leapfrog step.  The library adds
+ * no integrator on top of it; nbody_step and nbody_step_adaptive are unchanged.
+ * Pair arithmetic, in the context precision T, every operation rounded once:
+ *   dx = xj - x (dy, dz likewise)      wx = vxj - ux (wy, wz likewise)
+ *   inv as nbody_field states it: it follows NBODY_OPT_ARITH (d2 in the FMA3 form or the reference's five roundings; v_rsq_f32 or under a
+ *       strict mode (float)(1.0 / sqrt((double)d2)); fp64 contexts: the fma-contracted d2, the refined v_rsq_f64 seed or under a strict
+ *       mode IEEE sqrt and divide)
+ *   inv2 = inv * inv      inv3 = inv * inv2
+ *   rv = fma(dx, wx, fma(dy, wy, dz * wz))           one form in every arithmetic
+ *   c = (T)3 * rv         b = c * inv2
+ *   tx = fma(-b, dx, wx)  (ty, tz likewise)
+ *   ax = fma(dx, inv3, ax)  (ay, az likewise)        the field's three fma, unchanged
+ *   jx = fma(tx, inv3, jx)  (jy, jz likewise)
+ * ORDER (fixed by N alone; it is the potential's):
+ *   level 1: the sources in blocks of 1024 consecutive bodies; per block the six accumulators above from +0 in ascending j; for
+ *            j == skip[p] all six keep their values;
+ *   level 2: the blocks' six sums converted to fp64 and added in ascending block order from zero, each rounded once to T.
+ * The bits of a query's result depend on the N source positions and velocities, the query (x, u), its skip, the arithmetic and the
+ * precision, and on nothing else — not on m, on where the query stands in the array, on which of the two forms brings it, on the launch
+ * shape (NBODY_JERK_SPLIT below), on the force configuration or on the device or rank count.  No atomics: two calls return identical bits.
+ * DOMAIN: a point on a body that moves with that body's velocity gets +0 from it in both outputs; a point on a body with another
+ * velocity gets +0 in the acceleration and w eps^(-3/2) in the jerk.  A separation whose square overflows gives inv = 0 and contributes
+ * +0 to both as long as 3 rv does not overflow; beyond that b = inf * 0 and the jerk is NaN.  A NaN position or velocity of a body
+ * poisons the jerk of every query that does not skip it.
+ * nbody_jerk(_d): points and velocities: m words {x, y, z, ignored} and {ux, uy, uz, ignored} in the context precision, host memory.
+ *   accel: m words {ax, ay, az, 0}; jerk: m words {jx, jy, jz, 0}; either may be NULL, not both.  skip: NULL, or m ints, each -1 or a
+ *   global body index in [0, N).  The points are divided over the devices as nbody_field divides them; nbody_init_rank: every rank
+ *   evaluates the queries IT was given on its own device, m may differ between ranks.
+ * nbody_jerk_rows(_d): rows exactly as in nbody_timescale_rows (nbody_init: first_row is a global index, the range may span devices;
+ *   nbody_init_rank: a row of the rank's own slice).  Row i's query is (r_i, v_i) with skip = i: bit for bit what nbody_jerk returns for
+ *   it.  The queries are read from device memory where they lie; nothing makes a round trip through the host.
+ * All four bring the other slices' positions first and then ALL N velocities to every device, as nbody_timescale_rows does (one device
+ * reads its own; the devices of an nbody_init context copy each other's slices; an nbody_init_rank job gathers them with the transport
+ * it uses for positions): an nbody_init_rank job is collective through these two gathers only, every rank calls.  They leave positions,
+ * velocities, the arrival counters, the captured step graph and the force-kernel timer as they were.
+ * Environment, read on every call: NBODY_JERK_SPLIT = k >= 1 walks the sources in min(k, blocks) chunks of whole blocks side by side
+ * (unset or 0: chosen from m and the CU count); NBODY_JERK_SCRATCH_MB (default 256) bounds the per-block sums a split launch stores,
+ * larger calls go in consecutive batches of queries.  Same bits in every case.
+ * NBODY_ERR_NOT_INIT without a context; NBODY_ERR_ARG, checked before anything is launched or written, for points == NULL,
+ * velocities == NULL, both outputs NULL, m < 1, a bad row range or a skip value outside [-1, N); NBODY_ERR_STATE for the other
+ * precision's entry point or while the mailbox is served. */
+int nbody_jerk(const float *points, const float *velocities, int m, const int *skip, float *accel, float *jerk);
+int nbody_jerk_d(const double *points, const double *velocities, int m, const int *skip, double *accel, double *jerk);
+int nbody_jerk_rows(int first_row, int n_rows, float *accel, float *jerk);
+int nbody_jerk_rows_d(int first_row, int n_rows, double *accel, double *jerk);
+
 /* ---- nearest neighbour, radius count, closest pair: how close the bodies on the device get (not in the reference) ----
  * A query is a point x with an optional excluded body.  In the context precision T, for every body j on the device:
  *   dx = xj - x;  dy = yj - y;  dz = zj - z;   d2_j = fma(dx, dx, fma(dy, dy, dz * dz))

@@ -45,6 +45,7 @@ SYMBOLS = [
     "nbody_pair_histogram", "nbody_pair_histogram_d", "nbody_tidal", "nbody_tidal_d",
     "nbody_timescale_rows", "nbody_timescale_rows_d", "nbody_min_timescale", "nbody_min_timescale_d",
     "nbody_step_adaptive", "nbody_step_adaptive_d",
+    "nbody_jerk", "nbody_jerk_d", "nbody_jerk_rows", "nbody_jerk_rows_d",
 ]
 
 
@@ -115,6 +116,8 @@ def load():
         "nbody_timescale_rows": [i, i, fp, C.POINTER(i), fp], "nbody_timescale_rows_d": [i, i, dp, C.POINTER(i), dp],
         "nbody_min_timescale": [fp, C.POINTER(i), C.POINTER(i), fp], "nbody_min_timescale_d": [dp, C.POINTER(i), C.POINTER(i), dp],
         "nbody_step_adaptive": [f, f, f, f, i, dp, C.POINTER(i)], "nbody_step_adaptive_d": [d, d, d, d, i, dp, C.POINTER(i)],
+        "nbody_jerk": [fp, fp, i, C.POINTER(i), fp, fp], "nbody_jerk_d": [dp, dp, i, C.POINTER(i), dp, dp],
+        "nbody_jerk_rows": [i, i, fp, fp], "nbody_jerk_rows_d": [i, i, dp, dp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

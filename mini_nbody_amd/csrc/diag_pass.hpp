@@ -4,7 +4,7 @@
 // one-query-per-lane kernel: the lane, the wave's skip window, the chunk's sources.
 // energy_args.hpp, point_sums_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp, hist_args.hpp and timescale_args.hpp include it.  Like them it stays apart from the force path's hashed
 // source (nbody_args.hpp, nbody_kernels.hpp, kernels.hip, force_loop_gfx950.inc), of which it reads nbody_args.hpp (kSoftBits, NB_CONST) only.
-// The kernels' loops are different computations and stay in their files; the field's and the tidal tensor's are one (point_sums.hip).
+// The kernels' loops are different computations and stay in their files; the field's, the tidal tensor's and the jerk's are one (point_sums.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

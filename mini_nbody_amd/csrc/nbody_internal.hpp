@@ -9,7 +9,7 @@
 //   query_pass.hpp what they share on the host: ranges over the locals, upload, the split's batches, launch-then-copy-back, the ranks' words
 //   energy.hip    the energy pass's kernels (energy_args.hpp: its argument block and launch functions)
 //   energy.cpp    nbody_energy, nbody_potential_rows(_d): the energy pass on every local and the sum over the ranks
-//   point_sums.hip the field and tidal passes' kernels: one skeleton of blocked sums, a statement per pass (point_sums_args.hpp: the
+//   point_sums.hip the field, tidal and jerk passes' kernels: one skeleton of blocked sums, a statement per pass (point_sums_args.hpp: the
 //                  passes, their argument block and launch functions)
 //   point_sums.cpp nbody_field(_d), nbody_tidal(_d): acceleration and potential, and the tidal tensor, at the caller's points, the
 //                  points divided over the locals
@@ -31,7 +31,7 @@
 // Data layout in HBM (per rank; N bodies in total, the rank owns n_local of them starting at first_body):
 //   pos[2]   2 x N words      full position set, double-buffered: a step reads pos[cur] and writes the
 //                             rank's slice of pos[cur^1]; the other slices of pos[cur^1] arrive over xGMI
-//   vel      n_local words    never leaves the rank in a step; the pair time-scale pass gathers a copy of all N (ts_vel, full_scratch)
+//   vel      n_local words    never leaves the rank in a step; the pair time-scale and jerk passes gather a copy of all N (ts_vel, full_scratch)
 //   partial  nseg x rows'     per-source-segment partial forces (unused when nseg == 1); rows' = the launch's rows rounded up to 64
 //   tickets  1 per 64 rows    arrival counters of the in-launch combine (zero between steps)
 //   force    n_local words    last combined forces (parity entry points)
@@ -138,13 +138,14 @@ struct Local {
   DevMem en_phi;                       // ... and phi of the rows asked for (context precision)
   DevMem q_points, q_skip;             // field, tidal, neighbour, knn and radial-count pass (query_pass.hpp): this local's range of the caller's points and skip indices ...
   DevMem q_scratch;                    // ... and what a launch whose sources are split leaves for its combine (point_sums_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp, hist_args.hpp, timescale_args.hpp)
-  DevMem q_out[2];                     // field and tidal pass (point_sums.cpp): the points' outputs (context precision), shared as q_points is
+  DevMem q_out[2];                     // field, tidal and jerk pass (point_sums.cpp): the points' outputs (context precision), shared as q_points is
+  DevMem q_vel;                        // jerk pass (point_sums.cpp): this local's range of the caller's point velocities
   DevMem nb_idx, nb_d2, nb_count;      // neighbour pass (neighbors.cpp): the queries' outputs (d2 in the context precision) ...
   DevMem nb_best;                      // ... and the ranks' closest pairs, one BestPair at word `rank` (all P after an all-gather)
   DevMem kn_idx, kn_d2;                // knn pass (knn.cpp): the queries' outputs, k entries each (d2 in the context precision)
   DevMem hi_count;                     // radial-count pass (hist.cpp): the queries' counts, n_bins each ...
   DevMem hi_sums;                      // ... and the ranks' pair-histogram sums, NBODY_HIST_MAX_BINS 64-bit sums at word `rank` (all P after an all-gather)
-  DevMem ts_vel;                       // pair time-scale pass (timescale.cpp): all N velocity words, gathered at the start of a call (several devices in one process) ...
+  DevMem ts_vel;                       // pair time-scale and jerk pass (query_pass.hpp, gather_velocities): all N velocity words, gathered at the start of a call (several devices in one process) ...
   DevMem ts_tau2, ts_idx, ts_d2;       // ... the rows' outputs (tau2 and d2min in the context precision) ...
   DevMem ts_best;                      // ... and the ranks' bests, one BestScale at word `rank` (all P after an all-gather)
   DevMem fo_label, fo_rows, fo_min;    // fof pass (fof.cpp): the N labels of a round, this local's range of the active rows and their m_i

@@ -1,11 +1,14 @@
-// point_sums.cpp — nbody_field(_d) and nbody_tidal(_d): the field (acceleration and potential) and the tidal tensor of the bodies on the
-// device at m points the caller brings (point_sums.hip).  Host C++ only; one flow, the pass (point_sums_args.hpp) says what differs.
-// Flow (query_pass.hpp): reconfigure(), complete_positions() (the other slices, as nbody_forces_rows brings them), then per local its
-// contiguous range of the points: upload, the launch (and the combine launch when the sources are split) on the local's compute stream,
-// stream sync, copy back.  nbody_init_rank contexts: every rank evaluates the points IT was given on its own device; the call is
-// collective only through complete_positions().
-// A call reads pos[cur] and writes only the Local's q_* buffers: positions, velocities, arrival counters, partial forces, the captured
-// step graph and the force-kernel timer stay as they were.  Nothing outside this file refers to it.
+// point_sums.cpp — nbody_field(_d), nbody_tidal(_d), nbody_jerk(_d) and nbody_jerk_rows(_d): the field (acceleration and potential),
+// the tidal tensor and the jerk of the bodies on the device at m points the caller brings, and the jerk at rows of the state itself
+// (point_sums.hip).  Host C++ only; one flow, the pass (point_sums_args.hpp) and the queries say what differs.
+// Flow (query_pass.hpp): reconfigure(), complete_positions() (the other slices, as nbody_forces_rows brings them), a pass with
+// velocities then gather_velocities() (all N of them where every local's kernel can read them), then per local its contiguous range of
+// the points — or its rows of the window, which are read where they lie: nothing is uploaded —: upload, the launch (and the combine
+// launch when the sources are split) on the local's compute stream, stream sync, copy back.  nbody_init_rank contexts: every rank
+// evaluates the points IT was given (its own rows) on its own device; the call is collective only through complete_positions() and
+// gather_velocities().
+// A call reads pos[cur] (and vel) and writes only the Local's q_* buffers (and ts_vel, full_scratch): positions, velocities, arrival
+// counters, partial forces, the captured step graph and the force-kernel timer stay as they were.  Nothing outside this file refers to it.
 #include "query_pass.hpp"
 #include "point_sums_args.hpp"
 
@@ -15,12 +18,17 @@ namespace nbi {
 
 namespace {
 
-// points [r.first, r.first + r.cnt) of the call on local L (uploaded; the outputs asked for left in q_out for the copy back)
-int launch_point_sums(Local& L, const PointPass& pass, const void* points, const int* skip, const Range& r, void* const (&out)[2]) {
+// The queries of a call.  Points: the caller's arrays in host memory (velocities: a pass with velocities only).  Rows (points ==
+// null): the window's bodies themselves, each leaving itself out.
+struct Queries { const void* points; const void* velocities; const int* skip; };
+
+// queries [r.first, r.first + r.cnt) of the call on local L — points of the call (uploaded) or rows of L's slice — with the outputs
+// asked for left in q_out for the copy back
+int launch_point_sums(Local& L, const PointPass& pass, const Queries& q, const Range& r, void* const (&out)[2]) {
   HIPC(hipSetDevice(L.device));
   const size_t wb = word_bytes(), es = elem_bytes();
   const size_t ob[2] = {pass.out_values[0] * es, pass.out_values[1] * es};   // bytes per point of each output
-  NBC(upload_queries(L, points, skip, r.first, r.cnt));
+  if (q.points) NBC(upload_queries(L, q.points, q.skip, r.first, r.cnt, q.velocities));
   for (int i = 0; i < 2; ++i)
     if (out[i]) NBC(L.q_out[i].ensure((size_t)r.cnt * ob[i]));
   const int n_blocks = source_blocks();
@@ -30,8 +38,14 @@ int launch_point_sums(Local& L, const PointPass& pass, const void* points, const
     PointSumsArgs a;
     memset(&a, 0, sizeof(a));
     a.src = L.pos[L.cur];
-    a.points = L.q_points.as<char>() + (size_t)b0 * wb;
-    a.skip = skip ? L.q_skip.as<int>() + b0 : nullptr;
+    if (pass.velocities) a.vsrc = velocities_of(L);
+    if (q.points) {
+      a.points = L.q_points.as<char>() + (size_t)b0 * wb;
+      a.skip = q.skip ? L.q_skip.as<int>() + b0 : nullptr;
+      if (q.velocities) a.pvel = L.q_vel.as<char>() + (size_t)b0 * wb;
+    } else {
+      a.first = L.first + r.first + b0;
+    }
     for (int i = 0; i < 2; ++i) a.out[i] = out[i] ? L.q_out[i].as<char>() + (size_t)b0 * ob[i] : nullptr;
     a.scratch = plan.chunks > 1 ? L.q_scratch.as<void>() : nullptr;
     a.n_src = g.n;
@@ -44,20 +58,36 @@ int launch_point_sums(Local& L, const PointPass& pass, const void* points, const
   });
 }
 
-// out: the caller's arrays, null where the pass has no such output or the caller does not ask for it; at least one
-int point_sums_impl(const PointPass& pass, const void* points, int m, const int* skip, void* out0, void* out1) {
-  void* const out[2] = {out0, out1};
-  if (!g.init) return NBODY_ERR_NOT_INIT;
-  if (!points || m < 1 || (!out[0] && !out[1])) return NBODY_ERR_ARG;
-  NBC(check_skip(skip, m));
+// the checked call: what every form does once its arguments hold.  range_of(l): local l's part of the queries
+template <typename RangeOf>
+int run_point_sums(const PointPass& pass, const Queries& q, RangeOf&& range_of, void* const (&out)[2]) {
   NBC(reconfigure());
   NBC(complete_positions());
-  return run_on_locals([&](int l) { return points_of(m, l); },
-                       [&](Local& L, const Range& r) { return launch_point_sums(L, pass, points, skip, r, out); },
+  if (pass.velocities) NBC(gather_velocities());
+  return run_on_locals(range_of, [&](Local& L, const Range& r) { return launch_point_sums(L, pass, q, r, out); },
                        [&](Local& L, const Range& r) {
                          NBC(copy_out(out[0], r.out, L.q_out[0], r.cnt, pass.out_values[0] * elem_bytes()));
                          return copy_out(out[1], r.out, L.q_out[1], r.cnt, pass.out_values[1] * elem_bytes());
                        });
+}
+
+// out: the caller's arrays, null where the pass has no such output or the caller does not ask for it; at least one
+int point_sums_impl(const PointPass& pass, const void* points, const void* velocities, int m, const int* skip, void* out0, void* out1) {
+  void* const out[2] = {out0, out1};
+  if (!g.init) return NBODY_ERR_NOT_INIT;
+  if (!points || (pass.velocities && !velocities) || m < 1 || (!out[0] && !out[1])) return NBODY_ERR_ARG;
+  NBC(check_skip(skip, m));
+  return run_point_sums(pass, {points, velocities, skip}, [&](int l) { return points_of(m, l); }, out);
+}
+
+// the rows form of a pass with velocities: rows as nbody_timescale_rows takes them
+int point_sums_rows_impl(const PointPass& pass, int first_row, int n_rows, void* out0, void* out1) {
+  void* const out[2] = {out0, out1};
+  if (!g.init) return NBODY_ERR_NOT_INIT;
+  if (!out[0] && !out[1]) return NBODY_ERR_ARG;
+  RowWindow w;   // rows as in nbody_forces_rows
+  NBC(w.open(first_row, n_rows));
+  return run_point_sums(pass, {nullptr, nullptr, nullptr}, [&](int l) { return rows_of(w, l); }, out);
 }
 
 }  // namespace
@@ -69,16 +99,28 @@ using namespace nbi;
 extern "C" {
 
 int nbody_field(const float* points, int m, const int* skip, float* accel, float* phi) { NB_ENTER(0);
-  return point_sums_impl(kFieldPass, points, m, skip, accel, phi);
+  return point_sums_impl(kFieldPass, points, nullptr, m, skip, accel, phi);
 }
 int nbody_field_d(const double* points, int m, const int* skip, double* accel, double* phi) { NB_ENTER(1);
-  return point_sums_impl(kFieldPass, points, m, skip, accel, phi);
+  return point_sums_impl(kFieldPass, points, nullptr, m, skip, accel, phi);
 }
 int nbody_tidal(const float* points, int m, const int* skip, float* tensor) { NB_ENTER(0);
-  return point_sums_impl(kTidalPass, points, m, skip, tensor, nullptr);
+  return point_sums_impl(kTidalPass, points, nullptr, m, skip, tensor, nullptr);
 }
 int nbody_tidal_d(const double* points, int m, const int* skip, double* tensor) { NB_ENTER(1);
-  return point_sums_impl(kTidalPass, points, m, skip, tensor, nullptr);
+  return point_sums_impl(kTidalPass, points, nullptr, m, skip, tensor, nullptr);
+}
+int nbody_jerk(const float* points, const float* velocities, int m, const int* skip, float* accel, float* jerk) { NB_ENTER(0);
+  return point_sums_impl(kJerkPass, points, velocities, m, skip, accel, jerk);
+}
+int nbody_jerk_d(const double* points, const double* velocities, int m, const int* skip, double* accel, double* jerk) { NB_ENTER(1);
+  return point_sums_impl(kJerkPass, points, velocities, m, skip, accel, jerk);
+}
+int nbody_jerk_rows(int first_row, int n_rows, float* accel, float* jerk) { NB_ENTER(0);
+  return point_sums_rows_impl(kJerkPass, first_row, n_rows, accel, jerk);
+}
+int nbody_jerk_rows_d(int first_row, int n_rows, double* accel, double* jerk) { NB_ENTER(1);
+  return point_sums_rows_impl(kJerkPass, first_row, n_rows, accel, jerk);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
-// point_sums.hip — the device code of the two point-sum passes: the field (acceleration and potential) and the tidal tensor T = grad a =
-// -grad grad phi of the N bodies on the device at m arbitrary points (point_sums_args.hpp states the order, include/nbody.h the
-// definitions).  One skeleton — a kernel of blocked level-1 sums, its combine, one launcher pair — and a statement per pass of what
+// point_sums.hip — the device code of the three point-sum passes: the field (acceleration and potential), the tidal tensor T = grad a =
+// -grad grad phi and the jerk da/dt of the N bodies on the device at m arbitrary points or rows (point_sums_args.hpp states the order,
+// include/nbody.h the definitions).  One skeleton — a kernel of blocked level-1 sums, its combine, one launcher pair — and a statement per pass of what
 // differs: the number of sums, the pair, the store.  Compiles on its own; device.hip puts it into the library's one code object after
 // kernels.hip and energy.hip.  Reads nbody_args.hpp (f4, d4, NB_CONST) and nothing else of the force path: d2 and 1/sqrt are
 // diag_pass.hpp's inv_dist, the potential's; the field's cube and three fma follow the force's pair_f32 / pair_f64.  gfx950 only.
@@ -23,6 +23,7 @@ namespace {
 
 struct FieldSums {
   static constexpr int kSums = kFieldPass.sums;   // {ax, ay, az, s}
+  static constexpr bool kVel = kFieldPass.velocities;
   // 3 sub, d2, 1/sqrt, 2 mul (the force's cube), 3 fma, 1 add
   template <int ARITH, bool CMP, typename T, typename V4>
   static __device__ __forceinline__ void pair(const V4 p, const V4 me, T eps, int j, int sk, T (&c)[kSums]) {
@@ -43,6 +44,7 @@ struct FieldSums {
 
 struct TidalSums {
   static constexpr int kSums = kTidalPass.sums;   // {qxx, qyy, qzz, qxy, qxz, qyz, s3}
+  static constexpr bool kVel = kTidalPass.velocities;
   // 3 sub, d2, 1/sqrt, 3 mul (inv2, inv3, inv5), 1 mul (w = 3 inv5), 3 mul (w d), 6 fma, 1 add: 21 VALU + 1 transcendental in the fp32
   // timed form
   template <int ARITH, bool CMP, typename T, typename V4>
@@ -69,10 +71,61 @@ struct TidalSums {
   }
 };
 
+struct JerkSums {
+  static constexpr int kSums = kJerkPass.sums;   // {ax, ay, az, jx, jy, jz}
+  static constexpr bool kVel = kJerkPass.velocities;   // pair takes the two velocities beside the two positions
+  // 6 sub, d2, 1/sqrt, 2 mul (the cube), 1 mul + 2 fma (d . w), 2 mul (3 rv, inv2), 3 fma (t), 3 fma (the field's), 3 fma: 25 VALU + 1
+  // transcendental in the fp32 timed form.  p, me: positions; u, mv: velocities of the source and of the query
+  template <int ARITH, bool CMP, typename T, typename V4>
+  static __device__ __forceinline__ void pair(const V4 p, const V4 u, const V4 me, const V4 mv, T eps, int j, int sk, T (&c)[kSums]) {
+    const T dx = p.x - me.x, dy = p.y - me.y, dz = p.z - me.z;
+    const T wx = u.x - mv.x, wy = u.y - mv.y, wz = u.z - mv.z;
+    const T inv = inv_dist<ARITH>(dx, dy, dz, eps);
+    const T inv2 = inv * inv;
+    const T inv3 = inv * inv2;
+    const T rv = fma_of(dx, wx, fma_of(dy, wy, dz * wz));
+    const T b = ((T)3 * rv) * inv2;
+    const T tx = fma_of(-b, dx, wx), ty = fma_of(-b, dy, wy), tz = fma_of(-b, dz, wz);
+    const T ax = fma_of(dx, inv3, c[0]), ay = fma_of(dy, inv3, c[1]), az = fma_of(dz, inv3, c[2]);
+    const T jx = fma_of(tx, inv3, c[3]), jy = fma_of(ty, inv3, c[4]), jz = fma_of(tz, inv3, c[5]);
+    if (CMP && j == sk) return;
+    c[0] = ax; c[1] = ay; c[2] = az; c[3] = jx; c[4] = jy; c[5] = jz;
+  }
+  template <typename T, typename V4>
+  static __device__ __forceinline__ void store(const PointSumsArgs& a, int p, const double (&l2)[kSums]) {
+    if (a.out[0]) ((V4*)a.out[0])[p] = V4{(T)l2[0], (T)l2[1], (T)l2[2], (T)0};
+    if (a.out[1]) ((V4*)a.out[1])[p] = V4{(T)l2[3], (T)l2[4], (T)l2[5], (T)0};
+  }
+};
+
 // ---- the skeleton ----
 
+// The query of lane pc: its point, (a pass with velocities) its velocity, and the source it leaves out (SKIP = false: -1).  A pass
+// with velocities also has the rows form (a.points == null): query pc is source a.first + pc, read from src and vsrc, and leaves
+// itself out.
+template <typename V4>
+struct QueryWords { V4 me, mv; int own; };
+template <class P, typename V4, bool SKIP>
+__device__ __forceinline__ QueryWords<V4> query_words(const PointSumsArgs& a, int pc) {
+  if constexpr (P::kVel) {
+    if (!a.points) return {((const V4*)a.src)[a.first + pc], ((const V4*)a.vsrc)[a.first + pc], SKIP ? a.first + pc : -1};
+    return {((const V4*)a.points)[pc], ((const V4*)a.pvel)[pc], SKIP ? a.skip[pc] : -1};
+  } else {
+    return {((const V4*)a.points)[pc], V4{}, SKIP ? a.skip[pc] : -1};
+  }
+}
+
+// source j into the sums c: its position and (a pass with velocities) its velocity, both wave-uniform scalar loads
+template <class P, int ARITH, bool CMP, typename T, typename V4>
+__device__ __forceinline__ void pair_of(const NB_CONST V4* src, const NB_CONST V4* vsrc, int j, const V4 me, const V4 mv, T eps, int sk,
+                                        T (&c)[P::kSums]) {
+  if constexpr (P::kVel) P::template pair<ARITH, CMP, T, V4>(src[j], vsrc[j], me, mv, eps, j, sk, c);
+  else P::template pair<ARITH, CMP, T, V4>(src[j], me, eps, j, sk, c);
+}
+
 // One point per lane, kLanes points per workgroup; workgroup (x, y) walks the blocks of chunk y for the points of x.  Sources
-// arrive with wave-uniform scalar loads (address space 4, as energy_kernel).  Lanes beyond m stay in the wave-uniform loops clamped to
+// arrive with wave-uniform scalar loads (address space 4, as energy_kernel) — in a pass with velocities as two streams, positions and
+// velocities, as timescale_kernel's.  Lanes beyond m stay in the wave-uniform loops clamped to
 // the last point and store nothing.  SKIP: only the aligned 64-source windows that overlap [lowest, highest] skip index of the wave's
 // 64 points compare j with skip (a wave-uniform branch); every other window, and every window of the SKIP = false form, is the pass's
 // branch-free pair (field: 3 sub, 3 fma, 1 rsq, 2 mul, 3 fma and 1 add).
@@ -80,10 +133,11 @@ template <class P, typename T, typename V4, int ARITH, bool SKIP>
 __global__ void __launch_bounds__(kLanes) block_sums_kernel(PointSumsArgs a) {
   constexpr int S = P::kSums;
   const auto [p, live, pc] = lane_of(a.m);
-  const V4 me = ((const V4*)a.points)[pc];
-  const auto [sk, wlo, whi] = wave_skip_window<SKIP>(SKIP ? a.skip[pc] : -1);
+  const auto [me, mv, own] = query_words<P, V4, SKIP>(a, pc);
+  const auto [sk, wlo, whi] = wave_skip_window<SKIP>(own);
   const T eps = soft<T>();
   const NB_CONST V4* src = scalar_src<V4>(a.src);
+  const NB_CONST V4* vsrc = scalar_src<V4>(P::kVel ? a.vsrc : nullptr);
   T* sc = (T*)a.scratch;
   const auto [blk0, blk1] = chunk_of(a.chunk_blocks, a.n_blocks);
   double l2[S] = {};
@@ -95,13 +149,13 @@ __global__ void __launch_bounds__(kLanes) block_sums_kernel(PointSumsArgs a) {
     for (; j + 64 <= b1; j += 64) {
       if (!SKIP || j + 63 < wlo || j > whi) {
 #pragma unroll 8
-        for (int k = 0; k < 64; ++k) P::template pair<ARITH, false, T, V4>(src[j + k], me, eps, j + k, sk, c);
+        for (int k = 0; k < 64; ++k) pair_of<P, ARITH, false, T, V4>(src, vsrc, j + k, me, mv, eps, sk, c);
       } else {
 #pragma unroll 8
-        for (int k = 0; k < 64; ++k) P::template pair<ARITH, true, T, V4>(src[j + k], me, eps, j + k, sk, c);
+        for (int k = 0; k < 64; ++k) pair_of<P, ARITH, true, T, V4>(src, vsrc, j + k, me, mv, eps, sk, c);
       }
     }
-    for (; j < b1; ++j) P::template pair<ARITH, SKIP, T, V4>(src[j], me, eps, j, sk, c);   // the last block's tail (N not a multiple of 64)
+    for (; j < b1; ++j) pair_of<P, ARITH, SKIP, T, V4>(src, vsrc, j, me, mv, eps, sk, c);   // the last block's tail (N not a multiple of 64)
     if (sc) {
       if (live) {
         const size_t w = (size_t)blk * S * (size_t)a.m + (size_t)p;
@@ -136,13 +190,13 @@ __global__ void __launch_bounds__(kLanes) block_sums_combine(PointSumsArgs a) {
 template <class P, typename T, typename V4, int ARITH>
 void launch_sums_one(hipStream_t st, int chunks, const PointSumsArgs& a) {
   const dim3 grid((a.m + kLanes - 1) / kLanes, chunks);
-  if (a.skip) hipLaunchKernelGGL((block_sums_kernel<P, T, V4, ARITH, true>), grid, dim3(kLanes), 0, st, a);
+  if (a.skip || !a.points) hipLaunchKernelGGL((block_sums_kernel<P, T, V4, ARITH, true>), grid, dim3(kLanes), 0, st, a);   // (rows leave themselves out)
   else hipLaunchKernelGGL((block_sums_kernel<P, T, V4, ARITH, false>), grid, dim3(kLanes), 0, st, a);
 }
 
 template <class P>
-int launch_sums(int fp64, int arith, hipStream_t st, int chunks, const PointSumsArgs& a) {
-  if (bad_point_sums_launch(a, chunks)) return (int)hipErrorInvalidValue;
+int launch_sums(const PointPass& pass, int fp64, int arith, hipStream_t st, int chunks, const PointSumsArgs& a) {
+  if (bad_point_sums_launch(a, chunks) || bad_point_sums_queries(pass, a)) return (int)hipErrorInvalidValue;
   if (fp64) {   // fp64 contexts have one d2 form: REFERENCE = FMA3, REFERENCE_STRICT = STRICT
     if (arith & kStrict) launch_sums_one<P, double, d4, kStrict>(st, chunks, a);
     else launch_sums_one<P, double, d4, 0>(st, chunks, a);
@@ -171,10 +225,12 @@ int launch_combine(int fp64, hipStream_t st, const PointSumsArgs& a) {
 namespace nbl {
 
 NBP_HIDDEN int launch_point_sums_kernel(const PointPass& pass, int fp64, int arith, hipStream_t st, int chunks, const PointSumsArgs& a) {
-  return pass.id == kTidalPass.id ? launch_sums<TidalSums>(fp64, arith, st, chunks, a) : launch_sums<FieldSums>(fp64, arith, st, chunks, a);
+  if (pass.id == kJerkPass.id) return launch_sums<JerkSums>(pass, fp64, arith, st, chunks, a);
+  return pass.id == kTidalPass.id ? launch_sums<TidalSums>(pass, fp64, arith, st, chunks, a) : launch_sums<FieldSums>(pass, fp64, arith, st, chunks, a);
 }
 
 NBP_HIDDEN int launch_point_sums_combine_kernel(const PointPass& pass, int fp64, hipStream_t st, const PointSumsArgs& a) {
+  if (pass.id == kJerkPass.id) return launch_combine<JerkSums>(fp64, st, a);
   return pass.id == kTidalPass.id ? launch_combine<TidalSums>(fp64, st, a) : launch_combine<FieldSums>(fp64, st, a);
 }
 

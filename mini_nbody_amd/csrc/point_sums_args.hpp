@@ -1,16 +1,18 @@
-// point_sums_args.hpp — what point_sums.cpp (host) and point_sums.hip (device) agree on: the two point-sum passes (the field and the
-// tidal tensor of the N bodies at m arbitrary points), their one argument block and the launch functions of point_sums.hip.  Like
+// point_sums_args.hpp — what point_sums.cpp (host) and point_sums.hip (device) agree on: the three point-sum passes (the field, the
+// tidal tensor and the jerk of the N bodies at m arbitrary points), their one argument block and the launch functions of point_sums.hip.  Like
 // energy_args.hpp it stays apart from nbody_args.hpp, the force path's hashed kernel source.
 //
-// The order of every sum (include/nbody.h, "field at arbitrary points" and "tidal tensor at arbitrary points") is fixed by N alone and
+// The order of every sum (include/nbody.h, "field at arbitrary points", "tidal tensor at arbitrary points" and "jerk") is fixed by N alone and
 // is the potential's.  A pass has `sums` accumulators per point:
 //   level 1  sources in blocks of nbd::kSrcBlock consecutive bodies; per block the accumulators from +0 in ascending j in the context
 //            precision; j == skip[p] leaves all of them as they are.
 //              field (4)  ax = fma(dx, inv3, ax), ay, az likewise, s = s + inv;
 //              tidal (7)  w = 3 inv5, q_ab = fma(w d_a, d_b, q_ab) for ab = xx, yy, zz, xy, xz, yz, s3 = s3 + inv3;
+//              jerk (6)   the field's ax, ay, az; with w = v_j - u, b = 3 (d . w) inv2, t_a = fma(-b, d_a, w_a): j_a = fma(t_a, inv3, j_a);
 //   level 2  the blocks' sums converted to fp64 and added in ascending block order from zero, then rounded once.
 //              field      accel = (T){A}, phi = (T)(0 - S);
-//              tidal      T_aa = (T)(Q_aa - S3), T_ab = (T)Q_ab.
+//              tidal      T_aa = (T)(Q_aa - S3), T_ab = (T)Q_ab;
+//              jerk       accel = (T){A}, jerk = (T){J}.
 // Level 2 happens in registers when one workgroup walks every block of its points (grid.y = 1, scratch == null).  When the sources are
 // split over grid.y chunks of whole blocks, every workgroup stores its blocks' level-1 sums — per BLOCK, never per chunk, which is
 // what keeps the bits independent of the number of chunks — and the combine kernel adds them.
@@ -23,16 +25,19 @@ namespace nbp {
 
 // A pass, as the host and the launch functions see it; point_sums.hip states its pair arithmetic and its store.
 struct PointPass {
-  int id;                       // which of the two
+  int id;                       // which of the three
   int sums;                     // kSums: level-1 sums of a point and block
   int out_values[2];            // kOut: values of the context precision per point in each output (0: the pass has no such output)
   const char* split_env;        // the host's variables: the forced number of chunks ...
   const char* scratch_mb_env;   // ... and the bound of the scratch (query_pass.hpp, block_split)
+  int velocities;               // 1: the pair reads the velocities of both sides too (vsrc, pvel), and the queries may be rows (first)
 };
 // field: sums {ax, ay, az, s}; out[0] = accel, words {ax, ay, az, 0}, out[1] = phi; either may be null
 inline constexpr PointPass kFieldPass = {0, 4, {4, 1}, "NBODY_FIELD_SPLIT", "NBODY_FIELD_SCRATCH_MB"};
 // tidal: sums {qxx, qyy, qzz, qxy, qxz, qyz, s3}; out[0] = the tensor, values {xx, yy, zz, xy, xz, yz}, out[1] stays null
 inline constexpr PointPass kTidalPass = {1, 7, {6, 0}, "NBODY_TIDAL_SPLIT", "NBODY_TIDAL_SCRATCH_MB"};
+// jerk: sums {ax, ay, az, jx, jy, jz}; out[0] = accel, words {ax, ay, az, 0}, out[1] = jerk, words {jx, jy, jz, 0}; either may be null
+inline constexpr PointPass kJerkPass = {2, 6, {4, 4}, "NBODY_JERK_SPLIT", "NBODY_JERK_SCRATCH_MB", 1};
 
 struct PointSumsArgs {
   const void* src;      // all N source words (16-B or 32-B {x, y, z, w}), ascending
@@ -45,6 +50,11 @@ struct PointSumsArgs {
   int m;                // points of this launch
   int n_blocks;         // ceil(N / nbd::kSrcBlock)
   int chunk_blocks;     // blocks per chunk: workgroup (x, y) walks blocks [y * chunk_blocks, min((y + 1) * chunk_blocks, n_blocks))
+  // a pass with velocities only (the others leave these zero):
+  const void* vsrc;     // all N velocity words of the sources, ascending, as src
+  const void* pvel;     // [m] words {ux, uy, uz, ignored}: the points' velocities
+  int first;            // points == null, the rows form: query p is source first + p — its point src[first + p], its velocity
+                        // vsrc[first + p] — and leaves itself out (skip and pvel stay null)
 };
 
 // scratch bytes of a launch of m points (per-block sums: independent of the number of chunks)
@@ -56,6 +66,14 @@ inline bool bad_point_sums_launch(const PointSumsArgs& a, int chunks) {
   return a.m <= 0 || chunks < 1 || (chunks > 1 && !a.scratch) || (!a.out[0] && !a.out[1]);
 }
 inline bool bad_point_sums_combine(const PointSumsArgs& a) { return a.m <= 0 || !a.scratch || (!a.out[0] && !a.out[1]); }
+// ... and what the launch refuses of the queries: no points where the pass has no rows form, a pass with velocities without the
+// sources' or the points' velocities, a skip array or point velocities beside rows, rows outside the sources
+inline bool bad_point_sums_queries(const PointPass& pass, const PointSumsArgs& a) {
+  if (!pass.velocities) return !a.points;
+  if (!a.vsrc) return true;
+  if (a.points) return !a.pvel;
+  return a.skip || a.pvel || a.first < 0 || a.first > a.n_src - a.m;
+}
 
 }  // namespace nbp
 

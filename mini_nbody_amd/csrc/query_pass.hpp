@@ -2,9 +2,9 @@
 // rows or points, every local takes a contiguous range of them, launches on its compute stream — in batches over a split of the
 // sources when the pass asks for one — and the results are copied back once the stream has drained.  A pass says what differs: which
 // range a local gets, what to launch, which outputs go where, and which of the two split rules (a SplitPlan) it follows: chunk_split,
-// for the five distance passes whose scratch is per chunk, or block_split, for the field and tidal passes, whose scratch is per block.
+// for the five distance passes whose scratch is per chunk, or block_split, for the field, tidal and jerk passes, whose scratch is per block.
 // The points, skip indices and split scratch of a call live in one set of buffers per Local (q_points, q_skip, q_scratch; q_out, the
-// outputs of the field and tidal passes, likewise), whichever pass runs: every call drains the streams it used before it returns, so no two calls ever use them at once.
+// outputs of the field, tidal and jerk passes, and q_vel, the jerk's point velocities, likewise), whichever pass runs: every call drains the streams it used before it returns, so no two calls ever use them at once.
 #pragma once
 #include "nbody_internal.hpp"
 #include "diag_pass.hpp"
@@ -62,7 +62,7 @@ inline SplitPlan chunk_split(const char* split_env, const char* scratch_mb_env, 
   return {chunks, chunk_blocks, batch};
 }
 
-// The split of the field and tidal passes, whose scratch is per BLOCK (values level-1 sums of `es` bytes for every point and block:
+// The split of the field, tidal and jerk passes, whose scratch is per BLOCK (values level-1 sums of `es` bytes for every point and block:
 // point_sums_args.hpp), so its size per point does not depend on the number of chunks: the points whose per-block sums fit
 // the bound of scratch_mb_env go together, in whole workgroups, and the chunks are chosen anew for such a batch — split_env forces their
 // number.  It reads its MB bound as an integer (env_ll; 256 when unset) where chunk_split takes fractions (atof).
@@ -123,10 +123,15 @@ inline Range rows_of(const RowWindow& w, int l) {
 }
 
 // points [p0, p0 + cnt) of the call and their skip indices (or null) into L's q_points / q_skip (L's device is current)
-inline int upload_queries(Local& L, const void* points, const int* skip, int p0, int cnt) {
+// velocities: the points' velocity words (a pass that reads them: the jerk), into L's q_vel likewise
+inline int upload_queries(Local& L, const void* points, const int* skip, int p0, int cnt, const void* velocities = nullptr) {
   const size_t wb = word_bytes();
   NBC(L.q_points.ensure((size_t)cnt * wb));
   HIPC(hipMemcpy(L.q_points, (const char*)points + (size_t)p0 * wb, (size_t)cnt * wb, hipMemcpyHostToDevice));
+  if (velocities) {
+    NBC(L.q_vel.ensure((size_t)cnt * wb));
+    HIPC(hipMemcpy(L.q_vel, (const char*)velocities + (size_t)p0 * wb, (size_t)cnt * wb, hipMemcpyHostToDevice));
+  }
   if (skip) {
     NBC(L.q_skip.ensure((size_t)cnt * sizeof(int)));
     HIPC(hipMemcpy(L.q_skip, skip + p0, (size_t)cnt * sizeof(int), hipMemcpyHostToDevice));
@@ -157,6 +162,33 @@ int run_on_locals(RangeOf&& range_of, Launch&& launch, CopyBack&& copy_back) {
     NBC(copy_back(L, r));
   }
   return NBODY_OK;
+}
+
+// All N velocity words where the kernels of every local can read them (the pair time-scale and the jerk pass).  One device: vel itself, no copy.  Several devices in one
+// process: every local's ts_vel, filled by device-to-device copies of the locals' slices (hipMemcpyPeerAsync, as the positions travel
+// in enqueue_gather) on its compute stream, which the launch follows.  Several processes: the collective gather of a sharded array
+// into full_scratch with the transport in use (gather_sharded_multiprocess).  The streams are drained first: a step may still be
+// writing the velocities.
+inline int gather_velocities() {
+  if (g.nranks == 1) return NBODY_OK;
+  NBC(sync_all());
+  if (g.multiprocess) return gather_sharded_multiprocess(g.loc[0], g.loc[0].vel);
+  const size_t wb = word_bytes();
+  for (int l = 0; l < g.nlocal; ++l) {
+    Local& L = g.loc[l];
+    HIPC(hipSetDevice(L.device));
+    NBC(L.ts_vel.ensure((size_t)g.n * wb));
+    for (int o = 0; o < g.nlocal; ++o) {
+      const Local& O = g.loc[o];
+      if (O.n_local > 0)
+        HIPC(hipMemcpyPeerAsync(word_ptr(L.ts_vel, O.first), L.device, O.vel, O.device, (size_t)O.n_local * wb, L.compute));
+    }
+  }
+  return NBODY_OK;
+}
+inline const void* velocities_of(const Local& L) {
+  if (g.nranks == 1) return L.vel;
+  return g.multiprocess ? L.full_scratch.as<void>() : L.ts_vel.as<void>();
 }
 
 // Word `rank` (bytes_per_rank, written on the compute stream) of every rank's L.*buf into host_words[0 .. P): processes exchange the

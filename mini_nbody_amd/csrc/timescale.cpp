@@ -2,7 +2,7 @@
 // squared |r_ij|^2 / |v_ij|^2, the body that gives it and the smallest squared distance; the best of the whole system; and a shared
 // adaptive time step on top of the existing step (timescale.hip).  Host C++ only, in the shape of neighbors.cpp.  Flow (query_pass.hpp):
 // reconfigure(), complete_positions() (the other slices, as nbody_forces_rows brings them), all N velocities where every local's
-// kernel can read them (gather_velocities below), then per local its rows of the window: the launch (and the combine launch when the
+// kernel can read them (query_pass.hpp's gather_velocities), then per local its rows of the window: the launch (and the combine launch when the
 // sources are split) on the local's compute stream, stream sync, copy back.  The system form runs the rows pass over every local's own
 // rows, reduces them to the local's best on the device and picks the winner among the devices' or ranks' words in rank order on the
 // host; processes exchange the words through the transport they use for positions (allgather_rank_words), as the closest pair's.
@@ -27,33 +27,6 @@ namespace {
 constexpr int kTimescaleFill = 16;
 
 struct Want { bool tau2, idx, d2; };
-
-// All N velocity words where the kernels of every local can read them.  One device: vel itself, no copy.  Several devices in one
-// process: every local's ts_vel, filled by device-to-device copies of the locals' slices (hipMemcpyPeerAsync, as the positions travel
-// in enqueue_gather) on its compute stream, which the launch follows.  Several processes: the collective gather of a sharded array
-// into full_scratch with the transport in use (gather_sharded_multiprocess).  The streams are drained first: a step may still be
-// writing the velocities.
-int gather_velocities() {
-  if (g.nranks == 1) return NBODY_OK;
-  NBC(sync_all());
-  if (g.multiprocess) return gather_sharded_multiprocess(g.loc[0], g.loc[0].vel);
-  const size_t wb = word_bytes();
-  for (int l = 0; l < g.nlocal; ++l) {
-    Local& L = g.loc[l];
-    HIPC(hipSetDevice(L.device));
-    NBC(L.ts_vel.ensure((size_t)g.n * wb));
-    for (int o = 0; o < g.nlocal; ++o) {
-      const Local& O = g.loc[o];
-      if (O.n_local > 0)
-        HIPC(hipMemcpyPeerAsync(word_ptr(L.ts_vel, O.first), L.device, O.vel, O.device, (size_t)O.n_local * wb, L.compute));
-    }
-  }
-  return NBODY_OK;
-}
-const void* velocities_of(const Local& L) {
-  if (g.nranks == 1) return L.vel;
-  return g.multiprocess ? L.full_scratch.as<void>() : L.ts_vel.as<void>();
-}
 
 // rows [r.first, r.first + r.cnt) of L's slice, with the outputs left in ts_tau2 / ts_idx / ts_d2 for the copy back
 int launch_timescale(Local& L, const Range& r, const Want& w) {

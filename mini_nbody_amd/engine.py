@@ -195,6 +195,35 @@ class NBody:
                    t.ctypes.data_as(C.POINTER(ct))))
         return t
 
+    def jerk_at(self, points, velocities, skip=None):
+        """(accel, jerk), each (m, 4) in the context dtype, of the bodies on the device at m phase-space points (nbody_jerk): accel the
+        a(x) of field(), bit for bit, jerk its time derivative for a point that moves with velocity u,
+        j(x, u) = sum_j (w inv^3 - 3 (d . w) d inv^5), d = r_j - x, w = v_j - u, over ALL j.  points, velocities: (m, 4) words or (m, 3),
+        padded as tidal() pads them; skip as in field().  Collective in a multi-rank job (every rank brings its own queries)."""
+        p, m, sk = self._queries(points, skip)
+        u, mu, _ = self._queries(velocities, None)
+        if mu != m:
+            raise ValueError("expected one velocity per point")
+        ct = C.c_double if self.fp64 else C.c_float
+        a, j = np.empty((m, 4), self.dtype), np.empty((m, 4), self.dtype)
+        fn = self.lib.nbody_jerk_d if self.fp64 else self.lib.nbody_jerk
+        L.check(fn(p.ctypes.data_as(C.POINTER(ct)), u.ctypes.data_as(C.POINTER(ct)), m,
+                   sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None, a.ctypes.data_as(C.POINTER(ct)), j.ctypes.data_as(C.POINTER(ct))))
+        return a, j
+
+    def jerk(self, first_row=0, n_rows=None):
+        """(accel, jerk), each (n_rows, 4) in the context dtype, of n_rows bodies from first_row (rows as in timescales(); default: all of
+        them) from the state on the device (nbody_jerk_rows): row i is jerk_at(r_i, v_i, skip=i) bit for bit, read where it lies on the
+        device.  Collective in a multi-rank job."""
+        if n_rows is None:
+            n_rows = self.info(L.INFO_N_LOCAL if self._by_rank else L.INFO_N) - int(first_row)
+        m = int(n_rows)
+        ct = C.c_double if self.fp64 else C.c_float
+        a, j = np.empty((max(m, 0), 4), self.dtype), np.empty((max(m, 0), 4), self.dtype)
+        fn = self.lib.nbody_jerk_rows_d if self.fp64 else self.lib.nbody_jerk_rows
+        L.check(fn(int(first_row), m, a.ctypes.data_as(C.POINTER(ct)), j.ctypes.data_as(C.POINTER(ct))))
+        return a, j
+
     def _near_out(self, m, r2):
         ct = C.c_double if self.fp64 else C.c_float
         idx, d2 = np.empty(m, np.int32), np.empty(m, self.dtype)
@@ -473,6 +502,18 @@ def tidal_matrix(t6):
     if t6.shape[-1:] != (6,):
         raise ValueError("expected six values {xx, yy, zz, xy, xz, yz} per point")
     return t6[..., [[0, 3, 4], [3, 1, 5], [4, 5, 2]]]
+
+
+def aarseth_dt(accel, jerk, eta):
+    """eta |a| / |j| per row in fp64, the Aarseth time step from NBody.jerk() or jerk_at(): accel, jerk (m, 4) or (m, 3) (the first three
+    components count), +inf where |j| = 0."""
+    a, j = np.asarray(accel, np.float64), np.asarray(jerk, np.float64)
+    if a.ndim != 2 or a.shape != j.shape or a.shape[1] not in (3, 4):
+        raise ValueError("expected accel and jerk of one shape, (m, 4) or (m, 3)")
+    na, nj = np.sqrt((a[:, :3] ** 2).sum(1)), np.sqrt((j[:, :3] ** 2).sum(1))
+    dt = np.full(len(a), np.inf)
+    np.divide(float(eta) * na, nj, out=dt, where=nj != 0)
+    return dt
 
 
 def comm_plan(form, rank, nranks, n):

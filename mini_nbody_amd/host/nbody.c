@@ -8,13 +8,15 @@
  *
  * usage: nbody [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K]
  *              [--sum seq|blocked] [--block K] [--one-launch | --two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16]
- *              [--energy] [--field M] [--tidal M] [--closest-pair] [--pair-histogram B] [--adaptive ETA]
+ *              [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA]
  * --energy: E = T + U, T and U of the state on the device (nbody_energy) before the first iteration and after the last, and the
  * relative drift, outside the timed region.
  * --field M: after the last iteration, acceleration and potential of the state on the device (nbody_field) at M points — the position
  * words of an M-body system of the same initial conditions with seed 4242 — as plain ascending fp64 sums, outside the timed region.
  * --tidal M: after the last iteration, the tidal tensor of the state on the device (nbody_tidal) at the M points of --field M: its trace
  * and its six values {xx, yy, zz, xy, xz, yz} as plain ascending fp64 sums over the points, outside the timed region.
+ * --jerk M (1 <= M <= N): after the last iteration, acceleration and jerk of rows 0 .. M - 1 of the state on the device
+ * (nbody_jerk_rows), each as three plain ascending fp64 sums over the rows, outside the timed region.
  * --closest-pair: after the last iteration, the two bodies of the state on the device that are closest and their plain squared distance
  * (nbody_closest_pair), outside the timed region.
  * --pair-histogram B (1 <= B <= 32): after the last iteration, one line "pair histogram: c0 c1 ... c(B-1)", the number of unordered
@@ -125,6 +127,33 @@ static int print_tidal(int m, int fp64) {
   return 0;
 }
 
+/* the line of --jerk: the three components of the acceleration and of the jerk summed over rows 0 .. m - 1, ascending, in fp64 */
+static int print_jerk(int m, int fp64) {
+  const size_t words = (size_t)m * 4;
+  double a_sum[3] = { 0.0, 0.0, 0.0 }, j_sum[3] = { 0.0, 0.0, 0.0 };
+  int rc;
+  if (!fp64) {
+    float *buf = (float *)malloc(2 * words * sizeof(float));
+    if (!buf) return 3;
+    float *acc = buf, *jerk = buf + words;
+    rc = nbody_jerk_rows(0, m, acc, jerk);
+    for (int p = 0; p < m && !rc; ++p)
+      for (int c = 0; c < 3; ++c) { a_sum[c] += (double)acc[4 * p + c]; j_sum[c] += (double)jerk[4 * p + c]; }
+    free(buf);
+  } else {
+    double *buf = (double *)malloc(2 * words * sizeof(double));
+    if (!buf) return 3;
+    double *acc = buf, *jerk = buf + words;
+    rc = nbody_jerk_rows_d(0, m, acc, jerk);
+    for (int p = 0; p < m && !rc; ++p)
+      for (int c = 0; c < 3; ++c) { a_sum[c] += acc[4 * p + c]; j_sum[c] += jerk[4 * p + c]; }
+    free(buf);
+  }
+  if (rc) { fprintf(stderr, "nbody_jerk_rows failed: %s\n", nbody_error_string(rc)); return 1; }
+  printf("jerk of %d rows: a_sum %.17g %.17g %.17g j_sum %.17g %.17g %.17g\n", m, a_sum[0], a_sum[1], a_sum[2], j_sum[0], j_sum[1], j_sum[2]);
+  return 0;
+}
+
 /* the line of --closest-pair */
 static int print_closest_pair(int fp64) {
   int i = -1, j = -1, rc;
@@ -184,7 +213,7 @@ static int print_pair_histogram(int bins, int fp64) {
 }
 
 int main(int argc, char **argv) {
-  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0, tidal = 0, closest = 0, pair_hist = 0;
+  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0, tidal = 0, jerk = 0, closest = 0, pair_hist = 0;
   double e0 = 0.0, adaptive = 0.0;
   unsigned long long seed = NBODY_IC_DEFAULT_SEED;
   for (int a = 1; a < argc; ++a) {
@@ -199,6 +228,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--energy")) energy = 1;
     else if (!strcmp(argv[a], "--field") && a + 1 < argc) field = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--tidal") && a + 1 < argc) tidal = atoi(argv[++a]);
+    else if (!strcmp(argv[a], "--jerk") && a + 1 < argc) jerk = atoi(argv[++a]);
     else if (!strcmp(argv[a], "--closest-pair")) closest = 1;
     else if (!strcmp(argv[a], "--pair-histogram") && a + 1 < argc) { pair_hist = atoi(argv[++a]); if (pair_hist < 1 || pair_hist > NBODY_HIST_MAX_BINS) { fprintf(stderr, "--pair-histogram needs 1 <= B <= %d\n", NBODY_HIST_MAX_BINS); return 2; } }
     else if (!strcmp(argv[a], "--adaptive") && a + 1 < argc) { adaptive = atof(argv[++a]); if (!(adaptive > 0.0) || adaptive > 1e300) { fprintf(stderr, "--adaptive needs ETA > 0\n"); return 2; } }
@@ -211,10 +241,11 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--block") && a + 1 < argc) block = atoi(argv[++a]);
     else if (argv[a][0] != '-' && npos == 0) { n = atoi(argv[a]); npos++; }
     else if (argv[a][0] != '-' && npos == 1) { iters = atoi(argv[a]); npos++; }
-    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--tidal M] [--closest-pair] [--pair-histogram B] [--adaptive ETA]\n", argv[0]); return 2; }
+    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA]\n", argv[0]); return 2; }
   }
   if (field < 0) { fprintf(stderr, "--field needs M >= 1\n"); return 2; }
   if (tidal < 0) { fprintf(stderr, "--tidal needs M >= 1\n"); return 2; }
+  if (jerk < 0 || jerk > n) { fprintf(stderr, "--jerk needs 1 <= M <= N\n"); return 2; }
   if (n <= 0 || iters < 2) { fprintf(stderr, "need N > 0 and iters >= 2 (iteration 1 is warm-up)\n"); return 2; }
   const float dt = 0.01f;
   const size_t words = (size_t)n * 4;
@@ -263,10 +294,11 @@ int main(int argc, char **argv) {
       total = now_s() - t0;
       CHECK(nbody_download(&p));
     }
-    if ((energy || field || tidal || closest || pair_hist || adaptive > 0.0) && host_loop) CHECK(nbody_upload(&p));
+    if ((energy || field || tidal || jerk || closest || pair_hist || adaptive > 0.0) && host_loop) CHECK(nbody_upload(&p));
     if (energy && print_energy(iters, &e0, 0)) return 1;
     if (field && print_field(field, 0)) return 1;
     if (tidal && print_tidal(tidal, 0)) return 1;
+    if (jerk && print_jerk(jerk, 0)) return 1;
     if (closest && print_closest_pair(0)) return 1;
     if (pair_hist && print_pair_histogram(pair_hist, 0)) return 1;
     if (adaptive > 0.0 && print_min_timescale(adaptive, 0)) return 1;
@@ -298,10 +330,11 @@ int main(int argc, char **argv) {
       total = now_s() - t0;
       CHECK(nbody_download_d(&p));
     }
-    if ((energy || field || tidal || closest || pair_hist || adaptive > 0.0) && host_loop) CHECK(nbody_upload_d(&p));
+    if ((energy || field || tidal || jerk || closest || pair_hist || adaptive > 0.0) && host_loop) CHECK(nbody_upload_d(&p));
     if (energy && print_energy(iters, &e0, 0)) return 1;
     if (field && print_field(field, 1)) return 1;
     if (tidal && print_tidal(tidal, 1)) return 1;
+    if (jerk && print_jerk(jerk, 1)) return 1;
     if (closest && print_closest_pair(1)) return 1;
     if (pair_hist && print_pair_histogram(pair_hist, 1)) return 1;
     if (adaptive > 0.0 && print_min_timescale(adaptive, 1)) return 1;

@@ -2,7 +2,7 @@
  *
  * Plain C99: pointers, ints, floats.  No HIP, torch or C++ types cross this
  * boundary.  The library behind it is hand-written HIP for gfx950
- * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, point_sums.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp); there is
+ * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip, hermite.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, point_sums.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp, hermite.cpp); there is
  * no CPU fallback: every entry
  * point fails with NBODY_ERR_NO_DEVICE when no GPU is usable.
  *
@@ -474,6 +474,50 @@ int nbody_jerk(const float *points, const float *velocities, int m, const int *s
 int nbody_jerk_d(const double *points, const double *velocities, int m, const int *skip, double *accel, double *jerk);
 int nbody_jerk_rows(int first_row, int n_rows, float *accel, float *jerk);
 int nbody_jerk_rows_d(int first_row, int n_rows, double *accel, double *jerk);
+
+/* ---- fourth-order Hermite integrator: predict, evaluate, correct on the jerk pass (not in the reference) ----
+ * nbody_step is a kick followed by a drift: first order.  nbody_step_hermite(_d) advances the state on the device by nsteps steps of
+ * the Makino–Aarseth Hermite scheme in its PEC form with a shared dt: one jerk rows pass per step plus one at the start of the call.
+ * T is the context precision; every operation is rounded once, products are fused only where fma is written.
+ *   start of a call   (a0, j0) of every row at (r, v): exactly what nbody_jerk_rows returns (skip = self, arithmetic after NBODY_OPT_ARITH)
+ *   coefficients      once per step in T from h = dt:  h2 = h * h   c2 = h2 * (T)0.5   c3 = (h2 * h) / (T)6   hh = h * (T)0.5
+ *                     c12 = h2 / (T)12   (IEEE quotients)
+ *   predict           xp = fma(c3, j0, fma(c2, a0, fma(h, v0, x0)))      vp = fma(c2, j0, fma(h, a0, v0))        per component
+ *   evaluate          (a1, j1): the same rows pass over the predicted state — the predicted positions and velocities of all N bodies are
+ *                     the sources, row i's query is (xp_i, vp_i) and leaves itself out
+ *   correct           v1 = fma(c12, j0 - j1, fma(hh, a0 + a1, v0))      x1 = fma(c12, a0 - a1, fma(hh, v0 + v1, x0))   per component
+ *   carried           the position word's w bit for bit; the velocity word's fourth value stays as it is
+ *   next step         (a0, j0) := (a1, j1): the usual PEC form does not evaluate again at the corrected state
+ * A CALL IS STATELESS: it evaluates (a0, j0) afresh from the state it finds, so nothing has to be invalidated by uploads, nbody_step or
+ * the mailbox.  A call of k steps takes k + 1 passes; k calls of one step are k restarts, take 2k passes and in general give other bits
+ * than one call of k steps.  Both are defined by the statement above.
+ * The jerk pass's sums are ordered by N alone and the predictor and corrector are elementwise, so a Hermite step — unlike nbody_step, whose
+ * sums follow the launch configuration — gives the same bits on one device, on several, in an nbody_init_rank job of any size and under
+ * any source split (NBODY_JERK_SPLIT, NBODY_JERK_SCRATCH_MB) or force configuration.
+ * The call returns with the state written (it is synchronous); NBODY_INFO_STEPS_DONE counts Hermite steps as well.  Afterwards
+ * nbody_download, nbody_forces_rows, nbody_jerk_rows and nbody_energy see the corrected state of all bodies, and a later nbody_step
+ * gives what it gives on a fresh context uploaded with that state.  Arrival counters, the captured step graph and the force-kernel timer
+ * stay as they were.  In an nbody_init_rank job the call is collective (every rank calls with the same arguments) through the position
+ * and velocity gathers and the exchange of the ranks' best values only.
+ * A negative dt is legal (the scheme runs backwards).  NBODY_ERR_ARG for nsteps < 1 or a dt that is not finite; NBODY_ERR_NOT_INIT without
+ * a context; NBODY_ERR_STATE for the other precision's entry point or while the mailbox is served.
+ * nbody_min_aarseth (both precisions): runs the rows pass on the current state and, in binary64 from the T values, contraction off,
+ * takes per row a2 = (ax*ax + ay*ay) + az*az, j2 likewise and q_i = a2 / j2.  *q = the smallest q_i, *row = the lowest global row that
+ * reaches it; a NaN or +inf q_i (j2 = 0) is never chosen; with no candidate *q = +inf and *row = -1.  Either pointer may be NULL, not
+ * both (NBODY_ERR_ARG).  The reduction runs on the device in a fixed order; the devices' or ranks' bests are exchanged as
+ * nbody_min_timescale exchanges its own and folded in rank order with strict <.  A minimum is exact: the same values on every rank, for
+ * every device count and split.
+ * nbody_step_hermite_adaptive(_d): the shared Aarseth step, in the shape of nbody_step_adaptive: from t = 0, everything but the step in
+ * binary64 on the host.  After the opening evaluation and after every step, while t < t_end and fewer than max_steps steps were taken:
+ *     q = the minimum above over the (a, j) the integrator carries (no extra pass);  h = eta * sqrt(q);  h = min(h, dt_max);
+ *     h = max(h, dt_min);  if (t + h > t_end) h = t_end - t;  dt = h rounded once to T;  one Hermite step of dt;  t += (double)dt.
+ * Argument checks, *t_reached and *steps_taken (either may be NULL) as in nbody_step_adaptive: NBODY_ERR_ARG unless eta, t_end, dt_min
+ * and dt_max are finite, eta > 0, 0 < dt_min <= dt_max, t_end > 0 and max_steps >= 1; running into max_steps is no error. */
+int nbody_step_hermite(float dt, int nsteps);
+int nbody_step_hermite_d(double dt, int nsteps);
+int nbody_min_aarseth(double *q, int *row);
+int nbody_step_hermite_adaptive(float eta, float t_end, float dt_min, float dt_max, int max_steps, double *t_reached, int *steps_taken);
+int nbody_step_hermite_adaptive_d(double eta, double t_end, double dt_min, double dt_max, int max_steps, double *t_reached, int *steps_taken);
 
 /* ---- nearest neighbour, radius count, closest pair: how close the bodies on the device get (not in the reference) ----
  * A query is a point x with an optional excluded body.  In the context precision T, for every body j on the device:

@@ -46,6 +46,7 @@ SYMBOLS = [
     "nbody_timescale_rows", "nbody_timescale_rows_d", "nbody_min_timescale", "nbody_min_timescale_d",
     "nbody_step_adaptive", "nbody_step_adaptive_d",
     "nbody_jerk", "nbody_jerk_d", "nbody_jerk_rows", "nbody_jerk_rows_d",
+    "nbody_step_hermite", "nbody_step_hermite_d", "nbody_min_aarseth", "nbody_step_hermite_adaptive", "nbody_step_hermite_adaptive_d",
 ]
 
 
@@ -118,6 +119,8 @@ def load():
         "nbody_step_adaptive": [f, f, f, f, i, dp, C.POINTER(i)], "nbody_step_adaptive_d": [d, d, d, d, i, dp, C.POINTER(i)],
         "nbody_jerk": [fp, fp, i, C.POINTER(i), fp, fp], "nbody_jerk_d": [dp, dp, i, C.POINTER(i), dp, dp],
         "nbody_jerk_rows": [i, i, fp, fp], "nbody_jerk_rows_d": [i, i, dp, dp],
+        "nbody_step_hermite": [f, i], "nbody_step_hermite_d": [d, i], "nbody_min_aarseth": [dp, C.POINTER(i)],
+        "nbody_step_hermite_adaptive": [f, f, f, f, i, dp, C.POINTER(i)], "nbody_step_hermite_adaptive_d": [d, d, d, d, i, dp, C.POINTER(i)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -172,8 +172,8 @@ int alloc_local(Local& L) {
   NBC(L.vel.ensure((L.n_local + pad) * wb));
   NBC(L.force.ensure((L.n_local + pad) * wb));
   NBC(L.tickets.ensure(ticket_words(L.n_local) * sizeof(unsigned), true));
-  HIPC(hipMemset(L.vel, 0, (L.n_local + pad) * wb));
-  HIPC(hipMemset(L.force, 0, (L.n_local + pad) * wb));
+  NBC(DevMem::zero_now(L.vel, (L.n_local + pad) * wb));
+  NBC(DevMem::zero_now(L.force, (L.n_local + pad) * wb));
   HIPC(hipEventCreateWithFlags(L.ev_own_ready.put(), hipEventDisableTiming));
   HIPC(hipEventCreateWithFlags(L.ev_comm_go.put(), hipEventDisableTiming));
   for (int s = 0; s < g.nranks && s < kMaxRanks; ++s) HIPC(hipEventCreateWithFlags(L.ev_gather[s].put(), hipEventDisableTiming));

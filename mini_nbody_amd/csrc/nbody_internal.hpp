@@ -23,7 +23,10 @@
 //   hist.cpp      nbody_radial_counts_rows(_d), nbody_radial_counts(_d), nbody_pair_histogram(_d): bodies per shell of distance, pair counts
 //   timescale.hip the pair time-scale pass's kernels (timescale_args.hpp: its argument block and launch functions)
 //   timescale.cpp nbody_timescale_rows(_d), nbody_min_timescale(_d), nbody_step_adaptive(_d): pair crossing times, the shared adaptive step
-// Only kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip and timescale.hip are device code (a minute of hipcc, as one code object through device.hip);
+//   hermite.hip   the Hermite step's predictor, corrector and best-row reduction (hermite_args.hpp: their argument block and launch functions)
+//   hermite.cpp   nbody_step_hermite(_d), nbody_min_aarseth, nbody_step_hermite_adaptive(_d): the fourth-order Hermite step on the jerk rows
+//                 pass of point_sums.cpp, the smallest |a|^2 / |j|^2 of the system and the shared Aarseth time step
+// Only kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip and hermite.hip are device code (a minute of hipcc, as one code object through device.hip);
 // the others are host C++ (seconds).  gfx950 only, no CPU fallback anywhere.
 // Ownership: every stream, event, device and pinned allocation the context uses lives in an owning handle (Stream, Event, DevMem, Pinned,
 // below) that is a member of Global or of one of its Locals; nbody_shutdown() releases them all, and nothing does at process exit (see `g`).
@@ -101,7 +104,15 @@ struct DevMem : Owned<void*, hipFree> {
     reset(); bytes = 0;
     HIPC(hipMalloc(&h, need));
     bytes = need;
-    if (zero) HIPC(hipMemset(h, 0, need));
+    if (zero) NBC(zero_now(h, need));
+    return NBODY_OK;
+  }
+  // hipMemset of device memory does not wait for the fill, which runs on the null stream — and the context's streams are
+  // hipStreamNonBlocking, so nothing they do later is ordered behind it: the zeros of nbody_init could land on an upload's copy.
+  // The fill is drained before anything else may touch the buffer.
+  static int zero_now(void* p, size_t bytes) {
+    HIPC(hipMemset(p, 0, bytes));
+    HIPC(hipStreamSynchronize(nullptr));
     return NBODY_OK;
   }
 };
@@ -149,6 +160,9 @@ struct Local {
   DevMem ts_tau2, ts_idx, ts_d2;       // ... the rows' outputs (tau2 and d2min in the context precision) ...
   DevMem ts_best;                      // ... and the ranks' bests, one BestScale at word `rank` (all P after an all-gather)
   DevMem fo_label, fo_rows, fo_min;    // fof pass (fof.cpp): the N labels of a round, this local's range of the active rows and their m_i
+  DevMem he_pos0, he_vel0;             // Hermite step (hermite.cpp): the own rows' (x0, v0) of the step under way, n_local words each ...
+  DevMem he_acc[2], he_jerk[2];        // ... their acceleration and jerk words at the start of the step and at the predicted state ...
+  DevMem he_best;                      // ... and the ranks' smallest |a|^2 / |j|^2, one BestRatio at word `rank` (all P after an all-gather)
   int cur = 0;
   bool all_present = true;             // pos[cur] holds every slice
   Event ev_own_ready;                  // the rank's slice of pos[cur] is written

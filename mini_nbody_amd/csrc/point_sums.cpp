@@ -8,7 +8,8 @@
 // evaluates the points IT was given (its own rows) on its own device; the call is collective only through complete_positions() and
 // gather_velocities().
 // A call reads pos[cur] (and vel) and writes only the Local's q_* buffers (and ts_vel, full_scratch): positions, velocities, arrival
-// counters, partial forces, the captured step graph and the force-kernel timer stay as they were.  Nothing outside this file refers to it.
+// counters, partial forces, the captured step graph and the force-kernel timer stay as they were.  One internal entry
+// (jerk_own_rows_on_device, query_pass.hpp) serves the Hermite step of hermite.cpp.
 #include "query_pass.hpp"
 #include "point_sums_args.hpp"
 
@@ -23,14 +24,15 @@ namespace {
 struct Queries { const void* points; const void* velocities; const int* skip; };
 
 // queries [r.first, r.first + r.cnt) of the call on local L — points of the call (uploaded) or rows of L's slice — with the outputs
-// asked for left in q_out for the copy back
-int launch_point_sums(Local& L, const PointPass& pass, const Queries& q, const Range& r, void* const (&out)[2]) {
+// asked for left in q_out for the copy back, or (dev) in the device buffers the caller names, which it has sized
+int launch_point_sums(Local& L, const PointPass& pass, const Queries& q, const Range& r, void* const (&out)[2], bool dev = false) {
   HIPC(hipSetDevice(L.device));
   const size_t wb = word_bytes(), es = elem_bytes();
   const size_t ob[2] = {pass.out_values[0] * es, pass.out_values[1] * es};   // bytes per point of each output
   if (q.points) NBC(upload_queries(L, q.points, q.skip, r.first, r.cnt, q.velocities));
   for (int i = 0; i < 2; ++i)
-    if (out[i]) NBC(L.q_out[i].ensure((size_t)r.cnt * ob[i]));
+    if (out[i] && !dev) NBC(L.q_out[i].ensure((size_t)r.cnt * ob[i]));
+  char* const base[2] = {dev ? (char*)out[0] : L.q_out[0].as<char>(), dev ? (char*)out[1] : L.q_out[1].as<char>()};
   const int n_blocks = source_blocks();
   const SplitPlan plan = block_split(pass.split_env, pass.scratch_mb_env, r.cnt, n_blocks, pass.sums, es);
   if (plan.chunks > 1) NBC(L.q_scratch.ensure(point_sums_scratch_bytes((size_t)plan.batch, (size_t)n_blocks, (size_t)pass.sums, es)));
@@ -46,7 +48,7 @@ int launch_point_sums(Local& L, const PointPass& pass, const Queries& q, const R
     } else {
       a.first = L.first + r.first + b0;
     }
-    for (int i = 0; i < 2; ++i) a.out[i] = out[i] ? L.q_out[i].as<char>() + (size_t)b0 * ob[i] : nullptr;
+    for (int i = 0; i < 2; ++i) a.out[i] = out[i] ? base[i] + (size_t)b0 * ob[i] : nullptr;
     a.scratch = plan.chunks > 1 ? L.q_scratch.as<void>() : nullptr;
     a.n_src = g.n;
     a.m = m;
@@ -91,6 +93,15 @@ int point_sums_rows_impl(const PointPass& pass, int first_row, int n_rows, void*
 }
 
 }  // namespace
+
+// The jerk rows pass over L's own rows into accel and jerk, n_local words each in L's device memory: the split and the batches of
+// launch_point_sums, no copy back (hermite.cpp).  The caller has made pos[cur] complete and gathered the velocities; the launches are
+// left on L's compute stream.
+int jerk_own_rows_on_device(Local& L, void* accel, void* jerk) {
+  if (L.n_local <= 0) return NBODY_OK;
+  void* const out[2] = {accel, jerk};
+  return launch_point_sums(L, kJerkPass, {nullptr, nullptr, nullptr}, {0, L.n_local, 0}, out, true);
+}
 
 }  // namespace nbi
 

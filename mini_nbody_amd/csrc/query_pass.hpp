@@ -1,4 +1,4 @@
-// query_pass.hpp — the host side that the diagnostic passes share (energy.cpp, point_sums.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp; host C++ only): a call brings
+// query_pass.hpp — the host side that the diagnostic passes share (energy.cpp, point_sums.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp, and hermite.cpp for its gathers; host C++ only): a call brings
 // rows or points, every local takes a contiguous range of them, launches on its compute stream — in batches over a split of the
 // sources when the pass asks for one — and the results are copied back once the stream has drained.  A pass says what differs: which
 // range a local gets, what to launch, which outputs go where, and which of the two split rules (a SplitPlan) it follows: chunk_split,
@@ -205,5 +205,9 @@ inline int gather_rank_words(DevMem Local::*buf, void* host_words, int bytes_per
   }
   return NBODY_OK;
 }
+
+// ---- point_sums.cpp ----
+// the jerk rows pass over L's own rows into device buffers the caller names (n_local words each), no copy back: see there
+int jerk_own_rows_on_device(Local& L, void* accel, void* jerk);
 
 }  // namespace nbi

@@ -425,6 +425,30 @@ class NBody:
         L.check(fn(eta, t_end, dt_min, dt_max, int(max_steps), C.byref(t), C.byref(steps)))
         return t.value, steps.value
 
+    def step_hermite(self, dt, nsteps=1):
+        """nsteps fourth-order Hermite steps of a shared dt on the state on the device (nbody_step_hermite): predict, one jerk rows
+        pass over the predicted state, correct.  A call evaluates (a, j) afresh at its start — k + 1 passes for k steps — so k calls
+        of one step are k restarts and in general give other bits than one call of k steps.  Same bits on any number of devices or
+        ranks.  Synchronous; collective in a multi-rank job."""
+        L.check((self.lib.nbody_step_hermite_d if self.fp64 else self.lib.nbody_step_hermite)(float(dt), int(nsteps)))
+
+    def min_aarseth(self):
+        """(q, row) of the whole system (nbody_min_aarseth): the smallest |a|^2 / |j|^2 over the rows of jerk(), in binary64, and
+        the lowest global row that reaches it; (inf, -1) when no row has a finite one.  eta * sqrt(q) is the shared Aarseth step.
+        Collective in a multi-rank job; every rank gets the same values."""
+        q, row = C.c_double(), C.c_int()
+        L.check(self.lib.nbody_min_aarseth(C.byref(q), C.byref(row)))
+        return q.value, row.value
+
+    def step_hermite_adaptive(self, t_end, eta, dt_min, dt_max, max_steps=1000000):
+        """(t_reached, steps): Hermite steps of a shared dt = eta * sqrt(min_i |a_i|^2 / |j_i|^2) clamped to [dt_min, dt_max] from
+        t = 0 until t_end or max_steps (nbody_step_hermite_adaptive); the minimum comes from the (a, j) the integrator carries, no
+        extra pass.  Collective in a multi-rank job."""
+        t, steps = C.c_double(0.0), C.c_int(0)
+        fn = self.lib.nbody_step_hermite_adaptive_d if self.fp64 else self.lib.nbody_step_hermite_adaptive
+        L.check(fn(eta, t_end, dt_min, dt_max, int(max_steps), C.byref(t), C.byref(steps)))
+        return t.value, steps.value
+
     def comm_selftest(self):
         """Push a patterned array through the RCCL calls of the multi-GPU path (all-gather + one ring step); returns
         the bytes this rank received.  Needs the communicator of NBody(..., rank=, nranks=, uid=)."""

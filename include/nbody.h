@@ -2,7 +2,7 @@
  *
  * Plain C99: pointers, ints, floats.  No HIP, torch or C++ types cross this
  * boundary.  The library behind it is hand-written HIP for gfx950
- * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip, hermite.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, point_sums.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp, hermite.cpp); there is
+ * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip, hermite.hip, hermite_block.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, point_sums.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp, hermite.cpp, hermite_block.cpp); there is
  * no CPU fallback: every entry
  * point fails with NBODY_ERR_NO_DEVICE when no GPU is usable.
  *
@@ -518,6 +518,37 @@ int nbody_step_hermite_d(double dt, int nsteps);
 int nbody_min_aarseth(double *q, int *row);
 int nbody_step_hermite_adaptive(float eta, float t_end, float dt_min, float dt_max, int max_steps, double *t_reached, int *steps_taken);
 int nbody_step_hermite_adaptive_d(double eta, double t_end, double dt_min, double dt_max, int max_steps, double *t_reached, int *steps_taken);
+
+/* ---- individual block time steps: the Hermite integrator with a step per body, quantised to powers of two (not in the reference) ----
+ * nbody_step_hermite_adaptive gives all N bodies the step of the worst pair.  nbody_step_hermite_block(_d) advances the state on the
+ * device by nblocks * dt_max with a step per body: level k has the step dt_max * 2^-k, k = 0 .. levels - 1, and only the bodies that are
+ * due are evaluated, against the predicted state of all the others (NBODY6, phiGRAPE, Sapporo).  T is the context precision.
+ *   time          integer ticks (64-bit) of unit = dt_max * 2^-(levels - 1), computed in T (exact: it is checked normal).  Row i carries a
+ *                 tick t0_i, a level k_i and its base (x0, v0, a0, j0) at t0_i; its step is s_i = 2^(levels - 1 - k_i) ticks.
+ *   wanted level  of a row from its (a, j), in binary64, contraction off: q = a2 / j2 as nbody_min_aarseth forms it, e = eta2 * q with
+ *                 eta2 = eta * eta from the T value of eta, lim[k] = (d * 2^-k)^2 with d = (double)dt_max; want = the smallest k with
+ *                 lim[k] <= e, levels - 1 if there is none, and 0 when q is not < +inf (NaN or +inf: a lone body, a row with zero jerk).
+ *                 No square root; the only division is q's.
+ *   start         base := the state; (a0, j0) := what nbody_jerk_rows returns; t0 := 0; k := want.
+ *   a sub-step    tau := the smallest t0_i + s_i over all rows of all ranks.  Every row is predicted from its base to tau by the
+ *                 predictor above with h_i = (T)(tau - t0_i) * unit (the integer is below 2^23 + 1: one rounding) and the coefficients
+ *                 of h_i.  The ACTIVE rows, those with t0_i + s_i = tau, are evaluated by the jerk at points: the query is the row's
+ *                 predicted (x, v) with skip = its own index, the sources the predicted state of all N bodies.  They alone are
+ *                 corrected by the corrector above with their own h_i (= s_i * unit): base := (x1, v1, a1, j1), t0 := tau; then with
+ *                 w = want(a1, j1): w > k: k := w;  w < k and tau mod 2^(levels - k) == 0: k := k - 1 (one doubling, onto an aligned
+ *                 time only);  otherwise k stays.
+ *   end           when tau = nblocks * 2^(levels - 1).  Every t0_i is a multiple of s_i, so no row steps over a multiple of
+ *                 2^(levels - 1) and at each such multiple every row is active: the call ends with every body at the same time.
+ * With levels = 1 the call is nbody_step_hermite(dt_max, nblocks) bit for bit, in every arithmetic.  Like it the call is stateless
+ * ((a0, j0) afresh, levels assigned anew), synchronous, gives the same bits however the work is laid out, leaves alone what
+ * nbody_step_hermite leaves alone and is collective in an nbody_init_rank job (a rank without an active row takes part in the gathers).
+ * *substeps = the number of distinct times visited, *row_evals = the sum of the active counts over them (the pass at the start of the
+ * call is in neither); either may be NULL.  NBODY_INFO_STEPS_DONE advances by the number of sub-steps.
+ * NBODY_ERR_ARG, the state untouched: eta or dt_max not finite or <= 0, levels < 1 or > 24, nblocks < 1, dt_max * 2^-(levels - 1) below
+ * the smallest normal of T.  NBODY_ERR_NOT_INIT without a context; NBODY_ERR_STATE for the other precision's entry point or while the
+ * mailbox is served. */
+int nbody_step_hermite_block(float eta, float dt_max, int levels, int nblocks, long long *substeps, long long *row_evals);
+int nbody_step_hermite_block_d(double eta, double dt_max, int levels, int nblocks, long long *substeps, long long *row_evals);
 
 /* ---- nearest neighbour, radius count, closest pair: how close the bodies on the device get (not in the reference) ----
  * A query is a point x with an optional excluded body.  In the context precision T, for every body j on the device:

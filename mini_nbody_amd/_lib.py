@@ -47,6 +47,7 @@ SYMBOLS = [
     "nbody_step_adaptive", "nbody_step_adaptive_d",
     "nbody_jerk", "nbody_jerk_d", "nbody_jerk_rows", "nbody_jerk_rows_d",
     "nbody_step_hermite", "nbody_step_hermite_d", "nbody_min_aarseth", "nbody_step_hermite_adaptive", "nbody_step_hermite_adaptive_d",
+    "nbody_step_hermite_block", "nbody_step_hermite_block_d",
 ]
 
 
@@ -121,6 +122,8 @@ def load():
         "nbody_jerk_rows": [i, i, fp, fp], "nbody_jerk_rows_d": [i, i, dp, dp],
         "nbody_step_hermite": [f, i], "nbody_step_hermite_d": [d, i], "nbody_min_aarseth": [dp, C.POINTER(i)],
         "nbody_step_hermite_adaptive": [f, f, f, f, i, dp, C.POINTER(i)], "nbody_step_hermite_adaptive_d": [d, d, d, d, i, dp, C.POINTER(i)],
+        "nbody_step_hermite_block": [f, f, i, i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
+        "nbody_step_hermite_block_d": [d, d, i, i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

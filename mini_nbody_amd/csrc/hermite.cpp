@@ -8,8 +8,9 @@
 // and the jerk pass reads it where it always reads; the corrector then writes the own slice again.  cur never changes, so the captured
 // step graph stays valid; the other slices of pos[cur] are marked not present (all_present) and are brought by whoever needs them
 // next, as after integrate().  No force kernel is launched: arrival counters, partial forces and the force-kernel timer stay as they
-// were.  A call keeps nothing between calls: (a0, j0) is evaluated afresh at its start.  Nothing outside this file refers to it.
-#include "query_pass.hpp"
+// were.  A call keeps nothing between calls: (a0, j0) is evaluated afresh at its start.  hermite_block.cpp builds on the opening, the
+// gathers and the mark of a rewritten slice (hermite_host.hpp); nothing else outside this file refers to it.
+#include "hermite_host.hpp"
 #include "hermite_args.hpp"
 
 #include <cmath>
@@ -47,10 +48,7 @@ int ensure_buffers() {
 // its own jerk pass only.  The drain puts every corrector (and the next predictor) behind every copy; complete_positions() ends in
 // the same drain for the positions, and the gather of several processes synchronises by itself.
 int evaluate(int k) {
-  if (g.nranks > 1) NBC(sync_all());
-  NBC(complete_positions());
-  NBC(gather_velocities());
-  if (g.nranks > 1 && !g.multiprocess) NBC(sync_all());
+  NBC(hermite_gather_state());
   for (int l = 0; l < g.nlocal; ++l) NBC(jerk_own_rows_on_device(g.loc[l], g.loc[l].he_acc[k], g.loc[l].he_jerk[k]));
   return NBODY_OK;
 }
@@ -72,13 +70,6 @@ HermiteArgs args_of(Local& L, int k, double h) {
   return a;
 }
 
-// the own slice of pos[cur] has been rewritten on L's compute stream: what the next gather waits for
-int own_slice_written(Local& L) {
-  HIPC(hipEventRecord(L.ev_own_ready, L.compute));
-  L.all_present = (g.nranks == 1);
-  return NBODY_OK;
-}
-
 // one step of h (a value of the context precision) from (a0, j0) in he_*[*k]; leaves (a1, j1) in he_*[*k ^ 1] and flips *k
 int one_step(double h, int* k) {
   for (int l = 0; l < g.nlocal; ++l) {
@@ -86,7 +77,7 @@ int one_step(double h, int* k) {
     if (L.n_local <= 0) continue;
     HIPC(hipSetDevice(L.device));
     HIPC((hipError_t)nbl::launch_hermite_predict_kernel(g.fp64, L.compute, args_of(L, *k, h)));
-    NBC(own_slice_written(L));
+    NBC(hermite_own_slice_written(L));
   }
   NBC(evaluate(*k ^ 1));
   for (int l = 0; l < g.nlocal; ++l) {
@@ -97,7 +88,7 @@ int one_step(double h, int* k) {
     a.a1 = L.he_acc[*k ^ 1];
     a.j1 = L.he_jerk[*k ^ 1];
     HIPC((hipError_t)nbl::launch_hermite_correct_kernel(g.fp64, L.compute, a));
-    NBC(own_slice_written(L));
+    NBC(hermite_own_slice_written(L));
   }
   *k ^= 1;
   g.steps_done++;
@@ -125,17 +116,10 @@ int best_of(int k, double* q, int* row) {
   return NBODY_OK;
 }
 
-// what every call starts with: the configuration, the buffers, (a0, j0) of the state it finds into he_*[0]
-int open_call() {
-  NBC(reconfigure());
-  NBC(ensure_buffers());
-  return evaluate(0);
-}
-
 int step_hermite_impl(double dt, int nsteps) {
   if (!g.init) return NBODY_ERR_NOT_INIT;
   if (nsteps < 1 || !std::isfinite(dt)) return NBODY_ERR_ARG;
-  NBC(open_call());
+  NBC(hermite_open_call());
   int k = 0;
   for (int s = 0; s < nsteps; ++s) NBC(one_step(dt, &k));
   return sync_all();
@@ -144,7 +128,7 @@ int step_hermite_impl(double dt, int nsteps) {
 int min_aarseth_impl(double* q, int* row) {
   if (!g.init) return NBODY_ERR_NOT_INIT;
   if (!q && !row) return NBODY_ERR_ARG;
-  NBC(open_call());
+  NBC(hermite_open_call());
   double bq = 0.0;
   int br = -1;
   NBC(best_of(0, &bq, &br));
@@ -159,7 +143,7 @@ int step_hermite_adaptive_impl(double eta, double t_end, double dt_min, double d
   if (!g.init) return NBODY_ERR_NOT_INIT;
   if (!std::isfinite(eta) || !std::isfinite(t_end) || !std::isfinite(dt_min) || !std::isfinite(dt_max)) return NBODY_ERR_ARG;
   if (eta <= 0.0 || dt_min <= 0.0 || dt_max < dt_min || t_end <= 0.0 || max_steps < 1) return NBODY_ERR_ARG;
-  NBC(open_call());
+  NBC(hermite_open_call());
   double t = 0.0;
   int steps = 0, k = 0;
   while (t < t_end && steps < max_steps) {
@@ -181,6 +165,27 @@ int step_hermite_adaptive_impl(double eta, double t_end, double dt_min, double d
 }
 
 }  // namespace
+
+// ---- shared with hermite_block.cpp (hermite_host.hpp) ----
+int hermite_gather_state() {
+  if (g.nranks > 1) NBC(sync_all());
+  NBC(complete_positions());
+  NBC(gather_velocities());
+  if (g.nranks > 1 && !g.multiprocess) NBC(sync_all());
+  return NBODY_OK;
+}
+
+int hermite_own_slice_written(Local& L) {
+  HIPC(hipEventRecord(L.ev_own_ready, L.compute));
+  L.all_present = (g.nranks == 1);
+  return NBODY_OK;
+}
+
+int hermite_open_call() {
+  NBC(reconfigure());
+  NBC(ensure_buffers());
+  return evaluate(0);
+}
 
 }  // namespace nbi
 

@@ -60,16 +60,7 @@ __global__ void __launch_bounds__(kLanes) hermite_correct(const HermiteArgs a) {
   ((V4*)a.vel)[p] = v1;
 }
 
-// q of a row in binary64 from the T values: a2 = (ax ax + ay ay) + az az, j2 likewise, q = a2 / j2 (0 / 0 = NaN, a2 / 0 = +inf)
-template <typename V4>
-__device__ __forceinline__ double ratio_of(const V4 a, const V4 j) {
-  const double ax = (double)a.x, ay = (double)a.y, az = (double)a.z, jx = (double)j.x, jy = (double)j.y, jz = (double)j.z;
-  const double a2 = (ax * ax + ay * ay) + az * az;
-  const double j2 = (jx * jx + jy * jy) + jz * jz;
-  return a2 / j2;
-}
-
-// the best of a device's rows, in timescale_best's two-level form: lane t takes rows t, t + 256, ... ascending with strict < from +inf
+// the best of a device's rows, in timescale_best's two-level form: lane t takes rows t, t + 256, ... ascending with strict < from +inf (q = ratio_of, hermite_args.hpp)
 // (a NaN or +inf q is below nothing), lane 0 then the 256 lanes' bests by (q, row).  One workgroup, no atomics.
 template <typename V4>
 __global__ void __launch_bounds__(kLanes) hermite_best(const V4* accel, const V4* jerk, int rows, int first, BestRatio* out) {

@@ -15,11 +15,13 @@
 
 namespace nbh {
 
-// the coefficients of a step of h, in T: h2 = h * h, c2 = h2 * 0.5, c3 = (h2 * h) / 6, hh = h * 0.5, c12 = h2 / 12 (IEEE quotients)
+// the coefficients of a step of h, in T: h2 = h * h, c2 = h2 * 0.5, c3 = (h2 * h) / 6, hh = h * 0.5, c12 = h2 / 12 (IEEE quotients).
+// Host and device: the shared step forms them once on the host, the block step (hermite_block.hip) per row on the device, where the
+// plain / of a file compiled with contraction off is the correctly rounded quotient too (timescale.hip relies on the same).
 template <typename T>
 struct Coefficients { T h, c2, c3, hh, c12; };
 template <typename T>
-inline Coefficients<T> coefficients_of(T h) {
+__host__ __device__ inline Coefficients<T> coefficients_of(T h) {
   const T h2 = h * h;   // (products and quotients only: nothing here can be contracted)
   return {h, h2 * (T)0.5, (h2 * h) / (T)6, h * (T)0.5, h2 / (T)12};
 }
@@ -41,6 +43,15 @@ struct HermiteArgs {
 // what the two launches refuse
 inline bool bad_hermite_predict(const HermiteArgs& a) { return a.rows <= 0 || !a.pos || !a.vel || !a.pos0 || !a.vel0 || !a.a0 || !a.j0; }
 inline bool bad_hermite_correct(const HermiteArgs& a) { return bad_hermite_predict(a) || !a.a1 || !a.j1; }
+
+// q of a row in binary64 from the T values: a2 = (ax ax + ay ay) + az az, j2 likewise, q = a2 / j2 (0 / 0 = NaN, a2 / 0 = +inf)
+template <typename V4>
+__host__ __device__ inline double ratio_of(const V4 a, const V4 j) {
+  const double ax = (double)a.x, ay = (double)a.y, az = (double)a.z, jx = (double)j.x, jy = (double)j.y, jz = (double)j.z;
+  const double a2 = (ax * ax + ay * ay) + az * az;
+  const double j2 = (jx * jx + jy * jy) + jz * jz;
+  return a2 / j2;
+}
 
 // what hermite_best leaves per device or rank: the smallest q = a2 / j2 of its rows (binary64, from the T values) with the lowest global
 // row that reaches it; row < 0: no candidate, q = +inf

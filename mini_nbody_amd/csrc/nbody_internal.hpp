@@ -26,7 +26,11 @@
 //   hermite.hip   the Hermite step's predictor, corrector and best-row reduction (hermite_args.hpp: their argument block and launch functions)
 //   hermite.cpp   nbody_step_hermite(_d), nbody_min_aarseth, nbody_step_hermite_adaptive(_d): the fourth-order Hermite step on the jerk rows
 //                 pass of point_sums.cpp, the smallest |a|^2 / |j|^2 of the system and the shared Aarseth time step
-// Only kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip and hermite.hip are device code (a minute of hipcc, as one code object through device.hip);
+//                 (hermite_host.hpp: what it shares with hermite_block.cpp)
+//   hermite_block.hip the block step's scheduler kernels: init, predict-to-tau, next-time, compact-and-gather, correct-and-assign
+//                 (hermite_block_args.hpp: their argument block, the level rules and launch functions)
+//   hermite_block.cpp nbody_step_hermite_block(_d): individual block time steps, the active rows evaluated by the jerk points pass
+// Only kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip, hermite.hip and hermite_block.hip are device code (a minute of hipcc, as one code object through device.hip);
 // the others are host C++ (seconds).  gfx950 only, no CPU fallback anywhere.
 // Ownership: every stream, event, device and pinned allocation the context uses lives in an owning handle (Stream, Event, DevMem, Pinned,
 // below) that is a member of Global or of one of its Locals; nbody_shutdown() releases them all, and nothing does at process exit (see `g`).
@@ -163,6 +167,9 @@ struct Local {
   DevMem he_pos0, he_vel0;             // Hermite step (hermite.cpp): the own rows' (x0, v0) of the step under way, n_local words each ...
   DevMem he_acc[2], he_jerk[2];        // ... their acceleration and jerk words at the start of the step and at the predicted state ...
   DevMem he_best;                      // ... and the ranks' smallest |a|^2 / |j|^2, one BestRatio at word `rank` (all P after an all-gather)
+  DevMem hb_tick, hb_level;            // block time steps (hermite_block.cpp): the own rows' ticks (64-bit) and levels; their base is he_pos0, he_vel0, he_acc[0], he_jerk[0] ...
+  DevMem hb_counts, hb_active;         // ... the active rows of a sub-step per tile of 256 rows and their ascending list (their queries go to q_points, q_vel, q_skip) ...
+  DevMem hb_next;                      // ... and the ranks' next times, one NextTime at word `rank` (all P after an all-gather)
   int cur = 0;
   bool all_present = true;             // pos[cur] holds every slice
   Event ev_own_ready;                  // the rank's slice of pos[cur] is written

@@ -8,8 +8,8 @@
 // evaluates the points IT was given (its own rows) on its own device; the call is collective only through complete_positions() and
 // gather_velocities().
 // A call reads pos[cur] (and vel) and writes only the Local's q_* buffers (and ts_vel, full_scratch): positions, velocities, arrival
-// counters, partial forces, the captured step graph and the force-kernel timer stay as they were.  One internal entry
-// (jerk_own_rows_on_device, query_pass.hpp) serves the Hermite step of hermite.cpp.
+// counters, partial forces, the captured step graph and the force-kernel timer stay as they were.  Two internal entries (query_pass.hpp)
+// serve the Hermite integrator: jerk_own_rows_on_device the step of hermite.cpp, jerk_points_on_device the block step of hermite_block.cpp.
 #include "query_pass.hpp"
 #include "point_sums_args.hpp"
 
@@ -20,8 +20,9 @@ namespace nbi {
 namespace {
 
 // The queries of a call.  Points: the caller's arrays in host memory (velocities: a pass with velocities only).  Rows (points ==
-// null): the window's bodies themselves, each leaving itself out.
-struct Queries { const void* points; const void* velocities; const int* skip; };
+// null): the window's bodies themselves, each leaving itself out.  on_device: the three are the local's own q_points, q_vel and q_skip,
+// which a kernel has filled: nothing is uploaded.
+struct Queries { const void* points; const void* velocities; const int* skip; bool on_device = false; };
 
 // queries [r.first, r.first + r.cnt) of the call on local L — points of the call (uploaded) or rows of L's slice — with the outputs
 // asked for left in q_out for the copy back, or (dev) in the device buffers the caller names, which it has sized
@@ -29,7 +30,7 @@ int launch_point_sums(Local& L, const PointPass& pass, const Queries& q, const R
   HIPC(hipSetDevice(L.device));
   const size_t wb = word_bytes(), es = elem_bytes();
   const size_t ob[2] = {pass.out_values[0] * es, pass.out_values[1] * es};   // bytes per point of each output
-  if (q.points) NBC(upload_queries(L, q.points, q.skip, r.first, r.cnt, q.velocities));
+  if (q.points && !q.on_device) NBC(upload_queries(L, q.points, q.skip, r.first, r.cnt, q.velocities));
   for (int i = 0; i < 2; ++i)
     if (out[i] && !dev) NBC(L.q_out[i].ensure((size_t)r.cnt * ob[i]));
   char* const base[2] = {dev ? (char*)out[0] : L.q_out[0].as<char>(), dev ? (char*)out[1] : L.q_out[1].as<char>()};
@@ -101,6 +102,16 @@ int jerk_own_rows_on_device(Local& L, void* accel, void* jerk) {
   if (L.n_local <= 0) return NBODY_OK;
   void* const out[2] = {accel, jerk};
   return launch_point_sums(L, kJerkPass, {nullptr, nullptr, nullptr}, {0, L.n_local, 0}, out, true);
+}
+
+// The jerk points pass over m queries a kernel has left in L's q_points, q_vel and q_skip (the block step of hermite_block.cpp: the
+// active rows' predicted words and global indices) into accel and jerk, m words each in L's device memory: the same split and batches,
+// nothing uploaded, no copy back.  The caller has made pos[cur] complete and gathered the velocities; the launches are left on L's
+// compute stream.
+int jerk_points_on_device(Local& L, int m, void* accel, void* jerk) {
+  if (m <= 0) return NBODY_OK;
+  void* const out[2] = {accel, jerk};
+  return launch_point_sums(L, kJerkPass, {L.q_points.as<void>(), L.q_vel.as<void>(), L.q_skip.as<int>(), true}, {0, m, 0}, out, true);
 }
 
 }  // namespace nbi

@@ -209,5 +209,7 @@ inline int gather_rank_words(DevMem Local::*buf, void* host_words, int bytes_per
 // ---- point_sums.cpp ----
 // the jerk rows pass over L's own rows into device buffers the caller names (n_local words each), no copy back: see there
 int jerk_own_rows_on_device(Local& L, void* accel, void* jerk);
+// the jerk points pass over m queries already in L's q_points, q_vel and q_skip, into device buffers likewise (m words each): see there
+int jerk_points_on_device(Local& L, int m, void* accel, void* jerk);
 
 }  // namespace nbi

@@ -449,6 +449,17 @@ class NBody:
         L.check(fn(eta, t_end, dt_min, dt_max, int(max_steps), C.byref(t), C.byref(steps)))
         return t.value, steps.value
 
+    def step_hermite_block(self, dt_max, nblocks=1, eta=0.02, levels=8):
+        """(substeps, row_evals): the state advanced by nblocks * dt_max with individual block time steps (nbody_step_hermite_block):
+        level k has the step dt_max * 2^-k, k < levels; a sub-step predicts every body to the system's next time and evaluates and
+        corrects only the bodies that are due, which then take the level eta^2 |a|^2 / |j|^2 asks for.  substeps: the distinct times
+        visited; row_evals: the sum of the active counts.  levels = 1 is step_hermite(dt_max, nblocks) bit for bit.  Stateless,
+        synchronous; same bits on any number of devices or ranks; collective in a multi-rank job."""
+        steps, evals = C.c_longlong(0), C.c_longlong(0)
+        fn = self.lib.nbody_step_hermite_block_d if self.fp64 else self.lib.nbody_step_hermite_block
+        L.check(fn(float(eta), float(dt_max), int(levels), int(nblocks), C.byref(steps), C.byref(evals)))
+        return steps.value, evals.value
+
     def comm_selftest(self):
         """Push a patterned array through the RCCL calls of the multi-GPU path (all-gather + one ring step); returns
         the bytes this rank received.  Needs the communicator of NBody(..., rank=, nranks=, uid=)."""

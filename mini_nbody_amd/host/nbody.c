@@ -8,11 +8,14 @@
  *
  * usage: nbody [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K]
  *              [--sum seq|blocked] [--block K] [--one-launch | --two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16]
- *              [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--hermite]
+ *              [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--hermite] [--hermite-block LEVELS]
  * --hermite: the device loop's iterations are fourth-order Hermite steps (nbody_step_hermite) instead of kick-drift steps: one warm-up
  * call of one step, the initial state uploaded again, then ONE timed call of all `iters` steps (a call opens with a jerk pass of its own,
  * so two calls would not be one run: include/nbody.h, "a call is stateless"); the time per step is that call's over iters.  Refused
  * together with --host-loop.
+ * --hermite-block LEVELS (1 <= LEVELS <= 24): as --hermite, but an iteration is one block of dt_max = 0.01 with individual block time
+ * steps on LEVELS levels and eta = 0.02 (nbody_step_hermite_block); one more line, "hermite block: LEVELS levels, S sub-steps, R row
+ * evaluations (F of sub-steps x N)", gives the timed call's counters.  LEVELS = 1 is --hermite bit for bit.
  * --energy: E = T + U, T and U of the state on the device (nbody_energy) before the first iteration and after the last, and the
  * relative drift, outside the timed region.
  * --field M: after the last iteration, acceleration and potential of the state on the device (nbody_field) at M points — the position
@@ -217,7 +220,7 @@ static int print_pair_histogram(int bins, int fp64) {
 }
 
 int main(int argc, char **argv) {
-  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0, tidal = 0, jerk = 0, closest = 0, pair_hist = 0, hermite = 0;
+  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0, tidal = 0, jerk = 0, closest = 0, pair_hist = 0, hermite = 0, block_levels = 0;
   double e0 = 0.0, adaptive = 0.0;
   unsigned long long seed = NBODY_IC_DEFAULT_SEED;
   for (int a = 1; a < argc; ++a) {
@@ -228,6 +231,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--fp64")) fp64 = 1;
     else if (!strcmp(argv[a], "--host-loop")) host_loop = 1;
     else if (!strcmp(argv[a], "--hermite")) hermite = 1;
+    else if (!strcmp(argv[a], "--hermite-block") && a + 1 < argc) { hermite = 1; block_levels = atoi(argv[++a]); if (block_levels < 1 || block_levels > 24) { fprintf(stderr, "--hermite-block needs 1 <= LEVELS <= 24\n"); return 2; } }
     else if (!strcmp(argv[a], "--strict")) strict = 1;
     else if (!strcmp(argv[a], "--rtl")) rtl = 1;
     else if (!strcmp(argv[a], "--energy")) energy = 1;
@@ -246,7 +250,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--block") && a + 1 < argc) block = atoi(argv[++a]);
     else if (argv[a][0] != '-' && npos == 0) { n = atoi(argv[a]); npos++; }
     else if (argv[a][0] != '-' && npos == 1) { iters = atoi(argv[a]); npos++; }
-    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--hermite]\n", argv[0]); return 2; }
+    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--hermite] [--hermite-block LEVELS]\n", argv[0]); return 2; }
   }
   if (field < 0) { fprintf(stderr, "--field needs M >= 1\n"); return 2; }
   if (tidal < 0) { fprintf(stderr, "--tidal needs M >= 1\n"); return 2; }
@@ -276,6 +280,8 @@ int main(int argc, char **argv) {
   if (overlap >= 0) CHECK(nbody_set_option(NBODY_OPT_OVERLAP, overlap));        /* multi-GPU: 0 gather first, 1 own slice then the rest, 2 per arriving slice */
 
   double total = 0.0;
+  long long substeps = 0, row_evals = 0;
+  const float block_eta = 0.02f;
   if (!fp64) {
     float *buf = (float *)malloc(2 * words * sizeof(float));
     if (!buf) return 3;
@@ -292,10 +298,12 @@ int main(int argc, char **argv) {
       }
     } else if (hermite) {
       CHECK(nbody_upload(&p));
-      CHECK(nbody_step_hermite(dt, 1));   /* warm-up; the call returns with the state written */
+      if (block_levels) CHECK(nbody_step_hermite_block(block_eta, dt, block_levels, 1, NULL, NULL));
+      else CHECK(nbody_step_hermite(dt, 1));   /* warm-up; the call returns with the state written */
       CHECK(nbody_upload(&p));
       double t0 = now_s();
-      CHECK(nbody_step_hermite(dt, iters));
+      if (block_levels) CHECK(nbody_step_hermite_block(block_eta, dt, block_levels, iters, &substeps, &row_evals));
+      else CHECK(nbody_step_hermite(dt, iters));
       total = now_s() - t0;
       CHECK(nbody_download(&p));
     } else {
@@ -336,10 +344,12 @@ int main(int argc, char **argv) {
       }
     } else if (hermite) {
       CHECK(nbody_upload_d(&p));
-      CHECK(nbody_step_hermite_d(dt, 1));
+      if (block_levels) CHECK(nbody_step_hermite_block_d(block_eta, dt, block_levels, 1, NULL, NULL));
+      else CHECK(nbody_step_hermite_d(dt, 1));
       CHECK(nbody_upload_d(&p));
       double t0 = now_s();
-      CHECK(nbody_step_hermite_d(dt, iters));
+      if (block_levels) CHECK(nbody_step_hermite_block_d(block_eta, dt, block_levels, iters, &substeps, &row_evals));
+      else CHECK(nbody_step_hermite_d(dt, iters));
       total = now_s() - t0;
       CHECK(nbody_download_d(&p));
     } else {
@@ -365,6 +375,9 @@ int main(int argc, char **argv) {
     printf("checksum (sum of positions): %.17g %.17g %.17g\n", cx, cy, cz);
     free(buf);
   }
+  if (block_levels)
+    printf("hermite block: %d levels, %lld sub-steps, %lld row evaluations (%.4f of sub-steps x N)\n", block_levels, substeps, row_evals,
+           (double)row_evals / ((double)substeps * (double)n));
   double avg = total / (double)(hermite ? iters : iters - 1);
   long long info_r = 0, info_s = 0, info_b = 0, info_l = 0, info_w = 0;
   nbody_get_info(NBODY_INFO_WSPLIT, &info_w);
@@ -373,7 +386,7 @@ int main(int argc, char **argv) {
   nbody_get_info(NBODY_INFO_SUM_BLOCK, &info_b);
   nbody_get_info(NBODY_INFO_LAUNCHES_PER_STEP, &info_l);
   printf("%d Bodies (%s, %d GPU%s, %s loop, %lld bodies/lane, %lld segments x %lld pieces, sum block %lld, %lld launch%s/step): average %0.3f Billion Interactions / second (%.3f ms / step)\n",
-         n, fp64 ? "fp64" : "fp32", gpus, gpus > 1 ? "s" : "", host_loop ? "host" : hermite ? "device Hermite" : "device", info_r, info_s, info_w, info_b, info_l,
+         n, fp64 ? "fp64" : "fp32", gpus, gpus > 1 ? "s" : "", host_loop ? "host" : block_levels ? "device Hermite block" : hermite ? "device Hermite" : "device", info_r, info_s, info_w, info_b, info_l,
          info_l > 1 ? "es" : "", 1e-9 * (double)n * (double)n / avg, 1e3 * avg);
   nbody_shutdown();
   return 0;

@@ -12,15 +12,15 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-s
 all: lib host oracle microbench
 
 # The library = ONE device code object (device.hip: the force path's kernels.hip — the nbk kernels + the launch functions that pick an
-# instantiation, ~45 s of hipcc — the energy pass's energy.hip, the field, tidal and jerk passes' point_sums.hip, the neighbour pass's neighbors.hip, the k-nearest-neighbour pass's knn.hip, the friends-of-friends pass's fof.hip, the radial-count pass's hist.hip, the pair time-scale pass's timescale.hip, the Hermite step's hermite.hip and the block step's hermite_block.hip) and twelve
-# host-only C++ files (context, comm, mailbox, energy, point_sums, neighbors, knn, fof, hist, timescale, hermite, hermite_block: seconds each) behind csrc/nbody_internal.hpp.  A host-side edit relinks in seconds.
+# instantiation, ~45 s of hipcc — the energy pass's energy.hip, the field, tidal and jerk passes' point_sums.hip, the neighbour pass's neighbors.hip, the k-nearest-neighbour pass's knn.hip, the friends-of-friends pass's fof.hip, the radial-count pass's hist.hip, the pair time-scale pass's timescale.hip, the pair binding-energy pass's pair_energy.hip, the Hermite step's hermite.hip and the block step's hermite_block.hip) and thirteen
+# host-only C++ files (context, comm, mailbox, energy, point_sums, neighbors, knn, fof, hist, timescale, pair_energy, hermite, hermite_block: seconds each) behind csrc/nbody_internal.hpp.  A host-side edit relinks in seconds.
 # The eight diagnostic passes share csrc/diag_pass.hpp (device code — the distance passes' pair distance and query preamble included — the sizes
 # their hosts read and the guard of a split launch) and csrc/query_pass.hpp (host only: the flow of a call and the two split rules).
 HOSTFLAGS := -O2 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function
 OBJ      := build/obj
 KERNEL_SRC := $(CSRC)/kernels.hip $(CSRC)/nbody_kernels.hpp $(CSRC)/nbody_args.hpp $(CSRC)/force_loop_gfx950.inc
 HOST_HDR := $(CSRC)/nbody_internal.hpp $(CSRC)/nbody_args.hpp $(CSRC)/query_pass.hpp $(CSRC)/diag_pass.hpp include/nbody.h
-HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o $(OBJ)/energy.o $(OBJ)/point_sums.o $(OBJ)/neighbors.o $(OBJ)/knn.o $(OBJ)/fof.o $(OBJ)/hist.o $(OBJ)/timescale.o $(OBJ)/hermite.o $(OBJ)/hermite_block.o
+HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o $(OBJ)/energy.o $(OBJ)/point_sums.o $(OBJ)/neighbors.o $(OBJ)/knn.o $(OBJ)/fof.o $(OBJ)/hist.o $(OBJ)/timescale.o $(OBJ)/pair_energy.o $(OBJ)/hermite.o $(OBJ)/hermite_block.o
 # the energy diagnostics' device code (energy.hip, seconds of hipcc on its own) reads nbody_args.hpp and changes nothing of the force path's
 # hashed source (KERNEL_SRC); device.hip compiles it with kernels.hip into the library's one code object.  Its host side is energy.cpp, one
 # of HOST_OBJ.  What it shares with the seven passes below is diag_pass.hpp, which is no part of the hashed source either.
@@ -39,6 +39,9 @@ FOF_SRC := $(CSRC)/fof.hip $(CSRC)/fof_args.hpp
 HIST_SRC := $(CSRC)/hist.hip $(CSRC)/hist_args.hpp
 # the pair time-scale pass (pair crossing times, the closest distance, the shared adaptive step) likewise: timescale.hip beside hist.hip, timescale.cpp one of HOST_OBJ
 TIMESCALE_SRC := $(CSRC)/timescale.hip $(CSRC)/timescale_args.hpp
+# the pair binding-energy pass (every body's most bound partner, the binaries and their elements) likewise: pair_energy.hip beside timescale.hip, with
+# which it shares diag_pass.hpp's pair_walk; pair_energy.cpp one of HOST_OBJ
+PAIR_ENERGY_SRC := $(CSRC)/pair_energy.hip $(CSRC)/pair_energy_args.hpp
 # the Hermite step's elementwise kernels (predictor, corrector, the best-row reduction) likewise: hermite.hip beside timescale.hip, hermite.cpp one
 # of HOST_OBJ; its all-pairs work is the jerk pass of point_sums.hip
 HERMITE_SRC := $(CSRC)/hermite.hip $(CSRC)/hermite_args.hpp
@@ -46,7 +49,7 @@ HERMITE_SRC := $(CSRC)/hermite.hip $(CSRC)/hermite_args.hpp
 # likewise: hermite_block.hip beside hermite.hip, hermite_block.cpp one of HOST_OBJ; it shares hermite.cpp's opening and gathers through
 # hermite_host.hpp, and its all-pairs work is the jerk points pass of point_sums.hip
 HERMITE_BLOCK_SRC := $(CSRC)/hermite_block.hip $(CSRC)/hermite_block_args.hpp
-DEVICE_SRC := $(CSRC)/device.hip $(KERNEL_SRC) $(CSRC)/diag_pass.hpp $(ENERGY_SRC) $(POINT_SUMS_SRC) $(NEIGHBORS_SRC) $(KNN_SRC) $(FOF_SRC) $(HIST_SRC) $(TIMESCALE_SRC) $(HERMITE_SRC) $(HERMITE_BLOCK_SRC)
+DEVICE_SRC := $(CSRC)/device.hip $(KERNEL_SRC) $(CSRC)/diag_pass.hpp $(ENERGY_SRC) $(POINT_SUMS_SRC) $(NEIGHBORS_SRC) $(KNN_SRC) $(FOF_SRC) $(HIST_SRC) $(TIMESCALE_SRC) $(PAIR_ENERGY_SRC) $(HERMITE_SRC) $(HERMITE_BLOCK_SRC)
 
 lib: $(PKG)/libnbody_hip.so
 $(OBJ)/device.o: $(DEVICE_SRC) $(HOST_HDR)
@@ -62,6 +65,7 @@ $(OBJ)/knn.o: $(CSRC)/knn_args.hpp
 $(OBJ)/fof.o: $(CSRC)/fof_args.hpp
 $(OBJ)/hist.o: $(CSRC)/hist_args.hpp
 $(OBJ)/timescale.o: $(CSRC)/timescale_args.hpp
+$(OBJ)/pair_energy.o: $(CSRC)/pair_energy_args.hpp
 $(OBJ)/hermite.o: $(CSRC)/hermite_args.hpp $(CSRC)/hermite_host.hpp
 $(OBJ)/hermite_block.o: $(CSRC)/hermite_args.hpp $(CSRC)/hermite_host.hpp $(CSRC)/hermite_block_args.hpp
 $(PKG)/libnbody_hip.so: $(OBJ)/device.o $(HOST_OBJ)

@@ -2,7 +2,7 @@
  *
  * Plain C99: pointers, ints, floats.  No HIP, torch or C++ types cross this
  * boundary.  The library behind it is hand-written HIP for gfx950
- * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip, hermite.hip, hermite_block.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, point_sums.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp, hermite.cpp, hermite_block.cpp); there is
+ * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip, pair_energy.hip, hermite.hip, hermite_block.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, point_sums.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp, pair_energy.cpp, hermite.cpp, hermite_block.cpp); there is
  * no CPU fallback: every entry
  * point fails with NBODY_ERR_NO_DEVICE when no GPU is usable.
  *
@@ -753,6 +753,54 @@ int nbody_min_timescale(float *tau2, int *i, int *j, float *d2min);
 int nbody_min_timescale_d(double *tau2, int *i, int *j, double *d2min);
 int nbody_step_adaptive(float eta, float t_end, float dt_min, float dt_max, int max_steps, double *t_reached, int *steps_taken);
 int nbody_step_adaptive_d(double eta, double t_end, double dt_min, double dt_max, int max_steps, double *t_reached, int *steps_taken);
+
+/* ---- pair binding energies and binaries: which pairs are bound, and on what orbit (not in the reference) ----
+ * Masses are unit and G = 1, so the relative orbit of a pair has mu = 2.  In the context precision T, for a row i and every body j != i:
+ *   dx = xj - xi (dy, dz likewise)         d2 = fma(dx, dx, fma(dy, dy, dz * dz))     the neighbour pass's plain d2, unchanged
+ *   ux = vxj - vxi (uy, uz likewise)       v2 = fma(ux, ux, fma(uy, uy, uz * uz))     the time-scale pass's v2, unchanged
+ *   s  = d2 + eps                          eps the force's softening
+ *   inv = 1 / sqrt(s)                      binary32: the value (float)(1.0 / sqrt((double)s)), the strict modes' 1/sqrt;
+ *                                          binary64: the IEEE sqrt followed by the IEEE divide
+ *   e  = fma((T)0.5, v2, (T)-2 * inv)      the specific orbital energy v^2 / 2 - mu / r of the softened pair, rounded once
+ * every operation rounded once, contraction off, and none of it follows NBODY_OPT_ARITH: one definition per precision.  The softening
+ * keeps coincident distinct bodies at the finite e = v2 / 2 - 2 / sqrt(eps) instead of -inf.
+ *   e      the lowest e over j, in T.  A NaN e (a NaN coordinate anywhere in the pair) is never chosen, nor is e = +inf (a v2 that
+ *          overflowed): it is not below +inf.  A d2 that overflows gives inv = +0 and e = v2 / 2, a legitimate non-negative candidate.
+ *   idx    the j that gives it, on equal values the lowest j: what an ascending scan from (+inf, -1) that replaces on strict < arrives
+ *          at.  Without a candidate (N = 1, every e NaN or +inf): idx = -1, e = +inf.
+ * e_ij and e_ji have the same bits (the differences change sign, their squares do not).  A minimum of individually rounded values is
+ * exact: the values depend on the N positions and velocities and the row alone — not on the number of rows, on the launch shape
+ * (NBODY_PAIR_ENERGY_SPLIT below), on the arithmetic, on the force configuration or on the device or rank count.  No atomics: two calls
+ * return identical values.
+ * nbody_pair_energy_rows(_d): rows exactly as in nbody_timescale_rows (nbody_init: first_row is a global index, the range may span
+ *   devices; nbody_init_rank: a row of the rank's own slice).  The idx returned are always GLOBAL body indices.  e or idx may be NULL
+ *   (not both).  It brings the other slices' positions first and then ALL N velocities to every device, exactly as
+ *   nbody_timescale_rows does, so it is collective in an nbody_init_rank job.
+ * nbody_binaries (both precisions): the rows pass over all N global rows, then on the host, in ascending i, every pair i < j with
+ *   idx[i] == j, idx[j] == i and e[i] < e_max: the mutually most bound pairs.  *n_pairs is the number found and may exceed max_pairs; the
+ *   first min(*n_pairs, max_pairs) are written to i[k], j[k] and elements[NBODY_BINARY_WORDS * k ..] = {E, a, ecc, period}.  With
+ *   max_pairs == 0 the three arrays may be NULL and the call only counts.  e_max <= 0; e_max = -inf is legal and lists nothing.  A body
+ *   whose best partner prefers someone else is NOT listed — this is how a hierarchy shows: of a triple, only the inner pair is.
+ *   The rows are divided in contiguous ranges over the process's devices; in an nbody_init_rank job every rank walks all N rows on its
+ *   own device, as nbody_fof does — P times the work of one rank, paid for a list that is the same on every rank without an exchange
+ *   beyond the gathers above (which keep the call collective).
+ *   The elements are computed on the host in binary64 from the two members' T-valued state converted exactly, in this order:
+ *     d = r_j - r_i;  u = v_j - v_i;  s = ((dx*dx + dy*dy) + dz*dz) + (double)eps;  r = sqrt(s);  v2 = (ux*ux + uy*uy) + uz*uz;
+ *     E = 0.5*v2 - 2.0/r;  a = -1.0/E;  L2 = |d x u|^2 (c = d x u, (cx*cx + cy*cy) + cz*cz);  ecc = sqrt(max(0, 1 + (0.5*E)*L2));
+ *     period = pi * sqrt(((2*a)*a)*a)
+ *   Membership is decided by the T-valued e of the pass; the elements are a convenience.  A marginal pair may show E >= 0, and a and
+ *   period are then what the formulas give (a negative a, a NaN period).
+ * Both leave positions, velocities, the arrival counters, the captured step graph and the force-kernel timer as they were.
+ * Environment, read on every call: NBODY_PAIR_ENERGY_SPLIT = k >= 1 walks the sources in min(k, blocks of 1024) chunks side by side
+ * (unset or 0: chosen from the number of rows and the CU count); NBODY_PAIR_ENERGY_SCRATCH_MB (default 256, fractions allowed) bounds
+ * the 8 (fp64: 12) bytes per row and chunk a split launch stores, larger calls go in consecutive batches of rows.  Same values in every case.
+ * NBODY_ERR_NOT_INIT without a context; NBODY_ERR_ARG, checked before anything is launched or written, for a bad row range, both
+ * outputs NULL, an e_max that is NaN or > 0, max_pairs < 0, n_pairs == NULL or a NULL array with max_pairs > 0; NBODY_ERR_STATE for the
+ * other precision's rows entry point or while the mailbox is served. */
+#define NBODY_BINARY_WORDS 4
+int nbody_pair_energy_rows(int first_row, int n_rows, float *e, int *idx);
+int nbody_pair_energy_rows_d(int first_row, int n_rows, double *e, int *idx);
+int nbody_binaries(double e_max, int max_pairs, int *n_pairs, int *i, int *j, double *elements);
 
 #ifdef __cplusplus
 }

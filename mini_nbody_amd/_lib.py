@@ -26,6 +26,7 @@ COMM_RING, COMM_ALLGATHER, COMM_AUTO, COMM_DIRECT = 0, 1, 2, 3
 
 KNN_MAX = 32   # NBODY_KNN_MAX
 HIST_MAX_BINS = 32   # NBODY_HIST_MAX_BINS
+BINARY_WORDS = 4   # NBODY_BINARY_WORDS: {E, a, ecc, period}
 
 ERR_NOT_INIT, ERR_ARG, ERR_NO_DEVICE, ERR_RCCL_LOAD, ERR_STATE, ERR_UNSUPPORTED = 1001, 1002, 1003, 1004, 1005, 1006
 
@@ -45,6 +46,7 @@ SYMBOLS = [
     "nbody_pair_histogram", "nbody_pair_histogram_d", "nbody_tidal", "nbody_tidal_d",
     "nbody_timescale_rows", "nbody_timescale_rows_d", "nbody_min_timescale", "nbody_min_timescale_d",
     "nbody_step_adaptive", "nbody_step_adaptive_d",
+    "nbody_pair_energy_rows", "nbody_pair_energy_rows_d", "nbody_binaries",
     "nbody_jerk", "nbody_jerk_d", "nbody_jerk_rows", "nbody_jerk_rows_d",
     "nbody_step_hermite", "nbody_step_hermite_d", "nbody_min_aarseth", "nbody_step_hermite_adaptive", "nbody_step_hermite_adaptive_d",
     "nbody_step_hermite_block", "nbody_step_hermite_block_d",
@@ -118,6 +120,8 @@ def load():
         "nbody_timescale_rows": [i, i, fp, C.POINTER(i), fp], "nbody_timescale_rows_d": [i, i, dp, C.POINTER(i), dp],
         "nbody_min_timescale": [fp, C.POINTER(i), C.POINTER(i), fp], "nbody_min_timescale_d": [dp, C.POINTER(i), C.POINTER(i), dp],
         "nbody_step_adaptive": [f, f, f, f, i, dp, C.POINTER(i)], "nbody_step_adaptive_d": [d, d, d, d, i, dp, C.POINTER(i)],
+        "nbody_pair_energy_rows": [i, i, fp, C.POINTER(i)], "nbody_pair_energy_rows_d": [i, i, dp, C.POINTER(i)],
+        "nbody_binaries": [d, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), dp],
         "nbody_jerk": [fp, fp, i, C.POINTER(i), fp, fp], "nbody_jerk_d": [dp, dp, i, C.POINTER(i), dp, dp],
         "nbody_jerk_rows": [i, i, fp, fp], "nbody_jerk_rows_d": [i, i, dp, dp],
         "nbody_step_hermite": [f, i], "nbody_step_hermite_d": [d, i], "nbody_min_aarseth": [dp, C.POINTER(i)],

@@ -1,10 +1,11 @@
-// diag_pass.hpp — what the diagnostic passes (energy, field, tidal tensor, neighbours, k nearest neighbours, friends-of-friends, radial counts, pair time scales) share, stated once: the two launch constants their hosts and
+// diag_pass.hpp — what the diagnostic passes (energy, field, tidal tensor, neighbours, k nearest neighbours, friends-of-friends, radial counts, pair time scales, pair binding energies) share, stated once: the two launch constants their hosts and
 // kernels agree on and the guard of a launch over split sources; for device code, the pair arithmetic of the potential, the plain
-// squared distance of the five distance passes (neighbours, k nearest neighbours, friends-of-friends, radial counts, pair time scales) and the preamble of a
-// one-query-per-lane kernel: the lane, the wave's skip window, the chunk's sources.
-// energy_args.hpp, point_sums_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp, hist_args.hpp and timescale_args.hpp include it.  Like them it stays apart from the force path's hashed
+// squared distance of the six distance passes (neighbours, k nearest neighbours, friends-of-friends, radial counts, pair time scales, pair binding energies), the preamble of a
+// one-query-per-lane kernel: the lane, the wave's skip window, the chunk's sources; and the two-stream walk of the two passes that read velocities too (pair_walk).
+// energy_args.hpp, point_sums_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp, hist_args.hpp, timescale_args.hpp and pair_energy_args.hpp include it.  Like them it stays apart from the force path's hashed
 // source (nbody_args.hpp, nbody_kernels.hpp, kernels.hip, force_loop_gfx950.inc), of which it reads nbody_args.hpp (kSoftBits, NB_CONST) only.
-// The kernels' loops are different computations and stay in their files; the field's, the tidal tensor's and the jerk's are one (point_sums.hip).
+// The kernels' loops are different computations and stay in their files; the field's, the tidal tensor's and the jerk's are one (point_sums.hip),
+// and so are the pair time-scale and the pair binding-energy pass's (pair_walk below).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -159,6 +160,42 @@ __device__ __forceinline__ Query<V4> query_of(const A& a, int pc) {
   const auto [sk, wlo, whi] = wave_skip_window<SKIP>(!SKIP ? -1 : a.points ? a.skip[pc] : a.first + pc);
   const auto [s0, s1] = chunk_sources(a);
   return {me, sk, wlo, whi, scalar_src<V4>(a.src), s0, s1};
+}
+
+// THE walk of the two passes that read two bodies' positions and velocities together (pair time scales: timescale.hip; pair binding
+// energies: pair_energy.hip), the body of their hot kernels, for any argument block query_of takes that has vsrc, scratch and m besides.
+// One row per lane, kLanes rows per workgroup; workgroup (x, y) walks the blocks of chunk y for the rows of x.  Positions and velocities
+// of the sources arrive as two streams of wave-uniform scalar loads (address space 4); the lane's own two words are vector loads.  Lanes
+// beyond m stay in the wave-uniform loops clamped to the last row and store nothing.  Only the aligned 64-source windows that overlap
+// the wave's own rows [wlo, whi] compare j with the row's index (a wave-uniform branch), and so does the tail (N not a multiple of 64).
+// A pass states what differs, as a type P with
+//   State                                              what a lane carries: the ascending scan's state
+//   static State start()                               the state before the first source
+//   static void pair<CMP>(p, u, me, mv, j, sk, State&) the statement of record: one pair (p, u: the source's position and velocity word;
+//                                                      me, mv: the row's), CMP as plain_d2's
+//   static void to_scratch(a, w, State)                a split launch: the chunk's result of row p at w = chunk * m + p
+//   static void to_outputs(a, p, State)                an unsplit launch: row p's results
+template <typename V4, class P, class A>
+__device__ __forceinline__ void pair_walk(const A& a) {
+  const auto [p, live, pc] = lane_of(a.m);
+  const auto [me, sk, wlo, whi, src, s0, s1] = query_of<V4, true>(a, pc);
+  const V4 mv = ((const V4*)a.vsrc)[a.first + pc];
+  const NB_CONST V4* vsrc = scalar_src<V4>(a.vsrc);
+  typename P::State c = P::start();
+  int j = s0;
+  for (; j + 64 <= s1; j += 64) {
+    if (j + 63 < wlo || j > whi) {
+#pragma unroll 4
+      for (int k = 0; k < 64; ++k) P::template pair<false>(src[j + k], vsrc[j + k], me, mv, j + k, sk, c);
+    } else {
+#pragma unroll 4
+      for (int k = 0; k < 64; ++k) P::template pair<true>(src[j + k], vsrc[j + k], me, mv, j + k, sk, c);
+    }
+  }
+  for (; j < s1; ++j) P::template pair<true>(src[j], vsrc[j], me, mv, j, sk, c);
+  if (!live) return;
+  if (a.scratch) P::to_scratch(a, (size_t)blockIdx.y * (size_t)a.m + (size_t)p, c);
+  else P::to_outputs(a, p, c);
 }
 
 }  // namespace nbd

@@ -23,6 +23,8 @@
 //   hist.cpp      nbody_radial_counts_rows(_d), nbody_radial_counts(_d), nbody_pair_histogram(_d): bodies per shell of distance, pair counts
 //   timescale.hip the pair time-scale pass's kernels (timescale_args.hpp: its argument block and launch functions)
 //   timescale.cpp nbody_timescale_rows(_d), nbody_min_timescale(_d), nbody_step_adaptive(_d): pair crossing times, the shared adaptive step
+//   pair_energy.hip the pair binding-energy pass's kernels (pair_energy_args.hpp: its argument block and launch functions)
+//   pair_energy.cpp nbody_pair_energy_rows(_d), nbody_binaries: every body's most bound partner, the mutually most bound pairs and their elements
 //   hermite.hip   the Hermite step's predictor, corrector and best-row reduction (hermite_args.hpp: their argument block and launch functions)
 //   hermite.cpp   nbody_step_hermite(_d), nbody_min_aarseth, nbody_step_hermite_adaptive(_d): the fourth-order Hermite step on the jerk rows
 //                 pass of point_sums.cpp, the smallest |a|^2 / |j|^2 of the system and the shared Aarseth time step
@@ -30,7 +32,7 @@
 //   hermite_block.hip the block step's scheduler kernels: init, predict-to-tau, next-time, compact-and-gather, correct-and-assign
 //                 (hermite_block_args.hpp: their argument block, the level rules and launch functions)
 //   hermite_block.cpp nbody_step_hermite_block(_d): individual block time steps, the active rows evaluated by the jerk points pass
-// Only kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip, hermite.hip and hermite_block.hip are device code (a minute of hipcc, as one code object through device.hip);
+// Only kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip, pair_energy.hip, hermite.hip and hermite_block.hip are device code (a minute of hipcc, as one code object through device.hip);
 // the others are host C++ (seconds).  gfx950 only, no CPU fallback anywhere.
 // Ownership: every stream, event, device and pinned allocation the context uses lives in an owning handle (Stream, Event, DevMem, Pinned,
 // below) that is a member of Global or of one of its Locals; nbody_shutdown() releases them all, and nothing does at process exit (see `g`).
@@ -163,6 +165,7 @@ struct Local {
   DevMem ts_vel;                       // pair time-scale and jerk pass (query_pass.hpp, gather_velocities): all N velocity words, gathered at the start of a call (several devices in one process) ...
   DevMem ts_tau2, ts_idx, ts_d2;       // ... the rows' outputs (tau2 and d2min in the context precision) ...
   DevMem ts_best;                      // ... and the ranks' bests, one BestScale at word `rank` (all P after an all-gather)
+  DevMem pe_e, pe_idx;                 // pair binding-energy pass (pair_energy.cpp): the rows' outputs (e in the context precision)
   DevMem fo_label, fo_rows, fo_min;    // fof pass (fof.cpp): the N labels of a round, this local's range of the active rows and their m_i
   DevMem he_pos0, he_vel0;             // Hermite step (hermite.cpp): the own rows' (x0, v0) of the step under way, n_local words each ...
   DevMem he_acc[2], he_jerk[2];        // ... their acceleration and jerk words at the start of the step and at the predicted state ...

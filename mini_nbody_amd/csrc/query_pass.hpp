@@ -1,4 +1,4 @@
-// query_pass.hpp — the host side that the diagnostic passes share (energy.cpp, point_sums.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp, and hermite.cpp for its gathers; host C++ only): a call brings
+// query_pass.hpp — the host side that the diagnostic passes share (energy.cpp, point_sums.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp, pair_energy.cpp, and hermite.cpp for its gathers; host C++ only): a call brings
 // rows or points, every local takes a contiguous range of them, launches on its compute stream — in batches over a split of the
 // sources when the pass asks for one — and the results are copied back once the stream has drained.  A pass says what differs: which
 // range a local gets, what to launch, which outputs go where, and which of the two split rules (a SplitPlan) it follows: chunk_split,
@@ -164,7 +164,7 @@ int run_on_locals(RangeOf&& range_of, Launch&& launch, CopyBack&& copy_back) {
   return NBODY_OK;
 }
 
-// All N velocity words where the kernels of every local can read them (the pair time-scale and the jerk pass).  One device: vel itself, no copy.  Several devices in one
+// All N velocity words where the kernels of every local can read them (the pair time-scale, the pair binding-energy and the jerk pass).  One device: vel itself, no copy.  Several devices in one
 // process: every local's ts_vel, filled by device-to-device copies of the locals' slices (hipMemcpyPeerAsync, as the positions travel
 // in enqueue_gather) on its compute stream, which the launch follows.  Several processes: the collective gather of a sharded array
 // into full_scratch with the transport in use (gather_sharded_multiprocess).  The streams are drained first: a step may still be

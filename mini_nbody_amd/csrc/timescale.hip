@@ -23,52 +23,39 @@ namespace {
 template <typename T>
 struct Scale { T tau2; int idx; T d2min; };
 
-// the statement of record: one pair of the ascending scan that replaces on strict <.  CMP: the excluded body's (j == sk) d2 is a quiet
-// NaN (plain_d2), and so is its q, whatever v2 is: a NaN is below nothing.  q = +inf (v2 = 0 < d2, an overflowed d2) is not below +inf.
-template <bool CMP, typename T, typename V4>
-__device__ __forceinline__ void scan_pair(const V4 p, const V4 u, const V4 me, const V4 mv, int j, int sk, Scale<T>& c) {
-  const T d2 = plain_d2<CMP, T, V4>(p, me, j, sk);
-  const T v2 = plain_d2<T, V4>(u, mv);
-  const T q = d2 / v2;
-  const bool less = q < c.tau2;
-  c.tau2 = less ? q : c.tau2;
-  c.idx = less ? j : c.idx;
-  c.d2min = min_of(c.d2min, d2);
-}
-
-// One row per lane, kLanes rows per workgroup; workgroup (x, y) walks the blocks of chunk y for the rows of x.  Positions and
-// velocities of the sources arrive as two streams of wave-uniform scalar loads (address space 4, as neighbors_kernel); the lane's own
-// two words are vector loads.  Lanes beyond m stay in the wave-uniform loops clamped to the last row and store nothing.  Only the
-// aligned 64-source windows that overlap the wave's own rows compare j with the row's index (a wave-uniform branch).
+// what the pass makes of diag_pass.hpp's pair_walk
 template <typename T, typename V4>
-__global__ void __launch_bounds__(kLanes) timescale_kernel(TimescaleArgs a) {
-  const auto [p, live, pc] = lane_of(a.m);
-  const auto [me, sk, wlo, whi, src, s0, s1] = query_of<V4, true>(a, pc);
-  const V4 mv = ((const V4*)a.vsrc)[a.first + pc];
-  const NB_CONST V4* vsrc = scalar_src<V4>(a.vsrc);
-  Scale<T> c = {inf_of<T>(), -1, inf_of<T>()};
-  int j = s0;
-  for (; j + 64 <= s1; j += 64) {
-    if (j + 63 < wlo || j > whi) {
-#pragma unroll 4
-      for (int k = 0; k < 64; ++k) scan_pair<false, T, V4>(src[j + k], vsrc[j + k], me, mv, j + k, sk, c);
-    } else {
-#pragma unroll 4
-      for (int k = 0; k < 64; ++k) scan_pair<true, T, V4>(src[j + k], vsrc[j + k], me, mv, j + k, sk, c);
-    }
+struct TimescalePass {
+  using State = Scale<T>;
+  static __device__ __forceinline__ State start() { return {inf_of<T>(), -1, inf_of<T>()}; }
+  // the statement of record: one pair of the ascending scan that replaces on strict <.  CMP: the excluded body's (j == sk) d2 is a quiet
+  // NaN (plain_d2), and so is its q, whatever v2 is: a NaN is below nothing.  q = +inf (v2 = 0 < d2, an overflowed d2) is not below +inf.
+  template <bool CMP>
+  static __device__ __forceinline__ void pair(const V4 p, const V4 u, const V4 me, const V4 mv, int j, int sk, State& c) {
+    const T d2 = plain_d2<CMP, T, V4>(p, me, j, sk);
+    const T v2 = plain_d2<T, V4>(u, mv);
+    const T q = d2 / v2;
+    const bool less = q < c.tau2;
+    c.tau2 = less ? q : c.tau2;
+    c.idx = less ? j : c.idx;
+    c.d2min = min_of(c.d2min, d2);
   }
-  for (; j < s1; ++j) scan_pair<true, T, V4>(src[j], vsrc[j], me, mv, j, sk, c);   // the tail (N not a multiple of 64)
-  if (!live) return;
-  if (a.scratch) {
-    const size_t w = (size_t)blockIdx.y * (size_t)a.m + (size_t)p;
+  static __device__ __forceinline__ void to_scratch(const TimescaleArgs& a, size_t w, const State& c) {
     ((T*)scratch_tau2(a))[w] = c.tau2;
     ((T*)scratch_d2(a, sizeof(T)))[w] = c.d2min;
     scratch_idx(a, sizeof(T))[w] = c.idx;
-  } else {
+  }
+  static __device__ __forceinline__ void to_outputs(const TimescaleArgs& a, int p, const State& c) {
     if (a.tau2) ((T*)a.tau2)[p] = c.tau2;
     if (a.idx) a.idx[p] = c.idx;
     if (a.d2min) ((T*)a.d2min)[p] = c.d2min;
   }
+};
+
+// the walk is diag_pass.hpp's pair_walk, shared with pair_energy.hip: one row per lane, both source streams as scalar loads
+template <typename T, typename V4>
+__global__ void __launch_bounds__(kLanes) timescale_kernel(TimescaleArgs a) {
+  pair_walk<V4, TimescalePass<T, V4>>(a);
 }
 
 // the chunks of a split launch in ascending order: strict < for both minima; one row per lane (a wave reads 64 consecutive values)

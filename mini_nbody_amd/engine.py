@@ -32,6 +32,7 @@ class NBody:
         self._by_rank = rank is not None   # rows are those of this rank's slice (nbody_init_rank)
         self._open = True
         self.fof_rounds = None             # link passes of the last fof() call
+        self.binaries_found = None         # pairs the last binaries() call found (it may have returned fewer: max_pairs)
 
     # ---- options / info ----
     def set_option(self, key, value):
@@ -424,6 +425,39 @@ class NBody:
         fn = self.lib.nbody_step_adaptive_d if self.fp64 else self.lib.nbody_step_adaptive
         L.check(fn(eta, t_end, dt_min, dt_max, int(max_steps), C.byref(t), C.byref(steps)))
         return t.value, steps.value
+
+    def pair_energy(self, first_row=0, n_rows=None):
+        """(e, idx) of n_rows bodies from first_row (rows as in timescales(); default: all of them) from the state on the device
+        (nbody_pair_energy_rows): e the lowest specific two-body energy v2 / 2 - 2 / sqrt(d2 + eps) over the other bodies in the
+        context precision (+inf: none), idx the GLOBAL index of the body that gives it (-1: none; ties to the lowest index): every
+        body's most bound partner.  Collective in a multi-rank job."""
+        if n_rows is None:
+            n_rows = self.info(L.INFO_N_LOCAL if self._by_rank else L.INFO_N) - int(first_row)
+        m = int(n_rows)
+        ct = C.c_double if self.fp64 else C.c_float
+        e, idx = np.empty(m, self.dtype), np.empty(m, np.int32)
+        fn = self.lib.nbody_pair_energy_rows_d if self.fp64 else self.lib.nbody_pair_energy_rows
+        L.check(fn(int(first_row), m, e.ctypes.data_as(C.POINTER(ct)), idx.ctypes.data_as(C.POINTER(C.c_int))))
+        return e, idx
+
+    def binaries(self, e_max=0.0, max_pairs=None):
+        """(i, j, elements) of the binaries of the whole system (nbody_binaries): the pairs i < j that are each other's most bound
+        partner with a pair energy below e_max (<= 0), in ascending i; elements, (n, 4) float64, holds {E, a, ecc, period} per pair.
+        max_pairs=None counts first and then fetches all; otherwise at most max_pairs are returned and self.binaries_found holds the
+        number found.  A body whose best partner prefers someone else is not listed.  Collective in a multi-rank job; every rank
+        gets the same list."""
+        ip = C.POINTER(C.c_int)
+        found = C.c_int()
+        if max_pairs is None:
+            L.check(self.lib.nbody_binaries(float(e_max), 0, C.byref(found), None, None, None))
+            max_pairs = found.value
+        k = int(max_pairs)
+        i, j, el = np.empty(k, np.int32), np.empty(k, np.int32), np.empty((k, L.BINARY_WORDS), np.float64)
+        L.check(self.lib.nbody_binaries(float(e_max), k, C.byref(found), i.ctypes.data_as(ip), j.ctypes.data_as(ip),
+                                        el.ctypes.data_as(C.POINTER(C.c_double))))
+        self.binaries_found = found.value
+        n = min(found.value, k)
+        return i[:n], j[:n], el[:n]
 
     def step_hermite(self, dt, nsteps=1):
         """nsteps fourth-order Hermite steps of a shared dt on the state on the device (nbody_step_hermite): predict, one jerk rows

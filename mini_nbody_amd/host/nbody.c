@@ -8,7 +8,7 @@
  *
  * usage: nbody [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K]
  *              [--sum seq|blocked] [--block K] [--one-launch | --two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16]
- *              [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--hermite] [--hermite-block LEVELS]
+ *              [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--binaries] [--hermite] [--hermite-block LEVELS]
  * --hermite: the device loop's iterations are fourth-order Hermite steps (nbody_step_hermite) instead of kick-drift steps: one warm-up
  * call of one step, the initial state uploaded again, then ONE timed call of all `iters` steps (a call opens with a jerk pass of its own,
  * so two calls would not be one run: include/nbody.h, "a call is stateless"); the time per step is that call's over iters.  Refused
@@ -32,6 +32,9 @@
  * --adaptive ETA (ETA > 0): after the last iteration, one line "min timescale: tau2 ... pair i j d2min ... dt ...": the smallest pair
  * crossing time squared of the state on the device, the pair that gives it and the smallest squared distance (nbody_min_timescale), and
  * the step dt = ETA * sqrt(min(tau2, tff2)) that nbody_step_adaptive would take unclamped, in fp64, outside the timed region.
+ * --binaries: after the last iteration, one line "binaries: K", the number of mutually most bound pairs with a negative pair energy in
+ * the state on the device (nbody_binaries, e_max = 0), then up to five lines "binary: i j a ecc period", those with the smallest
+ * semi-major axis a in ascending order of a (equal a: the lower i first), outside the timed region.
  */
 #define _POSIX_C_SOURCE 199309L
 #include <math.h>
@@ -197,6 +200,34 @@ static int print_min_timescale(double eta, int fp64) {
   return 0;
 }
 
+/* the lines of --binaries */
+static int print_binaries(void) {
+  int found = 0, rc = nbody_binaries(0.0, 0, &found, NULL, NULL, NULL);
+  if (rc) { fprintf(stderr, "nbody_binaries failed: %s\n", nbody_error_string(rc)); return 1; }
+  printf("binaries: %d\n", found);
+  if (found == 0) return 0;
+  int *ij = (int *)malloc(2 * (size_t)found * sizeof(int));
+  double *el = (double *)malloc((size_t)found * NBODY_BINARY_WORDS * sizeof(double));
+  char *shown = (char *)calloc((size_t)found, 1);
+  if (!ij || !el || !shown) { free(ij); free(el); free(shown); return 3; }
+  int k = 0;
+  rc = nbody_binaries(0.0, found, &k, ij, ij + found, el);
+  if (rc) fprintf(stderr, "nbody_binaries failed: %s\n", nbody_error_string(rc));
+  if (k > found) k = found;
+  for (int line = 0; !rc && line < 5 && line < k; ++line) {
+    int best = -1;
+    for (int q = 0; q < k; ++q)   /* ascending q is ascending i: strict < keeps the lower i; a NaN a is never shown */
+      if (!shown[q] && el[NBODY_BINARY_WORDS * q + 1] == el[NBODY_BINARY_WORDS * q + 1] &&
+          (best < 0 || el[NBODY_BINARY_WORDS * q + 1] < el[NBODY_BINARY_WORDS * best + 1])) best = q;
+    if (best < 0) break;
+    shown[best] = 1;
+    const double *w = el + NBODY_BINARY_WORDS * best;
+    printf("binary: %d %d %.17g %.17g %.17g\n", ij[best], ij[found + best], w[1], w[2], w[3]);
+  }
+  free(ij); free(el); free(shown);
+  return rc ? 1 : 0;
+}
+
 /* the line of --pair-histogram */
 static int print_pair_histogram(int bins, int fp64) {
   long long pairs[NBODY_HIST_MAX_BINS];
@@ -220,7 +251,7 @@ static int print_pair_histogram(int bins, int fp64) {
 }
 
 int main(int argc, char **argv) {
-  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0, tidal = 0, jerk = 0, closest = 0, pair_hist = 0, hermite = 0, block_levels = 0;
+  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0, tidal = 0, jerk = 0, closest = 0, pair_hist = 0, binaries = 0, hermite = 0, block_levels = 0;
   double e0 = 0.0, adaptive = 0.0;
   unsigned long long seed = NBODY_IC_DEFAULT_SEED;
   for (int a = 1; a < argc; ++a) {
@@ -241,6 +272,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--closest-pair")) closest = 1;
     else if (!strcmp(argv[a], "--pair-histogram") && a + 1 < argc) { pair_hist = atoi(argv[++a]); if (pair_hist < 1 || pair_hist > NBODY_HIST_MAX_BINS) { fprintf(stderr, "--pair-histogram needs 1 <= B <= %d\n", NBODY_HIST_MAX_BINS); return 2; } }
     else if (!strcmp(argv[a], "--adaptive") && a + 1 < argc) { adaptive = atof(argv[++a]); if (!(adaptive > 0.0) || adaptive > 1e300) { fprintf(stderr, "--adaptive needs ETA > 0\n"); return 2; } }
+    else if (!strcmp(argv[a], "--binaries")) binaries = 1;
     else if (!strcmp(argv[a], "--two-launch")) two_launch = 1;
     else if (!strcmp(argv[a], "--one-launch")) two_launch = 0;
     else if (!strcmp(argv[a], "--overlap") && a + 1 < argc) overlap = atoi(argv[++a]);
@@ -250,7 +282,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--block") && a + 1 < argc) block = atoi(argv[++a]);
     else if (argv[a][0] != '-' && npos == 0) { n = atoi(argv[a]); npos++; }
     else if (argv[a][0] != '-' && npos == 1) { iters = atoi(argv[a]); npos++; }
-    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--hermite] [--hermite-block LEVELS]\n", argv[0]); return 2; }
+    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--binaries] [--hermite] [--hermite-block LEVELS]\n", argv[0]); return 2; }
   }
   if (field < 0) { fprintf(stderr, "--field needs M >= 1\n"); return 2; }
   if (tidal < 0) { fprintf(stderr, "--tidal needs M >= 1\n"); return 2; }
@@ -316,7 +348,7 @@ int main(int argc, char **argv) {
       total = now_s() - t0;
       CHECK(nbody_download(&p));
     }
-    if ((energy || field || tidal || jerk || closest || pair_hist || adaptive > 0.0) && host_loop) CHECK(nbody_upload(&p));
+    if ((energy || field || tidal || jerk || closest || pair_hist || binaries || adaptive > 0.0) && host_loop) CHECK(nbody_upload(&p));
     if (energy && print_energy(iters, &e0, 0)) return 1;
     if (field && print_field(field, 0)) return 1;
     if (tidal && print_tidal(tidal, 0)) return 1;
@@ -324,6 +356,7 @@ int main(int argc, char **argv) {
     if (closest && print_closest_pair(0)) return 1;
     if (pair_hist && print_pair_histogram(pair_hist, 0)) return 1;
     if (adaptive > 0.0 && print_min_timescale(adaptive, 0)) return 1;
+    if (binaries && print_binaries()) return 1;
     double cx = 0, cy = 0, cz = 0;
     for (int i = 0; i < n; ++i) { cx += p.pos[4 * i]; cy += p.pos[4 * i + 1]; cz += p.pos[4 * i + 2]; }
     printf("checksum (sum of positions): %.9g %.9g %.9g\n", cx, cy, cz);
@@ -362,7 +395,7 @@ int main(int argc, char **argv) {
       total = now_s() - t0;
       CHECK(nbody_download_d(&p));
     }
-    if ((energy || field || tidal || jerk || closest || pair_hist || adaptive > 0.0) && host_loop) CHECK(nbody_upload_d(&p));
+    if ((energy || field || tidal || jerk || closest || pair_hist || binaries || adaptive > 0.0) && host_loop) CHECK(nbody_upload_d(&p));
     if (energy && print_energy(iters, &e0, 0)) return 1;
     if (field && print_field(field, 1)) return 1;
     if (tidal && print_tidal(tidal, 1)) return 1;
@@ -370,6 +403,7 @@ int main(int argc, char **argv) {
     if (closest && print_closest_pair(1)) return 1;
     if (pair_hist && print_pair_histogram(pair_hist, 1)) return 1;
     if (adaptive > 0.0 && print_min_timescale(adaptive, 1)) return 1;
+    if (binaries && print_binaries()) return 1;
     double cx = 0, cy = 0, cz = 0;
     for (int i = 0; i < n; ++i) { cx += p.pos[4 * i]; cy += p.pos[4 * i + 1]; cz += p.pos[4 * i + 2]; }
     printf("checksum (sum of positions): %.17g %.17g %.17g\n", cx, cy, cz);

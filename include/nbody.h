@@ -560,7 +560,9 @@ int nbody_step_hermite_block_d(double eta, double dt_max, int levels, int nblock
  *          on strict < arrives at.  A NaN d2_j is never chosen (nor is a d2_j that overflowed to +inf: it is not below +inf).  Without
  *          a candidate (N = 1 with that body skipped, every d2_j NaN): idx = -1, d2 = +inf.
  *   d2     that body's d2_j, in T.  A coincident distinct body gives +0, a legitimate answer.
- *   count  the number of non-skipped j with d2_j <= r2; r2 is given already squared, in T.  NaN is never counted.
+ *   count  the number of non-skipped j with d2_j <= r2; r2 is given already squared, in T.  NaN is never counted.  r2 = +inf is legal
+ *          and counts every j whose d2_j is not NaN, one that overflowed to +inf included (+inf <= +inf) — the same j that is never
+ *          chosen as idx and that no edge of the radial counts below holds, a +inf edge included (+inf < +inf is false).
  * A minimum and an integer count are exact: the bits depend on the N positions, the query and its skip alone — not on the number of
  * queries, on where the query stands, on the launch shape (NBODY_NEIGHBORS_SPLIT below), on the arithmetic, on the force configuration
  * or on the device or rank count.  No atomics: two calls return identical values.

@@ -1,8 +1,11 @@
 """One hostile system for the smooth passes (energy, potential, field) and the force path, stated once: the inputs a uniform cloud never
 produces — coincident bodies across a 64-source window edge and a 1024-source block edge, a separation whose square underflows, signed
 zeros, a near-subnormal body, bodies so far away that inv^2 or inv^3 is subnormal or zero while d2 is finite, squares that overflow, an
-infinity, a NaN — and the points and skip indices that land on the edges of the field pass's loops.  A plain helper module like
-field_common.py (no fixtures, no hooks)."""
+infinity, a NaN — and the points and skip indices that land on the edges of the field pass's loops; and, for the four passes that take
+the plain squared distance without a softening (neighbours, k nearest neighbours, friends-of-friends, radial counts), the same system
+with a subnormal d2, a d2 that overflows for all partners but one and an inf - inf planted on top (hostile_distance_system), its radii,
+edges and linking lengths, and hand-made two- and three-body systems.  A plain helper module like field_common.py (no fixtures, no
+hooks)."""
 import numpy as np
 
 VARIANTS = ("base", "overflow", "nan", "inf")
@@ -106,6 +109,129 @@ def hostile_points(nb, pos, m, variant):
             skip[p] = (p * 7919) % n
     skip[m - 1] = n - 1
     return pts, skip
+
+
+def distance_h(dtype):
+    """h of hostile_distance_system: 2^-70 (binary32) or 2^-520 (binary64) — h * h is far below the smallest subnormal's neighbours'
+    reach (4 h^2 = 2^11 or 2^36 smallest subnormals), and h is far above the ±tiny, ±1e-30 (1e-170) bodies around the origin"""
+    dtype = np.dtype(dtype).type
+    return dtype(2.0 ** -70 if dtype is np.float32 else 2.0 ** -520)
+
+
+def subnormal_between(dtype):
+    """6 h^2: a subnormal strictly between the planted pair's d2 = 4 h^2 and its d2 = 9 h^2 to the bodies at zero"""
+    h = float(distance_h(dtype))
+    return np.dtype(dtype).type(6.0 * h * h)
+
+
+def hostile_distance_system(nb, n, dtype, variant):
+    """(pos, vel, far) of hostile_system(...) with further rows overwritten on a copy, for the four passes that take the plain squared
+    distance without a softening (neighbours, k nearest neighbours, friends-of-friends, radial counts), where d2 itself can be
+    subnormal, underflow to +0 between distinct bodies, overflow, or be inf - inf:
+      rows 62, 65   (3h, 0, 0) and (5h, 0, 0), h = distance_h(dtype), either side of the 63 | 64 window edge: d2(62, 65) = 4 h^2 and
+                    d2 = 9 h^2 (25 h^2) to the bodies at zero (22, 23; 10, 11 and 64 are at zero as far as h can tell) are exact, non-zero
+                    and subnormal, so the two are each other's nearest — unless a subnormal is flushed, which ties them at 0 with rows
+                    10, 11, 22, 23 and 64.  Rows 22 and 23 get partners at exactly +0 (each other; 10, 11, 64 by underflow) followed by
+                    two distinct subnormal values.
+      row 66        "overflow": row 63's position with x four units in the last place up — d2(63, 66) is large and finite while both
+                    are at +inf from everybody else.  "inf": x = +inf as row 63's — inf - inf = NaN between the two, +inf to the rest.
+                    "base", "nan": the cloud body it was."""
+    pos, vel, far = hostile_system(nb, n, dtype, variant)
+    pos = pos.copy()
+    dtype = pos.dtype.type
+    assert n > 66
+    h = distance_h(dtype)
+    pos[62, :3] = [3 * h, 0, 0]
+    pos[65, :3] = [5 * h, 0, 0]
+    if variant == "overflow":
+        pos[66, :3] = pos[63, :3]
+        for _ in range(4):
+            pos[66, 0] = np.nextafter(pos[66, 0], dtype(np.inf))
+    elif variant == "inf":
+        pos[66, 0] = np.inf
+    return pos, vel, far
+
+
+DISTANCE_ROWS = (62, 65, 66)   # the rows hostile_distance_system overwrites
+
+
+def planted_rows(n, variant):
+    """every row of hostile_distance_system(...) whose distances were put where they are on purpose (those that exist at this n; row
+    40's 1e10 is an ordinary large position to a plain distance)"""
+    rows = {10, 11, 22, 23, 41, 62, 63, 64, 65, 66, n - 1, nan_row(n)} | ({1023, 1024, 1025, 1026, 1027, 1028} if n > 1028 else set())
+    return np.array(sorted(r for r in rows if 0 <= r < n), np.int64)
+
+
+def _r2_030(pos):
+    """the radius (squared) that holds about 30 % of the bodies around body 0 (neighbors_common.r2_for at 0.3, without its overflow
+    warnings), moved up by 2^-10 of itself: off body 0's own d2 it was read from, into the gap above it"""
+    with np.errstate(all="ignore"):
+        d = ((pos[:, :3].astype(np.float64) - pos[0, :3].astype(np.float64)) ** 2).sum(1)
+    return pos.dtype.type(np.sort(d)[min(len(d) - 1, int(0.3 * len(d)))] * (1.0 + 2.0 ** -10))
+
+
+def hostile_radii(pos):
+    """r2 for the neighbour count, in the dtype of pos: 0, the subnormal between the planted pair's two distances, the smallest normal,
+    a radius that holds about 30 % of the bodies around body 0, the largest finite, +inf"""
+    dtype = pos.dtype.type
+    fi = np.finfo(dtype)
+    return [dtype(0), subnormal_between(dtype), dtype(fi.tiny), _r2_030(pos), dtype(fi.max), dtype(np.inf)]
+
+
+def hostile_b2(pos):
+    """the linking lengths (squared) for friends-of-friends: the same six values"""
+    return hostile_radii(pos)
+
+
+HOSTILE_BINS = (3, 9, 17, 32)   # capacities 4, 16, 32 and the full 32: binary32 edges in SGPRs (up to 16) and in VGPRs (32)
+
+
+def hostile_edges(pos, n_bins):
+    """n_bins + 1 squared radii, non-decreasing, in the dtype of pos.  n_bins = 9, 17, 32:
+        -inf (9, 32) or nothing (17), 0, 0 (an empty bin), the subnormal between the planted pair's two distances, the smallest normal,
+        geometric steps from 1e-3 up to 12.5, the largest finite, +inf;
+    n_bins = 3 has room for four edges only: 0, 0, that subnormal, +inf."""
+    dtype = pos.dtype.type
+    fi = np.finfo(dtype)
+    assert n_bins in HOSTILE_BINS
+    if n_bins == 3:
+        return np.array([0, 0, subnormal_between(dtype), np.inf], dtype)
+    head = ([] if n_bins == 17 else [-np.inf]) + [0, 0, subnormal_between(dtype), fi.tiny]
+    steps = n_bins + 1 - len(head) - 2
+    e = np.array(head + list(np.geomspace(1e-3, 12.5, steps)) + [fi.max, np.inf], dtype)
+    assert len(e) == n_bins + 1 and not np.any(e[1:] < e[:-1])
+    return e
+
+
+def hand_made_distances(dtype):
+    """(systems, v): two- and three-body systems whose plain distances are known by construction, {name: (n, 4) positions}, and the
+    values their answers are made of — v.h2 = (2h)^2, an exact non-zero subnormal; v.u, a separation whose square underflows to +0;
+    v.big, a coordinate whose square overflows; v.max, the largest finite; v.sub, the smallest subnormal."""
+    dtype = np.dtype(dtype).type
+    f32 = dtype is np.float32
+    fi = np.finfo(dtype)
+    h = float(distance_h(dtype))
+    u, big = (1e-30, 1e30) if f32 else (1e-170, 1e200)
+
+    class v:
+        pass
+    v.h2, v.u, v.big, v.max, v.sub, v.inf = dtype(4 * h * h), dtype(u), dtype(big), dtype(fi.max), dtype(fi.smallest_subnormal), dtype(np.inf)
+    assert 0 < v.h2 < fi.tiny and v.u * v.u == 0 and v.u > 0
+    rows = {"alone": [[1, 2, 3]],
+            "coincident": [[1, 1, 1], [1, 1, 1]],
+            "underflow": [[0, 0, 0], [u, 0, 0]],                         # distinct, d2 = +0
+            "subnormal": [[0, 0, 0], [2 * h, 0, 0]],                     # d2 = v.h2
+            "overflow": [[0, 0, 0], [big, 0, 0], [0, 3, 0]],             # d2 = +inf to body 1, 9 between the other two
+            "nan": [[0, 0, 0], [np.nan, 0, 0], [0, 3, 0]],               # d2 = NaN to body 1
+            "inf": [[0, 0, 0], [np.inf, 0, 0], [0, 3, 0]],               # d2 = +inf to body 1
+            "two_inf": [[np.inf, 0, 0], [np.inf, 1, 0], [0, 0, 0]],      # inf - inf = NaN between 0 and 1, +inf to body 2
+            "tied": [[1, 1, 0], [1, 0, 1], [0, 1, 1]]}                   # every pair at d2 = 2
+    systems = {}
+    for name, xyz in rows.items():
+        pos = np.ones((len(xyz), 4), dtype)
+        pos[:, :3] = xyz
+        systems[name] = pos
+    return systems, v
 
 
 def near(x, far=()):

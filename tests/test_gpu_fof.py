@@ -13,6 +13,8 @@ from fof_common import CHAIN_N, b2_for, chain, make_ref, planted, round_bound
 from field_common import make_points, make_skip
 from pass_common import PLANS, check_step_untouched
 from ranks_common import run_ranks, shared_gpu_env, worker_source
+from specials_common import VARIANTS, hand_made_distances, hostile_b2, hostile_distance_system, nan_row
+from specials_common import SIZES as HOSTILE_SIZES
 
 pytestmark = pytest.mark.gpu
 ENV = ("NBODY_FOF_SPLIT", "NBODY_FOF_SCRATCH_MB", "NBODY_FOF_ALL_ROWS", "NBODY_KNN_SPLIT", "NBODY_KNN_SCRATCH_MB", "NBODY_NEIGHBORS_SPLIT",
@@ -32,11 +34,12 @@ def clean_env(monkeypatch):
         monkeypatch.delenv(k, raising=False)
 
 
-def check(eng, ref, pos, b2, what):
-    """one call against the statement: the same group array and count, the round bound; returns (group, rounds)"""
+def check(eng, ref, pos, b2, what, want=None):
+    """one call against the statement (want: ref.groups(pos, b2) where the caller has it already): the same group array and count, the
+    round bound; returns (group, rounds)"""
     n = len(pos)
     group, n_groups = eng.fof(b2)
-    want, want_groups = ref.groups(pos, b2)
+    want, want_groups = want or ref.groups(pos, b2)
     assert group.dtype == np.int32 and group.shape == (n,), what
     assert np.array_equal(group, want), what
     assert n_groups == want_groups == int((group == np.arange(n)).sum()), what
@@ -80,6 +83,78 @@ def test_planted_ties_coincident_bodies_and_a_nan_body(nb, ref, monkeypatch, fp6
             group, _ = check(eng, ref, pos, dtype(np.inf), (split, "inf"))
             assert group[200] == 200 and int((group == 0).sum()) == n - 1
         assert np.array_equal(seen[0][0], seen[1][0]) and seen[0][1] == seen[1][1]
+
+
+@pytest.mark.parametrize("fp64", [False, True])
+def test_hostile_system(nb, ref, monkeypatch, fp64):
+    """specials_common.hostile_distance_system integer for integer against fof_ref.c at every linking length of hostile_b2 — 0, which
+    links the distinct bodies whose d2 underflows to +0; a subnormal between the planted pair's d2 and its d2 to the bodies at zero,
+    which links that pair and nothing else to it; the smallest normal; an ordinary one; the largest finite, which a d2 that overflowed
+    is not within; +inf, which it is, while a NaN is not — every split (3 puts 1023 and 1024 in different chunks), with the active-row
+    list and with every row in every round, the round bound, and against the neighbour pass: a body is alone iff nobody is within b2."""
+    dtype = np.float64 if fp64 else np.float32
+    for n in HOSTILE_SIZES:
+        for variant in VARIANTS:
+            pos, vel, far = hostile_distance_system(nb, n, dtype, variant)
+            nans = int(variant == "nan")
+            with nb.NBody(n, fp64=fp64) as eng:
+                eng.upload(pos, vel)
+                for b2 in hostile_b2(pos):
+                    seen, want = set(), ref.groups(pos, b2)
+                    for all_rows in (None, "1"):
+                        if all_rows:
+                            monkeypatch.setenv("NBODY_FOF_ALL_ROWS", all_rows)
+                        for split in (None, "1", "2", "3"):
+                            if split:
+                                monkeypatch.setenv("NBODY_FOF_SPLIT", split)
+                            group, rounds = check(eng, ref, pos, b2, (n, variant, b2, all_rows, split), want)
+                            seen.add(rounds)
+                        monkeypatch.delenv("NBODY_FOF_SPLIT")
+                    monkeypatch.delenv("NBODY_FOF_ALL_ROWS")
+                    assert len(seen) == 1, (n, variant, b2, seen)   # the same rounds for every launch shape
+                    idx, d2, count = eng.neighbors(r2=b2)
+                    alone = np.bincount(group, minlength=n)[group] == 1
+                    with np.errstate(invalid="ignore"):   # the +inf of a body without a candidate is no distance
+                        assert np.array_equal(alone, count == 0) and np.array_equal(alone[idx >= 0], ~(d2 <= b2)[idx >= 0]), (n, variant, b2)
+                    if b2 == 0:
+                        assert all(group[i] == 10 for i in (10, 11, 22, 23, 64)) and int((group == 10).sum()) == 5 and group[62] == 62
+                        if n > 1028:
+                            members = [i for i in range(1023, 1029) if not (nans and i == 1024)]
+                            assert all(group[i] == 1023 for i in members) and int((group == 1023).sum()) == len(members)
+                    if 0 < b2 < np.finfo(dtype).tiny:
+                        assert group[62] == group[65] == 62 and int((group == 62).sum()) == 2 and int((group == 10).sum()) == 5
+                    if b2 == np.finfo(dtype).max and variant == "overflow":
+                        assert group[63] == group[66] == 63 and int((group == 63).sum()) == 2
+                    if b2 == np.finfo(dtype).max and variant == "inf":
+                        assert group[63] == 63 and group[66] == 66
+                    if np.isposinf(b2):
+                        assert int((group == 0).sum()) == n - nans and (not nans or group[nan_row(n)] == nan_row(n))
+
+
+@pytest.mark.parametrize("fp64", [False, True])
+def test_hand_made_specials(nb, ref, fp64):
+    """two- and three-body systems whose groups are known by construction (specials_common.hand_made_distances)"""
+    dtype = np.float64 if fp64 else np.float32
+    systems, v = hand_made_distances(dtype)
+    below = lambda x: np.nextafter(x, dtype(0))
+    cases = {   # name: {b2: group}
+        "alone": {0: [0], v.inf: [0]},
+        "coincident": {0: [0, 0], v.sub: [0, 0]},
+        "underflow": {0: [0, 0]},
+        "subnormal": {0: [0, 1], below(v.h2): [0, 1], v.h2: [0, 0]},
+        "overflow": {below(dtype(9)): [0, 1, 2], 9: [0, 1, 0], v.max: [0, 1, 0], v.inf: [0, 0, 0]},
+        "nan": {9: [0, 1, 0], v.inf: [0, 1, 0]},
+        "inf": {9: [0, 1, 0], v.max: [0, 1, 0], v.inf: [0, 0, 0]},
+        "two_inf": {v.max: [0, 1, 2], v.inf: [0, 0, 0]},   # inf - inf = NaN links nothing: the two meet through the finite body
+        "tied": {below(dtype(2)): [0, 1, 2], 2: [0, 0, 0]}}
+    assert set(cases) == set(systems)
+    for name, by_b2 in cases.items():
+        pos = systems[name]
+        with nb.NBody(len(pos), fp64=fp64) as eng:
+            eng.upload(pos, np.zeros_like(pos))
+            for b2, want in by_b2.items():
+                group, rounds = check(eng, ref, pos, dtype(b2), (name, b2))
+                assert list(group) == want, (name, b2)
 
 
 @pytest.mark.parametrize("fp64", [False, True])

@@ -14,6 +14,8 @@ import pytest
 from hist_common import BINS, count_edges, geom_edges, make_points, make_ref, make_skip, planted, r2_for, radius_edges, same
 from pass_common import FORCE_CONFIGS, check_step_untouched
 from ranks_common import ROOT, run_ranks, shared_gpu_env, worker_source
+from specials_common import (HOSTILE_BINS, POINT_COUNTS, SIZES, VARIANTS, hand_made_distances, hostile_distance_system, hostile_edges,
+                             hostile_points, hostile_radii)
 from test_gpu_neighbors import windows
 from test_hist_abi import check_planted
 
@@ -104,6 +106,85 @@ def test_one_bin_is_the_neighbour_pass_count(nb, monkeypatch, fp64):
                 assert same(eng.radial_counts(e)[:, 0], eng.neighbors(r2=r2)[2]), (loop, r2)
                 for sk in (None, skip):
                     assert same(eng.radial_counts_at(pts, e, sk)[:, 0], eng.nearest(pts, sk, r2=r2)[2]), (loop, r2)
+
+
+@pytest.mark.parametrize("loop", LOOPS)
+@pytest.mark.parametrize("fp64", [False, True])
+def test_hostile_system(nb, ref, monkeypatch, fp64, loop):
+    """specials_common.hostile_distance_system integer for integer against hist_ref.c with the edges of hostile_edges — a first edge of
+    -inf or 0, an empty bin at 0, a subnormal edge between the planted pair's d2 and its d2 to the bodies at zero, the smallest normal,
+    the largest finite (which a d2 that overflowed is not below) and +inf (nor below that) — at 3, 9, 17 and 32 bins (binary32: the
+    edges in SGPRs and in VGPRs), in both loop forms, every split (3 puts 1023 and 1024 in different chunks), windows of rows, the
+    points form; the pair histogram is half the rows' sums; one bin is the neighbour pass's count at every finite radius."""
+    monkeypatch.setenv("NBODY_HIST_LOOP", loop)
+    dtype = np.float64 if fp64 else np.float32
+    for n in SIZES:
+        for variant in VARIANTS:
+            pos, vel, far = hostile_distance_system(nb, n, dtype, variant)
+            edges = [hostile_edges(pos, b) for b in HOSTILE_BINS]
+            want_rows = [ref.rows(pos, e) for e in edges]
+            want_pairs = [ref.pairs(pos, e) for e in edges]
+            queries = [(pts, sk) for m in POINT_COUNTS for pts, skip in [hostile_points(nb, pos, m, variant)] for sk in (skip, None)]
+            want_points = [[ref.points(pos, pts, e, sk) for e in edges] for pts, sk in queries]
+            for e, rows, pairs in zip(edges, want_rows, want_pairs):
+                assert np.array_equal(rows.astype(np.int64).sum(0), 2 * pairs) and not np.any(rows[:, e[:-1] == e[1:]])
+                if variant in ("overflow", "inf"):
+                    assert rows[0].sum() < n - 1 and not np.any(rows[63, :-2])   # a +inf d2 is in no bin, not even one that ends at +inf
+            with nb.NBody(n, fp64=fp64) as eng:
+                eng.upload(pos, vel)
+                for split in (None, "1", "2", "3"):
+                    if split:
+                        monkeypatch.setenv("NBODY_HIST_SPLIT", split)
+                    tag = (n, variant, split)
+                    for e, rows, pairs in zip(edges, want_rows, want_pairs):
+                        for first, cnt in windows(n):
+                            assert same(eng.radial_counts(e, first, cnt), rows[first:first + cnt]), tag + (len(e), first)
+                        assert same(eng.pair_histogram(e), pairs), tag + (len(e),)
+                    for (pts, sk), wants in zip(queries, want_points):
+                        for e, want in zip(edges, wants):
+                            assert same(eng.radial_counts_at(pts, e, sk), want), tag + (len(e), len(pts), sk is not None)
+                monkeypatch.delenv("NBODY_HIST_SPLIT")
+                pts, skip = queries[-2]
+                for r2 in hostile_radii(pos)[:-1]:   # every finite one: 0, a subnormal, the smallest normal, an ordinary one, the largest
+                    with np.errstate(over="ignore"):   # the largest finite radius: the edge above it is +inf
+                        e = count_edges(r2, dtype)
+                    assert same(eng.radial_counts(e)[:, 0], eng.neighbors(r2=r2)[2]), (n, variant, r2)
+                    for sk in (None, skip):
+                        assert same(eng.radial_counts_at(pts, e, sk)[:, 0], eng.nearest(pts, sk, r2=r2)[2]), (n, variant, r2)
+                if variant in ("overflow", "inf"):   # ... and at r2 = +inf the count takes the +inf d2 that no edge does
+                    assert eng.neighbors(0, 1, r2=dtype(np.inf))[2][0] == n - 1 > eng.radial_counts(edges[-1], 0, 1).sum()
+
+
+@pytest.mark.parametrize("loop", LOOPS)
+@pytest.mark.parametrize("fp64", [False, True])
+def test_hand_made_specials(nb, ref, monkeypatch, fp64, loop):
+    """two- and three-body systems whose counts are known by construction (specials_common.hand_made_distances)"""
+    monkeypatch.setenv("NBODY_HIST_LOOP", loop)
+    dtype = np.float64 if fp64 else np.float32
+    systems, v = hand_made_distances(dtype)
+    inf, above = v.inf, lambda x: np.nextafter(dtype(x), dtype(np.inf))
+    cases = {   # name: (edges, counts per row)
+        "alone": ([-inf, 0, v.max, inf], [[0, 0, 0]]),
+        "coincident": ([-inf, 0, v.sub, inf], [[0, 1, 0]] * 2),            # +0 is in the bin that holds 0
+        "underflow": ([0, 0, v.sub, inf], [[0, 1, 0]] * 2),
+        "subnormal": ([0, v.sub, v.h2, above(v.h2), inf], [[0, 0, 1, 0]] * 2),   # not below its own value, below the next one
+        "overflow": ([0, 9, above(9), v.max, inf], [[0, 1, 0, 0], [0, 0, 0, 0], [0, 1, 0, 0]]),
+        "nan": ([-inf, 0, 9, above(9), inf], [[0, 0, 1, 0], [0, 0, 0, 0], [0, 0, 1, 0]]),
+        "inf": ([0, above(9), v.max, inf], [[1, 0, 0], [0, 0, 0], [1, 0, 0]]),
+        "two_inf": ([-inf, v.max, inf], [[0, 0]] * 3),
+        "tied": ([0, 2, above(2)], [[0, 2]] * 3)}
+    assert set(cases) == set(systems)
+    for name, (edges, counts) in cases.items():
+        pos = systems[name]
+        e, want = np.array(edges, dtype), np.array(counts, np.int32)
+        with nb.NBody(len(pos), fp64=fp64) as eng:
+            eng.upload(pos, np.zeros_like(pos))
+            got = eng.radial_counts(e)
+            assert same(got, want) and same(got, ref.rows(pos, e)), name
+            assert same(eng.radial_counts_at(pos, e, np.arange(len(pos), dtype=np.int32)), want), name
+            assert same(eng.radial_counts_at(pos, e), ref.points(pos, pos, e)), name
+            pairs = eng.pair_histogram(e)
+            assert same(pairs, want.astype(np.int64).sum(0) // 2) and same(pairs, ref.pairs(pos, e)), name
 
 
 @pytest.mark.parametrize("loop", LOOPS)

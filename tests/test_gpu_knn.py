@@ -11,6 +11,7 @@ import neighbors_common
 from knn_common import KS, bits, make_points, make_ref, make_skip, planted, same
 from pass_common import FORCE_CONFIGS, check_step_untouched
 from ranks_common import run_ranks, shared_gpu_env, worker_source
+from specials_common import POINT_COUNTS, SIZES, VARIANTS, hand_made_distances, hostile_distance_system, hostile_points, same_nan
 from test_gpu_neighbors import windows
 
 pytestmark = pytest.mark.gpu
@@ -104,6 +105,90 @@ def test_points_form(nb, ref, fp64):
         for bad in (0, 33, -1):
             with pytest.raises(ValueError):
                 eng.knn(bad)
+
+
+def agree(got, want):
+    """(idx, d2) against the reference's: idx equal, d2 with the same NaN mask and the same bits elsewhere"""
+    return np.array_equal(got[0], want[0]) and same_nan(got[1], want[1])
+
+
+@pytest.mark.parametrize("fp64", [False, True])
+def test_hostile_system(nb, ref, monkeypatch, fp64):
+    """specials_common.hostile_distance_system bit for bit against knn_ref.c: lists that run through +0 ties in ascending index and
+    then through two distinct subnormal values (rows 22, 23), lists of one entry and padding (rows 63, 66 of "overflow"), empty lists
+    (the NaN body; rows 63, 66 of "inf"), for k on both sides of the smallest capacity and at the largest, every split (3 puts 1023
+    and 1024 in different chunks), windows of rows and the points form; column 0 is the neighbour pass, k = 5 a prefix of k = 32."""
+    dtype = np.float64 if fp64 else np.float32
+    ks = (1, 4, 5, 32)
+    for n in SIZES:
+        for variant in VARIANTS:
+            pos, vel, far = hostile_distance_system(nb, n, dtype, variant)
+            want_rows = {k: ref.rows(pos, k) for k in ks}
+            queries = [(pts, sk) for m in POINT_COUNTS for pts, skip in [hostile_points(nb, pos, m, variant)] for sk in (skip, None)]
+            want_points = [{k: ref.points(pos, pts, k, sk) for k in ks} for pts, sk in queries]
+            idx, d2 = want_rows[32]
+            assert not np.any(np.isnan(d2)) and idx[62, 0] == 65 and idx[65, 0] == 62
+            for i, other in ((22, 23), (23, 22)):
+                assert list(idx[i, :6]) == sorted((10, 11, 64, other)) + [62, 65] and np.all(bits(d2[i, :4]) == 0)
+                assert 0 < d2[i, 4] < d2[i, 5] < np.finfo(dtype).tiny
+            if variant == "overflow":
+                assert list(idx[63, :2]) == [66, -1] and list(idx[66, :2]) == [63, -1] and np.isfinite(d2[63, 0]) and np.isposinf(d2[63, 1])
+            if variant == "inf":
+                assert np.all(idx[[63, 66]] == -1) and np.all(np.isposinf(d2[[63, 66]]))
+            with nb.NBody(n, fp64=fp64) as eng:
+                eng.upload(pos, vel)
+                for split in (None, "1", "2", "3"):
+                    if split:
+                        monkeypatch.setenv("NBODY_KNN_SPLIT", split)
+                    tag = (n, variant, split)
+                    got = {}
+                    for k in ks:
+                        for first, rows in windows(n):
+                            got[k, first] = eng.knn(k, first, rows)
+                            assert agree(got[k, first], tuple(w[first:first + rows] for w in want_rows[k])), tag + (k, first)
+                    assert agree((got[5, 0][0], got[5, 0][1]), (got[32, 0][0][:, :5], got[32, 0][1][:, :5])), tag
+                    near = eng.neighbors()
+                    assert np.array_equal(got[1, 0][0][:, 0], near[0]) and same_nan(got[1, 0][1][:, 0], near[1]), tag
+                    for (pts, sk), wants in zip(queries, want_points):
+                        at = {k: eng.knn_at(pts, k, sk) for k in ks}
+                        for k in ks:
+                            assert agree(at[k], wants[k]), tag + (k, len(pts), sk is not None)
+                        assert agree(at[5], (at[32][0][:, :5], at[32][1][:, :5])), tag
+                        near = eng.nearest(pts, sk)
+                        assert np.array_equal(at[1][0][:, 0], near[0]) and same_nan(at[1][1][:, 0], near[1]), tag
+                monkeypatch.delenv("NBODY_KNN_SPLIT")
+
+
+@pytest.mark.parametrize("fp64", [False, True])
+def test_hand_made_specials(nb, ref, fp64):
+    """two- and three-body systems whose answers are known by construction (specials_common.hand_made_distances): the constructed
+    lists at k = 2 (k = 1, 4 and 32 are their prefix and their padding), and the reference's"""
+    dtype = np.float64 if fp64 else np.float32
+    systems, v = hand_made_distances(dtype)
+    inf = v.inf
+    cases = {   # name: (idx, d2) at k = 2
+        "alone": ([[-1, -1]], [[inf, inf]]),
+        "coincident": ([[1, -1], [0, -1]], [[0, inf], [0, inf]]),
+        "underflow": ([[1, -1], [0, -1]], [[0, inf], [0, inf]]),
+        "subnormal": ([[1, -1], [0, -1]], [[v.h2, inf], [v.h2, inf]]),
+        "overflow": ([[2, -1], [-1, -1], [0, -1]], [[9, inf], [inf, inf], [9, inf]]),
+        "nan": ([[2, -1], [-1, -1], [0, -1]], [[9, inf], [inf, inf], [9, inf]]),
+        "inf": ([[2, -1], [-1, -1], [0, -1]], [[9, inf], [inf, inf], [9, inf]]),
+        "two_inf": ([[-1, -1]] * 3, [[inf, inf]] * 3),
+        "tied": ([[1, 2], [0, 2], [0, 1]], [[2, 2]] * 3)}
+    assert set(cases) == set(systems)
+    for name, (idx, d2) in cases.items():
+        pos = systems[name]
+        want = (np.array(idx, np.int32), np.array(d2, dtype))
+        with nb.NBody(len(pos), fp64=fp64) as eng:
+            eng.upload(pos, np.zeros_like(pos))
+            for k in (1, 2, 4, 32):
+                pad = max(0, k - 2)
+                made = (np.pad(want[0], ((0, 0), (0, pad)), constant_values=-1)[:, :k], np.pad(want[1], ((0, 0), (0, pad)), constant_values=inf)[:, :k])
+                got = eng.knn(k)
+                assert same(got, made) and same(got, ref.rows(pos, k)), (name, k)
+                assert same(eng.knn_at(pos, k, np.arange(len(pos), dtype=np.int32)), made), (name, k)
+                assert same(eng.knn_at(pos, k), ref.points(pos, pos, k)), (name, k)
 
 
 @pytest.mark.parametrize("fp64", [False, True])

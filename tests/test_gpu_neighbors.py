@@ -15,6 +15,8 @@ from field_common import make_points, make_skip
 from neighbors_common import bits, make_ref, planted, r2_for, same
 from pass_common import FORCE_CONFIGS, check_step_untouched
 from ranks_common import run_ranks, shared_gpu_env, worker_source
+from specials_common import (POINT_COUNTS, SIZES, VARIANTS, hand_made_distances, hostile_distance_system, hostile_points, hostile_radii,
+                             same_nan)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -128,6 +130,91 @@ def test_ties_and_specials(nb, ref, monkeypatch, fp64, loop):
         i, j, d = eng.closest_pair()
         assert (i, j) == (-1, -1) and np.isposinf(d)
         assert eng.nearest(one)[0][0] == 0 and eng.nearest(one, np.zeros(1, np.int32))[0][0] == -1
+
+
+def agree(got, want):
+    """(idx, d2, count) against the reference's: the integers equal, the floats with the same NaN mask and the same bits elsewhere"""
+    return np.array_equal(got[0], want[0]) and same_nan(got[1], want[1]) and np.array_equal(got[2], want[2])
+
+
+@pytest.mark.parametrize("fp64", [False, True])
+def test_hostile_system(nb, ref, monkeypatch, fp64):
+    """specials_common.hostile_distance_system — a subnormal d2 across the 63 | 64 window edge, d2 = +0 between distinct bodies, d2
+    that overflows for all partners but one, inf - inf, the NaN body, the coincident group across the 1023 | 1024 edge — bit for bit
+    against neighbors_ref.c: both loop forms, every split (3 puts 1023 and 1024 in different chunks), windows of rows, the points
+    form with and without skip, every radius of hostile_radii (0, a subnormal, the smallest normal, an ordinary one, the largest finite,
+    +inf), the closest pair.  What the reference itself is worth there: tests/test_specials_distance_reference.py."""
+    dtype = np.float64 if fp64 else np.float32
+    for n in SIZES:
+        for variant in VARIANTS:
+            pos, vel, far = hostile_distance_system(nb, n, dtype, variant)
+            radii = hostile_radii(pos)
+            want_rows = [ref.rows(pos, r2=r2) for r2 in radii]
+            queries = [(pts, sk) for m in POINT_COUNTS for pts, skip in [hostile_points(nb, pos, m, variant)] for sk in (skip, None)]
+            want_points = [[ref.points(pos, pts, sk, r2=r2) for r2 in radii] for pts, sk in queries]
+            want_pair = ref.closest_pair(pos)
+            idx, d2, cnt = want_rows[-1]
+            assert not np.any(np.isnan(d2)) and (idx[62], idx[65]) == (65, 62) and 0 < d2[62] < np.finfo(dtype).tiny   # a NaN is never chosen
+            if variant == "overflow":
+                assert (idx[63], idx[66]) == (66, 63) and np.isfinite(d2[63]) and cnt[0] == n - 1
+            if variant == "inf":
+                assert idx[63] == idx[66] == -1 and cnt[63] == n - 2 and cnt[0] == n - 1
+            with nb.NBody(n, fp64=fp64) as eng:
+                eng.upload(pos, vel)
+                for loop in ("1", "2"):
+                    monkeypatch.setenv("NBODY_NEIGHBORS_LOOP", loop)
+                    for split in (None, "1", "2", "3"):
+                        if split:
+                            monkeypatch.setenv("NBODY_NEIGHBORS_SPLIT", split)
+                        tag = (n, variant, loop, split)
+                        for r2, want in zip(radii, want_rows):
+                            for first, rows in windows(n):
+                                assert agree(eng.neighbors(first, rows, r2=r2), tuple(w[first:first + rows] for w in want)), tag + (r2, first)
+                        for (pts, sk), wants in zip(queries, want_points):
+                            for r2, want in zip(radii, wants):
+                                assert agree(eng.nearest(pts, sk, r2=r2), want), tag + (r2, len(pts), sk is not None)
+                        i, j, d = eng.closest_pair()
+                        assert (i, j) == want_pair[:2] == (10, 11) and bits(d) == bits(want_pair[2]) == 0, tag
+                    monkeypatch.delenv("NBODY_NEIGHBORS_SPLIT")
+
+
+@pytest.mark.parametrize("loop", ["1", "2"])
+@pytest.mark.parametrize("fp64", [False, True])
+def test_hand_made_specials(nb, ref, monkeypatch, fp64, loop):
+    """two- and three-body systems whose answers are known by construction (specials_common.hand_made_distances): the constructed
+    (idx, d2, count at each r2, closest pair), and the reference's"""
+    monkeypatch.setenv("NBODY_NEIGHBORS_LOOP", loop)
+    dtype = np.float64 if fp64 else np.float32
+    systems, v = hand_made_distances(dtype)
+    inf, below = v.inf, lambda x: np.nextafter(x, dtype(0))
+    cases = {   # name: (idx, d2, {r2: count}, closest pair)
+        "alone": ([-1], [inf], {v.max: [0], inf: [0]}, (-1, -1, inf)),
+        "coincident": ([1, 0], [0, 0], {0: [1, 1]}, (0, 1, 0)),
+        "underflow": ([1, 0], [0, 0], {0: [1, 1]}, (0, 1, 0)),
+        "subnormal": ([1, 0], [v.h2, v.h2], {0: [0, 0], below(v.h2): [0, 0], v.h2: [1, 1], inf: [1, 1]}, (0, 1, v.h2)),
+        "overflow": ([2, -1, 0], [9, inf, 9], {9: [1, 0, 1], v.max: [1, 0, 1], inf: [2, 2, 2]}, (0, 2, 9)),
+        "nan": ([2, -1, 0], [9, inf, 9], {v.max: [1, 0, 1], inf: [1, 0, 1]}, (0, 2, 9)),
+        "inf": ([2, -1, 0], [9, inf, 9], {v.max: [1, 0, 1], inf: [2, 2, 2]}, (0, 2, 9)),
+        "two_inf": ([-1, -1, -1], [inf, inf, inf], {v.max: [0, 0, 0], inf: [1, 1, 2]}, (-1, -1, inf)),
+        "tied": ([1, 0, 0], [2, 2, 2], {below(dtype(2)): [0, 0, 0], 2: [2, 2, 2]}, (0, 1, 2))}
+    assert set(cases) == set(systems)
+    for name, (idx, d2, counts, pair) in cases.items():
+        pos = systems[name]
+        with nb.NBody(len(pos), fp64=fp64) as eng:
+            eng.upload(pos, np.zeros_like(pos))
+            for r2, cnt in counts.items():
+                want = (np.array(idx, np.int32), np.array(d2, dtype), np.array(cnt, np.int32))
+                got = eng.neighbors(r2=dtype(r2))
+                assert same(got, want) and same(got, ref.rows(pos, r2=dtype(r2))), (name, r2)
+                # the same queries as points that skip their own body, and without a skip: the body itself at +0 (or nothing, where
+                # it is not at a distance from itself: NaN - NaN, inf - inf)
+                assert same(eng.nearest(pos, np.arange(len(pos), dtype=np.int32), r2=dtype(r2)), want), (name, r2)
+                own = eng.nearest(pos, r2=dtype(r2))
+                assert same(own, ref.points(pos, pos, r2=dtype(r2))), (name, r2)
+                finite = np.all(np.isfinite(pos[:, :3]), axis=1)
+                assert np.all(bits(own[1][finite]) == 0) and np.all(own[0][~finite] == want[0][~finite]), (name, r2)
+            i, j, d = eng.closest_pair()
+            assert (i, j) == pair[:2] == ref.closest_pair(pos)[:2] and bits(d) == bits(dtype(pair[2])) == bits(ref.closest_pair(pos)[2]), name
 
 
 def test_bits_do_not_depend_on_the_source_split_or_the_batches(nb, ref, monkeypatch):

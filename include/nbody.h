@@ -93,6 +93,25 @@ enum {
                               256-thread workgroup 16 rows x 16 partial sums, one (row, partial sum) per lane: four times the workgroups
                               where 64 rows per workgroup would leave CUs idle (N = 1024: 16 workgroups -> 64; NBODY_INFO_WSPLIT still
                               reports 16: sixteen partial sums per row, side by side). */
+  NBODY_OPT_MASSES = 18,   /* 0 (default): unit masses, the w of a position word is carried and never read.  1: body j has the mass
+                              m_j = the w of its position word AS IT LIES ON THE DEVICE, in the context precision — no separate array:
+                              uploaded with the positions, downloaded with them, carried bit for bit by every integrator and every
+                              gather.  The ordered-sum passes (energy and potential, field, tidal tensor, jerk) then weigh source j by
+                              m_j, one more rounding per pair ("with NBODY_OPT_MASSES" in each section below), and the Hermite
+                              integrators inherit it from the jerk; the distance passes and the pair time scale are geometry and
+                              kinematics and do not change.  The entry points whose physics is unit-mass — bodyForce(_d),
+                              nbody_step(_d), nbody_forces(_d), nbody_forces_rows(_d), nbody_step_adaptive(_d),
+                              nbody_pair_energy_rows(_d), nbody_binaries, nbody_mailbox_run, nbody_mailbox_serve(1, .) — answer
+                              NBODY_ERR_UNSUPPORTED while it is 1, before anything is launched, copied or written.  Setting it
+                              launches nothing and invalidates nothing: the captured step graph, the arrival counters and the timers
+                              stay.  With 0 every entry point returns the bits it returned without the option.  Any other value:
+                              NBODY_ERR_ARG.  DOMAIN: queries have no mass (the w of a `points` word is ignored); a NaN mass poisons
+                              every query that does not skip the body; an infinite mass gives +-inf or NaN; negative masses are
+                              computed as written and nothing is promised about them.  Three exact properties: with every w = 1
+                              the weighted form has the unweighted form's bits; multiplying every w by 2^k multiplies every output
+                              by 2^k exactly (short of overflow and subnormals); a body with w = +0 at a finite position leaves
+                              every sum it enters as it was, so massless bodies appended behind the massive ones change no bit of
+                              the massive rows' results and are themselves accelerated (tracers). */
   NBODY_OPT_ISA_PHASE = 10 /* NBODY_VARIANT_ISA: which generated form of the hand-scheduled loop runs (tools/gen_force_loop.py).
                               1 = the product loop (default); 0 = the same instructions placed one 4-byte phase off (-27 %, kept
                               so that the placement effect can be re-measured).  fp64: 1 = the product loop (VALU instructions at
@@ -150,7 +169,8 @@ enum { NBODY_INFO_N = 1, NBODY_INFO_N_LOCAL, NBODY_INFO_FIRST_BODY, NBODY_INFO_R
        NBODY_INFO_COMM_PRIORITY /* HIP priority of the transfer stream (0 = default priority) */,
        NBODY_INFO_DIAG_BUILD /* 1: this is libnbody_hip_diag.so (timing-only loop forms present) */,
        NBODY_INFO_MAILBOX_SERVED /* requests the mailbox's service thread has completed in this process */,
-       NBODY_INFO_MAILBOX_SERVING /* 1: nbody_mailbox_serve(1, .) is in effect */ };
+       NBODY_INFO_MAILBOX_SERVING /* 1: nbody_mailbox_serve(1, .) is in effect */,
+       NBODY_INFO_MASSES /* NBODY_OPT_MASSES: 0 or 1 */ };
 
 /* ---- lifetime ----
  * Replaces: power-up of the PL design + the ps_pl RAM allocation (S/top_level.vhd:100-117, 148-163). */
@@ -223,7 +243,8 @@ int nbody_download_d(BodySystemD *host);
 
 /* v_i += dt * sum_j (r_j - r_i) * (|r_j - r_i|^2 + 1e-9f)^(-3/2), all j including i; pos is read-only.
  * Host pointers, n must equal the n of nbody_init.  (upload, force kernel + kick, download of vel.)
- * Replaces one full pass of the FSM, S/top_level.vhd:176-272, followed by the host's kick. */
+ * Replaces one full pass of the FSM, S/top_level.vhd:176-272, followed by the host's kick.
+ * bodyForce(_d): NBODY_ERR_UNSUPPORTED while NBODY_OPT_MASSES is 1 (unit masses only), before anything is launched, copied or written. */
 int bodyForce(float *pos, float *vel, float dt, int n);
 /* r_i += v_i * dt.  Host pointers. */
 int integrate(float *pos, const float *vel, float dt, int n);
@@ -231,18 +252,21 @@ int bodyForce_d(double *pos, double *vel, double dt, int n);
 int integrate_d(double *pos, const double *vel, double dt, int n);
 
 /* Device-resident loop: nsteps x { bodyForce; integrate } on the uploaded state, no host round trip
- * per step; asynchronous (nbody_sync or nbody_download waits).  THE TIMED PATH. */
+ * per step; asynchronous (nbody_sync or nbody_download waits).  THE TIMED PATH.
+ * nbody_step(_d): NBODY_ERR_UNSUPPORTED while NBODY_OPT_MASSES is 1 (unit masses only), before anything is launched, copied or written. */
 int nbody_step(float dt, int nsteps);
 int nbody_step_d(double dt, int nsteps);
 int nbody_sync(void);
 
 /* Force-only entry point with the reference's word layouts: pos_words = N x {x, y, z, ignored}
- * (S/top_level.vhd:206-208), force_words = N x {Fx, Fy, Fz, 0} (S/compute_store.vhd:213, 242). */
+ * (S/top_level.vhd:206-208), force_words = N x {Fx, Fy, Fz, 0} (S/compute_store.vhd:213, 242).
+ * nbody_forces(_d): NBODY_ERR_UNSUPPORTED while NBODY_OPT_MASSES is 1 (unit masses only), before anything is launched, copied or written. */
 int nbody_forces(const float *pos_words, float *force_words, int n);
 int nbody_forces_d(const double *pos_words, double *force_words, int n);
 /* Forces on `n_rows` bodies starting at `first_row`, from the state already on the device (row-sampled parity checks at
  * N = 1M).  first_row: in an nbody_init context (one process, one or several devices) the GLOBAL body index — the range may
- * span devices; in an nbody_init_rank context the row within this rank's own slice. */
+ * span devices; in an nbody_init_rank context the row within this rank's own slice.
+ * nbody_forces_rows(_d): NBODY_ERR_UNSUPPORTED while NBODY_OPT_MASSES is 1 (unit masses only), before anything is launched, copied or written. */
 int nbody_forces_rows(int first_row, int n_rows, float *force_words);
 int nbody_forces_rows_d(int first_row, int n_rows, double *force_words);
 
@@ -296,7 +320,9 @@ int nbody_forces_rows_d(int first_row, int n_rows, double *force_words);
  *   nbody_get_info reports the context's own N and configuration (never a request's), NBODY_INFO_MAILBOX_SERVED counts completed
  *   requests; nbody_mailbox_rams, nbody_error_string, nbody_mailbox_serve and nbody_shutdown stay available.  on = 0 (and
  *   nbody_shutdown) stops and joins the thread.  The idle thread backs off from spinning to 50-us naps after ~0.1 s without a request.
- *   One-GPU fp32 contexts only. */
+ *   One-GPU fp32 contexts only.
+ * nbody_mailbox_run and nbody_mailbox_serve(1, .): NBODY_ERR_UNSUPPORTED while NBODY_OPT_MASSES is 1 (unit masses only), before anything is launched, copied or written.  A request is the reference's force pass.
+ *   nbody_mailbox_open opens a fresh context and thereby resets the option to 0, like every other option. */
 int nbody_mailbox_open(int capacity, int faithful);
 int nbody_mailbox_rams(void **ram_a, void **ram_b, int *capacity);
 int nbody_mailbox_run(void *ram_a, void *ram_b, int clock_khz);
@@ -343,7 +369,14 @@ int nbody_device_ptr(int which, void **ptr, size_t *bytes);
  * as in nbody_forces_rows.  Both bring the other slices' positions first (collective in nbody_init_rank contexts: every rank calls
  * them) and leave the step state as it was: positions, velocities, the captured step graph and the force-kernel timer
  * (nbody_kernel_time does not count energy launches).  NBODY_ERR_NOT_INIT without a context, NBODY_ERR_ARG for a null pointer or a bad
- * range, NBODY_ERR_STATE for the other precision's entry point or while the mailbox is served. */
+ * range, NBODY_ERR_STATE for the other precision's entry point or while the mailbox is served.
+ * With NBODY_OPT_MASSES: m_j = the w of body j's position word.  The level-1 sum of a row is s = fma(m_j, inv, s) in ascending j in the
+ * context precision — one operation where the unit-mass sum has its add — and for j == i s keeps its value (a select on s, not a
+ * zero term: with masses of either sign "adding 0" would not carry the argument); blocks, level 2 and phi_i = 0 - L2_i as above, so
+ * nbody_potential_rows returns phi_i = -sum_{j != i} m_j inv, per unit mass.  The totals' per-row terms are formed in binary64 from
+ * mi = (double)w_i, one plain binary64 product more each: mi * fma(vx, vx, fma(vy, vy, vz * vz)), mi * phi_i, mi * vx (vy, vz),
+ * mi * (y * vz - z * vy) (and its cyclic permutations); groups, ranks and their order are unchanged, so T = 1/2 sum m |v|^2,
+ * U = 1/2 sum m_i phi_i, P = sum m v, L = sum m r x v.  NBODY_ENERGY_WORDS stays 8. */
 enum { NBODY_ENERGY_KINETIC = 0, NBODY_ENERGY_POTENTIAL, NBODY_ENERGY_PX, NBODY_ENERGY_PY, NBODY_ENERGY_PZ,
        NBODY_ENERGY_LX, NBODY_ENERGY_LY, NBODY_ENERGY_LZ, NBODY_ENERGY_WORDS };
 int nbody_energy(double *out);
@@ -379,7 +412,10 @@ int nbody_potential_rows_d(int first_row, int n_rows, double *phi);
  * (unset or 0: chosen from m and the CU count, so that few points still fill the device); NBODY_FIELD_SCRATCH_MB (default 256) bounds the
  * per-block sums a split launch stores, larger calls go in consecutive batches of points.  Same bits in every case.
  * NBODY_ERR_NOT_INIT without a context; NBODY_ERR_ARG, checked before anything is launched, for points == NULL, m < 1, both outputs
- * NULL or a skip value outside [-1, N); NBODY_ERR_STATE for the other precision's entry point or while the mailbox is served. */
+ * NULL or a skip value outside [-1, N); NBODY_ERR_STATE for the other precision's entry point or while the mailbox is served.
+ * With NBODY_OPT_MASSES (m = the w of source j's position word; the w of a `points` word is still ignored): w3 = m * inv3, one more
+ * rounding in the context precision, then ax = fma(dx, w3, ax), ay and az likewise, and s = fma(m, inv, s).  Order of the sums, skip,
+ * blocks, level 2 and stores are unchanged: accel = sum m_j d inv^3, phi = -sum m_j inv. */
 int nbody_field(const float *points, int m, const int *skip, float *accel, float *phi);
 int nbody_field_d(const double *points, int m, const int *skip, double *accel, double *phi);
 
@@ -419,7 +455,9 @@ int nbody_field_d(const double *points, int m, const int *skip, double *accel, d
  * larger calls go in consecutive batches of points.  Same bits in every case.
  * NBODY_ERR_NOT_INIT without a context; NBODY_ERR_ARG, checked before anything is launched or written, for points == NULL,
  * tensor == NULL, m < 1 or a skip value outside [-1, N); NBODY_ERR_STATE for the other precision's entry point or while the mailbox is
- * served. */
+ * served.
+ * With NBODY_OPT_MASSES (m = the w of source j's position word): w = ((T)3 * inv5) * m, one more rounding; wx, wy, wz and the six fma
+ * as above; s3 = fma(m, inv3, s3).  Everything else is unchanged: T_ab = sum m_j (3 d_a d_b inv^5 - delta_ab inv^3). */
 int nbody_tidal(const float *points, int m, const int *skip, float *tensor);
 int nbody_tidal_d(const double *points, int m, const int *skip, double *tensor);
 
@@ -469,7 +507,10 @@ int nbody_tidal_d(const double *points, int m, const int *skip, double *tensor);
  * larger calls go in consecutive batches of queries.  Same bits in every case.
  * NBODY_ERR_NOT_INIT without a context; NBODY_ERR_ARG, checked before anything is launched or written, for points == NULL,
  * velocities == NULL, both outputs NULL, m < 1, a bad row range or a skip value outside [-1, N); NBODY_ERR_STATE for the other
- * precision's entry point or while the mailbox is served. */
+ * precision's entry point or while the mailbox is served.
+ * With NBODY_OPT_MASSES (m = the w of source j's position word; queries and rows-as-queries have no mass): w3 = m * inv3, one more
+ * rounding; the field's three fma with w3 and jx = fma(tx, w3, jx), jy and jz likewise; rv, b and t as above.  The acceleration is
+ * still nbody_field's bit for bit.  Both are per unit mass of the query, which is what an integrator needs. */
 int nbody_jerk(const float *points, const float *velocities, int m, const int *skip, float *accel, float *jerk);
 int nbody_jerk_d(const double *points, const double *velocities, int m, const int *skip, double *accel, double *jerk);
 int nbody_jerk_rows(int first_row, int n_rows, float *accel, float *jerk);
@@ -512,7 +553,12 @@ int nbody_jerk_rows_d(int first_row, int n_rows, double *accel, double *jerk);
  *     q = the minimum above over the (a, j) the integrator carries (no extra pass);  h = eta * sqrt(q);  h = min(h, dt_max);
  *     h = max(h, dt_min);  if (t + h > t_end) h = t_end - t;  dt = h rounded once to T;  one Hermite step of dt;  t += (double)dt.
  * Argument checks, *t_reached and *steps_taken (either may be NULL) as in nbody_step_adaptive: NBODY_ERR_ARG unless eta, t_end, dt_min
- * and dt_max are finite, eta > 0, 0 < dt_min <= dt_max, t_end > 0 and max_steps >= 1; running into max_steps is no error. */
+ * and dt_max are finite, eta > 0, 0 < dt_min <= dt_max, t_end > 0 and max_steps >= 1; running into max_steps is no error.
+ * With NBODY_OPT_MASSES: nbody_jerk_rows, nbody_step_hermite(_d), nbody_min_aarseth, nbody_step_hermite_adaptive(_d) and
+ * nbody_step_hermite_block(_d) inherit the masses from the jerk pass with no code of their own.  The acceleration and the jerk are per
+ * unit mass of the row, so predictor, corrector, the Aarseth ratio, the level rule and the counters are unchanged; predictor and
+ * corrector carry the w of a position word bit for bit, so the predicted state — the source array of the evaluation — holds the masses,
+ * and every gather moves whole words.  A body with w = +0 is a massless tracer: it is accelerated and moves no one. */
 int nbody_step_hermite(float dt, int nsteps);
 int nbody_step_hermite_d(double dt, int nsteps);
 int nbody_min_aarseth(double *q, int *row);
@@ -748,7 +794,9 @@ int nbody_pair_histogram_d(const double *edges2, int n_bins, long long *pairs);
  * 12 (fp64: 20) bytes per row and chunk a split launch stores, larger calls go in consecutive batches of rows.  Same values in every case.
  * NBODY_ERR_NOT_INIT without a context; NBODY_ERR_ARG, checked before anything is launched or written, for every output NULL, a bad row
  * range, a non-finite eta, t_end, dt_min or dt_max, eta <= 0, dt_min <= 0, dt_max < dt_min, t_end <= 0 or max_steps < 1;
- * NBODY_ERR_STATE for the other precision's entry point or while the mailbox is served. */
+ * NBODY_ERR_STATE for the other precision's entry point or while the mailbox is served.
+ * nbody_timescale_rows and nbody_min_timescale are kinematics and do not follow NBODY_OPT_MASSES.  nbody_step_adaptive(_d) — its
+ * free-fall time and its kick are unit-mass —: NBODY_ERR_UNSUPPORTED while NBODY_OPT_MASSES is 1 (unit masses only), before anything is launched, copied or written. */
 int nbody_timescale_rows(int first_row, int n_rows, float *tau2, int *idx, float *d2min);
 int nbody_timescale_rows_d(int first_row, int n_rows, double *tau2, int *idx, double *d2min);
 int nbody_min_timescale(float *tau2, int *i, int *j, float *d2min);
@@ -798,7 +846,9 @@ int nbody_step_adaptive_d(double eta, double t_end, double dt_min, double dt_max
  * the 8 (fp64: 12) bytes per row and chunk a split launch stores, larger calls go in consecutive batches of rows.  Same values in every case.
  * NBODY_ERR_NOT_INIT without a context; NBODY_ERR_ARG, checked before anything is launched or written, for a bad row range, both
  * outputs NULL, an e_max that is NaN or > 0, max_pairs < 0, n_pairs == NULL or a NULL array with max_pairs > 0; NBODY_ERR_STATE for the
- * other precision's rows entry point or while the mailbox is served. */
+ * other precision's rows entry point or while the mailbox is served.
+ * nbody_pair_energy_rows(_d) and nbody_binaries (mu = 2): NBODY_ERR_UNSUPPORTED while NBODY_OPT_MASSES is 1 (unit masses only), before anything is launched, copied or written.
+ * Mass-weighted pair energies and binaries (mu = m_i + m_j) are not built yet. */
 #define NBODY_BINARY_WORDS 4
 int nbody_pair_energy_rows(int first_row, int n_rows, float *e, int *idx);
 int nbody_pair_energy_rows_d(int first_row, int n_rows, double *e, int *idx);

@@ -875,6 +875,8 @@ int nbody_set_option(int key, int value) { NB_REFUSE_WHILE_SERVED();
       if (!nbl::diag_build() && isa_phase_is_diag(value) && !(g.init && g.fp64 && value == 2)) return NBODY_ERR_UNSUPPORTED;
       g.opt.isa_phase = value; break;
     case NBODY_OPT_WSPLIT: if (value != -1 && value != 1 && value != 4 && value != 16) return NBODY_ERR_ARG; g.opt.wsplit = value; break;
+    // a launch argument of the ordered-sum passes and nothing else: no launch, no sync, the step graph, counters and timers stay
+    case NBODY_OPT_MASSES: if (value != 0 && value != 1) return NBODY_ERR_ARG; g.opt.masses = value; return NBODY_OK;
     default: return NBODY_ERR_ARG;
   }
   if (g.init) { NBC(sync_all()); drop_step_graph(); return reconfigure(); }
@@ -919,6 +921,7 @@ int nbody_get_info(int key, long long* value) {
     case NBODY_INFO_MAILBOX_SERVED: *value = mailbox_served(); break;
     case NBODY_INFO_MAILBOX_SERVING: *value = mailbox_serving() ? 1 : 0; break;
     case NBODY_INFO_DIAG_BUILD: *value = nbl::diag_build() ? 1 : 0; break;
+    case NBODY_INFO_MASSES: *value = g.opt.masses; break;
     default: return NBODY_ERR_ARG;
   }
   return NBODY_OK;
@@ -968,20 +971,20 @@ int nbody_download(BodySystem* host) { NB_REFUSE_WHILE_SERVED(); if (!host) retu
 int nbody_upload_d(const BodySystemD* host) { NB_REFUSE_WHILE_SERVED(); if (!host) return NBODY_ERR_ARG; if (g.init && !g.fp64) return NBODY_ERR_STATE; return upload_impl(host->pos, host->vel); }
 int nbody_download_d(BodySystemD* host) { NB_REFUSE_WHILE_SERVED(); if (!host) return NBODY_ERR_ARG; if (g.init && !g.fp64) return NBODY_ERR_STATE; return download_impl(host->pos, host->vel); }
 
-int bodyForce(float* pos, float* vel, float dt, int n) { NB_ENTER(0); return body_force_impl(pos, vel, dt, (double)dt, n); }
+int bodyForce(float* pos, float* vel, float dt, int n) { NB_ENTER_UNIT_MASS(0); return body_force_impl(pos, vel, dt, (double)dt, n); }
 int integrate(float* pos, const float* vel, float dt, int n) { NB_ENTER(0); return integrate_impl(pos, vel, dt, (double)dt, n); }
-int bodyForce_d(double* pos, double* vel, double dt, int n) { NB_ENTER(1); return body_force_impl(pos, vel, (float)dt, dt, n); }
+int bodyForce_d(double* pos, double* vel, double dt, int n) { NB_ENTER_UNIT_MASS(1); return body_force_impl(pos, vel, (float)dt, dt, n); }
 int integrate_d(double* pos, const double* vel, double dt, int n) { NB_ENTER(1); return integrate_impl(pos, vel, (float)dt, dt, n); }
 
-int nbody_step(float dt, int nsteps) { NB_ENTER(0); return step_impl(dt, (double)dt, nsteps); }
-int nbody_step_d(double dt, int nsteps) { NB_ENTER(1); return step_impl((float)dt, dt, nsteps); }
+int nbody_step(float dt, int nsteps) { NB_ENTER_UNIT_MASS(0); return step_impl(dt, (double)dt, nsteps); }
+int nbody_step_d(double dt, int nsteps) { NB_ENTER_UNIT_MASS(1); return step_impl((float)dt, dt, nsteps); }
 int nbody_sync(void) { NB_REFUSE_WHILE_SERVED(); if (!g.init) return NBODY_ERR_NOT_INIT; return sync_all(); }
 
-int nbody_forces(const float* pos_words, float* force_words, int n) { NB_ENTER(0); return forces_impl(pos_words, force_words, n); }
-int nbody_forces_d(const double* pos_words, double* force_words, int n) { NB_ENTER(1); return forces_impl(pos_words, force_words, n); }
+int nbody_forces(const float* pos_words, float* force_words, int n) { NB_ENTER_UNIT_MASS(0); return forces_impl(pos_words, force_words, n); }
+int nbody_forces_d(const double* pos_words, double* force_words, int n) { NB_ENTER_UNIT_MASS(1); return forces_impl(pos_words, force_words, n); }
 
-int nbody_forces_rows(int first_row, int n_rows, float* force_words) { NB_ENTER(0); return forces_rows_impl(first_row, n_rows, force_words); }
-int nbody_forces_rows_d(int first_row, int n_rows, double* force_words) { NB_ENTER(1); return forces_rows_impl(first_row, n_rows, force_words); }
+int nbody_forces_rows(int first_row, int n_rows, float* force_words) { NB_ENTER_UNIT_MASS(0); return forces_rows_impl(first_row, n_rows, force_words); }
+int nbody_forces_rows_d(int first_row, int n_rows, double* force_words) { NB_ENTER_UNIT_MASS(1); return forces_rows_impl(first_row, n_rows, force_words); }
 
 // the summed spans of one of the locals' timers (locals run concurrently: the slowest device's) and how many they were
 static int timer_total(EventTimer Local::*timer, double* ms_total, long long* count, int reset) {

@@ -35,6 +35,7 @@ int launch_energy(Local& L, int row0, int row_count, bool totals) {
   a.first = L.first;
   a.row0 = row0;
   a.row_count = row_count;
+  a.masses = g.opt.masses;
   HIPC((hipError_t)nbl::launch_energy_kernel(g.fp64, g.opt.arith, L.compute, a));
   if (totals) {
     const int groups = (row_count + kEnergyRows - 1) / kEnergyRows;

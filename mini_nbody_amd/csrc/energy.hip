@@ -20,7 +20,16 @@ namespace {
 // wave-uniform scalar loads (address space 4, as force_smem_f32).  The self pair is skipped by a wave-uniform branch: only the one or two
 // aligned 64-source windows that overlap the wave's own 64 rows compare j with i (adding 0 in place of the self term changes no bit of a
 // sum of non-negative terms); every other window is 3 sub, 3 fma, 1 rsq and 1 add per pair.
-template <typename T, typename V4, int ARITH>
+// MASS (EnergyArgs::masses): s = fma(m_j, inv, s) with m_j the w of the source's word, and the self pair is a select on s — with
+// masses of either sign or a NaN the sum's terms are not non-negative, so the row's own term must not enter at all.  The rows' terms
+// of the totals are then mi = (double)w_i times the unit-mass terms, one fp64 product each.  MASS = false is the code it was.
+template <bool MASS, typename T>
+__device__ __forceinline__ T add_pair(T m, T inv, T s, bool self) {
+  if constexpr (MASS) return self ? s : fma_of(m, inv, s);
+  else return s + (self ? (T)0 : inv);
+}
+
+template <typename T, typename V4, int ARITH, bool MASS>
 __global__ void __launch_bounds__(kEnergyRows) energy_kernel(EnergyArgs a) {
   __shared__ double red[kEnergyWords][kEnergyRows];
   const int row_end = a.row0 + a.row_count;
@@ -44,21 +53,23 @@ __global__ void __launch_bounds__(kEnergyRows) energy_kernel(EnergyArgs a) {
 #pragma unroll 8
         for (int k = 0; k < 64; ++k) {
           const V4 p = src[j + k];
-          s += inv_dist<ARITH>(p.x - me.x, p.y - me.y, p.z - me.z, eps);
+          const T t = inv_dist<ARITH>(p.x - me.x, p.y - me.y, p.z - me.z, eps);
+          if constexpr (MASS) s = fma_of(p.w, t, s);
+          else s += t;
         }
       } else {
 #pragma unroll 8
         for (int k = 0; k < 64; ++k) {
           const V4 p = src[j + k];
           const T t = inv_dist<ARITH>(p.x - me.x, p.y - me.y, p.z - me.z, eps);
-          s += (j + k == i) ? (T)0 : t;
+          s = add_pair<MASS>(p.w, t, s, j + k == i);
         }
       }
     }
     for (; j < b1; ++j) {   // the last block's tail (N not a multiple of 64)
       const V4 p = src[j];
       const T t = inv_dist<ARITH>(p.x - me.x, p.y - me.y, p.z - me.z, eps);
-      s += (j == i) ? (T)0 : t;
+      s = add_pair<MASS>(p.w, t, s, j == i);
     }
     l2 += (double)s;
   }
@@ -68,12 +79,22 @@ __global__ void __launch_bounds__(kEnergyRows) energy_kernel(EnergyArgs a) {
   const V4 v = ((const V4*)a.vel)[live ? lr : row_end - 1];
   const double x = me.x, y = me.y, z = me.z, vx = v.x, vy = v.y, vz = v.z;
   const int t = (int)threadIdx.x;
-  red[0][t] = __builtin_fma(vx, vx, __builtin_fma(vy, vy, vz * vz));
-  red[1][t] = u;
-  red[2][t] = vx; red[3][t] = vy; red[4][t] = vz;
-  red[5][t] = y * vz - z * vy;
-  red[6][t] = z * vx - x * vz;
-  red[7][t] = x * vy - y * vx;
+  if constexpr (MASS) {
+    const double mi = me.w;
+    red[0][t] = mi * __builtin_fma(vx, vx, __builtin_fma(vy, vy, vz * vz));
+    red[1][t] = mi * u;
+    red[2][t] = mi * vx; red[3][t] = mi * vy; red[4][t] = mi * vz;
+    red[5][t] = mi * (y * vz - z * vy);
+    red[6][t] = mi * (z * vx - x * vz);
+    red[7][t] = mi * (x * vy - y * vx);
+  } else {
+    red[0][t] = __builtin_fma(vx, vx, __builtin_fma(vy, vy, vz * vz));
+    red[1][t] = u;
+    red[2][t] = vx; red[3][t] = vy; red[4][t] = vz;
+    red[5][t] = y * vz - z * vy;
+    red[6][t] = z * vx - x * vz;
+    red[7][t] = x * vy - y * vx;
+  }
   __syncthreads();
   if (t < kEnergyWords) {
     const int cnt = min(kEnergyRows, row_end - base);
@@ -94,7 +115,9 @@ __global__ void __launch_bounds__(64) energy_reduce(const double* part, int grou
 
 template <typename T, typename V4, int ARITH>
 void launch_one(hipStream_t st, const EnergyArgs& a) {
-  hipLaunchKernelGGL((energy_kernel<T, V4, ARITH>), dim3((a.row_count + kEnergyRows - 1) / kEnergyRows), dim3(kEnergyRows), 0, st, a);
+  const dim3 grid((a.row_count + kEnergyRows - 1) / kEnergyRows);
+  if (a.masses) hipLaunchKernelGGL((energy_kernel<T, V4, ARITH, true>), grid, dim3(kEnergyRows), 0, st, a);
+  else hipLaunchKernelGGL((energy_kernel<T, V4, ARITH, false>), grid, dim3(kEnergyRows), 0, st, a);
 }
 
 }  // namespace

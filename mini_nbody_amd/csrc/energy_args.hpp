@@ -4,10 +4,11 @@
 //
 // The order of every sum (include/nbody.h, "energy and potential") is fixed by N alone:
 //   level 1  sources in blocks of kEnergyBlock consecutive bodies, each block summed from zero in ascending order in the context
-//            precision, the self pair skipped;
+//            precision, the self pair skipped (with masses: s = fma(m_j, inv, s), the self pair leaves s as it is);
 //   level 2  the block sums converted to fp64 and added in ascending block order from zero: L2_i;  phi_i = 0 - L2_i.
 // Totals (one rank's rows): rows in groups of kEnergyRows from the rank's first body, each group summed in ascending row order in
-// fp64 (one partial per workgroup), then the groups' partials in ascending order (energy_reduce).
+// fp64 (one partial per workgroup), then the groups' partials in ascending order (energy_reduce).  With masses a row's eight terms
+// are each one fp64 product more: mi = (double)w_i times the unit-mass term.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,6 +29,8 @@ struct EnergyArgs {
   int first;         // global index of the rank's row 0
   int row0;          // first row (of the rank's slice) this launch handles
   int row_count;     // rows handled
+  int masses;        // NBODY_OPT_MASSES: 1 = s = fma(m_j, inv, s) with m_j the w of source j's word, and the rows' terms of the totals
+                     // times (double)w_i; 0 = unit masses, w is not read
 };
 
 }  // namespace nbe

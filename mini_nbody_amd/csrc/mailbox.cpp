@@ -274,6 +274,7 @@ int nbody_mailbox_run(void* ram_a, void* ram_b, int clock_khz) {
   if (!g.init) return NBODY_ERR_NOT_INIT;
   if (g.fp64 || !ram_a || !ram_b) return NBODY_ERR_ARG;
   NB_REFUSE_WHILE_SERVED();   // the service thread owns the mailbox: write BEGIN, poll word 0
+  NB_REFUSE_MASSES();         // a request is the reference's force pass: unit masses
   return mailbox_run_impl(ram_a, ram_b, clock_khz, false);
 }
 
@@ -282,6 +283,7 @@ int nbody_mailbox_serve(int on, int clock_khz) {
   if (!g.init) return NBODY_ERR_NOT_INIT;
   if (g.fp64 || g.nranks != 1) return NBODY_ERR_UNSUPPORTED;
   if (mailbox_serving()) { g_serve_khz.store(clock_khz, std::memory_order_relaxed); return NBODY_OK; }
+  NB_REFUSE_MASSES();   // (the option cannot change while the mailbox is served)
   NBC(mailbox_rams());
   NBC(sync_all());
   g_serve_khz.store(clock_khz, std::memory_order_relaxed);

@@ -74,6 +74,10 @@ extern std::atomic<int> g_last_line;
 #define NB_REFUSE_WHILE_SERVED() do { if (::nbi::mailbox_serving()) return NBODY_ERR_STATE; } while (0)
 // ... and an entry point that exists in two precisions — is_d = 0: the float form, 1: the _d form — answers it on a context of the other
 #define NB_ENTER(is_d) do { NB_REFUSE_WHILE_SERVED(); if (::nbi::g.init && (::nbi::g.fp64 != 0) != ((is_d) != 0)) return NBODY_ERR_STATE; } while (0)
+// ... and an entry point whose physics is unit-mass answers NBODY_ERR_UNSUPPORTED while NBODY_OPT_MASSES is 1, after the two checks
+// above and before anything is launched, copied or written: a refusal, never a silently unweighted answer
+#define NB_REFUSE_MASSES() do { if (::nbi::g.opt.masses) return NBODY_ERR_UNSUPPORTED; } while (0)
+#define NB_ENTER_UNIT_MASS(is_d) do { NB_ENTER(is_d); NB_REFUSE_MASSES(); } while (0)
 #define HIPC(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { NB_MARK(); return (int)e_; } } while (0)
 #define NBC(expr) do { int e_ = (expr); if (e_ != NBODY_OK) return e_; } while (0)
 #define NCCLC(expr) do { ncclResult_t r_ = (expr); if (r_ != ncclSuccess) { NB_MARK(); return 2000 + (int)r_; } } while (0)
@@ -188,6 +192,7 @@ struct Options {
   int arith = NBODY_ARITH_FMA3, sum_order = NBODY_SUM_BLOCKED, sum_block = 1024, fuse = -1;
   int timing = 0, comm = NBODY_COMM_AUTO, overlap = 1, isa_phase = 1, waves_per_simd = 0, graph = 1, long_buffers = -1, xcd_map = -1;
   int wsplit = -1;
+  int masses = 0;   // NBODY_OPT_MASSES: the ordered-sum passes weigh source j by the w of its position word (a launch argument, no state)
 };
 
 // what happens to the force of a row once all its segments are summed, and the time step of a kick or drift

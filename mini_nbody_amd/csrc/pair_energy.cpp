@@ -148,13 +148,13 @@ using namespace nbi;
 
 extern "C" {
 
-int nbody_pair_energy_rows(int first_row, int n_rows, float* e, int* idx) { NB_ENTER(0);
+int nbody_pair_energy_rows(int first_row, int n_rows, float* e, int* idx) { NB_ENTER_UNIT_MASS(0);
   return rows_impl(first_row, n_rows, e, idx);
 }
-int nbody_pair_energy_rows_d(int first_row, int n_rows, double* e, int* idx) { NB_ENTER(1);
+int nbody_pair_energy_rows_d(int first_row, int n_rows, double* e, int* idx) { NB_ENTER_UNIT_MASS(1);
   return rows_impl(first_row, n_rows, e, idx);
 }
-int nbody_binaries(double e_max, int max_pairs, int* n_pairs, int* i, int* j, double* elements) { NB_REFUSE_WHILE_SERVED();
+int nbody_binaries(double e_max, int max_pairs, int* n_pairs, int* i, int* j, double* elements) { NB_REFUSE_WHILE_SERVED(); NB_REFUSE_MASSES();
   return binaries_impl(e_max, max_pairs, n_pairs, i, j, elements);
 }
 

@@ -55,6 +55,7 @@ int launch_point_sums(Local& L, const PointPass& pass, const Queries& q, const R
     a.m = m;
     a.n_blocks = n_blocks;
     a.chunk_blocks = plan.chunk_blocks;
+    a.masses = g.opt.masses;
     HIPC((hipError_t)nbl::launch_point_sums_kernel(pass, g.fp64, g.opt.arith, L.compute, plan.chunks, a));
     if (plan.chunks > 1) HIPC((hipError_t)nbl::launch_point_sums_combine_kernel(pass, g.fp64, L.compute, a));
     return NBODY_OK;

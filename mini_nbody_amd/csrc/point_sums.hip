@@ -21,17 +21,23 @@ namespace {
 // ---- the pass statements.  pair: one source into the level-1 sums c of a point; every intermediate comes before the CMP return, which
 // ---- keeps the CMP = false body free of branches; CMP: source j == sk leaves c as it is.  store: a point's result from its level-2 sums.
 
+// MASS (NBODY_OPT_MASSES = 1): the one extra rounding of a pair, m = the w of the source's word as it lies in src — x * m in this
+// operand order; MASS = false is x itself, so that the unweighted instantiations are what they were
+template <bool MASS, typename T>
+__device__ __forceinline__ T weighted(T m, T x) { if constexpr (MASS) return x * m; else return x; }
+
 struct FieldSums {
   static constexpr int kSums = kFieldPass.sums;   // {ax, ay, az, s}
   static constexpr bool kVel = kFieldPass.velocities;
-  // 3 sub, d2, 1/sqrt, 2 mul (the force's cube), 3 fma, 1 add
-  template <int ARITH, bool CMP, typename T, typename V4>
+  // 3 sub, d2, 1/sqrt, 2 mul (the force's cube), 3 fma, 1 add; MASS: 1 mul (w3 = m inv3) more, and the add is an fma
+  template <int ARITH, bool CMP, bool MASS, typename T, typename V4>
   static __device__ __forceinline__ void pair(const V4 p, const V4 me, T eps, int j, int sk, T (&c)[kSums]) {
     const T dx = p.x - me.x, dy = p.y - me.y, dz = p.z - me.z;
     const T inv = inv_dist<ARITH>(dx, dy, dz, eps);
     const T inv2 = inv * inv;
     const T inv3 = inv * inv2;
-    const T ax = fma_of(dx, inv3, c[0]), ay = fma_of(dy, inv3, c[1]), az = fma_of(dz, inv3, c[2]), s = c[3] + inv;
+    const T w3 = weighted<MASS>(p.w, inv3);
+    const T ax = fma_of(dx, w3, c[0]), ay = fma_of(dy, w3, c[1]), az = fma_of(dz, w3, c[2]), s = MASS ? fma_of(p.w, inv, c[3]) : c[3] + inv;
     if (CMP && j == sk) return;
     c[0] = ax; c[1] = ay; c[2] = az; c[3] = s;
   }
@@ -46,19 +52,19 @@ struct TidalSums {
   static constexpr int kSums = kTidalPass.sums;   // {qxx, qyy, qzz, qxy, qxz, qyz, s3}
   static constexpr bool kVel = kTidalPass.velocities;
   // 3 sub, d2, 1/sqrt, 3 mul (inv2, inv3, inv5), 1 mul (w = 3 inv5), 3 mul (w d), 6 fma, 1 add: 21 VALU + 1 transcendental in the fp32
-  // timed form
-  template <int ARITH, bool CMP, typename T, typename V4>
+  // timed form; MASS: 1 mul (w = (3 inv5) m) more, and the add is an fma
+  template <int ARITH, bool CMP, bool MASS, typename T, typename V4>
   static __device__ __forceinline__ void pair(const V4 p, const V4 me, T eps, int j, int sk, T (&c)[kSums]) {
     const T dx = p.x - me.x, dy = p.y - me.y, dz = p.z - me.z;
     const T inv = inv_dist<ARITH>(dx, dy, dz, eps);
     const T inv2 = inv * inv;
     const T inv3 = inv * inv2;
     const T inv5 = inv3 * inv2;
-    const T w = (T)3 * inv5;
+    const T w = weighted<MASS>(p.w, (T)3 * inv5);
     const T wx = w * dx, wy = w * dy, wz = w * dz;
     const T xx = fma_of(wx, dx, c[0]), yy = fma_of(wy, dy, c[1]), zz = fma_of(wz, dz, c[2]);
     const T xy = fma_of(wx, dy, c[3]), xz = fma_of(wx, dz, c[4]), yz = fma_of(wy, dz, c[5]);
-    const T s3 = c[6] + inv3;
+    const T s3 = MASS ? fma_of(p.w, inv3, c[6]) : c[6] + inv3;
     if (CMP && j == sk) return;
     c[0] = xx; c[1] = yy; c[2] = zz; c[3] = xy; c[4] = xz; c[5] = yz; c[6] = s3;
   }
@@ -75,8 +81,8 @@ struct JerkSums {
   static constexpr int kSums = kJerkPass.sums;   // {ax, ay, az, jx, jy, jz}
   static constexpr bool kVel = kJerkPass.velocities;   // pair takes the two velocities beside the two positions
   // 6 sub, d2, 1/sqrt, 2 mul (the cube), 1 mul + 2 fma (d . w), 2 mul (3 rv, inv2), 3 fma (t), 3 fma (the field's), 3 fma: 25 VALU + 1
-  // transcendental in the fp32 timed form.  p, me: positions; u, mv: velocities of the source and of the query
-  template <int ARITH, bool CMP, typename T, typename V4>
+  // transcendental in the fp32 timed form; MASS: 1 mul (w3 = m inv3) more.  p, me: positions; u, mv: velocities of the source and of the query
+  template <int ARITH, bool CMP, bool MASS, typename T, typename V4>
   static __device__ __forceinline__ void pair(const V4 p, const V4 u, const V4 me, const V4 mv, T eps, int j, int sk, T (&c)[kSums]) {
     const T dx = p.x - me.x, dy = p.y - me.y, dz = p.z - me.z;
     const T wx = u.x - mv.x, wy = u.y - mv.y, wz = u.z - mv.z;
@@ -86,8 +92,9 @@ struct JerkSums {
     const T rv = fma_of(dx, wx, fma_of(dy, wy, dz * wz));
     const T b = ((T)3 * rv) * inv2;
     const T tx = fma_of(-b, dx, wx), ty = fma_of(-b, dy, wy), tz = fma_of(-b, dz, wz);
-    const T ax = fma_of(dx, inv3, c[0]), ay = fma_of(dy, inv3, c[1]), az = fma_of(dz, inv3, c[2]);
-    const T jx = fma_of(tx, inv3, c[3]), jy = fma_of(ty, inv3, c[4]), jz = fma_of(tz, inv3, c[5]);
+    const T w3 = weighted<MASS>(p.w, inv3);
+    const T ax = fma_of(dx, w3, c[0]), ay = fma_of(dy, w3, c[1]), az = fma_of(dz, w3, c[2]);
+    const T jx = fma_of(tx, w3, c[3]), jy = fma_of(ty, w3, c[4]), jz = fma_of(tz, w3, c[5]);
     if (CMP && j == sk) return;
     c[0] = ax; c[1] = ay; c[2] = az; c[3] = jx; c[4] = jy; c[5] = jz;
   }
@@ -116,11 +123,11 @@ __device__ __forceinline__ QueryWords<V4> query_words(const PointSumsArgs& a, in
 }
 
 // source j into the sums c: its position and (a pass with velocities) its velocity, both wave-uniform scalar loads
-template <class P, int ARITH, bool CMP, typename T, typename V4>
+template <class P, int ARITH, bool CMP, bool MASS, typename T, typename V4>
 __device__ __forceinline__ void pair_of(const NB_CONST V4* src, const NB_CONST V4* vsrc, int j, const V4 me, const V4 mv, T eps, int sk,
                                         T (&c)[P::kSums]) {
-  if constexpr (P::kVel) P::template pair<ARITH, CMP, T, V4>(src[j], vsrc[j], me, mv, eps, j, sk, c);
-  else P::template pair<ARITH, CMP, T, V4>(src[j], me, eps, j, sk, c);
+  if constexpr (P::kVel) P::template pair<ARITH, CMP, MASS, T, V4>(src[j], vsrc[j], me, mv, eps, j, sk, c);
+  else P::template pair<ARITH, CMP, MASS, T, V4>(src[j], me, eps, j, sk, c);
 }
 
 // One point per lane, kLanes points per workgroup; workgroup (x, y) walks the blocks of chunk y for the points of x.  Sources
@@ -129,7 +136,7 @@ __device__ __forceinline__ void pair_of(const NB_CONST V4* src, const NB_CONST V
 // the last point and store nothing.  SKIP: only the aligned 64-source windows that overlap [lowest, highest] skip index of the wave's
 // 64 points compare j with skip (a wave-uniform branch); every other window, and every window of the SKIP = false form, is the pass's
 // branch-free pair (field: 3 sub, 3 fma, 1 rsq, 2 mul, 3 fma and 1 add).
-template <class P, typename T, typename V4, int ARITH, bool SKIP>
+template <class P, typename T, typename V4, int ARITH, bool SKIP, bool MASS>
 __global__ void __launch_bounds__(kLanes) block_sums_kernel(PointSumsArgs a) {
   constexpr int S = P::kSums;
   const auto [p, live, pc] = lane_of(a.m);
@@ -149,13 +156,13 @@ __global__ void __launch_bounds__(kLanes) block_sums_kernel(PointSumsArgs a) {
     for (; j + 64 <= b1; j += 64) {
       if (!SKIP || j + 63 < wlo || j > whi) {
 #pragma unroll 8
-        for (int k = 0; k < 64; ++k) pair_of<P, ARITH, false, T, V4>(src, vsrc, j + k, me, mv, eps, sk, c);
+        for (int k = 0; k < 64; ++k) pair_of<P, ARITH, false, MASS, T, V4>(src, vsrc, j + k, me, mv, eps, sk, c);
       } else {
 #pragma unroll 8
-        for (int k = 0; k < 64; ++k) pair_of<P, ARITH, true, T, V4>(src, vsrc, j + k, me, mv, eps, sk, c);
+        for (int k = 0; k < 64; ++k) pair_of<P, ARITH, true, MASS, T, V4>(src, vsrc, j + k, me, mv, eps, sk, c);
       }
     }
-    for (; j < b1; ++j) pair_of<P, ARITH, SKIP, T, V4>(src, vsrc, j, me, mv, eps, sk, c);   // the last block's tail (N not a multiple of 64)
+    for (; j < b1; ++j) pair_of<P, ARITH, SKIP, MASS, T, V4>(src, vsrc, j, me, mv, eps, sk, c);   // the last block's tail (N not a multiple of 64)
     if (sc) {
       if (live) {
         const size_t w = (size_t)blk * S * (size_t)a.m + (size_t)p;
@@ -187,11 +194,17 @@ __global__ void __launch_bounds__(kLanes) block_sums_combine(PointSumsArgs a) {
   P::template store<T, V4>(a, p, l2);
 }
 
-template <class P, typename T, typename V4, int ARITH>
+template <class P, typename T, typename V4, int ARITH, bool MASS>
 void launch_sums_one(hipStream_t st, int chunks, const PointSumsArgs& a) {
   const dim3 grid((a.m + kLanes - 1) / kLanes, chunks);
-  if (a.skip || !a.points) hipLaunchKernelGGL((block_sums_kernel<P, T, V4, ARITH, true>), grid, dim3(kLanes), 0, st, a);   // (rows leave themselves out)
-  else hipLaunchKernelGGL((block_sums_kernel<P, T, V4, ARITH, false>), grid, dim3(kLanes), 0, st, a);
+  if (a.skip || !a.points) hipLaunchKernelGGL((block_sums_kernel<P, T, V4, ARITH, true, MASS>), grid, dim3(kLanes), 0, st, a);   // (rows leave themselves out)
+  else hipLaunchKernelGGL((block_sums_kernel<P, T, V4, ARITH, false, MASS>), grid, dim3(kLanes), 0, st, a);
+}
+
+template <class P, typename T, typename V4, int ARITH>
+void launch_sums_one(hipStream_t st, int chunks, const PointSumsArgs& a) {
+  if (a.masses) launch_sums_one<P, T, V4, ARITH, true>(st, chunks, a);
+  else launch_sums_one<P, T, V4, ARITH, false>(st, chunks, a);
 }
 
 template <class P>

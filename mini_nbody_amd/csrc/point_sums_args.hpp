@@ -9,6 +9,8 @@
 //              field (4)  ax = fma(dx, inv3, ax), ay, az likewise, s = s + inv;
 //              tidal (7)  w = 3 inv5, q_ab = fma(w d_a, d_b, q_ab) for ab = xx, yy, zz, xy, xz, yz, s3 = s3 + inv3;
 //              jerk (6)   the field's ax, ay, az; with w = v_j - u, b = 3 (d . w) inv2, t_a = fma(-b, d_a, w_a): j_a = fma(t_a, inv3, j_a);
+//            with masses (PointSumsArgs::masses, m = the w of source j's word): field and jerk take w3 = m * inv3 where inv3 stands
+//            above, the tidal w = (3 inv5) * m; s = fma(m, inv, s), s3 = fma(m, inv3, s3).  Nothing else differs.
 //   level 2  the blocks' sums converted to fp64 and added in ascending block order from zero, then rounded once.
 //              field      accel = (T){A}, phi = (T)(0 - S);
 //              tidal      T_aa = (T)(Q_aa - S3), T_ab = (T)Q_ab;
@@ -55,6 +57,8 @@ struct PointSumsArgs {
   const void* pvel;     // [m] words {ux, uy, uz, ignored}: the points' velocities
   int first;            // points == null, the rows form: query p is source first + p — its point src[first + p], its velocity
                         // vsrc[first + p] — and leaves itself out (skip and pvel stay null)
+  int masses;           // NBODY_OPT_MASSES: 1 = source j weighs the w of its src word, one more rounding per pair (include/nbody.h); 0 =
+                        // unit masses, w is not read.  The w of a points word is ignored either way
 };
 
 // scratch bytes of a launch of m points (per-block sums: independent of the number of chunks)

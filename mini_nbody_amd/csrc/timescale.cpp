@@ -169,10 +169,10 @@ int nbody_min_timescale(float* tau2, int* i, int* j, float* d2min) { NB_ENTER(0)
 int nbody_min_timescale_d(double* tau2, int* i, int* j, double* d2min) { NB_ENTER(1);
   return min_timescale_impl(tau2, i, j, d2min);
 }
-int nbody_step_adaptive(float eta, float t_end, float dt_min, float dt_max, int max_steps, double* t_reached, int* steps_taken) { NB_ENTER(0);
+int nbody_step_adaptive(float eta, float t_end, float dt_min, float dt_max, int max_steps, double* t_reached, int* steps_taken) { NB_ENTER_UNIT_MASS(0);
   return step_adaptive_impl((double)eta, (double)t_end, (double)dt_min, (double)dt_max, max_steps, t_reached, steps_taken);
 }
-int nbody_step_adaptive_d(double eta, double t_end, double dt_min, double dt_max, int max_steps, double* t_reached, int* steps_taken) { NB_ENTER(1);
+int nbody_step_adaptive_d(double eta, double t_end, double dt_min, double dt_max, int max_steps, double* t_reached, int* steps_taken) { NB_ENTER_UNIT_MASS(1);
   return step_adaptive_impl(eta, t_end, dt_min, dt_max, max_steps, t_reached, steps_taken);
 }
 

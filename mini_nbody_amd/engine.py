@@ -56,7 +56,14 @@ class NBody:
                     isa_phase=self.info(L.INFO_ISA_PHASE), long_buffers=self.info(L.INFO_LONG_BUFFERS),
                     xcd_map=self.info(L.INFO_XCD_MAP), fuse=self.info(L.INFO_FUSE_COMBINE),
                     n_local=self.info(L.INFO_N_LOCAL), first_body=self.info(L.INFO_FIRST_BODY),
-                    rank=self.info(L.INFO_RANK), nranks=self.info(L.INFO_NRANKS))
+                    rank=self.info(L.INFO_RANK), nranks=self.info(L.INFO_NRANKS), masses=self.info(L.INFO_MASSES))
+
+    def use_masses(self, on=True):
+        """NBODY_OPT_MASSES: with on, body j has the mass pos[j, 3] — the w of its position word as it lies on the device, uploaded and
+        downloaded with the positions and carried by every integrator — in energy(), potential_rows(), field(), tidal(), jerk() and the
+        Hermite integrators; the unit-mass entry points (step, forces, bodyForce, step_adaptive, pair energies, binaries, the mailbox)
+        raise ERR_UNSUPPORTED until it is switched off again.  Launches nothing and invalidates nothing."""
+        self.set_option(L.OPT_MASSES, 1 if on else 0)
 
     # ---- state ----
     def _bs(self, pos, vel):
@@ -133,7 +140,8 @@ class NBody:
         return out
 
     def energy(self):
-        """Energy and momenta of the state on the device (nbody_energy; unit masses, G = 1, the force's softening): dict(kinetic,
+        """Energy and momenta of the state on the device (nbody_energy; unit masses, or after use_masses() the masses in pos[:, 3]; G = 1, the
+        force's softening): dict(kinetic,
         potential, total, momentum=(3,), angular_momentum=(3,)), fp64.  Collective in a multi-rank job; every rank gets the same bits."""
         out = np.zeros(L.ENERGY_WORDS, np.float64)
         L.check(self.lib.nbody_energy(out.ctypes.data_as(C.POINTER(C.c_double))))

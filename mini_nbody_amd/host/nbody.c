@@ -8,7 +8,7 @@
  *
  * usage: nbody [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K]
  *              [--sum seq|blocked] [--block K] [--one-launch | --two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16]
- *              [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--binaries] [--hermite] [--hermite-block LEVELS]
+ *              [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--binaries] [--hermite] [--hermite-block LEVELS] [--masses]
  * --hermite: the device loop's iterations are fourth-order Hermite steps (nbody_step_hermite) instead of kick-drift steps: one warm-up
  * call of one step, the initial state uploaded again, then ONE timed call of all `iters` steps (a call opens with a jerk pass of its own,
  * so two calls would not be one run: include/nbody.h, "a call is stateless"); the time per step is that call's over iters.  Refused
@@ -16,6 +16,9 @@
  * --hermite-block LEVELS (1 <= LEVELS <= 24): as --hermite, but an iteration is one block of dt_max = 0.01 with individual block time
  * steps on LEVELS levels and eta = 0.02 (nbody_step_hermite_block); one more line, "hermite block: LEVELS levels, S sub-steps, R row
  * evaluations (F of sub-steps x N)", gives the timed call's counters.  LEVELS = 1 is --hermite bit for bit.
+ * --masses (with --hermite or --hermite-block only; anything else is a usage error): body i gets the mass 2^-(i mod 4) in the w of its
+ * position word — exact in both precisions and fixed by i alone — NBODY_OPT_MASSES is switched on, and the --energy lines are printed:
+ * the weighted E, T and U before the first iteration and after the last.
  * --energy: E = T + U, T and U of the state on the device (nbody_energy) before the first iteration and after the last, and the
  * relative drift, outside the timed region.
  * --field M: after the last iteration, acceleration and potential of the state on the device (nbody_field) at M points — the position
@@ -251,7 +254,7 @@ static int print_pair_histogram(int bins, int fp64) {
 }
 
 int main(int argc, char **argv) {
-  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0, tidal = 0, jerk = 0, closest = 0, pair_hist = 0, binaries = 0, hermite = 0, block_levels = 0;
+  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0, tidal = 0, jerk = 0, closest = 0, pair_hist = 0, binaries = 0, hermite = 0, block_levels = 0, masses = 0;
   double e0 = 0.0, adaptive = 0.0;
   unsigned long long seed = NBODY_IC_DEFAULT_SEED;
   for (int a = 1; a < argc; ++a) {
@@ -263,6 +266,7 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--host-loop")) host_loop = 1;
     else if (!strcmp(argv[a], "--hermite")) hermite = 1;
     else if (!strcmp(argv[a], "--hermite-block") && a + 1 < argc) { hermite = 1; block_levels = atoi(argv[++a]); if (block_levels < 1 || block_levels > 24) { fprintf(stderr, "--hermite-block needs 1 <= LEVELS <= 24\n"); return 2; } }
+    else if (!strcmp(argv[a], "--masses")) masses = 1;
     else if (!strcmp(argv[a], "--strict")) strict = 1;
     else if (!strcmp(argv[a], "--rtl")) rtl = 1;
     else if (!strcmp(argv[a], "--energy")) energy = 1;
@@ -282,12 +286,14 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--block") && a + 1 < argc) block = atoi(argv[++a]);
     else if (argv[a][0] != '-' && npos == 0) { n = atoi(argv[a]); npos++; }
     else if (argv[a][0] != '-' && npos == 1) { iters = atoi(argv[a]); npos++; }
-    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--binaries] [--hermite] [--hermite-block LEVELS]\n", argv[0]); return 2; }
+    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--binaries] [--hermite] [--hermite-block LEVELS] [--masses]\n", argv[0]); return 2; }
   }
   if (field < 0) { fprintf(stderr, "--field needs M >= 1\n"); return 2; }
   if (tidal < 0) { fprintf(stderr, "--tidal needs M >= 1\n"); return 2; }
   if (jerk < 0 || jerk > n) { fprintf(stderr, "--jerk needs 1 <= M <= N\n"); return 2; }
   if (hermite && host_loop) { fprintf(stderr, "--hermite runs the device loop: not together with --host-loop\n"); return 2; }
+  if (masses && !hermite) { fprintf(stderr, "--masses needs --hermite or --hermite-block: the kick-drift step is unit-mass\n"); return 2; }
+  if (masses) energy = 1;
   if (n <= 0 || iters < 2) { fprintf(stderr, "need N > 0 and iters >= 2 (iteration 1 is warm-up)\n"); return 2; }
   const float dt = 0.01f;
   const size_t words = (size_t)n * 4;
@@ -303,6 +309,7 @@ int main(int argc, char **argv) {
     CHECK(nbody_set_option(NBODY_OPT_SUM_ORDER, NBODY_SUM_FPGA16));
     CHECK(nbody_set_option(NBODY_OPT_JSUB, 1));
   }
+  if (masses) CHECK(nbody_set_option(NBODY_OPT_MASSES, 1));                    /* m_j = the w of body j's position word */
   if (jsub > 0) CHECK(nbody_set_option(NBODY_OPT_JSUB, jsub));                 /* source segments (summation order) */
   if (sum >= 0) CHECK(nbody_set_option(NBODY_OPT_SUM_ORDER, sum));             /* one sequential sum per segment, or blocks */
   if (block > 0) CHECK(nbody_set_option(NBODY_OPT_SUM_BLOCK, block));
@@ -319,6 +326,7 @@ int main(int argc, char **argv) {
     if (!buf) return 3;
     BodySystem p = { buf, buf + words };
     nbody_ic_fill_f32(p.pos, p.vel, (size_t)n, 0, (size_t)n, seed);
+    if (masses) for (int i = 0; i < n; ++i) p.pos[4 * (size_t)i + 3] = ldexpf(1.0f, -(i % 4));
     if (energy) { CHECK(nbody_upload(&p)); if (print_energy(0, &e0, 1)) return 1; }
     if (host_loop) {
       for (int it = 1; it <= iters; ++it) {
@@ -366,6 +374,7 @@ int main(int argc, char **argv) {
     if (!buf) return 3;
     BodySystemD p = { buf, buf + words };
     nbody_ic_fill_f64(p.pos, p.vel, (size_t)n, 0, (size_t)n, seed);
+    if (masses) for (int i = 0; i < n; ++i) p.pos[4 * (size_t)i + 3] = ldexp(1.0, -(i % 4));
     if (energy) { CHECK(nbody_upload_d(&p)); if (print_energy(0, &e0, 1)) return 1; }
     if (host_loop) {
       for (int it = 1; it <= iters; ++it) {

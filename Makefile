@@ -12,21 +12,21 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-s
 all: lib host oracle microbench
 
 # The library = ONE device code object (device.hip: the force path's kernels.hip — the nbk kernels + the launch functions that pick an
-# instantiation, ~45 s of hipcc — the energy pass's energy.hip, the field, tidal and jerk passes' point_sums.hip, the neighbour pass's neighbors.hip, the k-nearest-neighbour pass's knn.hip, the friends-of-friends pass's fof.hip, the radial-count pass's hist.hip, the pair time-scale pass's timescale.hip, the pair binding-energy pass's pair_energy.hip, the Hermite step's hermite.hip and the block step's hermite_block.hip) and thirteen
-# host-only C++ files (context, comm, mailbox, energy, point_sums, neighbors, knn, fof, hist, timescale, pair_energy, hermite, hermite_block: seconds each) behind csrc/nbody_internal.hpp.  A host-side edit relinks in seconds.
+# instantiation, ~45 s of hipcc — the energy pass's energy.hip, the field, tidal, jerk and snap passes' point_sums.hip, the neighbour pass's neighbors.hip, the k-nearest-neighbour pass's knn.hip, the friends-of-friends pass's fof.hip, the radial-count pass's hist.hip, the pair time-scale pass's timescale.hip, the pair binding-energy pass's pair_energy.hip, the Hermite step's hermite.hip, the block step's hermite_block.hip and the sixth-order Hermite step's hermite6.hip) and fourteen
+# host-only C++ files (context, comm, mailbox, energy, point_sums, neighbors, knn, fof, hist, timescale, pair_energy, hermite, hermite_block, hermite6: seconds each) behind csrc/nbody_internal.hpp.  A host-side edit relinks in seconds.
 # The eight diagnostic passes share csrc/diag_pass.hpp (device code — the distance passes' pair distance and query preamble included — the sizes
 # their hosts read and the guard of a split launch) and csrc/query_pass.hpp (host only: the flow of a call and the two split rules).
 HOSTFLAGS := -O2 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function
 OBJ      := build/obj
 KERNEL_SRC := $(CSRC)/kernels.hip $(CSRC)/nbody_kernels.hpp $(CSRC)/nbody_args.hpp $(CSRC)/force_loop_gfx950.inc
 HOST_HDR := $(CSRC)/nbody_internal.hpp $(CSRC)/nbody_args.hpp $(CSRC)/query_pass.hpp $(CSRC)/diag_pass.hpp include/nbody.h
-HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o $(OBJ)/energy.o $(OBJ)/point_sums.o $(OBJ)/neighbors.o $(OBJ)/knn.o $(OBJ)/fof.o $(OBJ)/hist.o $(OBJ)/timescale.o $(OBJ)/pair_energy.o $(OBJ)/hermite.o $(OBJ)/hermite_block.o
+HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o $(OBJ)/energy.o $(OBJ)/point_sums.o $(OBJ)/neighbors.o $(OBJ)/knn.o $(OBJ)/fof.o $(OBJ)/hist.o $(OBJ)/timescale.o $(OBJ)/pair_energy.o $(OBJ)/hermite.o $(OBJ)/hermite_block.o $(OBJ)/hermite6.o
 # the energy diagnostics' device code (energy.hip, seconds of hipcc on its own) reads nbody_args.hpp and changes nothing of the force path's
 # hashed source (KERNEL_SRC); device.hip compiles it with kernels.hip into the library's one code object.  Its host side is energy.cpp, one
 # of HOST_OBJ.  What it shares with the seven passes below is diag_pass.hpp, which is no part of the hashed source either.
 ENERGY_SRC := $(CSRC)/energy.hip $(CSRC)/energy_args.hpp
 # the field pass (acceleration and potential at arbitrary points), the tidal pass (the tidal tensor there, the gradient of the field) and
-# the jerk pass (the field's time derivative at rows and phase-space points) in the same way, the three as one: point_sums.hip beside
+# the jerk pass (the field's time derivative at rows and phase-space points) and the snap pass (its second time derivative) in the same way, the four as one: point_sums.hip beside
 # energy.hip, point_sums.cpp one of HOST_OBJ
 POINT_SUMS_SRC := $(CSRC)/point_sums.hip $(CSRC)/point_sums_args.hpp
 # the neighbour pass (nearest body, radius count, closest pair) likewise: neighbors.hip beside point_sums.hip, neighbors.cpp one of HOST_OBJ
@@ -49,7 +49,11 @@ HERMITE_SRC := $(CSRC)/hermite.hip $(CSRC)/hermite_args.hpp
 # likewise: hermite_block.hip beside hermite.hip, hermite_block.cpp one of HOST_OBJ; it shares hermite.cpp's opening and gathers through
 # hermite_host.hpp, and its all-pairs work is the jerk points pass of point_sums.hip
 HERMITE_BLOCK_SRC := $(CSRC)/hermite_block.hip $(CSRC)/hermite_block_args.hpp
-DEVICE_SRC := $(CSRC)/device.hip $(KERNEL_SRC) $(CSRC)/diag_pass.hpp $(ENERGY_SRC) $(POINT_SUMS_SRC) $(NEIGHBORS_SRC) $(KNN_SRC) $(FOF_SRC) $(HIST_SRC) $(TIMESCALE_SRC) $(PAIR_ENERGY_SRC) $(HERMITE_SRC) $(HERMITE_BLOCK_SRC)
+# the sixth-order Hermite step's elementwise kernels (predictor, corrector with the crackle) likewise: hermite6.hip beside hermite_block.hip,
+# hermite6.cpp one of HOST_OBJ; it shares hermite.cpp's buffers, gathers, minimum and adaptive loop through hermite_host.hpp, and its
+# all-pairs work is the snap pass of point_sums.hip
+HERMITE6_SRC := $(CSRC)/hermite6.hip $(CSRC)/hermite6_args.hpp
+DEVICE_SRC := $(CSRC)/device.hip $(KERNEL_SRC) $(CSRC)/diag_pass.hpp $(ENERGY_SRC) $(POINT_SUMS_SRC) $(NEIGHBORS_SRC) $(KNN_SRC) $(FOF_SRC) $(HIST_SRC) $(TIMESCALE_SRC) $(PAIR_ENERGY_SRC) $(HERMITE_SRC) $(HERMITE_BLOCK_SRC) $(HERMITE6_SRC)
 
 lib: $(PKG)/libnbody_hip.so
 $(OBJ)/device.o: $(DEVICE_SRC) $(HOST_HDR)
@@ -68,6 +72,7 @@ $(OBJ)/timescale.o: $(CSRC)/timescale_args.hpp
 $(OBJ)/pair_energy.o: $(CSRC)/pair_energy_args.hpp
 $(OBJ)/hermite.o: $(CSRC)/hermite_args.hpp $(CSRC)/hermite_host.hpp
 $(OBJ)/hermite_block.o: $(CSRC)/hermite_args.hpp $(CSRC)/hermite_host.hpp $(CSRC)/hermite_block_args.hpp
+$(OBJ)/hermite6.o: $(CSRC)/hermite6_args.hpp $(CSRC)/hermite_host.hpp
 $(PKG)/libnbody_hip.so: $(OBJ)/device.o $(HOST_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -pthread -o $@ $^ -ldl
 

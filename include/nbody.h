@@ -516,6 +516,60 @@ int nbody_jerk_d(const double *points, const double *velocities, int m, const in
 int nbody_jerk_rows(int first_row, int n_rows, float *accel, float *jerk);
 int nbody_jerk_rows_d(int first_row, int n_rows, double *accel, double *jerk);
 
+/* ---- snap: the second time derivative of the acceleration, at rows and at phase-space points (not in the reference) ----
+ * For a point x that moves with velocity u and acceleration a_x and the N bodies on the device (positions r_j, velocities v_j,
+ * accelerations a_j), unit masses, G = 1, eps the force's softening, d = r_j - x, w = v_j - u, g = a_j - a_x, inv = (|d|^2 + eps)^(-1/2),
+ * alpha = (d . w) inv^2, beta = (w . w + d . g) inv^2 + alpha^2 (Nitadori & Makino 2008):
+ *   a(x)          = sum_j A_j,  A_j = d inv^3                          the acceleration of nbody_jerk, bit for bit
+ *   j(x, u)       = sum_j J_j,  J_j = w inv^3 - 3 alpha A_j            the jerk of nbody_jerk, bit for bit
+ *   s(x, u, a_x)  = d2a/dt2 = sum_j ( g inv^3 - 6 alpha J_j - 3 beta A_j )
+ * over ALL j; skip as in nbody_jerk.  The bodies' accelerations a_j are not part of the state: every call first runs the jerk rows pass
+ * over all N rows (a_j = the acceleration nbody_jerk_rows returns for row j) and brings the N words to every device; the query's own
+ * acceleration a_x is the caller's (points) or a_i (rows).  What it is for: the sixth-order Hermite scheme below and higher-order time
+ * step criteria.
+ * Pair arithmetic, in the context precision T, every operation rounded once.  d, w, inv, inv2, inv3, rv, c, b, t, the field's three fma
+ * and the jerk's three fma are nbody_jerk's to the letter, in every arithmetic; then
+ *   gx = axj - ax_x  (gy, gz likewise)
+ *   alpha = rv * inv2
+ *   q = fma(dx, gx, fma(dy, gy, fma(dz, gz, fma(wx, wx, fma(wy, wy, wz * wz)))))
+ *   beta = fma(alpha, alpha, q * inv2)
+ *   k6 = (T)6 * alpha     k3 = (T)3 * beta
+ *   ux = fma(-k3, dx, fma(-k6, tx, gx))  (uy, uz likewise)
+ *   sx = fma(ux, inv3, sx)  (sy, sz likewise)
+ * ORDER (fixed by N alone; it is the potential's):
+ *   level 1: the sources in blocks of 1024 consecutive bodies; per block the nine accumulators from +0 in ascending j; for
+ *            j == skip[p] all nine keep their values;
+ *   level 2: the blocks' nine sums converted to fp64 and added in ascending block order from zero, each rounded once to T.
+ * The bits of a query's result depend on the N source positions and velocities, the query (x, u, a_x), its skip, the arithmetic and the
+ * precision, and on nothing else — not on m, on where the query stands in the array, on which of the two forms brings it, on the launch
+ * shape (NBODY_SNAP_SPLIT, NBODY_JERK_SPLIT), on the force configuration or on the device or rank count.  No atomics.
+ * DOMAIN: a point on a body that moves with that body's velocity and acceleration gets +0 from it in all three outputs; with another
+ * acceleration it gets g eps^(-3/2) in the snap.  A separation whose square overflows gives inv = 0 and contributes +0 to all three as
+ * long as no product with it overflows; beyond that inf * 0 makes the jerk or the snap NaN.  A NaN position, velocity or acceleration of
+ * a body poisons the snap of every query that does not skip it — and a NaN position or velocity of ANY body, skipped or not, reaches
+ * the snap of every query through the accelerations a_j of the bodies beside it.
+ * nbody_snap(_d): points, velocities, accelerations: m words {., ., ., ignored} each in the context precision, host memory.  accel, jerk,
+ *   snap: m words {., ., ., 0} each; any may be NULL, not all three.  skip and the division of the points over devices and ranks as in
+ *   nbody_jerk.
+ * nbody_snap_rows(_d): rows exactly as in nbody_jerk_rows.  Row i's query is (r_i, v_i, a_i) with skip = i: bit for bit what nbody_snap
+ *   returns for it.  Nothing makes a round trip through the host.
+ * All four bring positions and velocities as nbody_jerk does, run the jerk rows pass on every device's own rows, bring ALL N
+ * accelerations to every device the same way (one device reads its own; the devices of an nbody_init context copy each other's; an
+ * nbody_init_rank job gathers them with the transport it uses for positions and then gathers the velocities again) and run the snap
+ * pass: two all-pairs passes per call.  An nbody_init_rank job is collective through the gathers only, every rank calls.  They leave
+ * positions, velocities, the arrival counters, the captured step graph and the force-kernel timer as they were.
+ * Environment, read on every call: NBODY_SNAP_SPLIT and NBODY_SNAP_SCRATCH_MB as NBODY_JERK_SPLIT and NBODY_JERK_SCRATCH_MB, for the
+ * snap pass (nine sums per point and block); the opening jerk pass follows its own two.  Same bits in every case.
+ * NBODY_ERR_NOT_INIT without a context; NBODY_ERR_ARG, checked before anything is launched or written, for points == NULL,
+ * velocities == NULL, accelerations == NULL, all three outputs NULL, m < 1, a bad row range or a skip value outside [-1, N);
+ * NBODY_ERR_STATE for the other precision's entry point or while the mailbox is served.
+ * With NBODY_OPT_MASSES (m = the w of source j's position word): w3 = m * inv3 as in nbody_jerk, and sx = fma(ux, w3, sx); the opening
+ * jerk pass is weighted too, so the a_j are the weighted accelerations.  All three outputs are per unit mass of the query. */
+int nbody_snap(const float *points, const float *velocities, const float *accelerations, int m, const int *skip, float *accel, float *jerk, float *snap);
+int nbody_snap_d(const double *points, const double *velocities, const double *accelerations, int m, const int *skip, double *accel, double *jerk, double *snap);
+int nbody_snap_rows(int first_row, int n_rows, float *accel, float *jerk, float *snap);
+int nbody_snap_rows_d(int first_row, int n_rows, double *accel, double *jerk, double *snap);
+
 /* ---- fourth-order Hermite integrator: predict, evaluate, correct on the jerk pass (not in the reference) ----
  * nbody_step is a kick followed by a drift: first order.  nbody_step_hermite(_d) advances the state on the device by nsteps steps of
  * the Makino–Aarseth Hermite scheme in its PEC form with a shared dt: one jerk rows pass per step plus one at the start of the call.
@@ -564,6 +618,44 @@ int nbody_step_hermite_d(double dt, int nsteps);
 int nbody_min_aarseth(double *q, int *row);
 int nbody_step_hermite_adaptive(float eta, float t_end, float dt_min, float dt_max, int max_steps, double *t_reached, int *steps_taken);
 int nbody_step_hermite_adaptive_d(double eta, double t_end, double dt_min, double dt_max, int max_steps, double *t_reached, int *steps_taken);
+
+/* ---- sixth-order Hermite integrator: predict, evaluate, correct on the snap pass (not in the reference) ----
+ * nbody_step_hermite6(_d) advances the state on the device by nsteps steps of the sixth-order Hermite scheme of Nitadori & Makino (2008)
+ * in its PEC form with a shared dt: one snap rows pass per step plus the two passes of nbody_snap_rows at the start of the call.  It
+ * carries acceleration a, jerk j, snap s and, for the predictor alone, the crackle c (the third derivative of a).  At the same number of
+ * steps it is far more accurate than the fourth-order scheme (Kepler pair, e = 0.5, to t = 1 in 128 steps, binary64: relative energy
+ * error 2.7e-10 against 1.8e-7) at about twice the pair arithmetic.  T is the context precision; every operation is rounded once,
+ * products are fused only where fma is written.
+ *   start of a call   (a0, j0, s0) of every row at (r, v): exactly what nbody_snap_rows returns; c0 = +0
+ *   coefficients      once per step in T from h = dt:  h2 = h * h   c2 = h2 * (T)0.5   c3 = (h2 * h) / (T)6   c4 = (h2 * h2) / (T)24
+ *                     c5 = ((h2 * h2) * h) / (T)120   hh = h * (T)0.5   c10 = h2 / (T)10   c120 = (h2 * h) / (T)120   r = (T)1 / h
+ *                     (IEEE quotients)
+ *   predict           xp = fma(c5, c0, fma(c4, s0, fma(c3, j0, fma(c2, a0, fma(h, v0, x0)))))
+ *                     vp = fma(c4, c0, fma(c3, s0, fma(c2, j0, fma(h, a0, v0))))
+ *                     ap = fma(c3, c0, fma(c2, s0, fma(h, j0, a0)))                                                per component
+ *   evaluate          (a1, j1, s1): the snap rows pass over the predicted state — the predicted positions, velocities and accelerations
+ *                     of all N bodies are the sources, row i's query is (xp_i, vp_i, ap_i) and leaves itself out
+ *   correct           v1 = fma(c120, s0 + s1, fma(c10, j0 - j1, fma(hh, a0 + a1, v0)))
+ *                     x1 = fma(c120, j0 + j1, fma(c10, a0 - a1, fma(hh, v0 + v1, x0)))                            per component
+ *   crackle           e1 = (T)60 * (a1 - a0)   e2 = fma((T)36, j1, (T)24 * j0)   e3 = fma((T)9, s1, (T)-3 * s0)
+ *                     c1 = r * fma(r, fma(r, e1, -e2), e3): the third derivative, at the end of the step, of the quintic through both
+ *                     evaluations.  Without it the scheme falls to fifth order
+ *   carried           the position word's w bit for bit; the velocity word's fourth value stays as it is
+ *   next step         (a0, j0, s0, c0) := (a1, j1, s1, c1)
+ * A CALL IS STATELESS, as nbody_step_hermite is: it evaluates (a0, j0, s0) afresh and starts from c0 = +0.  A call of k steps takes k + 2
+ * passes; k calls of one step are k restarts, take 3k passes and give other bits than one call of k steps.  Both are defined by the
+ * statement above.  Same bits on one device, on several, in an nbody_init_rank job of any size and under any source split
+ * (NBODY_SNAP_SPLIT, NBODY_SNAP_SCRATCH_MB, the jerk pass's two) or force configuration.
+ * Argument checks, the synchronous return, NBODY_INFO_STEPS_DONE, a negative dt, what later calls see and what stays untouched are as
+ * stated for nbody_step_hermite; an nbody_init_rank job is collective through the position, velocity and acceleration gathers and the
+ * exchange of the ranks' best values.  dt = 0 divides by zero in r: the state becomes NaN.
+ * nbody_step_hermite6_adaptive(_d): nbody_step_hermite_adaptive's loop, arguments, checks and outputs over sixth-order steps, with the same
+ * q = min_i |a_i|^2 / |j_i|^2 over the (a, j) the integrator carries.
+ * With NBODY_OPT_MASSES everything is inherited from the snap pass, as the fourth-order scheme inherits it from the jerk pass. */
+int nbody_step_hermite6(float dt, int nsteps);
+int nbody_step_hermite6_d(double dt, int nsteps);
+int nbody_step_hermite6_adaptive(float eta, float t_end, float dt_min, float dt_max, int max_steps, double *t_reached, int *steps_taken);
+int nbody_step_hermite6_adaptive_d(double eta, double t_end, double dt_min, double dt_max, int max_steps, double *t_reached, int *steps_taken);
 
 /* ---- individual block time steps: the Hermite integrator with a step per body, quantised to powers of two (not in the reference) ----
  * nbody_step_hermite_adaptive gives all N bodies the step of the worst pair.  nbody_step_hermite_block(_d) advances the state on the

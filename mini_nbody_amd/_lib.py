@@ -50,6 +50,8 @@ SYMBOLS = [
     "nbody_jerk", "nbody_jerk_d", "nbody_jerk_rows", "nbody_jerk_rows_d",
     "nbody_step_hermite", "nbody_step_hermite_d", "nbody_min_aarseth", "nbody_step_hermite_adaptive", "nbody_step_hermite_adaptive_d",
     "nbody_step_hermite_block", "nbody_step_hermite_block_d",
+    "nbody_snap", "nbody_snap_d", "nbody_snap_rows", "nbody_snap_rows_d",
+    "nbody_step_hermite6", "nbody_step_hermite6_d", "nbody_step_hermite6_adaptive", "nbody_step_hermite6_adaptive_d",
 ]
 
 
@@ -128,6 +130,10 @@ def load():
         "nbody_step_hermite_adaptive": [f, f, f, f, i, dp, C.POINTER(i)], "nbody_step_hermite_adaptive_d": [d, d, d, d, i, dp, C.POINTER(i)],
         "nbody_step_hermite_block": [f, f, i, i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
         "nbody_step_hermite_block_d": [d, d, i, i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
+        "nbody_snap": [fp, fp, fp, i, C.POINTER(i), fp, fp, fp], "nbody_snap_d": [dp, dp, dp, i, C.POINTER(i), dp, dp, dp],
+        "nbody_snap_rows": [i, i, fp, fp, fp], "nbody_snap_rows_d": [i, i, dp, dp, dp],
+        "nbody_step_hermite6": [f, i], "nbody_step_hermite6_d": [d, i],
+        "nbody_step_hermite6_adaptive": [f, f, f, f, i, dp, C.POINTER(i)], "nbody_step_hermite6_adaptive_d": [d, d, d, d, i, dp, C.POINTER(i)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -9,7 +9,8 @@
 // step graph stays valid; the other slices of pos[cur] are marked not present (all_present) and are brought by whoever needs them
 // next, as after integrate().  No force kernel is launched: arrival counters, partial forces and the force-kernel timer stay as they
 // were.  A call keeps nothing between calls: (a0, j0) is evaluated afresh at its start.  hermite_block.cpp builds on the opening, the
-// gathers and the mark of a rewritten slice (hermite_host.hpp); nothing else outside this file refers to it.
+// gathers and the mark of a rewritten slice, hermite6.cpp on the buffers, the gathers, the mark, the minimum and the adaptive loop
+// (hermite_host.hpp); nothing else outside this file refers to it.
 #include "hermite_host.hpp"
 #include "hermite_args.hpp"
 
@@ -22,8 +23,10 @@ namespace nbi {
 
 namespace {
 
-// the buffers of a call on every local that owns rows, and the ranks' words
-int ensure_buffers() {
+}  // namespace
+
+// the buffers of a call on every local that owns rows, and the ranks' words (hermite_host.hpp: hermite6.cpp takes them too)
+int hermite_ensure_buffers() {
   const size_t wb = word_bytes();
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
@@ -40,6 +43,8 @@ int ensure_buffers() {
   }
   return NBODY_OK;
 }
+
+namespace {
 
 // (a, j) of every own row at the state the live buffers hold, into he_acc[k] / he_jerk[k]: the rows form of the jerk pass.  Several
 // ranks: the streams are drained before anything travels (a gather writes into the buffer the previous evaluation read), and, with
@@ -95,9 +100,11 @@ int one_step(double h, int* k) {
   return NBODY_OK;
 }
 
+}  // namespace
+
 // the system's smallest q = |a|^2 / |j|^2 over he_acc[k] / he_jerk[k] with the lowest global row that reaches it; +inf and -1 where
 // there is none.  The same values on every rank.
-int best_of(int k, double* q, int* row) {
+int hermite_best_of(int k, double* q, int* row) {
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
     HIPC(hipSetDevice(L.device));
@@ -116,6 +123,8 @@ int best_of(int k, double* q, int* row) {
   return NBODY_OK;
 }
 
+namespace {
+
 int step_hermite_impl(double dt, int nsteps) {
   if (!g.init) return NBODY_ERR_NOT_INIT;
   if (nsteps < 1 || !std::isfinite(dt)) return NBODY_ERR_ARG;
@@ -131,7 +140,7 @@ int min_aarseth_impl(double* q, int* row) {
   NBC(hermite_open_call());
   double bq = 0.0;
   int br = -1;
-  NBC(best_of(0, &bq, &br));
+  NBC(hermite_best_of(0, &bq, &br));
   if (q) *q = bq;
   if (row) *row = br;
   return NBODY_OK;
@@ -140,28 +149,7 @@ int min_aarseth_impl(double* q, int* row) {
 // The shared Aarseth step (include/nbody.h states the loop).  Everything but the step itself is binary64 on the host; dt is rounded
 // once to the context precision, and t advances by the rounded value.  Every rank computes the same h from the same values.
 int step_hermite_adaptive_impl(double eta, double t_end, double dt_min, double dt_max, int max_steps, double* t_reached, int* steps_taken) {
-  if (!g.init) return NBODY_ERR_NOT_INIT;
-  if (!std::isfinite(eta) || !std::isfinite(t_end) || !std::isfinite(dt_min) || !std::isfinite(dt_max)) return NBODY_ERR_ARG;
-  if (eta <= 0.0 || dt_min <= 0.0 || dt_max < dt_min || t_end <= 0.0 || max_steps < 1) return NBODY_ERR_ARG;
-  NBC(hermite_open_call());
-  double t = 0.0;
-  int steps = 0, k = 0;
-  while (t < t_end && steps < max_steps) {
-    double q;
-    int row;
-    NBC(best_of(k, &q, &row));
-    double h = eta * std::sqrt(q);
-    h = h > dt_max ? dt_max : h;
-    h = h < dt_min ? dt_min : h;
-    if (t + h > t_end) h = t_end - t;
-    const double dt = g.fp64 ? h : (double)(float)h;
-    NBC(one_step(dt, &k));
-    t += dt;
-    ++steps;
-    if (t_reached) *t_reached = t;
-    if (steps_taken) *steps_taken = steps;
-  }
-  return sync_all();
+  return hermite_adaptive_loop(eta, t_end, dt_min, dt_max, max_steps, t_reached, steps_taken, hermite_open_call, one_step);
 }
 
 }  // namespace
@@ -183,7 +171,7 @@ int hermite_own_slice_written(Local& L) {
 
 int hermite_open_call() {
   NBC(reconfigure());
-  NBC(ensure_buffers());
+  NBC(hermite_ensure_buffers());
   return evaluate(0);
 }
 

@@ -1,8 +1,11 @@
-// hermite_host.hpp — what hermite.cpp shares with hermite_block.cpp (host C++ only): the opening of a Hermite call, the gathers that
-// bring the predicted state of all bodies to every device and rank, and the mark of a rewritten own slice.  hermite.cpp defines them;
-// none refers to a device symbol beyond those of hermite.hip and point_sums.hip.
+// hermite_host.hpp — what hermite.cpp shares with hermite_block.cpp and hermite6.cpp (host C++ only): the opening of a Hermite call,
+// its buffers, the gathers that bring the predicted state of all bodies to every device and rank, the mark of a rewritten own slice,
+// the system's smallest |a|^2 / |j|^2 and the shared Aarseth loop.  hermite.cpp defines them; none refers to a device symbol beyond those
+// of hermite.hip and point_sums.hip.
 #pragma once
 #include "query_pass.hpp"
+
+#include <cmath>
 
 namespace nbi {
 
@@ -13,5 +16,40 @@ int hermite_open_call();
 int hermite_gather_state();
 // the own slice of pos[cur] has been rewritten on L's compute stream: what the next gather waits for
 int hermite_own_slice_written(Local& L);
+// the buffers of a call (he_*) on every local that owns rows, and the ranks' words
+int hermite_ensure_buffers();
+// the system's smallest q = |a|^2 / |j|^2 over he_acc[k] / he_jerk[k] with the lowest global row that reaches it; +inf and -1 where
+// there is none.  The same values on every rank
+int hermite_best_of(int k, double* q, int* row);
+
+// The shared Aarseth step (include/nbody.h states the loop) over an integrator's opening, open(), and its step, step(dt, &k), which
+// leaves the carried (a, j) in he_acc[k] / he_jerk[k].  Everything but the step itself is binary64 on the host; dt is rounded once to
+// the context precision, and t advances by the rounded value.  Every rank computes the same h from the same values.
+template <typename Open, typename Step>
+int hermite_adaptive_loop(double eta, double t_end, double dt_min, double dt_max, int max_steps, double* t_reached, int* steps_taken,
+                          Open&& open, Step&& step) {
+  if (!g.init) return NBODY_ERR_NOT_INIT;
+  if (!std::isfinite(eta) || !std::isfinite(t_end) || !std::isfinite(dt_min) || !std::isfinite(dt_max)) return NBODY_ERR_ARG;
+  if (eta <= 0.0 || dt_min <= 0.0 || dt_max < dt_min || t_end <= 0.0 || max_steps < 1) return NBODY_ERR_ARG;
+  NBC(open());
+  double t = 0.0;
+  int steps = 0, k = 0;
+  while (t < t_end && steps < max_steps) {
+    double q;
+    int row;
+    NBC(hermite_best_of(k, &q, &row));
+    double h = eta * std::sqrt(q);
+    h = h > dt_max ? dt_max : h;
+    h = h < dt_min ? dt_min : h;
+    if (t + h > t_end) h = t_end - t;
+    const double dt = g.fp64 ? h : (double)(float)h;
+    NBC(step(dt, &k));
+    t += dt;
+    ++steps;
+    if (t_reached) *t_reached = t;
+    if (steps_taken) *steps_taken = steps;
+  }
+  return sync_all();
+}
 
 }  // namespace nbi

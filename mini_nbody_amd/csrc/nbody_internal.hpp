@@ -161,6 +161,8 @@ struct Local {
   DevMem q_scratch;                    // ... and what a launch whose sources are split leaves for its combine (point_sums_args.hpp, neighbors_args.hpp, knn_args.hpp, fof_args.hpp, hist_args.hpp, timescale_args.hpp)
   DevMem q_out[2];                     // field, tidal and jerk pass (point_sums.cpp): the points' outputs (context precision), shared as q_points is
   DevMem q_vel;                        // jerk pass (point_sums.cpp): this local's range of the caller's point velocities
+  DevMem q_acc, q_out2;                // snap pass (point_sums.cpp): this local's range of the caller's point accelerations, and the third output ...
+  DevMem sn_acc, sn_acc_all;           // ... the own rows' accelerations of the jerk rows pass a snap call opens with (n_local words), and all N acceleration words where the snap kernel reads them (query_pass.hpp, gather_accelerations)
   DevMem nb_idx, nb_d2, nb_count;      // neighbour pass (neighbors.cpp): the queries' outputs (d2 in the context precision) ...
   DevMem nb_best;                      // ... and the ranks' closest pairs, one BestPair at word `rank` (all P after an all-gather)
   DevMem kn_idx, kn_d2;                // knn pass (knn.cpp): the queries' outputs, k entries each (d2 in the context precision)
@@ -174,6 +176,7 @@ struct Local {
   DevMem he_pos0, he_vel0;             // Hermite step (hermite.cpp): the own rows' (x0, v0) of the step under way, n_local words each ...
   DevMem he_acc[2], he_jerk[2];        // ... their acceleration and jerk words at the start of the step and at the predicted state ...
   DevMem he_best;                      // ... and the ranks' smallest |a|^2 / |j|^2, one BestRatio at word `rank` (all P after an all-gather)
+  DevMem h6_snap[2], h6_crk, h6_ap;    // sixth-order Hermite step (hermite6.cpp): the own rows' snap words at both ends of the step, the crackle the next predictor takes and the predicted accelerations; the rest is he_pos0, he_vel0, he_acc, he_jerk, he_best
   DevMem hb_tick, hb_level;            // block time steps (hermite_block.cpp): the own rows' ticks (64-bit) and levels; their base is he_pos0, he_vel0, he_acc[0], he_jerk[0] ...
   DevMem hb_counts, hb_active;         // ... the active rows of a sub-step per tile of 256 rows and their ascending list (their queries go to q_points, q_vel, q_skip) ...
   DevMem hb_next;                      // ... and the ranks' next times, one NextTime at word `rank` (all P after an all-gather)

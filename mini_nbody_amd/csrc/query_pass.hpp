@@ -123,14 +123,20 @@ inline Range rows_of(const RowWindow& w, int l) {
 }
 
 // points [p0, p0 + cnt) of the call and their skip indices (or null) into L's q_points / q_skip (L's device is current)
-// velocities: the points' velocity words (a pass that reads them: the jerk), into L's q_vel likewise
-inline int upload_queries(Local& L, const void* points, const int* skip, int p0, int cnt, const void* velocities = nullptr) {
+// velocities: the points' velocity words (a pass that reads them: the jerk, the snap), into L's q_vel likewise; accelerations: the
+// points' acceleration words (the snap), into L's q_acc
+inline int upload_queries(Local& L, const void* points, const int* skip, int p0, int cnt, const void* velocities = nullptr,
+                          const void* accelerations = nullptr) {
   const size_t wb = word_bytes();
   NBC(L.q_points.ensure((size_t)cnt * wb));
   HIPC(hipMemcpy(L.q_points, (const char*)points + (size_t)p0 * wb, (size_t)cnt * wb, hipMemcpyHostToDevice));
   if (velocities) {
     NBC(L.q_vel.ensure((size_t)cnt * wb));
     HIPC(hipMemcpy(L.q_vel, (const char*)velocities + (size_t)p0 * wb, (size_t)cnt * wb, hipMemcpyHostToDevice));
+  }
+  if (accelerations) {
+    NBC(L.q_acc.ensure((size_t)cnt * wb));
+    HIPC(hipMemcpy(L.q_acc, (const char*)accelerations + (size_t)p0 * wb, (size_t)cnt * wb, hipMemcpyHostToDevice));
   }
   if (skip) {
     NBC(L.q_skip.ensure((size_t)cnt * sizeof(int)));
@@ -164,31 +170,60 @@ int run_on_locals(RangeOf&& range_of, Launch&& launch, CopyBack&& copy_back) {
   return NBODY_OK;
 }
 
-// All N velocity words where the kernels of every local can read them (the pair time-scale, the pair binding-energy and the jerk pass).  One device: vel itself, no copy.  Several devices in one
-// process: every local's ts_vel, filled by device-to-device copies of the locals' slices (hipMemcpyPeerAsync, as the positions travel
-// in enqueue_gather) on its compute stream, which the launch follows.  Several processes: the collective gather of a sharded array
-// into full_scratch with the transport in use (gather_sharded_multiprocess).  The streams are drained first: a step may still be
-// writing the velocities.
-inline int gather_velocities() {
+// All N words of an array every local holds its own rows of (own_of(L): n_local words in L's device memory) where the kernels of
+// every local can read them.  One device: the rows themselves, no copy.  Several devices in one process: every local's L.*all, filled
+// by device-to-device copies of the locals' rows (hipMemcpyPeerAsync, as the positions travel in enqueue_gather) on its compute
+// stream, which the launch follows.  Several processes: the collective gather of a sharded array into full_scratch with the transport
+// in use (gather_sharded_multiprocess) — and, keep: a device copy from there into L.*all, for an array that has to outlive the next
+// such gather.  The streams are drained first: a step may still be writing the rows.
+template <typename OwnOf>
+inline int gather_row_words(OwnOf&& own_of, DevMem Local::*all, bool keep) {
   if (g.nranks == 1) return NBODY_OK;
   NBC(sync_all());
-  if (g.multiprocess) return gather_sharded_multiprocess(g.loc[0], g.loc[0].vel);
   const size_t wb = word_bytes();
+  if (g.multiprocess) {
+    Local& L = g.loc[0];
+    NBC(gather_sharded_multiprocess(L, own_of(L)));
+    if (!keep) return NBODY_OK;
+    NBC((L.*all).ensure((size_t)g.n * wb));
+    HIPC(hipMemcpyAsync(L.*all, L.full_scratch, (size_t)g.n * wb, hipMemcpyDeviceToDevice, L.compute));
+    HIPC(hipStreamSynchronize(L.compute));   // full_scratch is free for the next gather
+    return NBODY_OK;
+  }
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
     HIPC(hipSetDevice(L.device));
-    NBC(L.ts_vel.ensure((size_t)g.n * wb));
+    NBC((L.*all).ensure((size_t)g.n * wb));
     for (int o = 0; o < g.nlocal; ++o) {
       const Local& O = g.loc[o];
       if (O.n_local > 0)
-        HIPC(hipMemcpyPeerAsync(word_ptr(L.ts_vel, O.first), L.device, O.vel, O.device, (size_t)O.n_local * wb, L.compute));
+        HIPC(hipMemcpyPeerAsync(word_ptr(L.*all, O.first), L.device, own_of(O), O.device, (size_t)O.n_local * wb, L.compute));
     }
   }
   return NBODY_OK;
 }
+
+// All N velocity words (the pair time-scale, the pair binding-energy, the jerk and the snap pass): vel itself, every local's ts_vel,
+// or full_scratch
+inline int gather_velocities() {
+  return gather_row_words([](const Local& L) -> const void* { return L.vel; }, &Local::ts_vel, false);
+}
 inline const void* velocities_of(const Local& L) {
   if (g.nranks == 1) return L.vel;
   return g.multiprocess ? L.full_scratch.as<void>() : L.ts_vel.as<void>();
+}
+
+// All N acceleration words (the snap pass) from the own rows' words in L.*own: L.*own itself, or every local's sn_acc_all — in an
+// nbody_init_rank job too, where the velocities go through full_scratch next.  Several devices in one process: the copies read every
+// owner's buffer on the READERS' streams, so the streams are drained again before anyone may write it (hermite.cpp says the same
+// of the velocities).
+inline int gather_accelerations(DevMem Local::*own) {
+  NBC(gather_row_words([own](const Local& L) -> const void* { return L.*own; }, &Local::sn_acc_all, true));
+  if (g.nranks > 1 && !g.multiprocess) NBC(sync_all());
+  return NBODY_OK;
+}
+inline const void* accelerations_of(const Local& L, DevMem Local::*own) {
+  return g.nranks == 1 ? (L.*own).as<void>() : L.sn_acc_all.as<void>();
 }
 
 // Word `rank` (bytes_per_rank, written on the compute stream) of every rank's L.*buf into host_words[0 .. P): processes exchange the
@@ -211,5 +246,10 @@ inline int gather_rank_words(DevMem Local::*buf, void* host_words, int bytes_per
 int jerk_own_rows_on_device(Local& L, void* accel, void* jerk);
 // the jerk points pass over m queries already in L's q_points, q_vel and q_skip, into device buffers likewise (m words each): see there
 int jerk_points_on_device(Local& L, int m, void* accel, void* jerk);
+// the snap rows pass over L's own rows against the N source accelerations in acc_all (L's device memory), into device buffers
+// likewise (n_local words each, any may be null, not all): see there
+int snap_own_rows_on_device(Local& L, const void* acc_all, void* accel, void* jerk, void* snap);
+// what a snap call opens with: the jerk rows pass on every local's own rows into sn_acc and the N accelerations to every device: see there
+int snap_open_accelerations();
 
 }  // namespace nbi

@@ -233,6 +233,37 @@ class NBody:
         L.check(fn(int(first_row), m, a.ctypes.data_as(C.POINTER(ct)), j.ctypes.data_as(C.POINTER(ct))))
         return a, j
 
+    def snap_at(self, points, velocities, accelerations, skip=None):
+        """(accel, jerk, snap), each (m, 4) in the context dtype, of the bodies on the device at m phase-space points (nbody_snap): accel
+        and jerk those of jerk_at(), bit for bit, snap the second time derivative of accel for a point that moves with velocity u and
+        acceleration a_x, s = sum_j (g inv^3 - 6 alpha J_j - 3 beta A_j) with g = a_j - a_x.  The bodies' own accelerations a_j come
+        from a jerk rows pass the call runs first.  points, velocities, accelerations: (m, 4) words or (m, 3); skip as in field().
+        Collective in a multi-rank job (every rank brings its own queries)."""
+        p, m, sk = self._queries(points, skip)
+        u, mu, _ = self._queries(velocities, None)
+        g, mg, _ = self._queries(accelerations, None)
+        if mu != m or mg != m:
+            raise ValueError("expected one velocity and one acceleration per point")
+        ct = C.c_double if self.fp64 else C.c_float
+        a, j, s = (np.empty((m, 4), self.dtype) for _ in range(3))
+        fn = self.lib.nbody_snap_d if self.fp64 else self.lib.nbody_snap
+        ptr = lambda x: x.ctypes.data_as(C.POINTER(ct))
+        L.check(fn(ptr(p), ptr(u), ptr(g), m, sk.ctypes.data_as(C.POINTER(C.c_int)) if sk is not None else None, ptr(a), ptr(j), ptr(s)))
+        return a, j, s
+
+    def snap(self, first_row=0, n_rows=None):
+        """(accel, jerk, snap), each (n_rows, 4) in the context dtype, of n_rows bodies from first_row (rows as in jerk(); default: all of
+        them) from the state on the device (nbody_snap_rows): row i is snap_at(r_i, v_i, a_i, skip=i) bit for bit, a_i being jerk()'s
+        acceleration of row i; accel and jerk are jerk()'s.  Two all-pairs passes.  Collective in a multi-rank job."""
+        if n_rows is None:
+            n_rows = self.info(L.INFO_N_LOCAL if self._by_rank else L.INFO_N) - int(first_row)
+        m = int(n_rows)
+        ct = C.c_double if self.fp64 else C.c_float
+        a, j, s = (np.empty((max(m, 0), 4), self.dtype) for _ in range(3))
+        fn = self.lib.nbody_snap_rows_d if self.fp64 else self.lib.nbody_snap_rows
+        L.check(fn(int(first_row), m, a.ctypes.data_as(C.POINTER(ct)), j.ctypes.data_as(C.POINTER(ct)), s.ctypes.data_as(C.POINTER(ct))))
+        return a, j, s
+
     def _near_out(self, m, r2):
         ct = C.c_double if self.fp64 else C.c_float
         idx, d2 = np.empty(m, np.int32), np.empty(m, self.dtype)
@@ -488,6 +519,22 @@ class NBody:
         extra pass.  Collective in a multi-rank job."""
         t, steps = C.c_double(0.0), C.c_int(0)
         fn = self.lib.nbody_step_hermite_adaptive_d if self.fp64 else self.lib.nbody_step_hermite_adaptive
+        L.check(fn(eta, t_end, dt_min, dt_max, int(max_steps), C.byref(t), C.byref(steps)))
+        return t.value, steps.value
+
+    def step_hermite6(self, dt, nsteps=1):
+        """nsteps sixth-order Hermite steps (Nitadori & Makino 2008) of a shared dt on the state on the device (nbody_step_hermite6):
+        predict positions, velocities and accelerations with (a, j, s) and the crackle carried from the step before, one snap rows pass
+        over the predicted state, correct.  A call evaluates (a, j, s) afresh at its start as snap() does — k + 2 passes for k steps —
+        and starts from a crackle of zero, so k calls of one step are k restarts and give other bits than one call of k steps.  Same
+        bits on any number of devices or ranks.  Synchronous; collective in a multi-rank job."""
+        L.check((self.lib.nbody_step_hermite6_d if self.fp64 else self.lib.nbody_step_hermite6)(float(dt), int(nsteps)))
+
+    def step_hermite6_adaptive(self, t_end, eta, dt_min, dt_max, max_steps=1000000):
+        """(t_reached, steps): step_hermite_adaptive()'s loop — the shared Aarseth step from the carried (a, j) — over sixth-order
+        Hermite steps (nbody_step_hermite6_adaptive).  Collective in a multi-rank job."""
+        t, steps = C.c_double(0.0), C.c_int(0)
+        fn = self.lib.nbody_step_hermite6_adaptive_d if self.fp64 else self.lib.nbody_step_hermite6_adaptive
         L.check(fn(eta, t_end, dt_min, dt_max, int(max_steps), C.byref(t), C.byref(steps)))
         return t.value, steps.value
 

@@ -20,7 +20,7 @@ HOSTFLAGS := -O2 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function
 OBJ      := build/obj
 KERNEL_SRC := $(CSRC)/kernels.hip $(CSRC)/nbody_kernels.hpp $(CSRC)/nbody_args.hpp $(CSRC)/force_loop_gfx950.inc
 HOST_HDR := $(CSRC)/nbody_internal.hpp $(CSRC)/nbody_args.hpp $(CSRC)/query_pass.hpp $(CSRC)/diag_pass.hpp include/nbody.h
-HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o $(OBJ)/energy.o $(OBJ)/point_sums.o $(OBJ)/neighbors.o $(OBJ)/knn.o $(OBJ)/fof.o $(OBJ)/hist.o $(OBJ)/timescale.o $(OBJ)/pair_energy.o $(OBJ)/hermite.o $(OBJ)/hermite_block.o $(OBJ)/hermite6.o
+HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o $(OBJ)/energy.o $(OBJ)/point_sums.o $(OBJ)/neighbors.o $(OBJ)/knn.o $(OBJ)/fof.o $(OBJ)/hist.o $(OBJ)/timescale.o $(OBJ)/pair_energy.o $(OBJ)/hermite.o $(OBJ)/hermite_block.o $(OBJ)/hermite6.o $(OBJ)/mutual.o
 # the energy diagnostics' device code (energy.hip, seconds of hipcc on its own) reads nbody_args.hpp and changes nothing of the force path's
 # hashed source (KERNEL_SRC); device.hip compiles it with kernels.hip into the library's one code object.  Its host side is energy.cpp, one
 # of HOST_OBJ.  What it shares with the seven passes below is diag_pass.hpp, which is no part of the hashed source either.
@@ -53,7 +53,10 @@ HERMITE_BLOCK_SRC := $(CSRC)/hermite_block.hip $(CSRC)/hermite_block_args.hpp
 # hermite6.cpp one of HOST_OBJ; it shares hermite.cpp's buffers, gathers, minimum and adaptive loop through hermite_host.hpp, and its
 # all-pairs work is the snap pass of point_sums.hip
 HERMITE6_SRC := $(CSRC)/hermite6.hip $(CSRC)/hermite6_args.hpp
-DEVICE_SRC := $(CSRC)/device.hip $(KERNEL_SRC) $(CSRC)/diag_pass.hpp $(ENERGY_SRC) $(POINT_SUMS_SRC) $(NEIGHBORS_SRC) $(KNN_SRC) $(FOF_SRC) $(HIST_SRC) $(TIMESCALE_SRC) $(PAIR_ENERGY_SRC) $(HERMITE_SRC) $(HERMITE_BLOCK_SRC) $(HERMITE6_SRC)
+# the mutual pairing of the full fp32 force pass (every unordered pair once, the ordered pass's bits): mutual.hip beside hermite6.hip — it reads
+# nbody_kernels.hpp for soft_f32 and apply_force and changes nothing of it — mutual.cpp one of HOST_OBJ
+MUTUAL_SRC := $(CSRC)/mutual.hip $(CSRC)/mutual_args.hpp
+DEVICE_SRC := $(CSRC)/device.hip $(KERNEL_SRC) $(CSRC)/diag_pass.hpp $(ENERGY_SRC) $(POINT_SUMS_SRC) $(NEIGHBORS_SRC) $(KNN_SRC) $(FOF_SRC) $(HIST_SRC) $(TIMESCALE_SRC) $(PAIR_ENERGY_SRC) $(HERMITE_SRC) $(HERMITE_BLOCK_SRC) $(HERMITE6_SRC) $(MUTUAL_SRC)
 
 lib: $(PKG)/libnbody_hip.so
 $(OBJ)/device.o: $(DEVICE_SRC) $(HOST_HDR)
@@ -73,6 +76,7 @@ $(OBJ)/pair_energy.o: $(CSRC)/pair_energy_args.hpp
 $(OBJ)/hermite.o: $(CSRC)/hermite_args.hpp $(CSRC)/hermite_host.hpp
 $(OBJ)/hermite_block.o: $(CSRC)/hermite_args.hpp $(CSRC)/hermite_host.hpp $(CSRC)/hermite_block_args.hpp
 $(OBJ)/hermite6.o: $(CSRC)/hermite6_args.hpp $(CSRC)/hermite_host.hpp
+$(OBJ)/mutual.o: $(CSRC)/mutual_args.hpp
 $(PKG)/libnbody_hip.so: $(OBJ)/device.o $(HOST_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -pthread -o $@ $^ -ldl
 

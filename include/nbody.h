@@ -112,6 +112,19 @@ enum {
                               by 2^k exactly (short of overflow and subnormals); a body with w = +0 at a finite position leaves
                               every sum it enters as it was, so massless bodies appended behind the massive ones change no bit of
                               the massive rows' results and are themselves accelerated (tracers). */
+  NBODY_OPT_PAIRING = 19,  /* NBODY_PAIRING_*: how a FULL fp32 force pass (nbody_step, nbody_forces, bodyForce, nbody_forces_rows over all
+                              rows) walks its pairs.  ORDERED: every row walks every source (each unordered pair evaluated twice).  MUTUAL:
+                              every unordered pair is evaluated once and feeds both rows — still one launch: the kernel leaves the
+                              level-1 sums of every (row, 1024-source block) in a table of N / 1024 x N 16-byte words (16 GiB at N = 2^20,
+                              allocated when a pass first takes this path), and the wave that writes the last word of a block of 1024 rows
+                              adds that block's sums in the ordered pass's own order:
+                              THE SAME BITS as ORDERED in the same configuration, except that a NaN may differ in sign and payload (the
+                              set of non-finite output words is the same).  Eligible: fp32, NBODY_ARITH_FMA3, NBODY_SUM_BLOCKED with
+                              NBODY_OPT_SUM_BLOCK 1024, unit masses, one rank on one device, all rows, N a multiple of 1024 and every piece
+                              boundary of the resolved segmentation (slices, segments, wave pieces) a multiple of 1024.  MUTUAL on a pass
+                              that is not eligible: NBODY_ERR_UNSUPPORTED before anything is launched.  AUTO (default): MUTUAL for
+                              eligible passes of >= 1048576 rows, else ORDERED.  If the table cannot be allocated the pass runs ORDERED and
+                              NBODY_INFO_PAIRING says so. */
   NBODY_OPT_ISA_PHASE = 10 /* NBODY_VARIANT_ISA: which generated form of the hand-scheduled loop runs (tools/gen_force_loop.py).
                               1 = the product loop (default); 0 = the same instructions placed one 4-byte phase off (-27 %, kept
                               so that the placement effect can be re-measured).  fp64: 1 = the product loop (VALU instructions at
@@ -149,6 +162,8 @@ enum { NBODY_SUM_SEQ = 0,          /* one accumulator per segment, sources ascen
                                       16 partial sums + an adder tree for the same reason (S/fxyz.vhd:129-145,
                                       S/final_adder.vhd:88-104): one fp32 accumulator over 2^20 terms is off by 1e-4.
                                       fp64 contexts always sum sequentially. */ };
+enum { NBODY_PAIRING_AUTO = 0, NBODY_PAIRING_ORDERED = 1, NBODY_PAIRING_MUTUAL = 2,
+       NBODY_PAIRING_NO_TABLE = 3 /* a value of NBODY_INFO_PAIRING only, not of the option */ };
 enum { NBODY_COMM_RING = 0,        /* P-1 ncclSend/ncclRecv ring steps, one event per arriving slice */
        NBODY_COMM_ALLGATHER = 1,   /* one in-place ncclAllGather (needs N divisible by the rank count, else ring) */
        NBODY_COMM_AUTO = 2,        /* default: ONE RCCL kernel per step, enqueued ahead of the force launch — ALLGATHER (RCCL's own ring over
@@ -171,6 +186,9 @@ enum { NBODY_INFO_N = 1, NBODY_INFO_N_LOCAL, NBODY_INFO_FIRST_BODY, NBODY_INFO_R
        NBODY_INFO_MAILBOX_SERVED /* requests the mailbox's service thread has completed in this process */,
        NBODY_INFO_MAILBOX_SERVING /* 1: nbody_mailbox_serve(1, .) is in effect */,
        NBODY_INFO_MASSES /* NBODY_OPT_MASSES: 0 or 1 */ };
+/* (a list of its own: the list above ends with NBODY_INFO_MASSES) */
+enum { NBODY_INFO_PAIRING = 31 /* what a step of the context takes: NBODY_PAIRING_ORDERED, NBODY_PAIRING_MUTUAL, or NBODY_PAIRING_NO_TABLE:
+                                  MUTUAL was chosen but its table could not be allocated, the pass runs ORDERED */ };
 
 /* ---- lifetime ----
  * Replaces: power-up of the PL design + the ps_pl RAM allocation (S/top_level.vhd:100-117, 148-163). */

@@ -12,15 +12,17 @@ LIB_PATH = os.environ.get("NBODY_LIB") or os.path.join(HERE, "libnbody_hip.so")
 
 # mirrors of the enums in include/nbody.h
 (OPT_VARIANT, OPT_IBLOCK, OPT_JSUB, OPT_JSLICES, OPT_ARITH, OPT_SUM_ORDER, OPT_TIMING, OPT_COMM, OPT_OVERLAP, OPT_ISA_PHASE,
- OPT_WAVES_PER_SIMD, OPT_GRAPH, OPT_SUM_BLOCK, OPT_FUSE_COMBINE, OPT_ISA_LONG_BUFFERS, OPT_XCD_MAP, OPT_WSPLIT, OPT_MASSES) = range(1, 19)
+ OPT_WAVES_PER_SIMD, OPT_GRAPH, OPT_SUM_BLOCK, OPT_FUSE_COMBINE, OPT_ISA_LONG_BUFFERS, OPT_XCD_MAP, OPT_WSPLIT, OPT_MASSES, OPT_PAIRING) = range(1, 20)
 VARIANT_AUTO, VARIANT_SMEM, VARIANT_LDS, VARIANT_READLANE, VARIANT_ISA = range(5)
 ARITH_FMA3, ARITH_REFERENCE, ARITH_STRICT, ARITH_REFERENCE_STRICT = 0, 1, 2, 3
 SUM_SEQ, SUM_FPGA16, SUM_BLOCKED = 0, 1, 2
+PAIRING_AUTO, PAIRING_ORDERED, PAIRING_MUTUAL = 0, 1, 2
 COMM_RING, COMM_ALLGATHER, COMM_AUTO, COMM_DIRECT = 0, 1, 2, 3
 (INFO_N, INFO_N_LOCAL, INFO_FIRST_BODY, INFO_RANK, INFO_NRANKS, INFO_VARIANT, INFO_IBLOCK, INFO_JSUB, INFO_NSEG,
  INFO_DEVICE, INFO_CU_COUNT, INFO_CLOCK_KHZ, INFO_FP64, INFO_TILE, INFO_STEPS_DONE, INFO_SUM_ORDER, INFO_SUM_BLOCK,
  INFO_LAUNCHES_PER_STEP, INFO_HAS_COMM, INFO_WSPLIT, INFO_ISA_PHASE, INFO_LONG_BUFFERS, INFO_XCD_MAP, INFO_FUSE_COMBINE,
  INFO_COMM_FORM, INFO_COMM_PRIORITY, INFO_DIAG_BUILD, INFO_MAILBOX_SERVED, INFO_MAILBOX_SERVING, INFO_MASSES) = range(1, 31)
+INFO_PAIRING = 31   # a list of its own in include/nbody.h
 
 (ENERGY_KINETIC, ENERGY_POTENTIAL, ENERGY_PX, ENERGY_PY, ENERGY_PZ, ENERGY_LX, ENERGY_LY, ENERGY_LZ, ENERGY_WORDS) = range(9)
 

@@ -20,6 +20,7 @@ namespace nbi {
 std::atomic<const char*> g_last_file{""};
 std::atomic<int> g_last_line{0};
 Global& g = *new Global;   // never destroyed: nbody_internal.hpp, at its declaration
+const MutualHooks* g_mutual = nullptr;   // set by mutual.cpp where it is linked
 
 namespace {
 
@@ -205,6 +206,7 @@ int zero_tickets() {
     Local& L = g.loc[l];
     HIPC(hipSetDevice(L.device));
     HIPC(hipMemsetAsync(L.tickets, 0, L.tickets.bytes, L.compute));
+    if (L.mutual_tickets) HIPC(hipMemsetAsync(L.mutual_tickets, 0, L.mutual_tickets.bytes, L.compute));   // the mutual pairing's counters likewise
   }
   g.tickets_dirty = false;
   return NBODY_OK;
@@ -351,6 +353,10 @@ int launch_combine(const Problem& p, Local& L, int row0, int row_count, const Fi
 }
 
 int force_pass(const Problem& p, Local& L, int row0, int row_count, const Finish& fin, const Redirect* rd) {
+  bool mutual = false;   // NBODY_OPT_PAIRING: the whole pass as mutual.cpp's launch
+  if (g_mutual) NBC(g_mutual->pass(p, L, row0, row_count, fin, rd, &mutual));
+  else if (g.opt.pairing == NBODY_PAIRING_MUTUAL) return NBODY_ERR_UNSUPPORTED;
+  if (mutual) return NBODY_OK;
   NBC(launch_force(p, L, row0, row_count, p.cfg.nslices - 1, p.cfg.nslices, fin, rd));
   return launch_combine(p, L, row0, row_count, fin, rd);
 }
@@ -393,7 +399,7 @@ int enqueue_step(float dt, double dt64) {
     }
     const Problem p = problem_of(L);
     if (P == 1) {
-      NBC(launch_force(p, L, 0, L.n_local, p.cfg.nslices - 1, p.cfg.nslices, fin));
+      NBC(force_pass(p, L, 0, L.n_local, fin));   // ordered (force launch, then the combine where it is a launch of its own) or mutual
     } else if (!need_gather) {
       NBC(launch_force(p, L, 0, L.n_local, L.rank, P, fin));
     } else if (g.opt.overlap == 2) {
@@ -411,7 +417,7 @@ int enqueue_step(float dt, double dt64) {
       NBC(wait_for_slice(L, L.ev_gather[P - 1]));
       NBC(launch_force(p, L, 0, L.n_local, L.rank, P, fin));
     }
-    NBC(launch_combine(p, L, 0, L.n_local, fin));
+    if (P > 1) NBC(launch_combine(p, L, 0, L.n_local, fin));
     // "own slice of pos[cur^1] written": what the next step's transfers wait for.  With one rank nothing does, and inside a
     // captured graph the record would be a node between two kernels.
     if (P > 1) HIPC(hipEventRecord(L.ev_own_ready, L.compute));
@@ -581,6 +587,7 @@ int step_impl(float dt, double dt64, int nsteps) {
   if (!g.init) return NBODY_ERR_NOT_INIT;
   if (nsteps < 0) return NBODY_ERR_ARG;
   NBC(reconfigure());
+  if (g_mutual) NBC(g_mutual->prepare_step());   // NBODY_OPT_PAIRING: its refusal before anything is launched, its table before anything is captured
   int s = 0;
   // One GPU, no per-kernel timing events, enough steps: replay a captured pair of steps.  A step is 1-2 kernel
   // launches + an event; below N ~ 10^5 the host launch path, not the GPU, sets the pace.
@@ -713,7 +720,7 @@ static int open_context(const void* uid128) {
       if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) { (void)hipGetLastError(); }
     }
   if (uid128) NBC(comm_create(L, g.nranks, L.rank, uid128));   // (also for nranks = 1: comm_create says why)
-  g.init = true; g.opt = Options();
+  g.init = true; g.opt = Options(); g.mutual_no_table = false;
   NBC(reconfigure());
   if (g.nranks > 1 && L.comm_h) {
     // One all-gather of the (zeroed) position buffer now: RCCL sets up its rings/channels lazily on the first
@@ -874,6 +881,10 @@ int nbody_set_option(int key, int value) { NB_REFUSE_WHILE_SERVED();
       // experiment encodings and timing-only forms (wrong results) are not in the product library: `make diag`
       if (!nbl::diag_build() && isa_phase_is_diag(value) && !(g.init && g.fp64 && value == 2)) return NBODY_ERR_UNSUPPORTED;
       g.opt.isa_phase = value; break;
+    case NBODY_OPT_PAIRING:
+      if (value < NBODY_PAIRING_AUTO || value > NBODY_PAIRING_MUTUAL) return NBODY_ERR_ARG;
+      if (g.init && g_mutual) { NBC(sync_all()); g_mutual->release(); }   // a table that could not be allocated is tried again; ORDERED keeps none
+      g.opt.pairing = value; break;
     case NBODY_OPT_WSPLIT: if (value != -1 && value != 1 && value != 4 && value != 16) return NBODY_ERR_ARG; g.opt.wsplit = value; break;
     // a launch argument of the ordered-sum passes and nothing else: no launch, no sync, the step graph, counters and timers stay
     case NBODY_OPT_MASSES: if (value != 0 && value != 1) return NBODY_ERR_ARG; g.opt.masses = value; return NBODY_OK;
@@ -908,6 +919,7 @@ int nbody_get_info(int key, long long* value) {
     case NBODY_INFO_LAUNCHES_PER_STEP: {
       const int force = g.nranks == 1 ? 1 : (g.opt.overlap == 2 ? g.nranks : (g.opt.overlap ? 2 : 1));
       *value = force + (finish_mode(g.cfg) == kFinishStore ? 1 : 0);
+      if (g_mutual && g_mutual->resolved_pairing() == NBODY_PAIRING_MUTUAL) *value = 1;   // the rows are finished inside its one launch
       break;
     }
     case NBODY_INFO_HAS_COMM: *value = L.comm_h ? 1 : 0; break;
@@ -922,6 +934,7 @@ int nbody_get_info(int key, long long* value) {
     case NBODY_INFO_MAILBOX_SERVING: *value = mailbox_serving() ? 1 : 0; break;
     case NBODY_INFO_DIAG_BUILD: *value = nbl::diag_build() ? 1 : 0; break;
     case NBODY_INFO_MASSES: *value = g.opt.masses; break;
+    case NBODY_INFO_PAIRING: *value = g_mutual ? g_mutual->resolved_pairing() : NBODY_PAIRING_ORDERED; break;
     default: return NBODY_ERR_ARG;
   }
   return NBODY_OK;

@@ -32,6 +32,9 @@
 //   hermite_block.hip the block step's scheduler kernels: init, predict-to-tau, next-time, compact-and-gather, correct-and-assign
 //                 (hermite_block_args.hpp: their argument block, the level rules and launch functions)
 //   hermite_block.cpp nbody_step_hermite_block(_d): individual block time steps, the active rows evaluated by the jerk points pass
+//   mutual.hip    the mutual pairing's kernel: every unordered pair of a full fp32 force pass once, the ordered pass's bits (mutual_args.hpp:
+//                 its argument block, the unit enumeration and launch function)
+//   mutual.cpp    which passes take the mutual pairing (NBODY_OPT_PAIRING), its table of level-1 sums and its launch
 // Only kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip, pair_energy.hip, hermite.hip and hermite_block.hip are device code (a minute of hipcc, as one code object through device.hip);
 // the others are host C++ (seconds).  gfx950 only, no CPU fallback anywhere.
 // Ownership: every stream, event, device and pinned allocation the context uses lives in an owning handle (Stream, Event, DevMem, Pinned,
@@ -180,6 +183,8 @@ struct Local {
   DevMem hb_tick, hb_level;            // block time steps (hermite_block.cpp): the own rows' ticks (64-bit) and levels; their base is he_pos0, he_vel0, he_acc[0], he_jerk[0] ...
   DevMem hb_counts, hb_active;         // ... the active rows of a sub-step per tile of 256 rows and their ascending list (their queries go to q_points, q_vel, q_skip) ...
   DevMem hb_next;                      // ... and the ranks' next times, one NextTime at word `rank` (all P after an all-gather)
+  DevMem mutual_table;                 // mutual pairing (mutual.cpp): the level-1 sums T[source block][row], N / 1024 x N words; allocated when a pass first takes that path ...
+  DevMem mutual_tickets;               // ... and its counters, one per row block: table words written so far (zero between passes)
   int cur = 0;
   bool all_present = true;             // pos[cur] holds every slice
   Event ev_own_ready;                  // the rank's slice of pos[cur] is written
@@ -195,6 +200,7 @@ struct Options {
   int arith = NBODY_ARITH_FMA3, sum_order = NBODY_SUM_BLOCKED, sum_block = 1024, fuse = -1;
   int timing = 0, comm = NBODY_COMM_AUTO, overlap = 1, isa_phase = 1, waves_per_simd = 0, graph = 1, long_buffers = -1, xcd_map = -1;
   int wsplit = -1;
+  int pairing = NBODY_PAIRING_AUTO;   // NBODY_OPT_PAIRING: which full fp32 force passes evaluate every unordered pair once (mutual.cpp)
   int masses = 0;   // NBODY_OPT_MASSES: the ordered-sum passes weigh source j by the w of its position word (a launch argument, no state)
 };
 
@@ -244,6 +250,7 @@ struct Global {
   Options opt;
   LaunchConfig cfg;
   bool comm_go_armed = false;     // the gather just enqueued recorded ev_comm_go (RCCL transport)
+  bool mutual_no_table = false;   // the mutual pairing's table could not be allocated: its passes run ordered (NBODY_INFO_PAIRING says so) until NBODY_OPT_PAIRING is set again
   bool tickets_dirty = false;     // a launch sequence failed part-way (TicketGuard): the arrival counters may be non-zero
   int cu_count = 0, clock_khz = 0;
   int comm_priority = 0;          // HIP priority of the transfer streams (0 = default)
@@ -311,6 +318,20 @@ int step_impl(float dt, double dt64, int nsteps);   // nbody_step(_d): nsteps st
 int forces_impl(const void* pos_words, void* force_words, int n);
 int device_count(int* ndev);
 int pick_device(int rank, int ndev);
+
+// ---- mutual.cpp: the mutual pairing of a full fp32 force pass (mutual_args.hpp), reached through g_mutual ----
+struct MutualHooks {
+  // The pass of problem p on L over rows [row0, row0 + row_count) in the mutual pairing, if NBODY_OPT_PAIRING and the pass's eligibility say
+  // so: *taken = true and its launch is enqueued (one timed span); *taken = false: the caller runs the ordered pass.  NBODY_ERR_UNSUPPORTED,
+  // nothing launched: NBODY_PAIRING_MUTUAL is forced and the pass is not eligible.
+  int (*pass)(const Problem& p, Local& L, int row0, int row_count, const Finish& fin, const Redirect* rd, bool* taken);
+  int (*prepare_step)();        // before a step is enqueued or captured: the refusal above, and the table allocated outside any capture
+  int (*resolved_pairing)();    // NBODY_INFO_PAIRING: what a step of the context takes
+  void (*release)();            // the tables freed (NBODY_OPT_PAIRING set: the next mutual pass allocates anew)
+};
+// mutual.cpp's functions once it is linked (the library: always); null in a program built from context.cpp without it, where every pass is
+// ordered and NBODY_PAIRING_MUTUAL is refused
+extern const MutualHooks* g_mutual;
 
 // ---- comm.cpp ----
 int rccl_load();

@@ -56,7 +56,8 @@ class NBody:
                     isa_phase=self.info(L.INFO_ISA_PHASE), long_buffers=self.info(L.INFO_LONG_BUFFERS),
                     xcd_map=self.info(L.INFO_XCD_MAP), fuse=self.info(L.INFO_FUSE_COMBINE),
                     n_local=self.info(L.INFO_N_LOCAL), first_body=self.info(L.INFO_FIRST_BODY),
-                    rank=self.info(L.INFO_RANK), nranks=self.info(L.INFO_NRANKS), masses=self.info(L.INFO_MASSES))
+                    rank=self.info(L.INFO_RANK), nranks=self.info(L.INFO_NRANKS), masses=self.info(L.INFO_MASSES),
+                    pairing={1: "ordered", 2: "mutual", 3: "ordered (no memory for the mutual table)"}.get(self.info(L.INFO_PAIRING), "?"))
 
     def use_masses(self, on=True):
         """NBODY_OPT_MASSES: with on, body j has the mass pos[j, 3] — the w of its position word as it lies on the device, uploaded and

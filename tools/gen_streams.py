@@ -71,6 +71,27 @@ bank_stream("bank_samereg", "v_fma_f32 d, a, a, c: a and c same bank (2 distinct
 bank_stream("bank_dst", "v_mul_f32: destination same bank as both sources (3 different regs, sources differ in bank)", lambda k: "v_mul_f32 v%d, v36, v41" % (64 + 4 * k))
 
 
+# ---- the one-lane shift of the mutual pairing (csrc/mutual.hip): v_mov_b32_dpp wave_shr:1, alone and between v_fma_f32
+DPP = "v_mov_b32_dpp v%d, v%d wave_shr:1 row_mask:0xf bank_mask:0xf"
+ins = [DPP % (65 + 4 * (k % 8), 36 + (k % 3)) for k in range(48)]
+add("dpp_shr", "v_mov_b32_dpp wave_shr:1 alone, 8 independent destinations", ins, vregs(ins))
+ins = []
+for k in range(24):
+    ins.append(DPP % (65 + 4 * (k % 8), 36 + (k % 3)))
+    ins.append("v_fma_f32 v%d, v37, v42, v%d" % (96 + 4 * (k % 8), 96 + 4 * (k % 8)))
+add("dpp_shr_fma1", "v_mov_b32_dpp wave_shr:1 and an independent v_fma_f32 alternating", ins, vregs(ins))
+ins = []
+for k in range(6):
+    ins.append(DPP % (65 + 4 * k, 36 + (k % 3)))
+    for j in range(7):
+        ins.append("v_fma_f32 v%d, v37, v42, v%d" % (96 + 4 * j, 96 + 4 * j))
+add("dpp_shr_fma7", "one v_mov_b32_dpp wave_shr:1 per seven independent v_fma_f32", ins, vregs(ins))
+ins = []
+for k in range(48):
+    ins.append("v_fma_f32 v%d, v37, v42, v%d" % (96 + 4 * (k % 8), 96 + 4 * (k % 8)))
+add("dpp_ref_fma", "the v_fma_f32 of the two streams above alone (the full-rate reference)", ins, vregs(ins))
+
+
 # ---- the pair interaction, C chains interleaved op by op.
 # per chain registers (bank in brackets): xi[1] yi[2] zi[3] | dx[1] dy[2] dz[3] | t[0] u[1] | ax[2] ay[3] az[1]
 # 3-VGPR-source instructions are only the final fmacs: (ax,dx,t) = banks (2,1,0), (ay,dy,t) = (3,2,0), (az,dz,t) = (1,3,0)

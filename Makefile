@@ -12,15 +12,15 @@ HIPFLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -ffp-contract=off -fno-s
 all: lib host oracle microbench
 
 # The library = ONE device code object (device.hip: the force path's kernels.hip — the nbk kernels + the launch functions that pick an
-# instantiation, ~45 s of hipcc — the energy pass's energy.hip, the field, tidal, jerk and snap passes' point_sums.hip, the neighbour pass's neighbors.hip, the k-nearest-neighbour pass's knn.hip, the friends-of-friends pass's fof.hip, the radial-count pass's hist.hip, the pair time-scale pass's timescale.hip, the pair binding-energy pass's pair_energy.hip, the Hermite step's hermite.hip, the block step's hermite_block.hip and the sixth-order Hermite step's hermite6.hip) and fourteen
-# host-only C++ files (context, comm, mailbox, energy, point_sums, neighbors, knn, fof, hist, timescale, pair_energy, hermite, hermite_block, hermite6: seconds each) behind csrc/nbody_internal.hpp.  A host-side edit relinks in seconds.
+# instantiation, ~45 s of hipcc — the energy pass's energy.hip, the field, tidal, jerk and snap passes' point_sums.hip, the neighbour pass's neighbors.hip, the k-nearest-neighbour pass's knn.hip, the friends-of-friends pass's fof.hip, the radial-count pass's hist.hip, the pair time-scale pass's timescale.hip, the pair binding-energy pass's pair_energy.hip, the Hermite step's hermite.hip, the block step's hermite_block.hip, the sixth-order Hermite step's hermite6.hip and the sixth-order block step's hermite6_block.hip) and fifteen
+# host-only C++ files (context, comm, mailbox, energy, point_sums, neighbors, knn, fof, hist, timescale, pair_energy, hermite, hermite_block, hermite6, hermite6_block: seconds each) behind csrc/nbody_internal.hpp.  A host-side edit relinks in seconds.
 # The eight diagnostic passes share csrc/diag_pass.hpp (device code — the distance passes' pair distance and query preamble included — the sizes
 # their hosts read and the guard of a split launch) and csrc/query_pass.hpp (host only: the flow of a call and the two split rules).
 HOSTFLAGS := -O2 -std=c++17 -fPIC -fvisibility=hidden -Wall -Wno-unused-function
 OBJ      := build/obj
 KERNEL_SRC := $(CSRC)/kernels.hip $(CSRC)/nbody_kernels.hpp $(CSRC)/nbody_args.hpp $(CSRC)/force_loop_gfx950.inc
 HOST_HDR := $(CSRC)/nbody_internal.hpp $(CSRC)/nbody_args.hpp $(CSRC)/query_pass.hpp $(CSRC)/diag_pass.hpp include/nbody.h
-HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o $(OBJ)/energy.o $(OBJ)/point_sums.o $(OBJ)/neighbors.o $(OBJ)/knn.o $(OBJ)/fof.o $(OBJ)/hist.o $(OBJ)/timescale.o $(OBJ)/pair_energy.o $(OBJ)/hermite.o $(OBJ)/hermite_block.o $(OBJ)/hermite6.o $(OBJ)/mutual.o
+HOST_OBJ := $(OBJ)/context.o $(OBJ)/comm.o $(OBJ)/mailbox.o $(OBJ)/energy.o $(OBJ)/point_sums.o $(OBJ)/neighbors.o $(OBJ)/knn.o $(OBJ)/fof.o $(OBJ)/hist.o $(OBJ)/timescale.o $(OBJ)/pair_energy.o $(OBJ)/hermite.o $(OBJ)/hermite_block.o $(OBJ)/hermite6.o $(OBJ)/hermite6_block.o $(OBJ)/mutual.o
 # the energy diagnostics' device code (energy.hip, seconds of hipcc on its own) reads nbody_args.hpp and changes nothing of the force path's
 # hashed source (KERNEL_SRC); device.hip compiles it with kernels.hip into the library's one code object.  Its host side is energy.cpp, one
 # of HOST_OBJ.  What it shares with the seven passes below is diag_pass.hpp, which is no part of the hashed source either.
@@ -53,10 +53,14 @@ HERMITE_BLOCK_SRC := $(CSRC)/hermite_block.hip $(CSRC)/hermite_block_args.hpp
 # hermite6.cpp one of HOST_OBJ; it shares hermite.cpp's buffers, gathers, minimum and adaptive loop through hermite_host.hpp, and its
 # all-pairs work is the snap pass of point_sums.hip
 HERMITE6_SRC := $(CSRC)/hermite6.hip $(CSRC)/hermite6_args.hpp
+# the sixth-order block step's scheduler kernels (init, predict-to-tau, compact-and-gather, correct-and-assign) likewise: hermite6_block.hip
+# beside hermite6.hip, hermite6_block.cpp one of HOST_OBJ; it opens as hermite6.cpp does and reads the next time as hermite_block.cpp does
+# (hermite_host.hpp), and its all-pairs work is the snap points pass of point_sums.hip
+HERMITE6_BLOCK_SRC := $(CSRC)/hermite6_block.hip $(CSRC)/hermite6_block_args.hpp
 # the mutual pairing of the full fp32 force pass (every unordered pair once, the ordered pass's bits): mutual.hip beside hermite6.hip — it reads
 # nbody_kernels.hpp for soft_f32 and apply_force and changes nothing of it — mutual.cpp one of HOST_OBJ
 MUTUAL_SRC := $(CSRC)/mutual.hip $(CSRC)/mutual_args.hpp
-DEVICE_SRC := $(CSRC)/device.hip $(KERNEL_SRC) $(CSRC)/diag_pass.hpp $(ENERGY_SRC) $(POINT_SUMS_SRC) $(NEIGHBORS_SRC) $(KNN_SRC) $(FOF_SRC) $(HIST_SRC) $(TIMESCALE_SRC) $(PAIR_ENERGY_SRC) $(HERMITE_SRC) $(HERMITE_BLOCK_SRC) $(HERMITE6_SRC) $(MUTUAL_SRC)
+DEVICE_SRC := $(CSRC)/device.hip $(KERNEL_SRC) $(CSRC)/diag_pass.hpp $(ENERGY_SRC) $(POINT_SUMS_SRC) $(NEIGHBORS_SRC) $(KNN_SRC) $(FOF_SRC) $(HIST_SRC) $(TIMESCALE_SRC) $(PAIR_ENERGY_SRC) $(HERMITE_SRC) $(HERMITE_BLOCK_SRC) $(HERMITE6_SRC) $(HERMITE6_BLOCK_SRC) $(MUTUAL_SRC)
 
 lib: $(PKG)/libnbody_hip.so
 $(OBJ)/device.o: $(DEVICE_SRC) $(HOST_HDR)
@@ -76,6 +80,7 @@ $(OBJ)/pair_energy.o: $(CSRC)/pair_energy_args.hpp
 $(OBJ)/hermite.o: $(CSRC)/hermite_args.hpp $(CSRC)/hermite_host.hpp
 $(OBJ)/hermite_block.o: $(CSRC)/hermite_args.hpp $(CSRC)/hermite_host.hpp $(CSRC)/hermite_block_args.hpp
 $(OBJ)/hermite6.o: $(CSRC)/hermite6_args.hpp $(CSRC)/hermite_host.hpp
+$(OBJ)/hermite6_block.o: $(CSRC)/hermite_args.hpp $(CSRC)/hermite_host.hpp $(CSRC)/hermite_block_args.hpp $(CSRC)/hermite6_args.hpp $(CSRC)/hermite6_block_args.hpp
 $(OBJ)/mutual.o: $(CSRC)/mutual_args.hpp
 $(PKG)/libnbody_hip.so: $(OBJ)/device.o $(HOST_OBJ)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -pthread -o $@ $^ -ldl

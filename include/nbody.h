@@ -2,7 +2,7 @@
  *
  * Plain C99: pointers, ints, floats.  No HIP, torch or C++ types cross this
  * boundary.  The library behind it is hand-written HIP for gfx950
- * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip, pair_energy.hip, hermite.hip, hermite_block.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, point_sums.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp, pair_energy.cpp, hermite.cpp, hermite_block.cpp); there is
+ * (mini_nbody_amd/csrc/: kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip, pair_energy.hip, hermite.hip, hermite_block.hip, hermite6.hip, hermite6_block.hip, mutual.hip + context.cpp, comm.cpp, mailbox.cpp, energy.cpp, point_sums.cpp, neighbors.cpp, knn.cpp, fof.cpp, hist.cpp, timescale.cpp, pair_energy.cpp, hermite.cpp, hermite_block.cpp, hermite6.cpp, hermite6_block.cpp, mutual.cpp); there is
  * no CPU fallback: every entry
  * point fails with NBODY_ERR_NO_DEVICE when no GPU is usable.
  *
@@ -705,6 +705,37 @@ int nbody_step_hermite6_adaptive_d(double eta, double t_end, double dt_min, doub
  * mailbox is served. */
 int nbody_step_hermite_block(float eta, float dt_max, int levels, int nblocks, long long *substeps, long long *row_evals);
 int nbody_step_hermite_block_d(double eta, double dt_max, int levels, int nblocks, long long *substeps, long long *row_evals);
+
+/* ---- sixth-order individual block time steps: the sixth-order Hermite integrator with a step per body (not in the reference) ----
+ * nbody_step_hermite6_block(_d) joins the two sections above: the sixth-order scheme of nbody_step_hermite6 on the scheduler of
+ * nbody_step_hermite_block.  Arguments, checks, return codes and counters are nbody_step_hermite_block's to the letter; the call advances
+ * the state on the device by nblocks * dt_max.  T is the context precision; every operation is rounded once, products are fused only
+ * where fma is written.
+ *   time          as above: integer ticks (64-bit) of unit = dt_max * 2^-(levels - 1), computed in T.  Row i carries a tick t0_i, a level
+ *                 k_i and its base (x0, v0, a0, j0, s0, c0) at t0_i, c the crackle; its step is s_i = 2^(levels - 1 - k_i) ticks.
+ *   wanted level  as above, from the row's (a, j) alone: the fourth-order ratio q = |a|^2 / |j|^2 — what nbody_step_hermite6_adaptive
+ *                 keeps for its shared step too.  The generalised Aarseth criterion of Nitadori & Makino over higher derivatives is not
+ *                 implemented.
+ *   start         base := the state; (a0, j0, s0) := what nbody_snap_rows returns (its two passes); c0 := +0; t0 := 0; k := want.
+ *   a sub-step    tau := the smallest t0_i + s_i over all rows of all ranks.  Every row is predicted from its base to tau with
+ *                 h_i = (T)(tau - t0_i) * unit and the sixth-order coefficients of h_i, formed per row exactly as stated above for h
+ *                 (IEEE quotients): xp, vp and ap by the three fma chains of the sixth-order predictor.  The ACTIVE rows, those with
+ *                 t0_i + s_i = tau, are evaluated by the snap at points: the query is the row's predicted (xp, vp, ap) with skip = its
+ *                 own index, the sources the predicted positions, velocities and accelerations of all N bodies.  They alone are
+ *                 corrected with their own h_i: v1, x1 and the crackle c1 of the sixth-order corrector with r = (T)1 / h_i;
+ *                 base := (x1, v1, a1, j1, s1, c1), t0 := tau; then the level moves as above with w = want(a1, j1).
+ *   carried       the position word's w and the velocity word's fourth value bit for bit.
+ *   end           as above: when tau = nblocks * 2^(levels - 1), with every body at that time.
+ * With levels = 1 the call is nbody_step_hermite6(dt_max, nblocks) bit for bit, in every arithmetic.  Like it the call is stateless
+ * ((a0, j0, s0) afresh, c0 = +0, levels assigned anew: two calls of one block give other bits than one call of two), synchronous, gives the
+ * same bits however the work is laid out (devices, ranks, NBODY_SNAP_SPLIT, NBODY_SNAP_SCRATCH_MB), never changes the live buffer,
+ * launches no force kernel, leaves alone what nbody_step_hermite leaves alone and is collective in an nbody_init_rank job through the
+ * position, velocity and acceleration gathers and the exchange of the ranks' next times (a rank without an active row takes part).
+ * *substeps, *row_evals (either may be NULL) and NBODY_INFO_STEPS_DONE (one per sub-step) as above; the two passes at the start of the call
+ * are in neither counter.  NBODY_ERR_ARG, NBODY_ERR_NOT_INIT and NBODY_ERR_STATE exactly as above, the state untouched.
+ * With NBODY_OPT_MASSES everything is inherited from the snap pass; a body with w = +0 is a massless tracer. */
+int nbody_step_hermite6_block(float eta, float dt_max, int levels, int nblocks, long long *substeps, long long *row_evals);
+int nbody_step_hermite6_block_d(double eta, double dt_max, int levels, int nblocks, long long *substeps, long long *row_evals);
 
 /* ---- nearest neighbour, radius count, closest pair: how close the bodies on the device get (not in the reference) ----
  * A query is a point x with an optional excluded body.  In the context precision T, for every body j on the device:

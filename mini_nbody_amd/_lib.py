@@ -54,6 +54,7 @@ SYMBOLS = [
     "nbody_step_hermite_block", "nbody_step_hermite_block_d",
     "nbody_snap", "nbody_snap_d", "nbody_snap_rows", "nbody_snap_rows_d",
     "nbody_step_hermite6", "nbody_step_hermite6_d", "nbody_step_hermite6_adaptive", "nbody_step_hermite6_adaptive_d",
+    "nbody_step_hermite6_block", "nbody_step_hermite6_block_d",
 ]
 
 
@@ -136,6 +137,8 @@ def load():
         "nbody_snap_rows": [i, i, fp, fp, fp], "nbody_snap_rows_d": [i, i, dp, dp, dp],
         "nbody_step_hermite6": [f, i], "nbody_step_hermite6_d": [d, i],
         "nbody_step_hermite6_adaptive": [f, f, f, f, i, dp, C.POINTER(i)], "nbody_step_hermite6_adaptive_d": [d, d, d, d, i, dp, C.POINTER(i)],
+        "nbody_step_hermite6_block": [f, f, i, i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
+        "nbody_step_hermite6_block_d": [d, d, i, i, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)

@@ -19,10 +19,9 @@ using namespace nbh6;
 
 namespace nbi {
 
-namespace {
-
 // the buffers of a call on every local that owns rows: hermite.cpp's, and the snap, crackle and predicted-acceleration words
-int ensure_buffers() {
+// (hermite_host.hpp: hermite6_block.cpp takes them too)
+int hermite6_ensure_buffers() {
   NBC(hermite_ensure_buffers());
   const size_t wb = word_bytes();
   for (int l = 0; l < g.nlocal; ++l) {
@@ -37,6 +36,8 @@ int ensure_buffers() {
   return NBODY_OK;
 }
 
+namespace {
+
 // (a, j, s) of every own row into he_acc[k] / he_jerk[k] / h6_snap[k] from the sources every device now holds and the N source
 // accelerations that lie in `own` on their owners
 int snap_rows(int k, DevMem Local::*own) {
@@ -47,11 +48,13 @@ int snap_rows(int k, DevMem Local::*own) {
   return NBODY_OK;
 }
 
+}  // namespace
+
 // what every call starts with: the configuration, the buffers, (a0, j0, s0) of the state it finds into slot 0 — the two passes of
-// nbody_snap_rows — and a crackle of +0
-int open_call() {
+// nbody_snap_rows — and a crackle of +0 (hermite_host.hpp: hermite6_block.cpp opens with it too)
+int hermite6_open_call() {
   NBC(reconfigure());
-  NBC(ensure_buffers());
+  NBC(hermite6_ensure_buffers());
   NBC(hermite_gather_state());
   NBC(snap_open_accelerations());
   NBC(snap_rows(0, &Local::sn_acc));
@@ -63,6 +66,8 @@ int open_call() {
   }
   return NBODY_OK;
 }
+
+namespace {
 
 Hermite6Args args_of(Local& L, int k, double h) {
   Hermite6Args a;
@@ -114,14 +119,14 @@ int one_step(double h, int* k) {
 int step_hermite6_impl(double dt, int nsteps) {
   if (!g.init) return NBODY_ERR_NOT_INIT;
   if (nsteps < 1 || !std::isfinite(dt)) return NBODY_ERR_ARG;
-  NBC(open_call());
+  NBC(hermite6_open_call());
   int k = 0;
   for (int s = 0; s < nsteps; ++s) NBC(one_step(dt, &k));
   return sync_all();
 }
 
 int step_hermite6_adaptive_impl(double eta, double t_end, double dt_min, double dt_max, int max_steps, double* t_reached, int* steps_taken) {
-  return hermite_adaptive_loop(eta, t_end, dt_min, dt_max, max_steps, t_reached, steps_taken, open_call, one_step);
+  return hermite_adaptive_loop(eta, t_end, dt_min, dt_max, max_steps, t_reached, steps_taken, hermite6_open_call, one_step);
 }
 
 }  // namespace

@@ -26,7 +26,7 @@ namespace nbh6 {
 template <typename T>
 struct Coefficients6 { T h, c2, c3, c4, c5, hh, c10, c120, r; };
 template <typename T>
-inline Coefficients6<T> coefficients6_of(T h) {
+__host__ __device__ inline Coefficients6<T> coefficients6_of(T h) {
   const T h2 = h * h;   // (products and quotients only: nothing here can be contracted)
   return {h, h2 * (T)0.5, (h2 * h) / (T)6, (h2 * h2) / (T)24, ((h2 * h2) * h) / (T)120, h * (T)0.5, h2 / (T)10, (h2 * h) / (T)120, (T)1 / h};
 }

@@ -25,8 +25,11 @@ namespace {
 
 int tiles_of(int rows) { return (rows + nbd::kLanes - 1) / nbd::kLanes; }
 
+}  // namespace
+
 // the scheduler's buffers on every local, and the query buffers of the jerk points pass for as many queries as the local has rows
-int ensure_block_buffers() {
+// (hermite_host.hpp: hermite6_block.cpp takes them too)
+int hermite_block_ensure_buffers() {
   const size_t wb = word_bytes();
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
@@ -44,6 +47,8 @@ int ensure_block_buffers() {
   }
   return NBODY_OK;
 }
+
+namespace {
 
 // what does not change during a call
 struct Scheme { int levels; double unit, eta2, lim[kMaxLevels]; };
@@ -78,14 +83,16 @@ BlockArgs args_of(Local& L, const Scheme& s, long long tau, int m) {
   return a;
 }
 
+}  // namespace
+
 // tau, the smallest next time over the rows of all ranks, per local the number of its rows that reach it and the system's number
-// (the same on every rank): one host read
-int next_time(const Scheme& s, long long* tau, int (&m)[kMaxLocal], long long* active) {
+// (the same on every rank): one host read (hermite_host.hpp: hermite6_block.cpp's sub-steps start with it too)
+int hermite_block_next_time(int levels, long long* tau, int (&m)[kMaxLocal], long long* active) {
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
     HIPC(hipSetDevice(L.device));
     HIPC((hipError_t)nbl::launch_hermite_block_next_kernel(L.compute, L.hb_tick.as<long long>(), L.hb_level.as<int>(), std::max(L.n_local, 0),
-                                                           s.levels, L.hb_next.as<NextTime>() + L.rank));
+                                                           levels, L.hb_next.as<NextTime>() + L.rank));
   }
   const NextTime none = {kNoTick, 0, 0};
   std::vector<NextTime> all((size_t)g.nranks, none);
@@ -103,6 +110,8 @@ int next_time(const Scheme& s, long long* tau, int (&m)[kMaxLocal], long long* a
   *tau = t;
   return NBODY_OK;
 }
+
+namespace {
 
 int one_substep(const Scheme& s, long long tau, const int (&m)[kMaxLocal]) {
   for (int l = 0; l < g.nlocal; ++l) {
@@ -141,7 +150,7 @@ int step_block_impl(double eta, double dt_max, int levels, int nblocks, long lon
     s.lim[k] = dk * dk;
   }
   NBC(hermite_open_call());
-  NBC(ensure_block_buffers());
+  NBC(hermite_block_ensure_buffers());
   for (int l = 0; l < g.nlocal; ++l) {
     Local& L = g.loc[l];
     if (L.n_local <= 0) continue;
@@ -153,7 +162,7 @@ int step_block_impl(double eta, double dt_max, int levels, int nblocks, long lon
   while (tau < end) {
     int m[kMaxLocal] = {0};
     long long active = 0;
-    NBC(next_time(s, &tau, m, &active));
+    NBC(hermite_block_next_time(s.levels, &tau, m, &active));
     if (tau > end) return NBODY_ERR_STATE;   // (the invariant: a step never crosses a multiple of 2^(levels - 1))
     NBC(one_substep(s, tau, m));
     ++steps;

@@ -1,7 +1,9 @@
-// hermite_host.hpp — what hermite.cpp shares with hermite_block.cpp and hermite6.cpp (host C++ only): the opening of a Hermite call,
+// hermite_host.hpp — what hermite.cpp shares with hermite_block.cpp, hermite6.cpp and hermite6_block.cpp (host C++ only): the opening of a Hermite call,
 // its buffers, the gathers that bring the predicted state of all bodies to every device and rank, the mark of a rewritten own slice,
 // the system's smallest |a|^2 / |j|^2 and the shared Aarseth loop.  hermite.cpp defines them; none refers to a device symbol beyond those
-// of hermite.hip and point_sums.hip.
+// of hermite.hip and point_sums.hip.  Two are hermite_block.cpp's (the scheduler's buffers and the next-time read; device symbol: the next-time
+// launch of hermite_block.hip) and two hermite6.cpp's (the sixth-order call's buffers and its opening; no device symbol beyond those of
+// point_sums.hip): hermite6_block.cpp builds on the four.
 #pragma once
 #include "query_pass.hpp"
 
@@ -21,6 +23,20 @@ int hermite_ensure_buffers();
 // the system's smallest q = |a|^2 / |j|^2 over he_acc[k] / he_jerk[k] with the lowest global row that reaches it; +inf and -1 where
 // there is none.  The same values on every rank
 int hermite_best_of(int k, double* q, int* row);
+
+// ---- hermite_block.cpp ----
+// the block scheduler's buffers (hb_*) on every local, and q_points, q_vel, q_skip for as many queries as the local has rows
+int hermite_block_ensure_buffers();
+// tau, the smallest next time t0_i + s_i over the rows of all ranks (hb_tick, hb_level; `levels` levels), m[l] the rows of local l that
+// reach it and *active the system's number, the same on every rank: one kernel per local and ONE host read
+int hermite_block_next_time(int levels, long long* tau, int (&m)[kMaxLocal], long long* active);
+
+// ---- hermite6.cpp ----
+// the buffers of a sixth-order call on every local that owns rows: those above and h6_snap, h6_crk, h6_ap
+int hermite6_ensure_buffers();
+// what every sixth-order call starts with: the configuration, the buffers, (a0, j0, s0) of the state it finds into he_acc[0], he_jerk[0],
+// h6_snap[0] — the two passes of nbody_snap_rows — and a crackle of +0 in h6_crk; the launches are left on the compute streams
+int hermite6_open_call();
 
 // The shared Aarseth step (include/nbody.h states the loop) over an integrator's opening, open(), and its step, step(dt, &k), which
 // leaves the carried (a, j) in he_acc[k] / he_jerk[k].  Everything but the step itself is binary64 on the host; dt is rounded once to

@@ -32,10 +32,18 @@
 //   hermite_block.hip the block step's scheduler kernels: init, predict-to-tau, next-time, compact-and-gather, correct-and-assign
 //                 (hermite_block_args.hpp: their argument block, the level rules and launch functions)
 //   hermite_block.cpp nbody_step_hermite_block(_d): individual block time steps, the active rows evaluated by the jerk points pass
+//   hermite6.hip  the sixth-order Hermite step's predictor and corrector with the crackle (hermite6_args.hpp: their argument block, the
+//                 coefficients of a step and launch functions)
+//   hermite6.cpp  nbody_step_hermite6(_d), nbody_step_hermite6_adaptive(_d): the sixth-order Hermite step on the snap rows pass
+//   hermite6_block.hip the sixth-order block step's scheduler kernels: init, predict-to-tau, compact-and-gather, correct-and-assign
+//                 (hermite6_block_args.hpp: their argument block and launch functions; the level rules and the next-time kernel are
+//                 hermite_block_args.hpp's)
+//   hermite6_block.cpp nbody_step_hermite6_block(_d): sixth-order individual block time steps, the active rows evaluated by the snap
+//                 points pass
 //   mutual.hip    the mutual pairing's kernel: every unordered pair of a full fp32 force pass once, the ordered pass's bits (mutual_args.hpp:
 //                 its argument block, the unit enumeration and launch function)
 //   mutual.cpp    which passes take the mutual pairing (NBODY_OPT_PAIRING), its table of level-1 sums and its launch
-// Only kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip, pair_energy.hip, hermite.hip and hermite_block.hip are device code (a minute of hipcc, as one code object through device.hip);
+// Only kernels.hip, energy.hip, point_sums.hip, neighbors.hip, knn.hip, fof.hip, hist.hip, timescale.hip, pair_energy.hip, hermite.hip, hermite_block.hip, hermite6.hip, hermite6_block.hip and mutual.hip are device code (a minute of hipcc, as one code object through device.hip);
 // the others are host C++ (seconds).  gfx950 only, no CPU fallback anywhere.
 // Ownership: every stream, event, device and pinned allocation the context uses lives in an owning handle (Stream, Event, DevMem, Pinned,
 // below) that is a member of Global or of one of its Locals; nbody_shutdown() releases them all, and nothing does at process exit (see `g`).
@@ -183,6 +191,7 @@ struct Local {
   DevMem hb_tick, hb_level;            // block time steps (hermite_block.cpp): the own rows' ticks (64-bit) and levels; their base is he_pos0, he_vel0, he_acc[0], he_jerk[0] ...
   DevMem hb_counts, hb_active;         // ... the active rows of a sub-step per tile of 256 rows and their ascending list (their queries go to q_points, q_vel, q_skip) ...
   DevMem hb_next;                      // ... and the ranks' next times, one NextTime at word `rank` (all P after an all-gather)
+                                       // sixth-order block time steps (hermite6_block.cpp): hb_* as above; the base is he_pos0, he_vel0, he_acc[0], he_jerk[0], h6_snap[0], h6_crk; he_acc[1], he_jerk[1], h6_snap[1] take the active rows' evaluations, h6_ap every own row's predicted acceleration, q_acc the queries' (no buffer of its own)
   DevMem mutual_table;                 // mutual pairing (mutual.cpp): the level-1 sums T[source block][row], N / 1024 x N words; allocated when a pass first takes that path ...
   DevMem mutual_tickets;               // ... and its counters, one per row block: table words written so far (zero between passes)
   int cur = 0;

@@ -8,8 +8,9 @@
 // evaluates the points IT was given (its own rows) on its own device; the call is collective only through complete_positions() and
 // gather_velocities().
 // A call reads pos[cur] (and vel) and writes only the Local's q_* buffers (and ts_vel, full_scratch): positions, velocities, arrival
-// counters, partial forces, the captured step graph and the force-kernel timer stay as they were.  Two internal entries (query_pass.hpp)
-// serve the Hermite integrator: jerk_own_rows_on_device the step of hermite.cpp, jerk_points_on_device the block step of hermite_block.cpp.
+// counters, partial forces, the captured step graph and the force-kernel timer stay as they were.  Internal entries (query_pass.hpp)
+// serve the Hermite integrators: jerk_own_rows_on_device the step of hermite.cpp, jerk_points_on_device the block step of
+// hermite_block.cpp, snap_own_rows_on_device the step of hermite6.cpp, snap_points_on_device the block step of hermite6_block.cpp.
 // The snap pass reads the sources' accelerations as a third stream.  A snap call makes them itself: the jerk rows pass over every
 // local's own rows into sn_acc, then gather_accelerations() (all N of them to every device: sn_acc itself or sn_acc_all), then the snap
 // pass; the sixth-order integrator (hermite6.cpp) brings predicted ones to snap_own_rows_on_device.
@@ -23,8 +24,8 @@ namespace nbi {
 namespace {
 
 // The queries of a call.  Points: the caller's arrays in host memory (velocities: a pass with velocities only).  Rows (points ==
-// null): the window's bodies themselves, each leaving itself out.  on_device: the three are the local's own q_points, q_vel and q_skip,
-// which a kernel has filled: nothing is uploaded.
+// null): the window's bodies themselves, each leaving itself out.  on_device: the three are the local's own q_points, q_vel and q_skip
+// (accelerations: q_acc too), which a kernel has filled: nothing is uploaded.
 struct Queries { const void* points; const void* velocities; const int* skip; bool on_device = false; const void* accelerations = nullptr; };
 constexpr int kOuts = 3;   // out[0], out[1] and out2 of PointSumsArgs
 
@@ -162,6 +163,17 @@ int jerk_points_on_device(Local& L, int m, void* accel, void* jerk) {
   if (m <= 0) return NBODY_OK;
   void* const out[kOuts] = {accel, jerk, nullptr};
   return launch_point_sums(L, kJerkPass, {L.q_points.as<void>(), L.q_vel.as<void>(), L.q_skip.as<int>(), true}, {0, m, 0}, out, true);
+}
+
+// The snap points pass likewise over m queries a kernel has left in L's q_points, q_vel, q_acc and q_skip (the sixth-order block step
+// of hermite6_block.cpp: the active rows' predicted words and global indices) into accel, jerk and snap, m words each in L's device
+// memory (any may be null, not all).  acc_all: the accelerations of all N sources in L's device memory, which the caller has gathered
+// with the positions and the velocities.
+int snap_points_on_device(Local& L, int m, const void* acc_all, void* accel, void* jerk, void* snap) {
+  if (m <= 0) return NBODY_OK;
+  void* const out[kOuts] = {accel, jerk, snap};
+  return launch_point_sums(L, kSnapPass, {L.q_points.as<void>(), L.q_vel.as<void>(), L.q_skip.as<int>(), true, L.q_acc.as<void>()}, {0, m, 0},
+                           out, true, acc_all);
 }
 
 }  // namespace nbi

@@ -249,6 +249,9 @@ int jerk_points_on_device(Local& L, int m, void* accel, void* jerk);
 // the snap rows pass over L's own rows against the N source accelerations in acc_all (L's device memory), into device buffers
 // likewise (n_local words each, any may be null, not all): see there
 int snap_own_rows_on_device(Local& L, const void* acc_all, void* accel, void* jerk, void* snap);
+// the snap points pass over m queries already in L's q_points, q_vel, q_acc and q_skip against the N source accelerations in acc_all,
+// into device buffers likewise (m words each, any may be null, not all): see there
+int snap_points_on_device(Local& L, int m, const void* acc_all, void* accel, void* jerk, void* snap);
 // what a snap call opens with: the jerk rows pass on every local's own rows into sn_acc and the N accelerations to every device: see there
 int snap_open_accelerations();
 

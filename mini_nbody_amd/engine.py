@@ -550,6 +550,17 @@ class NBody:
         L.check(fn(float(eta), float(dt_max), int(levels), int(nblocks), C.byref(steps), C.byref(evals)))
         return steps.value, evals.value
 
+    def step_hermite6_block(self, dt_max, nblocks=1, eta=0.02, levels=8):
+        """(substeps, row_evals): step_hermite_block() over the sixth-order scheme (nbody_step_hermite6_block): the call opens as
+        step_hermite6() does, a sub-step predicts every body's position, velocity and acceleration to the system's next time, and the
+        bodies that are due are evaluated by the snap pass and corrected with their own step, crackle included.  The levels follow
+        eta^2 |a|^2 / |j|^2 as in step_hermite_block().  levels = 1 is step_hermite6(dt_max, nblocks) bit for bit.  Stateless,
+        synchronous; same bits on any number of devices or ranks; collective in a multi-rank job."""
+        steps, evals = C.c_longlong(0), C.c_longlong(0)
+        fn = self.lib.nbody_step_hermite6_block_d if self.fp64 else self.lib.nbody_step_hermite6_block
+        L.check(fn(float(eta), float(dt_max), int(levels), int(nblocks), C.byref(steps), C.byref(evals)))
+        return steps.value, evals.value
+
     def comm_selftest(self):
         """Push a patterned array through the RCCL calls of the multi-GPU path (all-gather + one ring step); returns
         the bytes this rank received.  Needs the communicator of NBody(..., rank=, nranks=, uid=)."""

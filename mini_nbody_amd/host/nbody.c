@@ -8,7 +8,7 @@
  *
  * usage: nbody [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K]
  *              [--sum seq|blocked] [--block K] [--one-launch | --two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16]
- *              [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--binaries] [--hermite] [--hermite6] [--hermite-block LEVELS] [--masses]
+ *              [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--binaries] [--hermite] [--hermite6] [--hermite-block LEVELS] [--hermite6-block LEVELS] [--masses]
  * --hermite: the device loop's iterations are fourth-order Hermite steps (nbody_step_hermite) instead of kick-drift steps: one warm-up
  * call of one step, the initial state uploaded again, then ONE timed call of all `iters` steps (a call opens with a jerk pass of its own,
  * so two calls would not be one run: include/nbody.h, "a call is stateless"); the time per step is that call's over iters.  Refused
@@ -18,7 +18,10 @@
  * --hermite-block LEVELS (1 <= LEVELS <= 24): as --hermite, but an iteration is one block of dt_max = 0.01 with individual block time
  * steps on LEVELS levels and eta = 0.02 (nbody_step_hermite_block); one more line, "hermite block: LEVELS levels, S sub-steps, R row
  * evaluations (F of sub-steps x N)", gives the timed call's counters.  LEVELS = 1 is --hermite bit for bit.
- * --masses (with --hermite, --hermite6 or --hermite-block only; anything else is a usage error): body i gets the mass 2^-(i mod 4) in the w of its
+ * --hermite6-block LEVELS (1 <= LEVELS <= 24): as --hermite-block, over the sixth-order scheme (nbody_step_hermite6_block): the loop is
+ * named "device Hermite-6 block", the counters' line begins "hermite6 block:", and the --energy lines are printed as with --hermite6.
+ * LEVELS = 1 is --hermite6 bit for bit.  Not together with --hermite6 or --hermite-block.
+ * --masses (with --hermite, --hermite6, --hermite-block or --hermite6-block only; anything else is a usage error): body i gets the mass 2^-(i mod 4) in the w of its
  * position word — exact in both precisions and fixed by i alone — NBODY_OPT_MASSES is switched on, and the --energy lines are printed:
  * the weighted E, T and U before the first iteration and after the last.
  * --energy: E = T + U, T and U of the state on the device (nbody_energy) before the first iteration and after the last, and the
@@ -256,7 +259,7 @@ static int print_pair_histogram(int bins, int fp64) {
 }
 
 int main(int argc, char **argv) {
-  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0, tidal = 0, jerk = 0, closest = 0, pair_hist = 0, binaries = 0, hermite = 0, hermite6 = 0, block_levels = 0, masses = 0;
+  int n = 30000, iters = 10, gpus = 1, fp64 = 0, tile = 0, host_loop = 0, strict = 0, rtl = 0, npos = 0, jsub = 0, sum = -1, block = 0, two_launch = -1, long_buffers = -1, overlap = -1, wsplit = 0, energy = 0, field = 0, tidal = 0, jerk = 0, closest = 0, pair_hist = 0, binaries = 0, hermite = 0, hermite6 = 0, block_levels = 0, block4 = 0, block6 = 0, masses = 0;
   double e0 = 0.0, adaptive = 0.0;
   unsigned long long seed = NBODY_IC_DEFAULT_SEED;
   for (int a = 1; a < argc; ++a) {
@@ -268,7 +271,8 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--host-loop")) host_loop = 1;
     else if (!strcmp(argv[a], "--hermite")) hermite = 1;
     else if (!strcmp(argv[a], "--hermite6")) hermite = hermite6 = 1;
-    else if (!strcmp(argv[a], "--hermite-block") && a + 1 < argc) { hermite = 1; block_levels = atoi(argv[++a]); if (block_levels < 1 || block_levels > 24) { fprintf(stderr, "--hermite-block needs 1 <= LEVELS <= 24\n"); return 2; } }
+    else if (!strcmp(argv[a], "--hermite-block") && a + 1 < argc) { hermite = block4 = 1; block_levels = atoi(argv[++a]); if (block_levels < 1 || block_levels > 24) { fprintf(stderr, "--hermite-block needs 1 <= LEVELS <= 24\n"); return 2; } }
+    else if (!strcmp(argv[a], "--hermite6-block") && a + 1 < argc) { hermite = block6 = 1; block_levels = atoi(argv[++a]); if (block_levels < 1 || block_levels > 24) { fprintf(stderr, "--hermite6-block needs 1 <= LEVELS <= 24\n"); return 2; } }
     else if (!strcmp(argv[a], "--masses")) masses = 1;
     else if (!strcmp(argv[a], "--strict")) strict = 1;
     else if (!strcmp(argv[a], "--rtl")) rtl = 1;
@@ -289,15 +293,16 @@ int main(int argc, char **argv) {
     else if (!strcmp(argv[a], "--block") && a + 1 < argc) block = atoi(argv[++a]);
     else if (argv[a][0] != '-' && npos == 0) { n = atoi(argv[a]); npos++; }
     else if (argv[a][0] != '-' && npos == 1) { iters = atoi(argv[a]); npos++; }
-    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--binaries] [--hermite] [--hermite6] [--hermite-block LEVELS] [--masses]\n", argv[0]); return 2; }
+    else { fprintf(stderr, "usage: %s [N] [iters] [--gpus P] [--fp64] [--tile T] [--host-loop] [--seed S] [--strict] [--rtl] [--jsub K] [--sum seq|blocked] [--block K] [--one-launch|--two-launch] [--long-buffers 0|1] [--overlap 0|1|2] [--wsplit 1|4|16] [--energy] [--field M] [--tidal M] [--jerk M] [--closest-pair] [--pair-histogram B] [--adaptive ETA] [--binaries] [--hermite] [--hermite6] [--hermite-block LEVELS] [--hermite6-block LEVELS] [--masses]\n", argv[0]); return 2; }
   }
   if (field < 0) { fprintf(stderr, "--field needs M >= 1\n"); return 2; }
   if (tidal < 0) { fprintf(stderr, "--tidal needs M >= 1\n"); return 2; }
   if (jerk < 0 || jerk > n) { fprintf(stderr, "--jerk needs 1 <= M <= N\n"); return 2; }
   if (hermite && host_loop) { fprintf(stderr, "--hermite runs the device loop: not together with --host-loop\n"); return 2; }
   if (masses && !hermite) { fprintf(stderr, "--masses needs --hermite or --hermite-block: the kick-drift step is unit-mass\n"); return 2; }
+  if (block6 && (hermite6 || block4)) { fprintf(stderr, "--hermite6-block: not together with --hermite6 or --hermite-block\n"); return 2; }
   if (hermite6 && block_levels) { fprintf(stderr, "--hermite6 has a shared dt: not together with --hermite-block\n"); return 2; }
-  if (masses || hermite6) energy = 1;
+  if (masses || hermite6 || block6) energy = 1;
   if (n <= 0 || iters < 2) { fprintf(stderr, "need N > 0 and iters >= 2 (iteration 1 is warm-up)\n"); return 2; }
   const float dt = 0.01f;
   const size_t words = (size_t)n * 4;
@@ -342,12 +347,14 @@ int main(int argc, char **argv) {
       }
     } else if (hermite) {
       CHECK(nbody_upload(&p));
-      if (block_levels) CHECK(nbody_step_hermite_block(block_eta, dt, block_levels, 1, NULL, NULL));
+      if (block6) CHECK(nbody_step_hermite6_block(block_eta, dt, block_levels, 1, NULL, NULL));
+      else if (block_levels) CHECK(nbody_step_hermite_block(block_eta, dt, block_levels, 1, NULL, NULL));
       else if (hermite6) CHECK(nbody_step_hermite6(dt, 1));
       else CHECK(nbody_step_hermite(dt, 1));   /* warm-up; the call returns with the state written */
       CHECK(nbody_upload(&p));
       double t0 = now_s();
-      if (block_levels) CHECK(nbody_step_hermite_block(block_eta, dt, block_levels, iters, &substeps, &row_evals));
+      if (block6) CHECK(nbody_step_hermite6_block(block_eta, dt, block_levels, iters, &substeps, &row_evals));
+      else if (block_levels) CHECK(nbody_step_hermite_block(block_eta, dt, block_levels, iters, &substeps, &row_evals));
       else if (hermite6) CHECK(nbody_step_hermite6(dt, iters));
       else CHECK(nbody_step_hermite(dt, iters));
       total = now_s() - t0;
@@ -392,12 +399,14 @@ int main(int argc, char **argv) {
       }
     } else if (hermite) {
       CHECK(nbody_upload_d(&p));
-      if (block_levels) CHECK(nbody_step_hermite_block_d(block_eta, dt, block_levels, 1, NULL, NULL));
+      if (block6) CHECK(nbody_step_hermite6_block_d(block_eta, dt, block_levels, 1, NULL, NULL));
+      else if (block_levels) CHECK(nbody_step_hermite_block_d(block_eta, dt, block_levels, 1, NULL, NULL));
       else if (hermite6) CHECK(nbody_step_hermite6_d(dt, 1));
       else CHECK(nbody_step_hermite_d(dt, 1));
       CHECK(nbody_upload_d(&p));
       double t0 = now_s();
-      if (block_levels) CHECK(nbody_step_hermite_block_d(block_eta, dt, block_levels, iters, &substeps, &row_evals));
+      if (block6) CHECK(nbody_step_hermite6_block_d(block_eta, dt, block_levels, iters, &substeps, &row_evals));
+      else if (block_levels) CHECK(nbody_step_hermite_block_d(block_eta, dt, block_levels, iters, &substeps, &row_evals));
       else if (hermite6) CHECK(nbody_step_hermite6_d(dt, iters));
       else CHECK(nbody_step_hermite_d(dt, iters));
       total = now_s() - t0;
@@ -427,7 +436,7 @@ int main(int argc, char **argv) {
     free(buf);
   }
   if (block_levels)
-    printf("hermite block: %d levels, %lld sub-steps, %lld row evaluations (%.4f of sub-steps x N)\n", block_levels, substeps, row_evals,
+    printf("%s block: %d levels, %lld sub-steps, %lld row evaluations (%.4f of sub-steps x N)\n", block6 ? "hermite6" : "hermite", block_levels, substeps, row_evals,
            (double)row_evals / ((double)substeps * (double)n));
   double avg = total / (double)(hermite ? iters : iters - 1);
   long long info_r = 0, info_s = 0, info_b = 0, info_l = 0, info_w = 0;
@@ -437,7 +446,7 @@ int main(int argc, char **argv) {
   nbody_get_info(NBODY_INFO_SUM_BLOCK, &info_b);
   nbody_get_info(NBODY_INFO_LAUNCHES_PER_STEP, &info_l);
   printf("%d Bodies (%s, %d GPU%s, %s loop, %lld bodies/lane, %lld segments x %lld pieces, sum block %lld, %lld launch%s/step): average %0.3f Billion Interactions / second (%.3f ms / step)\n",
-         n, fp64 ? "fp64" : "fp32", gpus, gpus > 1 ? "s" : "", host_loop ? "host" : block_levels ? "device Hermite block" : hermite6 ? "device Hermite-6" : hermite ? "device Hermite" : "device", info_r, info_s, info_w, info_b, info_l,
+         n, fp64 ? "fp64" : "fp32", gpus, gpus > 1 ? "s" : "", host_loop ? "host" : block6 ? "device Hermite-6 block" : block_levels ? "device Hermite block" : hermite6 ? "device Hermite-6" : hermite ? "device Hermite" : "device", info_r, info_s, info_w, info_b, info_l,
          info_l > 1 ? "es" : "", 1e-9 * (double)n * (double)n / avg, 1e3 * avg);
   nbody_shutdown();
   return 0;

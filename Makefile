@@ -58,8 +58,9 @@ HERMITE6_SRC := $(CSRC)/hermite6.hip $(CSRC)/hermite6_args.hpp
 # (hermite_host.hpp), and its all-pairs work is the snap points pass of point_sums.hip
 HERMITE6_BLOCK_SRC := $(CSRC)/hermite6_block.hip $(CSRC)/hermite6_block_args.hpp
 # the mutual pairing of the full fp32 force pass (every unordered pair once, the ordered pass's bits): mutual.hip beside hermite6.hip — it reads
-# nbody_kernels.hpp for soft_f32 and apply_force and changes nothing of it — mutual.cpp one of HOST_OBJ
-MUTUAL_SRC := $(CSRC)/mutual.hip $(CSRC)/mutual_args.hpp
+# nbody_kernels.hpp for apply_force and changes nothing of it — mutual.cpp one of HOST_OBJ.  Its unit loop is generated
+# (tools/gen_mutual_loop.py -> mutual_loop_gfx950.inc, committed): `make lib` rebuilds the code object when it changes
+MUTUAL_SRC := $(CSRC)/mutual.hip $(CSRC)/mutual_args.hpp $(CSRC)/mutual_loop_gfx950.inc
 DEVICE_SRC := $(CSRC)/device.hip $(KERNEL_SRC) $(CSRC)/diag_pass.hpp $(ENERGY_SRC) $(POINT_SUMS_SRC) $(NEIGHBORS_SRC) $(KNN_SRC) $(FOF_SRC) $(HIST_SRC) $(TIMESCALE_SRC) $(PAIR_ENERGY_SRC) $(HERMITE_SRC) $(HERMITE_BLOCK_SRC) $(HERMITE6_SRC) $(HERMITE6_BLOCK_SRC) $(MUTUAL_SRC)
 
 lib: $(PKG)/libnbody_hip.so
@@ -117,7 +118,7 @@ build/microbench_roles: $(CSRC)/microbench_roles.hip
 	@mkdir -p build
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -o $@ $<
 # 0.5 MB of generated instruction streams: produced on demand, not tracked
-$(CSRC)/microbench_streams.inc: tools/gen_streams.py tools/gen_force_loop.py
+$(CSRC)/microbench_streams.inc: tools/gen_streams.py tools/gen_force_loop.py tools/gen_mutual_loop.py
 	python3 tools/gen_streams.py
 build/microbench_streams: $(CSRC)/microbench_streams.hip $(CSRC)/microbench_streams.inc
 	@mkdir -p build
@@ -135,9 +136,10 @@ build/microbench_gridsync: $(CSRC)/microbench_gridsync.hip
 	@mkdir -p build
 	$(HIPCC) --offload-arch=$(ARCH) -O3 -o $@ $<
 
-# generated sources: the hand-scheduled loop (committed) and the microbenchmark streams (not tracked)
+# generated sources: the hand-scheduled loops (committed) and the microbenchmark streams (not tracked)
 gen:
 	python3 tools/gen_force_loop.py
+	python3 tools/gen_mutual_loop.py
 	python3 tools/gen_streams.py
 
 isa: $(KERNEL_SRC)

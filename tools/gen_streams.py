@@ -543,6 +543,57 @@ for nm, order in (("p3_SFRMA", "SFRMA"), ("p3_RSFMA", "RSFMA"), ("p3_SFMAR", "SF
                         sorted(set(vregs(body3)), key=lambda r: int(r[1:])), pre))
 
 
+# ---- the systolic step of the mutual pairing (tools/gen_mutual_loop.py): the product order and the other orders considered, four steps
+# per stream (sources s36..s51), exec toggled as in the kernel (all lanes for the shifts, lane 0 for the new source, all lanes for the
+# pairs: the steady state), without the lane-63 store.  n counts the VALU instructions (249 per step); both placements.
+_spec = _ilu.spec_from_file_location("gen_mutual_loop", os.path.join(ROOT, "tools", "gen_mutual_loop.py"))
+_gml = _ilu.module_from_spec(_spec)
+_spec.loader.exec_module(_gml)
+
+EXEC_ALL, EXEC_LANE0 = ["s_mov_b64 exec, -1", "s_nop 0"], ["s_mov_b64 exec, 1", "s_nop 0"]
+
+
+def mstep_chain(k):
+    """the product: the six shifts between the steps, one chain, the previous row's accumulates in the transcendental's wait slot"""
+    sh = _gml.shifts()
+    return EXEC_ALL + sh + EXEC_LANE0 + _gml.inject(_gml.A_BASE, k) + EXEC_ALL + _gml.pairs()
+
+
+def mstep_hoist(k):
+    """the source's three shifts and the injection in row 15's wait slot (its subtractions were the last readers), the mirrored sums' after
+    row 15's accumulates.  In the kernel this order needs a second, masked copy of the step for fill and drain: the shifts run on all lanes"""
+    sh, p = _gml.shifts(), _gml.pairs()
+    at = max(n for n, i in enumerate(p) if i.startswith("v_rsq_f32")) + 1
+    return p[:at] + sh[:3] + EXEC_LANE0 + _gml.inject(_gml.A_BASE, k) + EXEC_ALL + p[at:] + sh[3:]
+
+
+def mstep_inter2(k):
+    """two rows' chains interleaved op by op (dependent instructions two slots apart), the accumulates behind their own cubes"""
+    g = _gml
+    ins = EXEC_ALL + g.shifts() + EXEC_LANE0 + g.inject(g.A_BASE, k) + EXEC_ALL
+    for a in range(0, g.ROWS, 2):
+        fa, fb = g.front(a), g.front(a + 1)
+        for x, y in zip(fa, fb):
+            ins += [x, y]
+        ca, cb = g.cube(a), g.cube(a + 1, g.U2)
+        ins += [ca[0], cb[0], ca[1], cb[1]] + g.acc(a) + g.acc(a + 1)
+    return ins
+
+
+for nm, fn, desc in (("mstep_chain", mstep_chain, "mutual step x 4, product order: shifts between steps, one chain, previous row's 6 fma after each rsq"),
+                     ("mstep_hoist", mstep_hoist, "mutual step x 4, the source's shifts and injection in row 15's rsq slot, the sums' shifts last"),
+                     ("mstep_inter2", mstep_inter2, "mutual step x 4, two rows interleaved op by op, accumulates behind their cubes")):
+    body = []
+    for k in range(4):
+        body += fn(k)
+    check_banks([i for i in body if i.startswith("v_") and "_dpp" not in i])
+    assert len([i for i in body if i.startswith("v_")]) == 4 * 249
+    for kk in (0, 1):
+        pre = [".p2align 6"] + ["s_nop 0"] * kk
+        streams.append(("%s_k%d" % (nm, kk), desc, body, len([i for i in body if i.startswith("v_")]),
+                        sorted(set(vregs(body)), key=lambda r: int(r[1:])), pre))
+
+
 def main():
     with open(OUT, "w") as f:
         f.write("// GENERATED by tools/gen_streams.py — do not edit.\n")

@@ -17,6 +17,14 @@ RSQ_SHARE = 6e-7   # v_rsq_f32's share of a timed binary32 pair in the mag measu
 # timed GPU bound 2 R_REF + RSQ_SHARE rests on it.  It is the budget tests/test_jerk_abi.py gives jerk_ref.c: the weight adds one
 # rounding per pair, 2^-24 = 6e-8 of a term.
 R_REF = 4.7e-6
+# The same figure on specials_common.hostile_dynamic_system with hostile_masses ("base", "overflow") at n = 70, 1100 and 2085, on the near
+# queries of hostile_points(…, 300, variant); tests/test_specials_dynamic_reference.py measures and asserts it.
+# Measured on the CPU, worst of both d2 forms, with and without skip: 9.531e-3 (the acceleration at n = 70; 2.23e-4 at n = 1100, 2.02e-4
+# at n = 2085; the jerk 4.5e-6 at the most) — the far body's figure, not the cloud's: its mass of 2^100 meets an inv^3 that binary32
+# holds as one subnormal bit (9.4e-46 rounded to 1.4e-45), a term of 1.2 with an error of 0.6 on every query alike, against a magnitude
+# sum of about 62 at n = 70.  No query's binary64 magnitude is non-finite, so the exclusion for that removes 0 of 300.  The constant is
+# the worst rounded up by 4.9 %.
+R_REF_HOSTILE = 1.0e-2
 
 
 def _p(a):

@@ -111,6 +111,88 @@ def hostile_points(nb, pos, m, variant):
     return pts, skip
 
 
+# ---- the dynamic passes (snap, sixth-order Hermite, block steps) and the masses ----
+
+DYNAMIC_FAST = 1e6   # the one fast velocity of hostile_dynamic_system, both precisions
+
+
+def hostile_dynamic_system(nb, n, dtype, variant):
+    """(pos, vel, far) of hostile_system(...) with the one velocity tamed: vel[6, 0] = 1e6 in both precisions, vel[7, 1] = 1e-6.
+    hostile_system's 1e18 (1e150) was put there for the energy totals.  In the snap w . w times inv^2 overflows with it (binary32: rows 6
+    and 37 at n = 70, 13 rows at n = 1100, the acceleration and the jerk stay finite), and the sixth-order predictor carries a row's
+    a0 + h j0 + c2 s0 + c3 c0 to every other row through g, so that one non-finite row leaves no finite row after one step: a test on
+    that input compares NaN with NaN and passes for almost any kernel.  With 1e6 every row of "base" and "overflow" stays finite through
+    three shared steps of 1/256 and through one block of eta 0.04, dt_max 1/256 on 8 levels, whose rows still spread over the levels
+    (1e9 or 1e50 stay finite too but leave levels 0 and 7 only; 1e12 or 1e75 do not stay finite).  tests/test_specials_reference.py
+    asserts all of it."""
+    pos, vel, far = hostile_system(nb, n, dtype, variant)
+    vel = vel.copy()
+    vel[6, 0] = DYNAMIC_FAST
+    vel[7, 1] = 1.0 / DYNAMIC_FAST
+    return pos, vel, far
+
+
+def hostile_point_words(nb, m, dtype, vel=None, acc=None):
+    """(pvel, pacc) for hostile_points(...) on hostile_dynamic_system(...)'s bodies: the cloud words of test_gpu_snap.point_words with
+      points 0 and 1   (both sit on body 0; point 0 skips it, point 1 does not) the body's own velocity vel[0] and acceleration acc[0],
+                       acc being the accelerations the pass gives the sources: w = g = +0 exactly on the coincident pair, which then adds
+                       +0 to all nine sums, so the two points get the same bits.  Without vel or acc: signed zeros in their place;
+      the last point   signed zeros, -0 +0 -0 in the velocity and +0 -0 +0 in the acceleration (at m = 1 it is point 0: the body's own
+                       words where they are given)."""
+    dtype = np.dtype(dtype).type
+    pvel, pacc = nb.make_bodies(m, seed=78, dtype=dtype)[1], nb.make_bodies(m, seed=79, dtype=dtype)[1]
+    for k in sorted({m - 1, min(1, m - 1), 0}, reverse=True):
+        pvel[k, :3] = [-0.0, 0.0, -0.0]
+        pacc[k, :3] = [0.0, -0.0, 0.0]
+        if k <= 1 and vel is not None:
+            pvel[k, :3] = vel[0, :3]
+        if k <= 1 and acc is not None:
+            pacc[k, :3] = acc[0, :3]
+    return pvel, pacc
+
+
+MASS_ROWS = {12: "+0", 13: "-0", 14: "smallest subnormal", 15: "smallest normal", 16: "2^20", 17: "2^-20", 22: "+0", 1024: "+0",
+             30: "negative", 41: "far and heavy"}
+INF_MASS_ROW = 33     # a finite cloud row
+NAN_PAYLOAD = 0x1234  # the "nan" variant's mass is a quiet NaN with this payload: a download must bring it back bit for bit
+
+
+def far_mass(dtype):
+    """the mass of the far body 41: 2^100 (binary32) or 2^300 (binary64) — its inv^3 is subnormal or zero while m * inv^3 would be
+    normal; small enough for m_i m_j of the energy totals to stay finite (2^700 in binary64 does not)"""
+    return np.dtype(dtype).type(2.0 ** 100 if np.dtype(dtype) == np.float32 else 2.0 ** 300)
+
+
+def hostile_masses(n, dtype, variant):
+    """n masses for the w of hostile_dynamic_system(...)'s positions: masses_common.random_masses (log-uniform in [0.25, 4)) with
+      rows 12 .. 17   +0, -0, the smallest subnormal, the smallest normal, 2^20, 2^-20
+      rows 22, 1024   +0 (a massless body at signed zeros, and one on the coincident group at the block edge)
+      row 30          -1.5: nothing is promised about negative masses, but the strict bits are the statement's
+      row 41          far_mass(dtype) on the far body
+    and per variant  "nan": a NaN with a payload on special_row(n, "nan");  "inf": +inf on row 33, a finite cloud body;
+    "overflow": +0 on body 63, whose d2 overflows.  A row that does not exist at this n is left out."""
+    from masses_common import random_masses
+    assert variant in VARIANTS
+    dtype = np.dtype(dtype).type
+    fi = np.finfo(dtype)
+    w = random_masses(n, 5, dtype)
+    planted = {12: 0.0, 13: -0.0, 14: fi.smallest_subnormal, 15: fi.tiny, 16: 2.0 ** 20, 17: 2.0 ** -20, 22: 0.0, 1024: 0.0, 30: -1.5,
+               41: far_mass(dtype)}
+    assert set(planted) == set(MASS_ROWS)
+    for i, v in planted.items():
+        if i < n:
+            w[i] = v
+    if variant == "nan":
+        u = {4: np.uint32, 8: np.uint64}[w.itemsize]
+        quiet = np.array([np.nan], dtype).view(u)
+        w[nan_row(n)] = (quiet | u(NAN_PAYLOAD)).view(dtype)[0]
+    elif variant == "inf":
+        w[INF_MASS_ROW] = np.inf
+    elif variant == "overflow":
+        w[63] = 0.0
+    return w
+
+
 def distance_h(dtype):
     """h of hostile_distance_system: 2^-70 (binary32) or 2^-520 (binary64) — h * h is far below the smallest subnormal's neighbours'
     reach (4 h^2 = 2^11 or 2^36 smallest subnormals), and h is far above the ±tiny, ±1e-30 (1e-170) bodies around the origin"""

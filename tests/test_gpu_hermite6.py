@@ -15,6 +15,8 @@ from hermite_common import compile_ref as compile_hermite4
 from hermite6_common import GAIN, MASS, ORDER_RATIO, REF, Hermite6Ref, compile_ref, kepler_energy_error
 from pass_common import same
 from ranks_common import run_ranks, shared_gpu_env, worker_source
+from specials_common import SIZES as HOSTILE_SIZES
+from specials_common import VARIANTS, hostile_dynamic_system, same_nan
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -278,3 +280,42 @@ def test_c_host_program_hermite6_lines(nb):
     for extra in (["--host-loop"], ["--hermite-block", "4"]):
         r = subprocess.run([exe, str(n), str(iters), "--hermite6"] + extra, capture_output=True, text=True, timeout=60)
         assert r.returncode == 2 and extra[0] in r.stderr, extra
+
+
+@pytest.mark.parametrize("arith", ["strict", "reference_strict", "fp64_strict"])
+def test_hostile_system_strict_steps(nb, ref, arith):
+    """specials_common.hostile_dynamic_system in every variant and size: one call of three steps of 1/256 and three calls of one step,
+    each the statement's bit for bit (NaN where it is NaN), both fourth values carried.  In "base" and "overflow" every row of the
+    downloaded state is finite — with hostile_system's own velocity of 1e18 (1e150) no row is after one step, and the comparison
+    would be NaN against NaN (tests/test_specials_dynamic_reference.py asserts the same of the statement)."""
+    fp64 = arith == "fp64_strict"
+    dtype = np.float64 if fp64 else np.float32
+    mode = nb.ARITH_REFERENCE_STRICT if arith == "reference_strict" else nb.ARITH_STRICT
+    flags = REF if mode == nb.ARITH_REFERENCE_STRICT else 0
+    dt = 1.0 / 256
+    differ = []
+    for n in HOSTILE_SIZES:
+        with nb.NBody(n, fp64=fp64) as eng:
+            eng.set_option(nb.OPT_ARITH, mode)
+            for variant in VARIANTS:
+                pos, vel, far = hostile_dynamic_system(nb, n, dtype, variant)
+                pos[:, 3] = np.arange(n, dtype=dtype) - 7.5
+                vel[:, 3] = 3.25
+                with np.errstate(all="ignore"):
+                    want = {"carried": ref.step(pos, vel, dtype, dt, 3, flags), "restarted": ref.restarted(pos, vel, dtype, dt, 3, flags)}
+                for form, calls in (("carried", (3,)), ("restarted", (1, 1, 1))):
+                    eng.upload(pos, vel)
+                    for k in calls:
+                        eng.step_hermite6(dt, k)
+                    got = eng.download()
+                    if not (same_nan(got[0], want[form][0]) and same_nan(got[1], want[form][1])):
+                        differ.append((n, variant, form))
+                    if not (same(got[0][:, 3], pos[:, 3]) and same(got[1][:, 3], vel[:, 3])):
+                        differ.append((n, variant, form, "fourth values"))
+                    if variant in ("base", "overflow") and not (np.all(np.isfinite(got[0])) and np.all(np.isfinite(got[1]))):
+                        differ.append((n, variant, form, "a row is not finite"))
+                    if variant in ("nan", "inf") and np.any(np.isfinite(got[0][:, :3]).all(1) & np.isfinite(got[1][:, :3]).all(1)):
+                        differ.append((n, variant, form, "a row escaped the poison"))
+                if variant in ("base", "overflow") and same(want["carried"], want["restarted"]):
+                    differ.append((n, variant, "the carried and the restarted form do not differ"))
+    assert not differ, differ

@@ -14,6 +14,8 @@ from hermite6_block_common import (ENERGY_RUN, ENERGY_STRICT_F32, ENERGY_TIMED_F
                                    compile_ref, energy_system, equal_slices)
 from pass_common import bits, same
 from ranks_common import run_ranks, shared_gpu_env, worker_source
+from specials_common import SIZES as HOSTILE_SIZES
+from specials_common import VARIANTS, hostile_dynamic_system, same_nan
 
 pytestmark = pytest.mark.gpu
 CASE8 = dict(GPU_CASE, levels=8)
@@ -296,3 +298,34 @@ def test_guards(nb):
         assert b32() == E.ERR_STATE
         assert b64(dt=1e-307, levels=8) == E.ERR_ARG                 # below the smallest normal binary64
         assert b64() == 0
+
+
+@pytest.mark.parametrize("arith", list(STRICT))
+def test_hostile_system_one_strict_block(nb, ref, arith):
+    """specials_common.hostile_dynamic_system in every variant and size, one block of dt_max = 1/256 on 8 levels with eta = 0.04 (the
+    fourth-order hostile test's run): the call returns, state and both counters are the statement's (NaN where it is NaN).  In "base"
+    and "overflow" every row stays finite and the block takes more than a hundred sub-steps on at least three levels; a row whose
+    (a, j) is NaN sits on level 0, so "nan" and "inf" take one sub-step of all n rows."""
+    fp64, mode, is_ref = STRICT[arith]
+    dtype = np.float64 if fp64 else np.float32
+    run = dict(eta=0.04, dt_max=1.0 / 256, levels=8, nblocks=1)
+    differ = []
+    for n in HOSTILE_SIZES:
+        with nb.NBody(n, fp64=fp64) as eng:
+            eng.set_option(nb.OPT_ARITH, getattr(nb, mode))
+            for variant in VARIANTS:
+                pos, vel, far = hostile_dynamic_system(nb, n, dtype, variant)
+                eng.upload(pos, vel)
+                with np.errstate(all="ignore"):
+                    wp, wv, wsteps, wevals, trace = ref.run(pos, vel, dtype, ref=is_ref, **run)
+                counters = block(eng, run)
+                got = eng.download()
+                if not (same_nan(got[0], wp) and same_nan(got[1], wv) and counters == (wsteps, wevals)):
+                    differ.append((n, variant, counters, (wsteps, wevals)))
+                if variant in ("nan", "inf"):
+                    assert (trace.level0 == 0).all() and (wsteps, wevals) == (1, n), (n, variant)
+                else:
+                    assert wsteps > 100 and trace.occupied_levels() >= 3, (n, variant, wsteps)
+                    if not (np.all(np.isfinite(got[0])) and np.all(np.isfinite(got[1]))):
+                        differ.append((n, variant, "a row is not finite"))
+    assert not differ, differ

@@ -13,10 +13,19 @@ import pytest
 
 from field_common import make_points, make_skip
 from jerk_common import TIMED_SHAPE
-from masses_common import (R_REF, RSQ_SHARE, SIZES, compile_masses_ref, kepler, numpy_field, numpy_jerk, numpy_totals, random_masses, with_masses,
-                           worst)
+from hermite6_block_common import Block6Ref
+from hermite6_block_common import compile_ref as compile_block6
+from hermite6_common import MASS as H6_MASS
+from hermite6_common import REF as H6_REF
+from hermite6_common import Hermite6Ref
+from hermite6_common import compile_ref as compile_hermite6
+from masses_common import (R_REF, R_REF_HOSTILE, RSQ_SHARE, SIZES, compile_masses_ref, kepler, numpy_field, numpy_jerk, numpy_totals, random_masses,
+                           with_masses, worst)
 from pass_common import bits, same
 from ranks_common import run_ranks, shared_gpu_env, worker_source
+from snap_common import SnapRef
+from specials_common import INF_MASS_ROW, VARIANTS, hostile_dynamic_system, hostile_masses, hostile_point_words, hostile_points, nan_row, near, same_nan
+from specials_common import SIZES as HOSTILE_SIZES
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -407,3 +416,205 @@ def test_c_host_program_masses(nb):
     assert energies[()] == [e0, e1], (energies, e0, e1)
     r = subprocess.run([exe, str(n), str(iters), "--masses"], capture_output=True, text=True, timeout=60)
     assert r.returncode == 2 and "--masses" in r.stderr
+
+
+# ---- the hostile system with hostile masses (specials_common.py) ----
+
+@pytest.fixture(scope="module")
+def dynamic_refs(tmp_path_factory):
+    """(tests/snap_ref.c, tests/hermite6_ref.c, tests/hermite6_block_ref.c): the statements of the weighted passes masses_ref.c leaves out"""
+    from field_common import compile_ref
+    d = tmp_path_factory.mktemp("masses_dynamic_ref")
+    return SnapRef(compile_ref(d, "snap_ref")), Hermite6Ref(compile_hermite6(d)), Block6Ref(compile_block6(d))
+
+
+def hostile_bodies(nb, n, dtype, variant, mass_variant=None):
+    """hostile_dynamic_system with hostile_masses in the w of the positions and canaries in the w of the velocities"""
+    pos, vel, far = hostile_dynamic_system(nb, n, dtype, variant)
+    pos = with_masses(pos, hostile_masses(n, dtype, variant if mass_variant is None else mass_variant))
+    vel[:, 3] = (np.arange(n) % 31).astype(dtype) + dtype(0.25)
+    return pos, vel
+
+
+def hostile_queries(nb, pos, vel, variant, m=300):
+    pts, skip = hostile_points(nb, pos, m, variant)
+    pts[:, 3] = 99.0
+    pvel, pacc = hostile_point_words(nb, m, pos.dtype.type, vel)
+    return pts, pvel, pacc, skip
+
+
+HOSTILE_RUN = dict(eta=0.04, dt_max=1.0 / 256, levels=8, nblocks=1)
+
+
+@pytest.mark.parametrize("arith", list(ARITHS))
+def test_hostile_masses_strict_bit_for_bit(nb, ref, dynamic_refs, arith):
+    """hostile_dynamic_system with hostile_masses in every variant and size, 300 hostile queries: the field with and without skip, the
+    tidal tensor, the jerk at points and at rows, potential_rows and energy() against tests/masses_ref.c, the snap at rows against
+    tests/snap_ref.c, one fourth-order and one sixth-order step of 1/256 and one block of each order (eta 0.04, dt_max 1/256, 8 levels)
+    with its counters against masses_ref.c, hermite6_ref.c and hermite6_block_ref.c — NaN for NaN, bit for bit elsewhere — and after
+    every integrator call the downloaded w is the uploaded w bit for bit: -0, the subnormal and the NaN's payload included."""
+    fp64, mode, r = ARITHS[arith]
+    dtype = np.float64 if fp64 else np.float32
+    snap_ref, h6_ref, b6_ref = dynamic_refs
+    flags = H6_MASS | (H6_REF if r else 0)
+    dt, run = 1.0 / 256, HOSTILE_RUN
+    differ = []
+    for n in HOSTILE_SIZES:
+        with nb.NBody(n, fp64=fp64) as eng:
+            eng.set_option(nb.OPT_ARITH, getattr(nb, mode))
+            eng.use_masses()
+            for variant in VARIANTS:
+                pos, vel = hostile_bodies(nb, n, dtype, variant)
+                pts, pvel, pacc, skip = hostile_queries(nb, pos, vel, variant)
+                eng.upload(pos, vel)
+                got = passes(eng, pts, pvel, skip) + eng.snap()
+                with np.errstate(all="ignore"):
+                    want = (*ref.field(pos, pts, dtype, None, r), *ref.field(pos, pts, dtype, skip, r), ref.tidal(pos, pts, dtype, skip, r),
+                            *ref.jerk(pos, vel, pts, pvel, dtype, skip, r), *ref.jerk_rows(pos, vel, dtype, r), ref.potential(pos, dtype, r),
+                            ref.totals(pos, vel, dtype, ref=r), *snap_ref.rows(pos, vel, dtype, ref=r, mass=True))
+                    steps = {"hermite": ref.hermite(pos, vel, dtype, dtype(dt), 1, r) + (None,),
+                             "hermite6": h6_ref.step(pos, vel, dtype, dt, 1, flags) + (None,),
+                             "hermite_block": (lambda o: (o[0], o[1], (o[2], o[3])))(ref.hermite_block(pos, vel, dtype, run["eta"], run["dt_max"], run["levels"], 1, r)),
+                             "hermite6_block": (lambda o: (o[0], o[1], (o[2], o[3])))(b6_ref.run(pos, vel, dtype, ref=r, mass=True, trace=False, **run))}
+                assert len(got) == len(want)
+                for k, (g, w) in enumerate(zip(got, want)):
+                    if not same_nan(np.asarray(g), np.asarray(w)):
+                        differ.append((n, variant, "pass %d" % k))
+                calls = {"hermite": lambda: eng.step_hermite(dt, 1), "hermite6": lambda: eng.step_hermite6(dt, 1),
+                         "hermite_block": lambda: eng.step_hermite_block(run["dt_max"], 1, eta=run["eta"], levels=run["levels"]),
+                         "hermite6_block": lambda: eng.step_hermite6_block(run["dt_max"], 1, eta=run["eta"], levels=run["levels"])}
+                for name, call in calls.items():
+                    eng.upload(pos, vel)
+                    counters = call()
+                    state = eng.download()
+                    wp, wv, wcounters = steps[name]
+                    if not (same_nan(state[0], wp) and same_nan(state[1], wv)):
+                        differ.append((n, variant, name))
+                    if wcounters is not None and tuple(counters) != wcounters:
+                        differ.append((n, variant, name, tuple(counters), wcounters))
+                    if not (same(state[0][:, 3], pos[:, 3]) and same(state[1][:, 3], vel[:, 3])):
+                        differ.append((n, variant, name, "the w of a word was not carried"))
+                    if variant in ("base", "overflow") and not (np.all(np.isfinite(state[0][:, :3])) and np.all(np.isfinite(state[1][:, :3]))):
+                        differ.append((n, variant, name, "a row is not finite"))
+    assert not differ, differ
+
+
+DOMAIN_MODES = {False: ("ARITH_FMA3", "ARITH_REFERENCE", "ARITH_STRICT", "ARITH_REFERENCE_STRICT"), True: ("ARITH_FMA3", "ARITH_STRICT")}
+
+
+def domain_passes(eng, pts, pvel, pacc, skip):
+    """(query passes, rows passes) of the weighted state on the device"""
+    return ((*eng.field(pts, skip), eng.tidal(pts, skip), *eng.jerk_at(pts, pvel, skip), *eng.snap_at(pts, pvel, pacc, skip)),
+            (*eng.jerk(), *eng.snap(), eng.potential_rows(0, eng.n)))
+
+
+@pytest.mark.parametrize("fp64", [False, True])
+def test_domain_sentences_of_the_masses(nb, fp64):
+    """What include/nbody.h says of the w of a position word (NBODY_OPT_MASSES, DOMAIN), directly, in every arithmetic, the timed ones
+    included, on the finite "base" bodies of hostile_dynamic_system so that nothing but the mass is special:
+      a NaN mass poisons the acceleration, the potential and the jerk of every query that does not skip the body, and no bit of a query
+      that does: those get what they get with 1.5 in its place — in the field, the tidal tensor, the jerk and the snap pass's
+      acceleration and jerk; the snap itself is NaN on every query, through the a_j of the sources beside the body;
+      an infinite mass leaves no finite contribution: every component of the acceleration and the potential of a query that does not
+      skip it is +-inf or NaN, and a query that skips it has the bits of the ordinary system;
+      moving bodies of mass +0 from one finite position to another — exactly onto a query, for the bodies on the window edge (63, 64)
+      and on the block edge (1023, 1024) as for one inside (12) — changes no bit of any query nor of any other row, in the field, the
+      tidal tensor, the jerk, the snap and potential_rows."""
+    dtype = np.float64 if fp64 else np.float32
+    differ = []
+    for n in HOSTILE_SIZES:
+        pos, vel = hostile_bodies(nb, n, dtype, "base")
+        row = nan_row(n)
+        pts, pvel, pacc, skip = hostile_queries(nb, pos, vel, "nan")     # its plan skips nan_row(n) on near cloud points
+        skip[200:210] = INF_MASS_ROW
+        ordinary = pos.copy()
+        ordinary[row, 3] = 1.5
+        special = {"nan": with_masses(ordinary, hostile_masses(n, dtype, "nan")), "inf": with_masses(ordinary, hostile_masses(n, dtype, "inf"))}
+        special["inf"][row, 3] = 1.5
+        movers = [b for b in (12, 63, 64, 1023, 1024) if b < n]
+        still, moved = ordinary.copy(), ordinary.copy()
+        still[movers, 3] = 0.0
+        moved[movers, 3] = 0.0
+        moved[movers, :3] = pts[[250 + 4 * k for k in range(len(movers))], :3]     # near cloud queries (192 ..), some with a skip
+        others = np.setdiff1d(np.arange(n), movers)
+        with nb.NBody(n, fp64=fp64) as eng:
+            eng.use_masses()
+            for mode in DOMAIN_MODES[fp64]:
+                eng.set_option(nb.OPT_ARITH, getattr(nb, mode))
+                eng.upload(ordinary, vel)
+                base_q, base_r = domain_passes(eng, pts, pvel, pacc, skip)
+                ok = near(pts)
+                assert all(np.all(np.isfinite(o[ok])) for o in base_q), (n, mode)
+                for kind, bad_row in (("nan", row), ("inf", INF_MASS_ROW)):
+                    eng.upload(special[kind], vel)
+                    q, rws = domain_passes(eng, pts, pvel, pacc, skip)
+                    sel = skip == bad_row
+                    assert sel.sum() >= 2
+                    a, phi, tid, ja, jj, sa, sj, ss = q
+                    seen = [k for k, (g, b) in enumerate(zip(q[:7], base_q[:7])) if not same(g[sel], b[sel])]
+                    if seen:
+                        differ.append((n, mode, kind, "a query that skips the body sees it in query passes", seen))
+                    # (the snap itself is out of a skip's reach: the body's mass is in the a_j of every source beside it, include/nbody.h "snap")
+                    if np.any(np.isfinite(ss[:, :3])):
+                        differ.append((n, mode, kind, "a finite snap beside non-finite accelerations of the sources"))
+                    if kind == "nan":
+                        if not all(np.all(np.isnan(o[~sel][:, :3])) for o in (a, ja, jj, sa, sj, ss)) or not np.all(np.isnan(phi[~sel])) or not np.all(np.isnan(tid[~sel])):
+                            differ.append((n, mode, kind, "a query that does not skip the body escaped"))
+                        hit = np.arange(n) != bad_row
+                        if not all(np.all(np.isnan(o[hit][:, :3])) for o in rws[:2]) or not np.all(np.isnan(rws[5][hit])) or not np.all(np.isnan(rws[4][:, :3])):
+                            differ.append((n, mode, kind, "a row escaped"))
+                        if not (np.all(np.isfinite(rws[0][bad_row])) and np.isfinite(rws[5][bad_row])):
+                            differ.append((n, mode, kind, "the body's own row has no mass of its own to meet"))
+                    else:
+                        if np.any(np.isfinite(a[~sel][:, :3])) or np.any(np.isfinite(ja[~sel][:, :3])) or np.any(np.isfinite(sa[~sel][:, :3])) or np.any(np.isfinite(phi[~sel])):
+                            differ.append((n, mode, kind, "a finite contribution of an infinite mass"))
+                        hit = np.arange(n) != bad_row
+                        if np.any(np.isfinite(rws[0][hit][:, :3])) or np.any(np.isfinite(rws[5][hit])):
+                            differ.append((n, mode, kind, "a row with a finite contribution of an infinite mass"))
+                eng.upload(still, vel)
+                still_q, still_r = domain_passes(eng, pts, pvel, pacc, skip)
+                eng.upload(moved, vel)
+                moved_q, moved_r = domain_passes(eng, pts, pvel, pacc, skip)
+                for k, (g, b) in enumerate(zip(moved_q, still_q)):
+                    if not same(g, b):
+                        differ.append((n, mode, "moved massless bodies", "query pass %d" % k, np.flatnonzero((bits(g) != bits(b)).reshape(len(g), -1).any(1))[:8]))
+                for k, (g, b) in enumerate(zip(moved_r, still_r)):
+                    if not same(g[others], b[others]):
+                        differ.append((n, mode, "moved massless bodies", "rows pass %d" % k, others[np.flatnonzero((bits(g[others]) != bits(b[others])).reshape(len(others), -1).any(1))[:8]]))
+                    if k < 5 and same(g[movers], b[movers]):     # (their potential is the far body's 2^100 / 1e15: the cloud is below its last place)
+                        differ.append((n, mode, "the massless bodies themselves did not notice their move", k))
+            eng.set_option(nb.OPT_ARITH, nb.ARITH_FMA3)
+    assert not differ, "\n".join(str(d) for d in differ)
+
+
+def test_hostile_masses_timed_fp32_within_the_bound(nb):
+    """hostile_dynamic_system with hostile_masses, "base" and "overflow", every size, 300 hostile queries with and without skip, both
+    timed binary32 arithmetics: |got - want64| / mag of the field and the jerk against numpy binary64 on the near queries whose binary64
+    magnitude sums are finite, within 2 r + v_rsq_f32's share (test_timed_fp32_within_the_bound's rule) with r =
+    masses_common.R_REF_HOSTILE, what masses_ref.c's strict binary32 keeps on this input (tests/test_specials_dynamic_reference.py).
+    r is the far body's figure: see masses_common.  The measured figures are printed."""
+    bound = 2 * R_REF_HOSTILE + RSQ_SHARE
+    worst_of = {}
+    for n in HOSTILE_SIZES:
+        with nb.NBody(n) as eng:
+            eng.use_masses()
+            for variant in ("base", "overflow"):
+                pos, vel = hostile_bodies(nb, n, np.float32, variant)
+                pts, pvel, pacc, hsk = hostile_queries(nb, pos, vel, variant)
+                eng.upload(pos, vel)
+                for skip in (None, hsk):
+                    wa, wphi, mag = numpy_field(pos, pts, skip)
+                    ja, jj, mag_a, mag_j = numpy_jerk(pos, vel, pts, pvel, skip)
+                    keep = near(pts) & np.all([np.isfinite(o).all(1) for o in (mag, mag_a, mag_j)], axis=0)
+                    assert keep.sum() >= 290, (n, variant)
+                    for mode in (nb.ARITH_FMA3, nb.ARITH_REFERENCE):
+                        eng.set_option(nb.OPT_ARITH, mode)
+                        a, phi = eng.field(pts, skip)
+                        a2, j = eng.jerk_at(pts, pvel, skip)
+                        assert same(a, a2), (n, variant, mode)
+                        figs = [worst(a[keep], wa[keep], mag[keep]), worst(a2[keep], ja[keep], mag_a[keep]), worst(j[keep], jj[keep], mag_j[keep])]
+                        worst_of[(n, mode)] = [max(x, y) for x, y in zip(worst_of.get((n, mode), [0.0] * 3), figs)]
+                eng.set_option(nb.OPT_ARITH, nb.ARITH_FMA3)
+    for (n, mode), e in sorted(worst_of.items()):
+        print("hostile masses timed fp32 n=%d arith %d: field accel %.3e, jerk's accel %.3e jerk %.3e (bound %.3e)" % (n, mode, *e, bound))
+    assert all(max(e) <= bound for e in worst_of.values()), worst_of

@@ -10,8 +10,10 @@ import pytest
 from field_common import compile_ref, make_points, make_skip
 from pass_common import bits, check_step_untouched, same
 from ranks_common import run_ranks, shared_gpu_env, worker_source
-from snap_common import TIMED_BOUND, TIMED_SHAPE, SnapRef, numpy_snap, worst
-from specials_common import same_nan
+from snap_common import TIMED_BOUND, TIMED_BOUND_HOSTILE, TIMED_SHAPE, SnapRef, numpy_snap, worst
+from specials_common import POINT_COUNTS as HOSTILE_POINT_COUNTS
+from specials_common import SIZES as HOSTILE_SIZES
+from specials_common import VARIANTS, hostile_dynamic_system, hostile_point_words, hostile_points, nan_row, near, same_nan, special_row
 
 pytestmark = pytest.mark.gpu
 SIZES = (1, 2, 63, 257, 1025, 2100)   # one body, a pair, a tail below a wave, a block edge, two blocks, three blocks with a tail
@@ -378,3 +380,173 @@ def test_guards(nb):
         reset()
         assert [call32(), rows32()] == [E.ERR_STATE] * 2 and untouched(o32)
         assert [call64(), rows64()] == [0, 0] and not untouched(o64)
+
+
+# ---- the hostile system (specials_common.py): what a uniform cloud never shows the pass ----
+
+def check_specials_directly(got, pts, skip, n, variant, what, planted=0):
+    """What include/nbody.h promises without any reference (test_gpu_jerk.py's check, extended to the snap): a skipped body leaves no
+    trace in the nine sums, so a finite query that skips the NaN, inf or overflow body has a finite acceleration (planted: how many such
+    queries there must be); a NaN body poisons the acceleration and the jerk of every query that does not skip it and, through the a_j
+    of the bodies beside it, the snap of EVERY query; and in the finite variants point 1, which sits on body 0 with that body's own
+    velocity and acceleration and does not skip it, gets +0 from it in all three outputs: the bits of point 0, which does skip it."""
+    a, j, s = got
+    special = special_row(n, variant)
+    sk = np.full(len(pts), -1, np.int32) if skip is None else skip
+    if special is not None:
+        clean = near(pts) & (sk == special)
+        assert clean.sum() >= planted, what
+        assert np.all(np.isfinite(a[clean])), what
+    if variant == "nan":
+        hit = sk != nan_row(n)
+        assert np.all(np.isnan(a[hit][:, :3])) and np.all(np.isnan(j[hit][:, :3])) and np.all(np.isnan(s[:, :3])), what
+    if variant in ("base", "overflow") and len(pts) > 1:
+        assert all(same(o[0], o[1]) and np.all(np.isfinite(o[:2])) for o in got), what
+
+
+def hostile_queries(nb, pos, vel, acc, m, variant):
+    pts, skip = hostile_points(nb, pos, m, variant)
+    pvel, pacc = hostile_point_words(nb, m, pos.dtype.type, vel, acc)
+    return pts, pvel, pacc, skip
+
+
+@pytest.mark.parametrize("arith", ["strict", "reference_strict", "fp64_strict"])
+def test_hostile_system_strict_bit_for_bit(nb, ref, arith, monkeypatch):
+    """hostile_dynamic_system in every variant and size, every query count, with and without the hostile skip, the one-launch form and
+    the scratch + combine form (NBODY_SNAP_SPLIT unset, 1, 2, 3), and the rows form: all three outputs bit for bit tests/snap_ref.c (NaN
+    for NaN), whose `continue` on j == skip is the definition.  The sources' accelerations are the statement's own first pass, which
+    the device's opening pass must reproduce; points 0 and 1 carry body 0's own velocity and acceleration."""
+    fp64 = arith == "fp64_strict"
+    dtype = np.float64 if fp64 else np.float32
+    mode = nb.ARITH_REFERENCE_STRICT if arith == "reference_strict" else nb.ARITH_STRICT
+    r = mode == nb.ARITH_REFERENCE_STRICT
+    differ = []
+    for n in HOSTILE_SIZES:
+        with nb.NBody(n, fp64=fp64) as eng:
+            eng.set_option(nb.OPT_ARITH, mode)
+            for variant in VARIANTS:
+                pos, vel, far = hostile_dynamic_system(nb, n, dtype, variant)
+                with np.errstate(all="ignore"):
+                    want_rows = ref.rows(pos, vel, dtype, ref=r)
+                eng.upload(pos, vel)
+                for m in HOSTILE_POINT_COUNTS:
+                    pts, pvel, pacc, hsk = hostile_queries(nb, pos, vel, want_rows[0], m, variant)
+                    for skip in (None, hsk):
+                        with np.errstate(all="ignore"):
+                            want = ref.f64(pos, vel, want_rows[0], pts, pvel, pacc, skip) if fp64 else ref.f32(pos, vel, want_rows[0], pts, pvel, pacc, skip, ref=r)
+                        what = (n, variant, m, skip is not None)
+                        planted = 2 if skip is not None and m >= 65 else 0
+                        check_specials_directly(want, pts, skip, n, variant, what, planted)     # the statement itself keeps the promise
+                        for split in (None, "1", "2", "3"):
+                            if split is None:
+                                monkeypatch.delenv("NBODY_SNAP_SPLIT", raising=False)
+                            else:
+                                monkeypatch.setenv("NBODY_SNAP_SPLIT", split)
+                            got = eng.snap_at(pts, pvel, pacc, skip)
+                            if not all(same_nan(g, w) for g, w in zip(got, want)):
+                                differ.append(what + (split, [int((bits(g) != bits(w)).any(1).sum()) for g, w in zip(got, want)]))
+                            check_specials_directly(got, pts, skip, n, variant, what + (split,), planted)
+                monkeypatch.delenv("NBODY_SNAP_SPLIT", raising=False)
+                rows = eng.snap()
+                if not all(same_nan(g, w) for g, w in zip(rows, want_rows)):
+                    differ.append((n, variant, "rows", [int((bits(g) != bits(w)).any(1).sum()) for g, w in zip(rows, want_rows)]))
+    assert not differ, differ   # every input where the device and the statement differ, none dropped
+
+
+def skipped_special_leaves_no_trace(nb, ref, eng, pos, vel, acc, queries_, n, variant, got, strict, is_ref):
+    """The queries that skip the variant's special body get, bit for bit, what they get once that body is an ordinary one: nothing of
+    it reaches their nine sums.  The acceleration and the jerk: against the device's own run with the body at (0.25, 0.25, 0.25) moving
+    with (0.5, 0.5, 0.5).  The snap cannot be compared that way — an ordinary body changes the a_j of every other source (include/nbody.h:
+    a NaN body reaches every snap through them) — so it is compared (a) in the strict modes against the statement on that ordinary body
+    with the device's own a_j and 0.75 in the body's acceleration word, and (b) in "overflow", in every arithmetic, against the device's
+    run with the body at another position whose square overflows and with another velocity: it gives every other source +0 as before."""
+    pts, pvel, pacc, skip = queries_
+    special = special_row(n, variant)
+    if special is None or skip is None or not np.any(skip == special):
+        return []
+    sel, differ = skip == special, []
+    tame_p, tame_v, tame_a = pos.copy(), vel.copy(), acc.copy()
+    tame_p[special, :3], tame_v[special, :3], tame_a[special, :3] = 0.25, 0.5, 0.75
+    eng.upload(tame_p, tame_v)
+    tame = eng.snap_at(pts, pvel, pacc, skip)
+    if not (same_nan(got[0][sel], tame[0][sel]) and same_nan(got[1][sel], tame[1][sel])):
+        differ.append("ordinary body: acceleration or jerk")
+    if strict:
+        with np.errstate(all="ignore"):
+            want = ref.of(pos.dtype)(tame_p, tame_v, tame_a, pts, pvel, pacc, skip, **({"ref": True} if is_ref else {}))
+        if not all(same_nan(g[sel], w[sel]) for g, w in zip(got, want)):
+            differ.append("ordinary body, its acceleration word included: the statement")
+    if variant == "overflow":
+        moved_p = pos.copy()
+        moved_p[special, :3] = -pos[special, [1, 2, 0]]
+        eng.upload(moved_p, tame_v)
+        moved = eng.snap_at(pts, pvel, pacc, skip)
+        if not all(same_nan(g[sel], w[sel]) for g, w in zip(got, moved)):
+            differ.append("moved body")
+    eng.upload(pos, vel)
+    return differ
+
+
+@pytest.mark.parametrize("fp64", [False, True])
+def test_hostile_system_every_arithmetic(nb, ref, fp64):
+    """Every arithmetic — the timed ones (v_rsq_f32; the v_rsq_f64 seed + one third-order step) and the strict ones — on
+    hostile_dynamic_system: all three outputs finite and NaN exactly where the strict statement of the same d2 form is, given the
+    accelerations the device's own opening pass gives the sources, in every variant, with and without skip; a skipped NaN, inf or
+    overflow body leaves no trace (skipped_special_leaves_no_trace); a NaN body poisons every query that does not skip it."""
+    dtype = np.float64 if fp64 else np.float32
+    modes = (nb.ARITH_FMA3, nb.ARITH_STRICT) if fp64 else (nb.ARITH_FMA3, nb.ARITH_REFERENCE, nb.ARITH_STRICT, nb.ARITH_REFERENCE_STRICT)
+    differ = []
+    for n in HOSTILE_SIZES:
+        with nb.NBody(n, fp64=fp64) as eng:
+            for variant in VARIANTS:
+                pos, vel, far = hostile_dynamic_system(nb, n, dtype, variant)
+                eng.upload(pos, vel)
+                for mode in modes:
+                    eng.set_option(nb.OPT_ARITH, mode)
+                    is_ref = mode in (nb.ARITH_REFERENCE, nb.ARITH_REFERENCE_STRICT)
+                    strict = mode in (nb.ARITH_STRICT, nb.ARITH_REFERENCE_STRICT)
+                    acc = eng.jerk()[0]
+                    pts, pvel, pacc, hsk = hostile_queries(nb, pos, vel, acc, 300, variant)
+                    for skip in (hsk, None):
+                        what = (n, variant, mode, skip is not None)
+                        with np.errstate(all="ignore"):
+                            want = ref.f64(pos, vel, acc, pts, pvel, pacc, skip) if fp64 else ref.f32(pos, vel, acc, pts, pvel, pacc, skip, ref=is_ref)
+                        got = eng.snap_at(pts, pvel, pacc, skip)
+                        for k, (g_, w) in enumerate(zip(got, want)):
+                            if not (np.array_equal(np.isfinite(g_), np.isfinite(w)) and np.array_equal(np.isnan(g_), np.isnan(w))):
+                                differ.append(what + (k, np.flatnonzero((np.isfinite(g_) != np.isfinite(w)).any(1) | (np.isnan(g_) != np.isnan(w)).any(1))[:8]))
+                        check_specials_directly(got, pts, skip, n, variant, what, 2 if skip is not None else 0)
+                        differ += [what + (d,) for d in skipped_special_leaves_no_trace(nb, ref, eng, pos, vel, acc, (pts, pvel, pacc, skip), n, variant, got,
+                                                                                        strict, is_ref)]
+                eng.set_option(nb.OPT_ARITH, nb.ARITH_FMA3)
+    assert not differ, differ   # an input where the patterns differ is reported, not dropped
+
+
+def test_hostile_system_timed_fp32_within_tolerance(nb):
+    """ "base" and "overflow", every size, 300 hostile queries with and without skip, both timed binary32 arithmetics: |got - want64| / mag
+    of the snap, the jerk and the acceleration on the near queries that are finite in binary64 (at least 290 of 300, asserted) within
+    snap_common.TIMED_BOUND_HOSTILE = 2 R_REF_HOSTILE + 7 * 2^-23 = 1.08e-5 — TIMED_BOUND's rule with the statement's own figure on this
+    system (4.93e-6, tests/test_specials_dynamic_reference.py).  want64 is numpy binary64 with the accelerations the device's own
+    opening pass gives the sources in the same arithmetic.
+    Measured on an MI355X, worst over sizes, variants and skip: see the printed lines."""
+    worst_of = {}
+    for n in HOSTILE_SIZES:
+        with nb.NBody(n) as eng:
+            for variant in ("base", "overflow"):
+                pos, vel, far = hostile_dynamic_system(nb, n, np.float32, variant)
+                eng.upload(pos, vel)
+                for mode in (nb.ARITH_FMA3, nb.ARITH_REFERENCE):
+                    eng.set_option(nb.OPT_ARITH, mode)
+                    acc = eng.jerk()[0]
+                    pts, pvel, pacc, hsk = hostile_queries(nb, pos, vel, acc, 300, variant)
+                    for skip in (hsk, None):
+                        got = eng.snap_at(pts, pvel, pacc, skip)
+                        full = numpy_snap(pos, vel, acc, pts, pvel, pacc, skip)
+                        keep = near(pts) & np.all([np.isfinite(o).all(1) for o in full], axis=0)
+                        assert keep.sum() >= 290, (n, variant, mode)
+                        e = [worst(got[i][keep], full[i][keep], full[3 + i][keep]) for i in range(3)]
+                        worst_of[(n, mode)] = [max(a, b) for a, b in zip(worst_of.get((n, mode), [0.0] * 3), e)]
+                eng.set_option(nb.OPT_ARITH, nb.ARITH_FMA3)
+    for (n, mode), e in sorted(worst_of.items()):
+        print("hostile timed fp32 n=%d arith %d: accel %.3e jerk %.3e snap %.3e (bound %.3e)" % (n, mode, *e, TIMED_BOUND_HOSTILE))
+    assert all(max(e) <= TIMED_BOUND_HOSTILE for e in worst_of.values()), worst_of
